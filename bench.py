@@ -6,9 +6,14 @@ backward + gradient all-reduce + Adam/EMA) of the VGG-16 detector at 512x512, ba
     python bench.py --gpus N --steps K --warmup W        (N > 1: spawns the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel:
-the implicit-GEMM conv, achieved TFLOP/s from HIP-event timing of every launch inside the timed
-steps) and, at N=1, `cpu_baseline` (the CPU oracle's train step on the host cores; baseline only).
+Prints ONE JSON line on rank 0 with the headline figure (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`).  A plain run sets up, warms up, times the K steps and prints that line;
+`--dump-outputs DIR` also writes what the last timed step computed (loss, score maps, a seeded sample of
+the updated parameters) as DIR/<name>.npy.  Everything else the benchmark measures runs only with `--full`:
+`roofline` (dominant kernel: the implicit-GEMM conv, achieved TFLOP/s from HIP-event timing of every launch
+inside the timed steps), the `exchange` A/B and its stand-in legs, the replica checks (N > 1), the short
+legs of the other BASELINE configs and, at N=1, `cpu_baseline` (the CPU oracle's train step on the host
+cores; baseline only).
 """
 import argparse
 import ctypes
@@ -163,6 +168,67 @@ def counters_from_profiles(dom):
 
 PROFILE_ROUND = "r06"
 
+DUMP_BUDGET_BYTES = 60 << 20          # --dump-outputs: the arrays of all files together (< 64 MB with the headers)
+DUMP_PARAM_SAMPLE = 1 << 20           # updated parameters: a fixed, seeded sample of this many values
+
+
+def _sample(a, k, seed):
+    """A fixed, seeded choice of k entries of the flattened array (ascending index), or all of it if k >= its size."""
+    a = a.reshape(-1)
+    if k >= a.size:
+        return a
+    idx = np.sort(np.random.default_rng(seed).choice(a.size, size=k, replace=False))
+    return a[idx]
+
+
+def dump_outputs(path, loss, maps, store):
+    """What the last timed step computed, as float32 .npy files under `path`: `loss` (the loss buffer: total, then its
+    terms), the step's forward outputs `maps` (name -> device tensor) and the state the optimiser left: a seeded sample
+    of the updated trainable parameters (`params_sample`) and every non-trainable (`moving_stats`: BN moving statistics).
+    The maps are written whole while everything fits DUMP_BUDGET_BYTES, else each as the same seeded sample fraction."""
+    os.makedirs(path, exist_ok=True)
+    out = {"loss": loss.data.detach().float().cpu().numpy(),
+           "params_sample": _sample(store.flat.detach().cpu().numpy(), DUMP_PARAM_SAMPLE, 1),
+           "moving_stats": store.flat_aux.detach().cpu().numpy()}
+    left = DUMP_BUDGET_BYTES // 4 - sum(a.size for a in out.values())         # float32 values still free
+    total = sum(t.numel() for t in maps.values())
+    for i, (name, t) in enumerate(maps.items()):
+        a = t.detach().float().cpu().numpy()
+        out[name] = a if total <= left else _sample(a, a.size * left // total, 2 + i)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(out)
+
+
+def headline(args, world, value, ms, loss_val, step, trace, dumped):
+    """The result line's headline fields (plain and --full runs alike)."""
+    from tensorflow_ocr_amd import _lib
+    out = {
+        "metric": "images/sec training, 512x512 ICDAR, VGG-16 EAST, batch 32, 1/2/4/8 GPU",
+        "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": _lib.STORAGE, "data": "synthetic",
+        "config": {"workload": "VGG-16 model_vgg + dice loss train step, %dx%d, batch %d per GPU, "
+                               "%s storage / f32 accumulate, Adam+EMA" % (args.size, args.size, args.batch, _lib.STORAGE),
+                   "global_batch": world * args.batch, "parallelism": "dp%d" % world,
+                   "loss_scale": args.loss_scale},
+        "loss": round(loss_val, 5),
+        "train_tflops": round(value * TRAIN_GFLOP_PER_IMG / 1e3 * (args.size / 512.0) ** 2, 1),
+    }
+    if getattr(step, "plan", None) is not None:
+        # train.schedule_guests: how much of the recorded step runs as guest / host pairs (DESIGN.md 3.5)
+        kinds = [e[0] if e[0] != "c" else (e[4][0] if e[4] is not None else "c") for e in step.plan]
+        paired = [e for e in step.plan if e[0] == "c" and e[4] is not None and e[4][0] == "guest" and e[4][-1] == "paired"]
+        out["guests"] = {"pairs": kinds.count("fork"), "guest_passes": sum(1 for k in kinds if k == "guest"),
+                         "weight_gradients": sum(1 for e in step.plan if e[0] == "c" and e[4] is not None and e[4][0] == "side" and len(e[4]) > 1),
+                         "guest_bytes_per_step_GB": round(sum(e[4][1] for e in paired) / 1e9, 2),
+                         "second_stream": "guest passes (<= 56 registers per lane) beside held-back weight-gradient slab kernels"}
+    if trace is not None:
+        out["loss_trace"] = trace
+    if dumped is not None:
+        out["dumped"] = dumped
+    return out
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -189,6 +255,10 @@ def main():
     ap.add_argument("--share-gpu", action="store_true", help="all ranks use cuda:0 (functional check only)")
     ap.add_argument("--force-pg", action="store_true", help="N=1 only: create a one-rank process group and run "
                     "the bucketed gradient exchange anyway (RCCL stream ordering on a one-GPU box)")
+    ap.add_argument("--full", action="store_true", help="also measure everything besides the headline figure: roofline, "
+                    "exchange A/B and stand-in legs, replica checks, the other BASELINE configs' legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one "
+                    "computed (rank 0) as DIR/<name>.npy, float32, at most 64 MB in all")
     args = ap.parse_args()
 
     # Plain `python bench.py --gpus N`: this process becomes the launcher of N ranks (one per GPU) and
@@ -206,7 +276,7 @@ def main():
     json_fd = os.dup(1)
     os.dup2(2, 1)
 
-    from tensorflow_ocr_amd import _lib, dist, ops, synthetic
+    from tensorflow_ocr_amd import dist, ops, synthetic
     from tensorflow_ocr_amd.graph import Graph
     from tensorflow_ocr_amd.nets import model_vgg_16 as M
     from tensorflow_ocr_amd.train import AdamOptimizer, TrainStep
@@ -239,8 +309,13 @@ def main():
     images, pixel, link, mask = synthetic.make_batch(rng, args.batch, args.size)
     batch = [torch.from_numpy(a).to(device) for a in (images, pixel, link, mask)]   # resident in HBM
 
+    # the forward outputs of the latest eager step; from the recorded (third) step on, their buffers are the ones every
+    # replayed step writes, so after the timed region they hold the last timed step's maps (--dump-outputs)
+    maps = {}
+
     def forward_loss(gr, im, px, lk, mk):
         f_score, f_geometry = M.model_vgg(im, is_training=True, graph=gr)
+        maps["pixel_cls"], maps["link_cls"] = f_score, f_geometry
         return M.loss(px, f_score, lk, f_geometry, mk, graph=gr)
 
     # N = 1 with the one-rank exchange recorded: the plan also holds, next to every bucket's all-reduce, a stand-in with
@@ -269,7 +344,7 @@ def main():
     for _ in range(args.warmup):
         loss = take(step(*batch))
     barrier()
-    ops.KERNEL_TIMING = []
+    ops.KERNEL_TIMING = [] if args.full else None          # per-launch HIP events for `roofline` (--full only)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = take(step(*batch))
@@ -285,6 +360,21 @@ def main():
         return float(t.item())
     dt = max_over_ranks(dt)
     loss_val = loss.item()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything below takes another step
+        dumped = dump_outputs(args.dump_outputs, loss, {k: v.data for k, v in maps.items()}, g.store)
+    if not args.full:
+        if rank == 0:
+            ms = dt / args.steps * 1e3
+            value = world * args.batch * args.steps / dt
+            out = headline(args, world, value, ms, loss_val, step, trace, dumped)
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        if td.is_available() and td.is_initialized():
+            td.barrier()
+            td.destroy_process_group()
+        return
 
     # data-parallel invariants, checked before the A/B below lets the towers drift: every rank trained on its OWN shard
     # (checksums of the input images all differ) and every rank holds the SAME parameters (identical initialisation, the
@@ -464,33 +554,12 @@ def main():
     if rank == 0:
         ms = dt / args.steps * 1e3
         value = world * args.batch * args.steps / dt
-        out = {
-            "metric": "images/sec training, 512x512 ICDAR, VGG-16 EAST, batch 32, 1/2/4/8 GPU",
-            "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": _lib.STORAGE, "data": "synthetic",
-            "config": {"workload": "VGG-16 model_vgg + dice loss train step, %dx%d, batch %d per GPU, "
-                                   "%s storage / f32 accumulate, Adam+EMA" % (args.size, args.size, args.batch, _lib.STORAGE),
-                       "global_batch": world * args.batch, "parallelism": "dp%d" % world,
-                       "loss_scale": args.loss_scale},
-            "loss": round(loss_val, 5),
-            "train_tflops": round(value * TRAIN_GFLOP_PER_IMG / 1e3 * (args.size / 512.0) ** 2, 1),
-            "roofline": roof,
-        }
-        if trace is not None:
-            out["loss_trace"] = trace
+        out = headline(args, world, value, ms, loss_val, step, trace, dumped)
+        out["roofline"] = roof
         if replicas is not None:
             out["replicas"] = replicas
         if comm is not None:
             out["exchange"] = comm
-        if getattr(step, "plan", None) is not None:
-            # train.schedule_guests: how much of the recorded step runs as guest / host pairs
-            kinds = [e[0] if e[0] != "c" else (e[4][0] if e[4] is not None else "c") for e in step.plan]
-            paired = [e for e in step.plan if e[0] == "c" and e[4] is not None and e[4][0] == "guest" and e[4][-1] == "paired"]
-            out["guests"] = {"pairs": kinds.count("fork"), "guest_passes": sum(1 for k in kinds if k == "guest"),
-                             "weight_gradients": sum(1 for e in step.plan if e[0] == "c" and e[4] is not None and e[4][0] == "side" and len(e[4]) > 1),
-                             "guest_bytes_per_step_GB": round(sum(e[4][1] for e in paired) / 1e9, 2),
-                             "second_stream": "guest passes (<= 56 registers per lane) beside held-back weight-gradient slab kernels"}
         if world == 1 and not args.no_config_legs:
             # free this process's activations first: the legs are children that need the HBM
             del step, batch

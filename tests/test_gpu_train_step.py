@@ -360,7 +360,8 @@ def _bench(args, timeout=540):
         args = [a for a in args if a != "--with-config-legs"]
     else:
         args = args + ["--no-config-legs"]
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args, env=env, stdout=subprocess.PIPE,
+    # these tests check the exchange, replica and roofline records: a --full run's
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full"] + args, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=timeout)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     # the contract: stdout is the ONE JSON line, nothing else (RCCL / gloo banners go to stderr: bench.py re-points fd 1)
@@ -424,3 +425,57 @@ def test_bench_default_single_gpu_line_reports_the_exchange(device):
     out2 = _bench(["--steps", "2", "--warmup", "1", "--batch", "2", "--size", "64", "--no-cpu-baseline", "--no-pg"])
     assert "exchange" not in out2
     assert abs(out2["loss"] - out["loss"]) < 1e-6            # a one-rank exchange changes nothing
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(device, tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: the result line carries the headline fields only, and DIR holds what
+    the LAST timed step computed — the same loss, score maps and updated parameters as an eager TrainStep taking the same
+    number of steps (3 engine-build + warm-up + timed) on bench.py's batch and initial weights."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from tensorflow_ocr_amd import _lib, synthetic
+    from tensorflow_ocr_amd.graph import Graph
+    from tensorflow_ocr_amd.nets import model_vgg_16 as M
+    from tensorflow_ocr_amd.train import AdamOptimizer, TrainStep
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    n, size, warmup, steps = 2, 64, 1, 2
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", str(n), "--size", str(size),
+                        "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(d)], env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=540)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout.decode()[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == steps and out["ms_per_step"] > 0 and out["dtype"] == _lib.STORAGE and out["higher_is_better"] is True
+    assert not {"roofline", "exchange", "configs", "cpu_baseline"} & set(out)
+    names = {"loss", "pixel_cls", "link_cls", "params_sample", "moving_stats"}
+    assert set(out["dumped"]) == names and {p.name for p in d.iterdir()} == {x + ".npy" for x in names}
+    got = {x: np.load(d / (x + ".npy")) for x in names}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(os.path.getsize(d / (x + ".npy")) for x in names) <= 64 << 20
+    assert abs(float(got["loss"][0]) - out["loss"]) < 1e-5
+
+    g = Graph(device, loss_scale=1024.0, seed=1)
+    batch = [torch.from_numpy(a).to(device) for a in synthetic.make_batch(np.random.default_rng(100), n, size)]
+    maps = {}
+
+    def fl(gr, im, px, lk, mk):
+        maps["pixel_cls"], maps["link_cls"] = M.model_vgg(im, is_training=True, graph=gr)
+        return M.loss(px, maps["pixel_cls"], lk, maps["link_cls"], mk, graph=gr)
+    step = TrainStep(g, fl, lambda gr: AdamOptimizer(gr, learning_rate=1e-4), replay=False)
+    for _ in range(3 + warmup + steps):
+        loss = step(*batch)
+    torch.cuda.synchronize()
+    assert abs(float(got["loss"][0]) - loss.item()) < 1e-5
+    for k in ("pixel_cls", "link_cls"):
+        ref = maps[k].data.float().cpu().numpy()
+        assert got[k].shape == ref.shape and np.abs(got[k] - ref).max() < 1e-3, k
+    ref = bench._sample(g.store.flat.cpu().numpy(), bench.DUMP_PARAM_SAMPLE, 1)
+    assert got["params_sample"].shape == ref.shape and np.allclose(got["params_sample"], ref, rtol=1e-5, atol=1e-7)
+    assert np.allclose(got["moving_stats"], g.store.flat_aux.cpu().numpy(), rtol=1e-4, atol=1e-6)

@@ -871,3 +871,31 @@ def test_rccl_rendezvous_second_gate_keeps_healthy_ranks_out_of_init(tmp_path):
     for r, (p, o) in enumerate(zip(ps, outs)):
         assert p.returncode == 0 and ("rank %d raised" % r) in o and "entered init" not in o, o[-2000:]
     assert "simulated store timeout" in outs[1] and "could not obtain the unique id" in outs[0]
+
+
+def test_bench_dump_outputs_fits_its_budget_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs (`--dump-outputs DIR`): float32 files, the parameters as a fixed seeded sample, the maps whole
+    while everything fits the budget and as seeded samples beyond it; two dumps of the same arrays are identical."""
+    import importlib
+    import types
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    store = types.SimpleNamespace(flat=torch.arange(3000, dtype=torch.float32), flat_aux=torch.ones(10))
+    loss = types.SimpleNamespace(data=torch.arange(10, dtype=torch.float32))
+    maps = {"pixel_cls": torch.rand(2, 10, 10, 2).half(), "link_cls": torch.rand(2, 10, 10, 16).half()}
+    monkeypatch.setattr(bench, "DUMP_PARAM_SAMPLE", 1000)
+    names = bench.dump_outputs(str(tmp_path / "a"), loss, maps, store)         # 4 MB budget: all of it fits
+    assert names == ["link_cls", "loss", "moving_stats", "params_sample", "pixel_cls"]
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["pixel_cls"].shape == (2, 10, 10, 2) and np.array_equal(a["link_cls"], maps["link_cls"].float().numpy())
+    p = a["params_sample"]
+    assert p.shape == (1000,) and np.all(np.diff(p) > 0) and p.max() < 3000          # a subset, ascending index
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 1400)                         # room for 380 map values
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), loss, maps, store)
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in names}
+    c = {n: np.load(tmp_path / "c" / (n + ".npy")) for n in names}
+    assert sum(v.size for v in b.values()) * 4 <= 4 * 1400
+    assert b["pixel_cls"].shape == (380 * 400 // 3600,) and b["link_cls"].shape == (380 * 3200 // 3600,)
+    assert all(np.array_equal(b[n], c[n]) for n in names) and np.array_equal(b["params_sample"], p)
