@@ -25,7 +25,8 @@ extern "C" {
 /* Bumped whenever an exported entry point changes its argument list (round 3 added arguments to
  * ocr_conv2d_bnred_f16, ocr_conv2d_bnred_tail_f16, ocr_bn_add_relu_f16, ocr_bn_relu_pool_idx_f16; round 4: the
  * batched head entry points and the seed-rank argument of ocr_link_cc_directed; round 5: the guest kernels).  The Python host refuses a
- * library whose ocr_abi_version() differs from the value it was written against (_lib.ABI_VERSION). */
+ * library whose ocr_abi_version() differs from the value it was written against (_lib.ABI_VERSION).
+ * New entry points do not bump it: ocr_conv2d_f32_split / ocr_conv2d_f32_split_workspace (the f16x2 precision) joined at 7. */
 #define OCR_ABI_VERSION 7
 
 enum {
@@ -590,6 +591,17 @@ int ocr_prep_images_f32(const void* images, int64_t npix, float mean_r, float me
 int ocr_bn_add_relu_f32(const void* y, const void* scale, const void* shift, const void* shortcut,
                         int64_t npix, int c, void* out, void* stream);
 int ocr_unpool_f32(const void* x, int n, int lh, int lw, int c, void* y, void* stream);
+/* f16x2 INFERENCE PRECISION (csrc/f16x2_infer.hip; Graph(precision="f16x2"), --precision f16x2): the convolution of the f32
+ * graph above on the 16-bit matrix cores at f32 accuracy (slim.conv2d: nets/vgg.py:14-39, nets/resnet_v1.py:97-105,
+ * nets/model_vgg_16.py:144).  Each f32 operand is carried as two IEEE halves, hi = half(v) and lo' = half((v - hi) * 2^11);
+ * x*w = xhi*whi + 2^-11 (xhi*wlo' + xlo'*whi) on v_mfma_f32_16x16x32_f16 with f32 accumulation (main and correction sums
+ * apart, joined in the epilogue).  IEEE half in BOTH libraries (f32 in, f32 out: independent of the 16-bit storage type).
+ * Same contract and flags as ocr_conv2d_f32_mfma, plus `workspace` (16-byte aligned, at least
+ * ocr_conv2d_f32_split_workspace(d) bytes): EVERY call splits and packs the weights into it on `stream`, then convolves.
+ * Range: |x|, |w| >= 65504 saturate to the largest finite half (wrong but finite result); NaN operands stay NaN. */
+size_t ocr_conv2d_f32_split_workspace(const ocr_conv_desc* d);
+int ocr_conv2d_f32_split(const ocr_conv_desc* d, const void* x, const void* w_hwio, const void* bias, void* y,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Fuse heads, BATCHED (round 4): one launch per kernel kind over the (up to four) feature maps the heads read

@@ -243,6 +243,7 @@ def main():
     ap.add_argument("--pixellink-loss", default="focal", choices=("focal", "plain"))
     ap.add_argument("--resnet-batch", type=int, default=64)
     ap.add_argument("--resnet-size", type=int, default=640)
+    ap.add_argument("--json-out", default=None, help="f16x2_forward: also write the result (with the source fingerprint) here")
     args = ap.parse_args()
     which = args.which.split(",")
     from tensorflow_ocr_amd.train import AdamOptimizer, MomentumOptimizer
@@ -359,6 +360,8 @@ def main():
         east_fwd_config()
     if "f32_forward" in which:
         f32_forward_config(args.steps, args.warmup)
+    if "f16x2_forward" in which:
+        f16x2_forward_config(args.steps, args.warmup, args.json_out)
 
 
 def east_fwd_config():
@@ -457,6 +460,88 @@ def f32_forward_config(steps, warmup):
                                 "PixelLinkNet 1024^2 b2 — the path that meets the 1e-3 score-map bar",
                       "dtype": "f32", "steps": steps, "ms_per_step": a["ms_per_forward"], "images_per_sec": a["images_per_sec"],
                       "tflops": a["tflops"], "frac_of_peak": a["frac_of_f32_mfma_peak"], "components": out}), flush=True)
+
+
+# the convolution shapes of model_vgg at 512^2 batch 8: (name, h = w, cin, cout, k, rate)
+VGG_512_B8_LAYERS = [("conv1_1", 512, 3, 64, 3, 1), ("conv1_2", 512, 64, 64, 3, 1), ("conv2_1", 256, 64, 128, 3, 1),
+                     ("conv2_2", 256, 128, 128, 3, 1), ("conv3_1", 128, 128, 256, 3, 1), ("conv3_2", 128, 256, 256, 3, 1),
+                     ("conv3_3", 128, 256, 256, 3, 1), ("conv4_1", 64, 256, 512, 3, 1), ("conv4_2", 64, 512, 512, 3, 1),
+                     ("conv4_3", 64, 512, 512, 3, 1), ("conv5_1", 32, 512, 512, 3, 1), ("conv5_2", 32, 512, 512, 3, 1),
+                     ("conv5_3", 32, 512, 512, 3, 1), ("fc6", 32, 512, 1024, 3, 6), ("fc7", 32, 1024, 1024, 1, 1),
+                     ("merge_1x1", 128, 256, 32, 1, 1)]
+
+
+def f16x2_layer_table(batch=8):
+    """Per layer: ocr_conv2d_f32_mfma vs ocr_conv2d_f32_split (weight packing included), device ms and TFLOP/s of USEFUL
+    FLOPs (one product per MAC, not the three MFMAs the split form issues)."""
+    from tensorflow_ocr_amd import ops
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(9)
+    rows = []
+    for name, hw, cin, cout, k, rate in VGG_512_B8_LAYERS:
+        x = torch.from_numpy(rng.standard_normal((batch, hw, hw, cin)).astype(np.float32)).to(dev)
+        w = torch.from_numpy((rng.standard_normal((k, k, cin, cout)) / np.sqrt(k * k * cin)).astype(np.float32)).to(dev)
+        d = ops.conv_desc((batch, hw, hw, cin), cout, k, k, 1, rate)
+        d.flags = 0
+        y = torch.empty((batch, d.oh, d.ow, cout), dtype=torch.float32, device=dev)
+        flop = 2.0 * batch * d.oh * d.ow * cout * k * k * cin
+        row = {"layer": name, "hw": hw, "cin": cin, "cout": cout, "k": k, "rate": rate, "gflop": round(flop / 1e9, 2)}
+        for _ in range(2):                                   # alternate the routes: clocks are shared
+            for route in ("mfma", "split"):
+                ms = dev_ms(lambda: ops.conv2d_f32(d, x, w, y, None, route=route), 1, 5)
+                row[route + "_dev_ms"] = round(min(ms, row.get(route + "_dev_ms", 1e9)), 4)
+        for route in ("mfma", "split"):
+            row[route + "_tflops"] = round(flop / row[route + "_dev_ms"] / 1e9, 1)
+        row["speedup"] = round(row["mfma_dev_ms"] / row["split_dev_ms"], 2)
+        row["split_frac_of_peak_over_3"] = round(row["split_tflops"] / (MFMA_PEAK_TFLOPS / 3), 3)
+        rows.append(row)
+        del x, w, y
+    return rows
+
+
+def f16x2_forward_config(steps, warmup, json_out=None):
+    """Graph(precision="f32") against Graph(precision="f16x2") — the same f32 graph with split-f16 operands on the 16-bit
+    matrix cores (csrc/f16x2_infer.hip) — in ONE process, alternating, with the same timed() helper: model_vgg 512^2 batch 8
+    and PixelLinkNet 1024^2 batch 2, then the per-layer table.  f32_forward_config stays what bench.py records."""
+    from tensorflow_ocr_amd import _lib
+    from tensorflow_ocr_amd.graph import Graph
+    from tensorflow_ocr_amd.nets import model_vgg_16 as M
+    from tensorflow_ocr_amd.nets import pixellink
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(3)
+    out = {}
+    for key, size, batch in (("model_vgg_512", 512, 8), ("pixellinknet_1024", 1024, 2)):
+        x = torch.from_numpy(rng.uniform(0, 255, (batch, size, size, 3)).astype(np.float32)).to(dev)
+        fwds = {}
+        for prec in ("f32", "f16x2"):
+            g = Graph(dev, seed=1, precision=prec)
+
+            def fwd(g=g):
+                if key.startswith("model_vgg"):
+                    M.model_vgg(x, is_training=False, graph=g)
+                else:
+                    pixellink.PixelLinkNet(x, graph=g)
+                g.reset_tape()
+            fwd()
+            fwds[prec] = fwd
+        best = {}
+        for _ in range(3):                                   # alternate: both see the same clocks and box
+            for prec in ("f32", "f16x2"):
+                best[prec] = min(best.get(prec, 1e9), timed(fwds[prec], warmup, steps))
+        out[key] = {"batch": batch, "size": size, "f32_ms": round(best["f32"] * 1e3, 3), "f16x2_ms": round(best["f16x2"] * 1e3, 3),
+                    "f32_over_f16x2": round(best["f32"] / best["f16x2"], 3)}
+        del fwds, x
+        torch.cuda.empty_cache()
+    res = {"config": "f16x2 inference forward vs f32 inference forward, same process, alternating: model_vgg 512^2 b8, "
+                     "PixelLinkNet 1024^2 b2", "steps": steps, "warmup": warmup, "ms_per_step": out["model_vgg_512"]["f16x2_ms"],
+           "components": out, "csrc_fingerprint": _lib.csrc_fingerprint()}
+    print(json.dumps(res), flush=True)
+    res["layers_model_vgg_512_b8"] = f16x2_layer_table()
+    print(json.dumps({"layers_model_vgg_512_b8": res["layers_model_vgg_512_b8"]}), flush=True)
+    if json_out:
+        with open(json_out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
 
 
 def dev_ms(fn, warmup=2, steps=10):

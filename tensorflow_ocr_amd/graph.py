@@ -214,10 +214,19 @@ class Graph:
         """precision: "f16" = the product path (f16 storage, f32 accumulate, MFMA kernels);
         "f32" = forward-only f32 INFERENCE precision (f32 storage and arithmetic, the convolutions on the matrix
         cores with v_mfma_f32_32x32x2_f32: layers_f32.py, csrc/f32_infer.hip): whole-graph outputs within 1e-3 of the
-        f32 reference (the north star's tolerance), ~10x the time of the 16-bit path."""
-        if precision not in ("f16", "f32"):
-            raise ValueError("precision must be 'f16' or 'f32'")
-        self.precision = precision
+        f32 reference (the north star's tolerance), ~10x the time of the 16-bit path;
+        "f16x2" = the same forward-only f32 graph (f32 storage, the same element-wise kernels) with every convolution on
+        the 16-bit matrix cores: each f32 operand is carried as two IEEE halves (hi, and the residual scaled by 2^11) and
+        a product costs three v_mfma_f32_16x16x32_f16 (ocr_conv2d_f32_split, csrc/f16x2_infer.hip): the accuracy of "f32",
+        faster.  Operand range: |x|, |w| < 65504; larger values saturate (finite, wrong); NaN stays NaN.
+        `precision` holds the STORAGE family the layer modules dispatch on ("f16" | "f32"; "f16x2" is stored as "f32"),
+        `precision_name` the name given here, `f32_conv_route` the ops.conv2d_f32 route of the f32 family (None: the
+        process default ops.F32_CONV; "split")."""
+        if precision not in ("f16", "f32", "f16x2"):
+            raise ValueError("precision must be 'f16', 'f32' or 'f16x2'")
+        self.precision_name = precision
+        self.precision = "f32" if precision == "f16x2" else precision
+        self.f32_conv_route = "split" if precision == "f16x2" else None
         self.device = torch.device(device)
         self.store = VariableStore(self.device)
         self.tape = []
@@ -228,6 +237,7 @@ class Graph:
         self.ws = None
         self.ws_small = None
         self.ws_wgrad = None
+        self.ws_split = None
         self.collections = {"losses": [], "update_ops": []}
         self.keepalive = None        # list while a step is being recorded (train.TrainStep)
 
@@ -260,6 +270,12 @@ class Graph:
             self.ws_small = ops.Workspace(self.device, 8 << 20)
             self.ws_wgrad = ops.Workspace(self.device, 160 << 20)   # weight-gradient slabs (side stream)
         return self.ws
+
+    def split_workspace(self):
+        """The tower's packed-weight arena of the "split" convolution route (ops.conv2d_f32), created on first use."""
+        if self.ws_split is None:
+            self.ws_split = ops.Workspace(self.device, 1 << 20)
+        return self.ws_split
 
     def empty(self, shape, dtype=F16):
         t = torch.empty(shape, dtype=dtype, device=self.device)
@@ -320,7 +336,7 @@ class Graph:
         called as soon as a closure has finished a set of parameter gradients — the hook the
         data-parallel all-reduce uses to overlap communication with the rest of backward."""
         if self.precision != "f16":
-            raise NotImplementedError("the f32 inference precision is forward-only")
+            raise NotImplementedError("the %s inference precision is forward-only" % self.precision_name)
         for fn, produces in reversed(self.tape):
             fn()
             if on_grads_ready is not None and produces:

@@ -6,7 +6,9 @@ run on the matrix cores in f32 (ocr_conv2d_f32_mfma: v_mfma_f32_32x32x2_f32, csr
 kernels are the f32 ones of the same file — all in the product library.  Purpose: outputs within the north star's 1e-3 of
 the f32 reference (tests/test_gpu_f32_verify.py, test_gpu_f32_mfma.py); the 16-bit MFMA kernels are checked layer by layer
 against that reference's 16-bit-storage mode.  OCR_F32_CONV=direct swaps in the plain direct convolution of
-libocr_verify.so (the independent checker).  No backward."""
+libocr_verify.so (the independent checker).  Graph(precision="f16x2") builds the same graph with `g.f32_conv_route ==
+"split"`: every convolution then runs split-f16 operands on the 16-bit matrix cores (ocr_conv2d_f32_split,
+csrc/f16x2_infer.hip; tests/test_gpu_f16x2.py), everything else is unchanged.  No backward."""
 from . import ops
 from .graph import Act, F32, constant, variance_scaling
 from ._lib import CONV_BIAS, CONV_RELU
@@ -35,12 +37,12 @@ def conv2d(g, x, cout, k, scope, *, stride=1, rate=1, normalizer="bn", relu=True
     y = g.empty((n, oh, ow, cout), F32)
     if normalizer != "bn":
         d.flags = CONV_BIAS | (CONV_RELU if relu else 0)
-        ops.conv2d_f32(d, x.data, wv.data, y, bias.data)
+        ops.conv2d_f32(d, x.data, wv.data, y, bias.data, route=g.f32_conv_route, workspace=g.split_workspace)
         a_full = Act(y, requires_grad=False, name=scope)
         a_pool = max_pool2d(g, a_full, 2, 2, scope=scope + "/pool") if pool else None
         return a_full, a_pool
     d.flags = 0
-    ops.conv2d_f32(d, x.data, wv.data, y)
+    ops.conv2d_f32(d, x.data, wv.data, y, route=g.f32_conv_route, workspace=g.split_workspace)
     scale, shift = g.empty((cout,), F32), g.empty((cout,), F32)
     if bn_training:
         mean, invstd = g.empty((cout,), F32), g.empty((cout,), F32)
@@ -87,7 +89,8 @@ def head_conv(g, feat, wv, C, z, bias=None):
     n, h, w, cin = feat.shape
     d = ops.conv_desc((n, h, w, cin), C, 1, 1, 1, 1)
     d.flags = CONV_BIAS if bias is not None else 0
-    ops.conv2d_f32(d, feat.data, wv.data, z, bias.data if bias is not None else None)
+    ops.conv2d_f32(d, feat.data, wv.data, z, bias.data if bias is not None else None, route=g.f32_conv_route,
+                   workspace=g.split_workspace)
 
 
 # ------------------------------------------------------------------ ResNet-v1 / EAST merge branch
@@ -106,7 +109,7 @@ def conv_bn_raw(g, x, cout, k, scope, *, stride=1, rate=1, is_training=True, wei
     d = ops.conv_desc((n, h, w, cin), cout, k, k, 1, rate)
     d.flags = 0
     y = g.empty((n, d.oh, d.ow, cout), F32)
-    ops.conv2d_f32(d, x.data, wv.data, y)
+    ops.conv2d_f32(d, x.data, wv.data, y, route=g.f32_conv_route, workspace=g.split_workspace)
     if stride > 1:
         oh, ow = (d.oh + stride - 1) // stride, (d.ow + stride - 1) // stride
         ys = g.empty((n, oh, ow, cout), F32)
@@ -166,9 +169,10 @@ def concat_conv_bn_relu(g, xa, xb, cout, scope, is_training=True):
     da = ops.conv_desc((n, h, w, ca), cout, 1, 1)
     db = ops.conv_desc((n, h, w, cb), cout, 1, 1)
     da.flags = 0
-    ops.conv2d_f32(da, xa.data, wv.data[0, 0, :ca], y)          # rows [0, ca) of the [ca+cb, cout] matrix
+    ops.conv2d_f32(da, xa.data, wv.data[0, 0, :ca], y, route=g.f32_conv_route,       # rows [0, ca) of the [ca+cb, cout] matrix
+                   workspace=g.split_workspace)
     db.flags = CONV_ACCUM_F16
-    ops.conv2d_f32(db, xb.data, wv.data[0, 0, ca:], y)
+    ops.conv2d_f32(db, xb.data, wv.data[0, 0, ca:], y, route=g.f32_conv_route, workspace=g.split_workspace)
     scale, shift = _bn_affine(g, y, gamma, beta, mm, mv, is_training, BN_EPS, BN_DECAY)
     a = Act(g.empty(y.shape, F32), requires_grad=False, name=scope)
     ops.bn_relu_f32(y, scale, shift, True, 0, a.data, None)

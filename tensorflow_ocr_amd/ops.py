@@ -1123,12 +1123,27 @@ def fill_(x, value=0.0):
 
 # ------------------------------------------------------------------- f32 inference precision
 # (product library: matrix-core f32 convolution + element-wise f32 kernels, csrc/f32_infer.hip; the plain direct
-#  convolution of libocr_verify.so / include/ocr_verify.h is its independent checker: F32_CONV = "direct")
+#  convolution of libocr_verify.so / include/ocr_verify.h is its independent checker: F32_CONV = "direct";
+#  F32_CONV = "split" runs every convolution of an f32 graph as Graph(precision="f16x2") does, csrc/f16x2_infer.hip)
 F32_CONV = __import__("os").environ.get("OCR_F32_CONV", "mfma")
 
 
-def conv2d_f32(d, x, w_hwio, y, bias=None, route=None):
-    if (route or F32_CONV) == "direct":
+def conv2d_f32_split_workspace(d):
+    return L.call_size("ocr_conv2d_f32_split_workspace", byref(d))
+
+
+def conv2d_f32(d, x, w_hwio, y, bias=None, route=None, workspace=None):
+    """route: None -> F32_CONV (OCR_F32_CONV: "mfma" | "direct" | "split"); "mfma" = v_mfma_f32_32x32x2_f32 (f32_infer.hip);
+    "direct" = the checker of libocr_verify.so; "split" = split-f16 operands on v_mfma_f32_16x16x32_f16 (f16x2_infer.hip),
+    the convolution of Graph(precision="f16x2").  workspace (split route only): a callable returning the caller's
+    stream-ordered `Workspace` for the packed weights (Graph.split_workspace: one arena per tower, like its other scratch);
+    without one the call takes a buffer of its own from the allocator."""
+    route = route or F32_CONV
+    if route == "split":
+        nbytes = conv2d_f32_split_workspace(d)
+        buf = workspace().get(nbytes) if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        L.call("ocr_conv2d_f32_split", byref(d), ptr(x), ptr(w_hwio), ptr(bias), ptr(y), ptr(buf), c_size_t(nbytes), _st())
+    elif route == "direct":
         L.call_verify("ocr_conv2d_f32", byref(d), ptr(x), ptr(w_hwio), ptr(bias), ptr(y), _st())
     else:
         L.call("ocr_conv2d_f32_mfma", byref(d), ptr(x), ptr(w_hwio), ptr(bias), ptr(y), _st())
