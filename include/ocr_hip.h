@@ -80,6 +80,11 @@ enum {
  *   stats  [ocr_conv2d_num_mtiles][2][cout] f32 or NULL (OCR_CONV_STATS): per
  *          output tile, the sum and sum of squares of the f16-rounded outputs;
  *          reduced by ocr_bn_finalize.
+ * Contract of the outputs, in every kernel family: the launch STORES every element of y (under
+ * OCR_CONV_ACCUM_F16 after reading it) and every one of the ocr_conv2d_num_mtiles rows of stats — tiles
+ * over a ragged edge and idle waves of the persistent kernel included, nothing is added to what was
+ * there — so neither buffer needs initialising, and nothing outside them is written
+ * (tests/test_gpu_conv_epilogues.py).
  * Requires cin % 32 == 0 and cout % 64 == 0. */
 int ocr_conv2d_f16(const ocr_conv_desc* d, const void* x, const void* w_kc,
                    const void* bias, void* y, void* stats, void* stream);
@@ -105,7 +110,10 @@ int ocr_conv2d_relu_pool_f16(const ocr_conv_desc* d, const void* x, const void* 
  * store_masked != 0: the STORED value is dz itself (the gradient past the layer's ReLU), not the raw gradient — for
  * layers without batch norm (PixelLink's VGG: activation = relu(conv + bias), nets/pixellink.py:41-48) pass their
  * activation as bn_y with scale 1, shift 0, mean 0, invstd 1: y then holds the gradient of (conv + bias) directly,
- * partial row kind 0 sums to the bias gradient (ocr_bn_bwd_sums) and ocr_bias_relu_bwd_f16's pass disappears. */
+ * partial row kind 0 sums to the bias gradient (ocr_bn_bwd_sums) and ocr_bias_relu_bwd_f16's pass disappears.
+ * `partial` follows the contract of `stats` above (every row written, no initialisation needed).  d->flags may carry
+ * OCR_CONV_ACCUM_F16 only (the hosts never combine it with the reduction; every kernel family serves it): y becomes
+ * round(round(conv) + y) and the sums are those of that stored total. */
 int ocr_conv2d_bnred_f16(const ocr_conv_desc* d, const void* x, const void* w_kc, void* y, void* partial,
                          const void* bn_y, const void* bn_scale, const void* bn_shift,
                          const void* bn_mean, const void* bn_invstd, int bn_relu, int store_masked, void* stream);

@@ -32,6 +32,25 @@ def test_bf16_build_layers_models_and_train_step(device):
     assert m and int(m.group(1)) >= 45 and "failed" not in r.stdout, tail
 
 
+def test_bf16_conv_epilogue_matrix(device):
+    """tests/test_gpu_conv_epilogues.py (kernel family x epilogue mode against float64) on the bf16 library: every
+    case of the matrix passes, at the bf16 bars stated in that file."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    try:
+        from test_gpu_conv_epilogues import CASES
+    finally:
+        sys.path.pop(0)
+    env = dict(os.environ, OCR_STORAGE="bf16")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider",
+                        os.path.join(ROOT, "tests", "test_gpu_conv_epilogues.py")],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    tail = (r.stdout + r.stderr)[-3000:]
+    assert r.returncode == 0, tail
+    import re
+    m = re.search(r"(\d+) passed", r.stdout)
+    assert m and int(m.group(1)) == len(CASES) and "failed" not in r.stdout, tail
+
+
 def test_bf16_resnet50_east_640_batch64_parity(device):
     """BASELINE configs[3] as quoted (bf16, batch 64, 640^2): n = 64 replicated == n = 2 in the bf16 library."""
     env = dict(os.environ, OCR_STORAGE="bf16")

@@ -10,6 +10,7 @@ weight gradients stay f32 (measured 1e-7..5e-7, bar 5e-6: accumulation order onl
 OCR_STORAGE=bf16 (libocr_hip_bf16.so, run by tests/test_gpu_bf16.py) the operands are exact bf16
 values and the single output rounding is 2^-8: bar 8e-3."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -20,37 +21,45 @@ from oracle import ocr_oracle as O
 pytestmark = pytest.mark.gpu
 
 SHAPES = [
-    # n, h,  w,  cin, cout, k, dil
-    (2, 16, 40, 64, 64, 3, 1),
-    (1, 24, 33, 64, 128, 3, 1),      # 16-row tile variant, ragged width
-    (2, 9, 11, 128, 64, 3, 1),
-    (1, 20, 32, 128, 256, 3, 1),     # 256-cout tile, 2 chunks
-    (1, 12, 12, 256, 512, 3, 1),
-    (1, 12, 12, 64, 128, 3, 6),      # fc6-style dilation (32-channel chunks)
-    (2, 12, 20, 256, 512, 3, 6),     # ... on 256 x 256 weight-gradient tiles: nine pointwise GEMMs by LDS-DMA, ragged rows
-    (3, 9, 37, 512, 256, 1, 1),      # 256 x 256 tiles, odd height and width, several images per split
-    (2, 8, 8, 128, 128, 1, 1),       # 1x1: 32x32x16 MFMA path
-    (1, 10, 34, 256, 64, 1, 1),
-    (1, 8, 8, 512, 1024, 1, 1),
-    (3, 7, 5, 32, 32, 3, 1),         # 32-channel partial blocks
-    (1, 17, 19, 96, 160, 3, 1),      # cin/cout not multiples of 64: 32-wide tiles
-    (2, 8, 32, 32, 64, 3, 1),        # 64-cout tile with 32-channel chunks
-    (1, 9, 20, 96, 64, 3, 1),
-    (1, 8, 16, 96, 128, 1, 1),
-    (2, 24, 40, 256, 256, 1, 1),     # pointwise GEMM kernel: 7.5 flat tiles, 256-cout tile
-    (1, 16, 32, 64, 64, 1, 1),       # ... 64-cout tile, one K stage
-    (1, 32, 32, 1024, 128, 1, 1),    # ... 128-cout tile, 16 K stages
-    (2, 100, 130, 64, 64, 3, 1),     # persistent weight-stationary 64-channel kernel: 130 ragged pixel tiles
-    (1, 128, 256, 64, 128, 3, 1),    # small-tile 4-wave kernel (conv3x3_w4s<128>), one chunk pair
-    (9, 64, 64, 64, 64, 3, 1),       # persistent kernel: more images than tiles per image
-    (3, 203, 230, 64, 64, 3, 1),     # ... 624 ragged tiles, 2 or 3 per workgroup
-    (2, 16, 40, 128, 64, 3, 1),      # conv3x3_w4s<64>, two chunk pairs
-    (2, 40, 64, 256, 128, 3, 1),     # ... <128>, four chunk pairs
-    (1, 24, 40, 192, 64, 3, 1),      # ... <64>, three chunk pairs (odd)
-    (2, 33, 70, 128, 256, 3, 1),     # 4-wave 3x3 kernel (conv3x3_w4): ragged rows and columns, 2 chunks
-    (1, 16, 64, 512, 512, 3, 1),     # ... 8 chunks x 18 steps, two cout tiles
-    (3, 8, 32, 64, 256, 3, 1),       # ... one chunk (prologue + tail only), several images
+    # n, h,  w,  cin, cout, k, dil, kernel the FORWARD launch is meant to reach (ocr_conv2d_variant; asserted below)
+    (2, 16, 40, 64, 64, 3, 1, "conv3x3_w4s_kernel<64>"),               # one chunk pair (too few tiles for the persistent kernel)
+    (1, 24, 33, 64, 128, 3, 1, "conv3x3_w4s_kernel<128>"),             # ragged width; input gradient on <64>
+    (2, 9, 11, 128, 64, 3, 1, "conv3x3_w4s_kernel<64>"),
+    (1, 20, 32, 128, 256, 3, 1, "conv3x3_w4_kernel"),                  # 256-cout tile, 2 chunks
+    (1, 12, 12, 256, 512, 3, 1, "conv3x3_w4_kernel"),
+    (1, 12, 12, 64, 128, 3, 6, "conv_igemm_kernel<128,32,2,1,16>"),    # fc6-style dilation: 16-row tile, 32-channel chunks (halo size)
+    (2, 12, 20, 256, 512, 3, 6, "conv_igemm_kernel<256,32,4,1,8>"),    # ... on 256 x 256 weight-gradient tiles: nine pointwise GEMMs by LDS-DMA, ragged rows
+    (3, 9, 37, 512, 256, 1, 1, "conv_igemm_kernel<256,64,4,0,8>"),     # 999 pixels (not the GEMM kernel); 256 x 256 weight-gradient tiles, several images per split
+    (2, 8, 8, 128, 128, 1, 1, "conv_pw_kernel<128,2>"),                # pointwise GEMM kernel, half a flat tile
+    (1, 10, 34, 256, 64, 1, 1, "conv_igemm_kernel<64,64,2,0,8>"),      # 1x1 on the tile kernel: 32x32x16 MFMA path
+    (1, 8, 8, 512, 1024, 1, 1, "conv_pw_kernel<256,4>"),
+    (3, 7, 5, 32, 32, 3, 1, "conv_igemm_kernel<32,32,1,1,8>"),         # 32-channel partial blocks
+    (1, 17, 19, 96, 160, 3, 1, "conv_igemm_kernel<32,32,1,1,8>"),      # cin/cout not multiples of 64: 32-wide tiles
+    (2, 8, 32, 32, 64, 3, 1, "conv_igemm_kernel<64,32,2,1,8>"),        # 64-cout tile with 32-channel chunks
+    (1, 9, 20, 96, 64, 3, 1, "conv_igemm_kernel<64,32,2,1,8>"),
+    (1, 8, 16, 96, 128, 1, 1, "conv_igemm_kernel<128,32,2,0,8>"),
+    (2, 24, 40, 256, 256, 1, 1, "conv_pw_kernel<256,4>"),              # pointwise GEMM kernel: 7.5 flat tiles, 256-cout tile
+    (1, 16, 32, 64, 64, 1, 1, "conv_pw_kernel<64,1>"),                 # ... 64-cout tile, one K stage
+    (1, 32, 32, 1024, 128, 1, 1, "conv_pw_kernel<128,2>"),             # ... 128-cout tile, 16 K stages
+    (2, 100, 130, 64, 64, 3, 1, "conv_c64_persist_kernel<64>"),        # persistent weight-stationary 64-channel kernel: 130 ragged pixel tiles
+    (1, 128, 256, 64, 128, 3, 1, "conv3x3_w4s_kernel<128>"),           # small-tile 4-wave kernel, one chunk pair
+    (9, 64, 64, 64, 64, 3, 1, "conv_c64_persist_kernel<64>"),          # persistent kernel: more images than tiles per image
+    (3, 203, 230, 64, 64, 3, 1, "conv_c64_persist_kernel<64>"),        # ... 624 ragged tiles, 2 or 3 per workgroup
+    (2, 16, 40, 128, 64, 3, 1, "conv3x3_w4s_kernel<64>"),              # two chunk pairs
+    (2, 40, 64, 256, 128, 3, 1, "conv3x3_w4s_kernel<128>"),            # four chunk pairs
+    (1, 24, 40, 192, 64, 3, 1, "conv3x3_w4s_kernel<64>"),              # three chunk pairs (odd)
+    (2, 33, 70, 128, 256, 3, 1, "conv3x3_w4_kernel"),                  # 4-wave 3x3 kernel: ragged rows and columns, 2 chunks
+    (1, 16, 64, 512, 512, 3, 1, "conv3x3_w4_kernel"),                  # ... 8 chunks x 18 steps, two cout tiles
+    (3, 8, 32, 64, 256, 3, 1, "conv3x3_w4_kernel"),                    # ... one chunk (prologue + tail only), several images
+    (1, 24, 33, 96, 128, 3, 1, "conv_igemm_kernel<128,32,2,1,16>"),    # 16-row generic tile at dilation 1 (cin % 64 != 0), ragged width
 ]
+VARIANT = {s[:7]: s[7] for s in SHAPES}
+# the library's family selectors (read once per process; tests/test_gpu_switches.py runs this sweep with one of them off,
+# so that the general kernels take the family's rows): the named kernel is asserted under the default selection, and a
+# family that is switched off must not be the one that runs
+SELECTORS = {"OCR_CONV_W4": "conv3x3_w4_kernel", "OCR_CONV_W4S": "conv3x3_w4s_kernel",
+             "OCR_CONV_PERSIST": "conv_c64_persist_kernel", "OCR_CONV_PW": "conv_pw_kernel"}
+FAMILIES_OFF = [name for env, name in SELECTORS.items() if os.environ.get(env) is not None and int(os.environ[env]) == 0]
 
 
 def _h(x):
@@ -58,7 +67,7 @@ def _h(x):
     return torch.from_numpy(np.asarray(x, np.float32)).to(O.STORAGE).float().numpy()
 
 
-@pytest.mark.parametrize("n,h,w,cin,cout,k,dil", SHAPES)
+@pytest.mark.parametrize("n,h,w,cin,cout,k,dil", [s[:7] for s in SHAPES])
 def test_conv_fwd_dgrad_wgrad(device, n, h, w, cin, cout, k, dil):
     from tensorflow_ocr_amd import ops
     from tensorflow_ocr_amd.ops import Workspace
@@ -80,6 +89,10 @@ def test_conv_fwd_dgrad_wgrad(device, n, h, w, cin, cout, k, dil):
     ops.pack_weights(wm, w_kc, w_ck)
     d = ops.conv_desc((n, h, w, cin), cout, k, k, 1, dil)
     d.flags = 0
+    if not FAMILIES_OFF:
+        assert ops.conv2d_variant(d) == VARIANT[(n, h, w, cin, cout, k, dil)]
+    else:
+        assert not ops.conv2d_variant(d).startswith(tuple(FAMILIES_OFF))
     y = torch.empty((n, h, w, cout), dtype=O.STORAGE, device=device)
     ops.conv2d(d, xd, w_kc, y)
     pt = dil * (k - 1) - d.pad_top

@@ -144,7 +144,7 @@ def test_resnet_east_step_with_one_switch_flipped(device, monkeypatch, flag):
 @pytest.mark.parametrize("env", ["OCR_CONV_W4=0", "OCR_CONV_W4S=0", "OCR_CONV_PERSIST=0", "OCR_CONV_PW=0", "OCR_WGRAD3=0"])
 def test_kernel_family_selectors_in_a_child_interpreter(device, env):
     """The library's family selectors (read once per process): the convolution ABI sweep of tests/test_gpu_conv_abi.py —
-    forward, input gradient, weight gradient of 29 shapes against the oracle — with one special family switched off, so the
+    forward, input gradient, weight gradient of every shape of its list against the oracle — with one special family switched off, so the
     general kernels take its shapes."""
     k, v = env.split("=")
     e = dict(os.environ)
