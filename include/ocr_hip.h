@@ -26,7 +26,9 @@ extern "C" {
  * ocr_conv2d_bnred_f16, ocr_conv2d_bnred_tail_f16, ocr_bn_add_relu_f16, ocr_bn_relu_pool_idx_f16; round 4: the
  * batched head entry points and the seed-rank argument of ocr_link_cc_directed; round 5: the guest kernels).  The Python host refuses a
  * library whose ocr_abi_version() differs from the value it was written against (_lib.ABI_VERSION).
- * New entry points do not bump it: ocr_conv2d_f32_split / ocr_conv2d_f32_split_workspace (the f16x2 precision) joined at 7. */
+ * New entry points do not bump it: ocr_conv2d_f32_split / ocr_conv2d_f32_split_workspace (the f16x2 precision) joined at 7,
+ * and so did ocr_conv2d_f32_mfma_ep / ocr_conv2d_f32_split_ep / ocr_subsample_f32 (the folded inference batch norm) with
+ * their flags OCR_CONV_AFFINE, OCR_CONV_RESIDUAL, OCR_CONV_ACCUM_IN: every older entry point ignores those bits. */
 #define OCR_ABI_VERSION 7
 
 enum {
@@ -68,7 +70,11 @@ enum {
   OCR_CONV_BIAS = 1,       /* y += bias[cout]                                  */
   OCR_CONV_RELU = 2,       /* y = max(y,0)                                     */
   OCR_CONV_STATS = 4,      /* also emit per-tile column sum / sum-of-squares   */
-  OCR_CONV_ACCUM_F16 = 8   /* y += previous y (dgrad into an existing grad)    */
+  OCR_CONV_ACCUM_F16 = 8,  /* y += previous y (dgrad into an existing grad)    */
+  /* ocr_conv2d_f32_mfma_ep / ocr_conv2d_f32_split_ep only (see there): */
+  OCR_CONV_AFFINE = 16,    /* y = y*scale[cout] + shift[cout] (frozen batch norm) */
+  OCR_CONV_RESIDUAL = 32,  /* y += residual[n,oh,ow,cout]                       */
+  OCR_CONV_ACCUM_IN = 64   /* conv += previous y BEFORE the steps above         */
 };
 
 /* Implicit-GEMM convolution, f16 in / f32 accumulate / f16 out, on MFMA.
@@ -587,6 +593,26 @@ int ocr_softmax_loss_bwd(const ocr_softmax_loss_desc* d, const void* pixel_logit
 /* flags: OCR_CONV_BIAS, OCR_CONV_RELU, OCR_CONV_ACCUM_F16 (here: y += conv, f32); any kernel size, stride, dilation */
 int ocr_conv2d_f32_mfma(const ocr_conv_desc* d, const void* x, const void* w_hwio, const void* bias, void* y,
                         void* stream);
+/* The same convolution with the whole f32 epilogue, so that a convolution, its inference-mode batch norm (moving statistics:
+ * a per-channel affine map known before the convolution starts), the bottleneck's residual add (nets/resnet_v1.py:104-111)
+ * and the ReLU are ONE kernel (Graph(fold_bn=True), layers_f32.py).  On the f32 accumulator, in this order:
+ *   1. OCR_CONV_ACCUM_IN    v += y_old               (y read and written in place by the same lane)
+ *   2. OCR_CONV_AFFINE      v = v*scale[co] + shift[co]     (the expression of ocr_bn_relu_f32)
+ *   3. OCR_CONV_BIAS        v += bias[co]
+ *   4. OCR_CONV_RESIDUAL    v += residual[pixel][co]        (residual must not overlap y)
+ *   5. OCR_CONV_RELU        v < 0 -> 0                      (a NaN stays NaN)
+ *   6. OCR_CONV_ACCUM_F16   v += y_old                      (after the ReLU: the meaning it has above)
+ * All operands f32: bias, scale, shift [cout]; residual [n,oh,ow,cout].  OCR_ERR_INVALID_ARG when a flag is set and its
+ * pointer is NULL, or when OCR_CONV_ACCUM_IN and OCR_CONV_ACCUM_F16 are both set.  Store contract as above: every element of
+ * y is stored, nothing outside it is written; a cout that is no multiple of 4 (or of the cout tile) and an unaligned y take
+ * scalar stores with the same arithmetic.  ocr_conv2d_f32_mfma / ocr_conv2d_f32_split are thin callers of the same kernels
+ * with steps 3, 5, 6 only (tests/test_gpu_fold_bn.py). */
+typedef struct { const void *bias, *scale, *shift, *residual; } ocr_conv_f32_epilogue;  /* f32; [cout] x3, [n,oh,ow,cout] */
+int ocr_conv2d_f32_mfma_ep(const ocr_conv_desc* d, const void* x, const void* w_hwio, const ocr_conv_f32_epilogue* epilogue,
+                           void* y, void* stream);
+/* y [n,ceil(h/stride),ceil(w/stride),c] = x[:, ::stride, ::stride, :]  (resnet_utils.subsample, nets/resnet_utils.py:59-72:
+ * the strided identity shortcut that the folded bottleneck tail reads as its residual) */
+int ocr_subsample_f32(const void* x, int n, int h, int w, int c, int stride, void* y, void* stream);
 int ocr_channel_stats_f32_num_partials(int64_t npix, int c);
 /* partial [T][2][c] f32 = per-strip (sum, sum of squares): input of ocr_bn_finalize */
 int ocr_channel_stats_f32(const void* x, int64_t npix, int c, void* partial, void* stream);
@@ -610,6 +636,9 @@ int ocr_unpool_f32(const void* x, int n, int lh, int lw, int c, void* y, void* s
 size_t ocr_conv2d_f32_split_workspace(const ocr_conv_desc* d);
 int ocr_conv2d_f32_split(const ocr_conv_desc* d, const void* x, const void* w_hwio, const void* bias, void* y,
                          void* workspace, size_t workspace_bytes, void* stream);
+/* ... with the epilogue of ocr_conv2d_f32_mfma_ep, applied to main + corr * 2^-11 */
+int ocr_conv2d_f32_split_ep(const ocr_conv_desc* d, const void* x, const void* w_hwio, const ocr_conv_f32_epilogue* epilogue,
+                            void* y, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Fuse heads, BATCHED (round 4): one launch per kernel kind over the (up to four) feature maps the heads read

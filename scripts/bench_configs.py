@@ -243,7 +243,8 @@ def main():
     ap.add_argument("--pixellink-loss", default="focal", choices=("focal", "plain"))
     ap.add_argument("--resnet-batch", type=int, default=64)
     ap.add_argument("--resnet-size", type=int, default=640)
-    ap.add_argument("--json-out", default=None, help="f16x2_forward: also write the result (with the source fingerprint) here")
+    ap.add_argument("--json-out", default=None, help="f16x2_forward / fold_bn_forward: also write the result (with the source "
+                    "fingerprint) here")
     args = ap.parse_args()
     which = args.which.split(",")
     from tensorflow_ocr_amd.train import AdamOptimizer, MomentumOptimizer
@@ -362,6 +363,10 @@ def main():
         f32_forward_config(args.steps, args.warmup)
     if "f16x2_forward" in which:
         f16x2_forward_config(args.steps, args.warmup, args.json_out)
+    if "fold_bn_forward" in which:
+        fold_bn_forward_config(args.steps, args.warmup, args.json_out)
+    if "fold_bn_trace" in which:
+        fold_bn_trace_body(args.steps)
 
 
 def east_fwd_config():
@@ -542,6 +547,98 @@ def f16x2_forward_config(steps, warmup, json_out=None):
         with open(json_out, "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
+
+
+def _fold_bn_forward(dev, prec, fold, x):
+    """test.py's network (model.model, is_training=False) as a GraphedForward, captured; -> callable."""
+    from tensorflow_ocr_amd.graph import Graph
+    from tensorflow_ocr_amd.infer import GraphedForward
+    from tensorflow_ocr_amd.nets import model
+    g = Graph(dev, seed=1, precision=prec, fold_bn=fold)
+
+    def network(gr, im):
+        px, lk = model.model(im, is_training=False, graph=gr)
+        return px.data, lk.data
+    fwd = GraphedForward(g, network, capture_after=0)
+    fwd(x)
+    torch.cuda.synchronize()
+    return lambda: fwd(x)
+
+
+def fold_bn_forward_config(steps, warmup, json_out=None, repeats=5):
+    """Graph(fold_bn=True) against Graph(fold_bn=False): test.py's graph (model.model, ResNet-v1-50 + heads, is_training=False)
+    at 512^2, batch 1 (test.py's case) and batch 8, precisions f32 and f16x2, each forward a captured HIP graph
+    (GraphedForward), the two ALTERNATING in one process; device time from HIP events.  Every repeat is recorded so that the
+    spread can be read next to the difference.  Then, in a process of its own, a rocprofv3 --kernel-trace --stats summary of
+    the folded f16x2 forward at batch 1."""
+    import csv
+    import glob
+    import os
+    import statistics
+    import subprocess
+    import sys
+    import tempfile
+    from tensorflow_ocr_amd import _lib
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(5)
+    cells = {}
+    for batch in (1, 8):
+        x = torch.from_numpy(rng.uniform(0, 255, (batch, 512, 512, 3)).astype(np.float32)).to(dev)
+        for prec in ("f16x2", "f32"):
+            fwds = {name: _fold_bn_forward(dev, prec, fold, x) for name, fold in (("unfolded", False), ("folded", True))}
+            runs = {"unfolded": [], "folded": []}
+            for _ in range(repeats):
+                for name in ("unfolded", "folded"):
+                    runs[name].append(round(dev_ms(fwds[name], warmup, steps), 4))
+            med = {k: statistics.median(v) for k, v in runs.items()}
+            cells["%s_b%d" % (prec, batch)] = {
+                "precision": prec, "batch": batch, "size": 512, "unfolded_ms": runs["unfolded"], "folded_ms": runs["folded"],
+                "unfolded_median_ms": round(med["unfolded"], 4), "folded_median_ms": round(med["folded"], 4),
+                "spread_ms": round(max(max(v) - min(v) for v in runs.values()), 4),
+                "unfolded_over_folded": round(med["unfolded"] / med["folded"], 3)}
+            print(json.dumps({"cell": "%s_b%d" % (prec, batch), **cells["%s_b%d" % (prec, batch)]}), flush=True)
+            del fwds
+            torch.cuda.empty_cache()
+        del x
+    res = {"config": "model.model (test.py's graph) 512^2, is_training=False, GraphedForward: fold_bn=True vs fold_bn=False, "
+                     "same process, alternating repeats", "steps": steps, "warmup": warmup, "repeats": repeats,
+           "ms_per_step": cells["f16x2_b1"]["folded_median_ms"], "components": cells,
+           "csrc_fingerprint": _lib.csrc_fingerprint()}
+    # kernel summary of the folded f16x2 forward, batch 1: a fresh process under the profiler, nothing else traced
+    torch.cuda.synchronize()
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable,
+               os.path.abspath(__file__), "--which", "fold_bn_trace", "--steps", str(max(steps, 10))]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+        rows = []
+        for f in glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True):
+            with open(f) as fh:
+                rows += list(csv.DictReader(fh))
+        if r.returncode != 0 or not rows:
+            res["kernel_stats_f16x2_folded_b1"] = {"error": "rocprofv3 run failed (%d): %s" % (r.returncode, r.stderr[-400:])}
+        else:
+            rows.sort(key=lambda q: -float(q["TotalDurationNs"]))
+            total = sum(float(q["TotalDurationNs"]) for q in rows)
+            res["kernel_stats_f16x2_folded_b1"] = {
+                "command": "rocprofv3 --kernel-trace --stats -- bench_configs.py --which fold_bn_trace (captured forward, "
+                           "warm-up and capture included)", "total_kernel_ms": round(total / 1e6, 3),
+                "top": [{"name": q["Name"][:90], "calls": int(q["Calls"]), "total_ms": round(float(q["TotalDurationNs"]) / 1e6, 3),
+                         "share": round(float(q["TotalDurationNs"]) / total, 4)} for q in rows[:12]]}
+    print(json.dumps({"kernel_stats_f16x2_folded_b1": res["kernel_stats_f16x2_folded_b1"]}), flush=True)
+    if json_out:
+        with open(json_out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+def fold_bn_trace_body(steps):
+    """What fold_bn_forward_config runs under rocprofv3: the folded f16x2 forward of test.py's graph, 512^2 batch 1."""
+    dev = torch.device("cuda", 0)
+    x = torch.from_numpy(np.random.default_rng(5).uniform(0, 255, (1, 512, 512, 3)).astype(np.float32)).to(dev)
+    fwd = _fold_bn_forward(dev, "f16x2", True, x)
+    for _ in range(steps):
+        fwd()
+    torch.cuda.synchronize()
 
 
 def dev_ms(fn, warmup=2, steps=10):

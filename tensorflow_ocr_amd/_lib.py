@@ -29,6 +29,8 @@ class ConvDesc(ctypes.Structure):
 
 
 CONV_BIAS, CONV_RELU, CONV_STATS, CONV_ACCUM_F16 = 1, 2, 4, 8
+# ocr_conv2d_f32_mfma_ep / ocr_conv2d_f32_split_ep only
+CONV_AFFINE, CONV_RESIDUAL, CONV_ACCUM_IN = 16, 32, 64
 
 
 class SoftmaxLossDesc(ctypes.Structure):

@@ -14,7 +14,7 @@
 // The operands are IEEE half in BOTH product libraries: f32 in, f32 out, so nothing here follows the 16-bit storage macro
 // of common.h (a bfloat16 split would need three planes).  Forward only.  Reference call sites as for ocr_conv2d_f32_mfma:
 // slim.conv2d (nets/vgg.py:14-39, nets/resnet_v1.py:97-105, nets/model_vgg_16.py:144).
-#include "common.h"
+#include "f32_conv_ep.h"
 
 namespace {
 
@@ -78,10 +78,11 @@ __global__ void pack_split_kernel(SplitP p, int TC, const float* __restrict__ w,
 // contiguous bytes (ds_write_b128 banks in 8-lane groups), and a wave's global load covers 16 pixels x 128 contiguous bytes.
 // Pipeline: only the GLOBAL LOADS of the next chunk overlap the MFMAs of the current one; the split arithmetic and the LDS
 // writes of every chunk run between the two barriers, serialised with the MFMAs (one LDS buffer, one wave per SIMD).
+// Epilogue: main + corr * 2^-11, then the steps of f32_conv_ep.h (inference batch norm, bias, residual, ReLU, accumulate).
 template <int WN>
 __global__ __launch_bounds__(256) void conv_f32_split_kernel(SplitP p, const float* __restrict__ x,
                                                              const h16x8* __restrict__ wp, size_t plane_elems,
-                                                             const float* __restrict__ bias, float* __restrict__ y) {
+                                                             F32Ep ep, float* __restrict__ y) {
   constexpr int WM = 4 / WN, TP = 64 * WM, TC = 64 * WN;
   constexpr int XI = TP * 4 / 256, WI = TC * 4 / 256;
   __shared__ h16x8 xs[2][4][TP];
@@ -107,6 +108,7 @@ __global__ __launch_bounds__(256) void conv_f32_split_kernel(SplitP p, const flo
   }
   const bool vec_c = (p.cin & 7) == 0 && ((uintptr_t)x & 15) == 0;
   const bool vec_o = (p.cout & 3) == 0 && ((uintptr_t)y & 15) == 0;
+  const bool vec_r = (p.cout & 3) == 0 && ((uintptr_t)ep.residual & 15) == 0;
   f32x4 accm[4][4], accc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
@@ -191,26 +193,14 @@ __global__ __launch_bounds__(256) void conv_f32_split_kernel(SplitP p, const flo
     const int q = p0 + wm * 64 + pb * 16 + r;
     if (q >= p.P) continue;
     float* yp = y + (size_t)q * p.cout;
+    const float* rp = ep.residual ? ep.residual + (size_t)q * p.cout : nullptr;
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) {
       const int co = co0 + wn * 64 + cb * 16 + 4 * g;
       float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[e] = accm[pb][cb][e] + accc[pb][cb][e] * kLoInv;
-        if (co + e < p.cout) {
-          if (p.flags & OCR_CONV_BIAS) v[e] += bias[co + e];
-          if ((p.flags & OCR_CONV_RELU) && v[e] < 0.f) v[e] = 0.f;
-          if (p.flags & OCR_CONV_ACCUM_F16) v[e] += yp[co + e];        // accumulate into y (concat-free 1x1 convs)
-        }
-      }
-      if (vec_o && co + 3 < p.cout) {
-        *reinterpret_cast<f32x4*>(yp + co) = f32x4{v[0], v[1], v[2], v[3]};
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (co + e < p.cout) yp[co + e] = v[e];
-      }
+      for (int e = 0; e < 4; ++e) v[e] = accm[pb][cb][e] + accc[pb][cb][e] * kLoInv;
+      f32_ep_store4(v, p.flags, ep, co, p.cout, vec_o, vec_r, yp, rp);
     }
   }
 }
@@ -226,6 +216,30 @@ size_t split_plane_elems(const ocr_conv_desc* d) {
   return (size_t)d->kh * d->kw * ocr_cdiv(d->cout, tc) * ocr_cdiv(d->cin, 32) * 4 * tc * 8;
 }
 
+int launch_split(const ocr_conv_desc* d, int flags, const void* x, const void* w_hwio, const F32Ep& ep, void* y,
+                 void* workspace, size_t workspace_bytes, void* stream) {
+  OCR_CHECK_ARG(split_desc_ok(d) && x && w_hwio && y && workspace);
+  OCR_CHECK_ARG(((uintptr_t)workspace & 15) == 0 && workspace_bytes >= ocr_conv2d_f32_split_workspace(d));
+  OCR_CHECK_SHAPE((size_t)d->n * d->oh * d->ow < (1ull << 31));
+  const int tc = split_tc(d->cout);
+  SplitP p{d->n, d->h, d->w, d->cin, d->oh, d->ow, d->cout, d->kh, d->kw, d->stride, d->dilation, d->pad_top, d->pad_left,
+           flags, d->n * d->oh * d->ow, ocr_cdiv(d->cin, 32), ocr_cdiv(d->cout, tc)};
+  const size_t plane = split_plane_elems(d), vecs = plane / 8;
+  h16x8* hi = static_cast<h16x8*>(workspace);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  size_t pb = (vecs + 255) / 256;
+  if (pb > 65536) pb = 65536;
+  hipLaunchKernelGGL(pack_split_kernel, dim3((unsigned)pb), dim3(256), 0, st, p, tc, static_cast<const float*>(w_hwio), hi,
+                     hi + vecs, vecs);
+  if (tc == 64)
+    hipLaunchKernelGGL(conv_f32_split_kernel<1>, dim3(ocr_cdiv(p.P, 256), p.nct), dim3(256), 0, st, p,
+                       static_cast<const float*>(x), hi, vecs, ep, static_cast<float*>(y));
+  else
+    hipLaunchKernelGGL(conv_f32_split_kernel<2>, dim3(ocr_cdiv(p.P, 128), p.nct), dim3(256), 0, st, p,
+                       static_cast<const float*>(x), hi, vecs, ep, static_cast<float*>(y));
+  return ocr_launch_status();
+}
+
 }  // namespace
 
 // bytes of the packed-weight workspace ocr_conv2d_f32_split needs for `d` (0: invalid descriptor)
@@ -237,27 +251,22 @@ extern "C" size_t ocr_conv2d_f32_split_workspace(const ocr_conv_desc* d) {
 // The contract of ocr_conv2d_f32_mfma (flags OCR_CONV_BIAS, OCR_CONV_RELU, OCR_CONV_ACCUM_F16; x f32 NHWC, w f32 HWIO, y f32
 // NHWC) plus the workspace: the weights are split and packed into it on `stream` by every call (a load_state_dict between
 // two calls can never meet stale planes), then the convolution reads them.  workspace: 16-byte aligned device memory.
+// A thin caller of the kernels of ocr_conv2d_f32_split_ep: the three flags it always took, nothing else.
 extern "C" int ocr_conv2d_f32_split(const ocr_conv_desc* d, const void* x, const void* w_hwio, const void* bias, void* y,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-  OCR_CHECK_ARG(split_desc_ok(d) && x && w_hwio && y && workspace);
+  OCR_CHECK_ARG(d);
   OCR_CHECK_ARG(!(d->flags & OCR_CONV_BIAS) || bias);
-  OCR_CHECK_ARG(((uintptr_t)workspace & 15) == 0 && workspace_bytes >= ocr_conv2d_f32_split_workspace(d));
-  OCR_CHECK_SHAPE((size_t)d->n * d->oh * d->ow < (1ull << 31));
-  const int tc = split_tc(d->cout);
-  SplitP p{d->n, d->h, d->w, d->cin, d->oh, d->ow, d->cout, d->kh, d->kw, d->stride, d->dilation, d->pad_top, d->pad_left,
-           d->flags, d->n * d->oh * d->ow, ocr_cdiv(d->cin, 32), ocr_cdiv(d->cout, tc)};
-  const size_t plane = split_plane_elems(d), vecs = plane / 8;
-  h16x8* hi = static_cast<h16x8*>(workspace);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  size_t pb = (vecs + 255) / 256;
-  if (pb > 65536) pb = 65536;
-  hipLaunchKernelGGL(pack_split_kernel, dim3((unsigned)pb), dim3(256), 0, st, p, tc, static_cast<const float*>(w_hwio), hi,
-                     hi + vecs, vecs);
-  if (tc == 64)
-    hipLaunchKernelGGL(conv_f32_split_kernel<1>, dim3(ocr_cdiv(p.P, 256), p.nct), dim3(256), 0, st, p,
-                       static_cast<const float*>(x), hi, vecs, static_cast<const float*>(bias), static_cast<float*>(y));
-  else
-    hipLaunchKernelGGL(conv_f32_split_kernel<2>, dim3(ocr_cdiv(p.P, 128), p.nct), dim3(256), 0, st, p,
-                       static_cast<const float*>(x), hi, vecs, static_cast<const float*>(bias), static_cast<float*>(y));
-  return ocr_launch_status();
+  return launch_split(d, d->flags & kF32PlainFlags, x, w_hwio, F32Ep{static_cast<const float*>(bias), nullptr, nullptr, nullptr},
+                      y, workspace, workspace_bytes, stream);
+}
+
+// ... with the whole epilogue of f32_conv_ep.h (OCR_CONV_AFFINE, OCR_CONV_RESIDUAL, OCR_CONV_ACCUM_IN as well): a frozen
+// batch norm, the bottleneck's residual add and the ReLU inside the convolution (Graph(fold_bn=True)).
+extern "C" int ocr_conv2d_f32_split_ep(const ocr_conv_desc* d, const void* x, const void* w_hwio,
+                                       const ocr_conv_f32_epilogue* epilogue, void* y, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  OCR_CHECK_ARG(d);
+  F32Ep ep;
+  OCR_CHECK_ARG(f32_ep_args(d->flags, epilogue, &ep));
+  return launch_split(d, d->flags & kF32EpFlags, x, w_hwio, ep, y, workspace, workspace_bytes, stream);
 }

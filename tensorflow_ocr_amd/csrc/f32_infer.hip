@@ -6,7 +6,7 @@
 // (DESIGN.md section 4).  Forward only.  Reference call sites as for the 16-bit kernels: slim.conv2d (nets/vgg.py:14-39,
 // nets/resnet_v1.py:97-105), slim.batch_norm (nets/model_vgg_16.py:144), slim.max_pool2d (nets/vgg.py:16-32),
 // mean_image_subtraction (nets/model_vgg_16.py:19-32), tf.image.resize_bilinear (nets/model.py:14-15).
-#include "common.h"
+#include "f32_conv_ep.h"
 
 namespace {
 
@@ -22,10 +22,11 @@ typedef float f32x16v __attribute__((ext_vector_type(16)));
 // Per (tap, 16-channel chunk): the 128 x 16 activation slice (zero where the tap falls outside the image) and the 16 x 64
 // HWIO weight slice are staged in LDS; a k-step of the MFMA takes 2 channels: lane l holds A[cout = l % 32][k = l / 32] and
 // B[k = l / 32][pixel = l % 32].  Activation rows are 17 floats apart (32 lanes x stride 17: conflict-free), weight rows 64.
+// Epilogue: the steps of f32_conv_ep.h (inference batch norm, bias, residual, ReLU, accumulate) on the accumulator.
 constexpr int kFM = 128, kFN = 64, kFK = 16, kFXS = kFK + 1;
 
 __global__ __launch_bounds__(256) void conv_f32_mfma_kernel(F32P p, const float* __restrict__ x, const float* __restrict__ w,
-                                                            const float* __restrict__ bias, float* __restrict__ y) {
+                                                            F32Ep ep, float* __restrict__ y) {
   __shared__ float xs[kFM * kFXS];
   __shared__ __attribute__((aligned(16))) float ws[kFK * kFN];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -47,7 +48,9 @@ __global__ __launch_bounds__(256) void conv_f32_mfma_kernel(F32P p, const float*
   }
   const int wk = tid >> 4, wc4 = (tid & 15) * 4;           // this thread's weight piece: row k, couts wc4..wc4+3
   const bool vec_c = (p.cin & 3) == 0 && ((uintptr_t)x & 15) == 0;
-  const bool vec_o = (p.cout & 3) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)y & 15) == 0;
+  const bool vec_w = (p.cout & 3) == 0 && ((uintptr_t)w & 15) == 0;
+  const bool vec_o = (p.cout & 3) == 0 && ((uintptr_t)y & 15) == 0;
+  const bool vec_r = (p.cout & 3) == 0 && ((uintptr_t)ep.residual & 15) == 0;
   f32x16v acc[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j)
@@ -74,7 +77,7 @@ __global__ __launch_bounds__(256) void conv_f32_mfma_kernel(F32P p, const float*
       {
         const int ci = c0 + wk, co = co0 + wc4;
         const float* wp = w + ((size_t)tap * p.cin + (ci < p.cin ? ci : 0)) * p.cout + co;
-        if (ci < p.cin && vec_o && co + 3 < p.cout) {
+        if (ci < p.cin && vec_w && co + 3 < p.cout) {
           const f32x4 v = *reinterpret_cast<const f32x4*>(wp);
           wv[0] = v[0]; wv[1] = v[1]; wv[2] = v[2]; wv[3] = v[3];
         } else {
@@ -104,6 +107,7 @@ __global__ __launch_bounds__(256) void conv_f32_mfma_kernel(F32P p, const float*
   const int q = p0 + wave * 32 + l32;
   if (q >= p.P) return;
   float* yp = y + (size_t)q * p.cout;
+  const float* rp = ep.residual ? ep.residual + (size_t)q * p.cout : nullptr;
 #pragma unroll
   for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -111,21 +115,8 @@ __global__ __launch_bounds__(256) void conv_f32_mfma_kernel(F32P p, const float*
       const int co = co0 + 32 * j + 8 * g4 + 4 * hh;
       float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[e] = acc[j][g4 * 4 + e];
-        if (co + e < p.cout) {
-          if (p.flags & OCR_CONV_BIAS) v[e] += bias[co + e];
-          if ((p.flags & OCR_CONV_RELU) && v[e] < 0.f) v[e] = 0.f;
-          if (p.flags & OCR_CONV_ACCUM_F16) v[e] += yp[co + e];        // accumulate into y (concat-free 1x1 convs)
-        }
-      }
-      if (vec_o && co + 3 < p.cout) {
-        *reinterpret_cast<f32x4*>(yp + co) = f32x4{v[0], v[1], v[2], v[3]};
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (co + e < p.cout) yp[co + e] = v[e];
-      }
+      for (int e = 0; e < 4; ++e) v[e] = acc[j][g4 * 4 + e];
+      f32_ep_store4(v, p.flags, ep, co, p.cout, vec_o, vec_r, yp, rp);
     }
 }
 
@@ -207,6 +198,28 @@ __global__ void maxpool_f32_kernel(const float* __restrict__ x, int n, int h, in
   }
 }
 
+// y[img][oy][ox][:] = x[img][oy * stride][ox * stride][:]   (resnet_utils.subsample, nets/resnet_utils.py:59-72): a plain
+// strided row copy, CV = 4 (16-byte pieces) when c % 4 == 0 and both tensors are 16-byte aligned, else 1
+template <int CV>
+__global__ void subsample_f32_kernel(const float* __restrict__ x, int h, int w, int c, int stride, int oh, int ow,
+                                     size_t total, float* __restrict__ y) {
+  const int cv = c / CV;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int ch = (int)(i % cv) * CV;
+    size_t u = i / cv;
+    const int ox = (int)(u % ow);
+    u /= ow;
+    const int oy = (int)(u % oh);
+    const size_t img = u / oh;
+    const float* xp = x + ((img * h + (size_t)oy * stride) * w + (size_t)ox * stride) * c + ch;
+    float* yp = y + ((img * oh + oy) * ow + ox) * c + ch;
+    if (CV == 4)
+      *reinterpret_cast<f32x4*>(yp) = *reinterpret_cast<const f32x4*>(xp);
+    else
+      *yp = *xp;
+  }
+}
+
 __global__ void prep_images_f32_kernel(const float* __restrict__ im, size_t npix, float m0, float m1, float m2,
                                        float* __restrict__ out) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) {
@@ -260,21 +273,41 @@ unsigned vgrid(size_t work) {
 
 }  // namespace
 
-// flags: OCR_CONV_BIAS, OCR_CONV_RELU, OCR_CONV_ACCUM_F16 (here: y += conv, f32).  x f32 NHWC, w f32 HWIO (the TF master
-// layout, no packing), y f32 NHWC.
-extern "C" int ocr_conv2d_f32_mfma(const ocr_conv_desc* d, const void* x, const void* w_hwio, const void* bias, void* y,
-                                   void* stream) {
+namespace {
+
+int launch_f32_mfma(const ocr_conv_desc* d, int flags, const void* x, const void* w_hwio, const F32Ep& ep, void* y,
+                    void* stream) {
   OCR_CHECK_ARG(d && x && w_hwio && y);
   OCR_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->oh > 0 && d->ow > 0 && d->cin > 0 && d->cout > 0);
   OCR_CHECK_ARG(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->dilation > 0);
-  OCR_CHECK_ARG(!(d->flags & OCR_CONV_BIAS) || bias);
   OCR_CHECK_SHAPE((size_t)d->n * d->oh * d->ow < (1ull << 31));
   F32P p{d->n, d->h, d->w, d->cin, d->oh, d->ow, d->cout, d->kh, d->kw, d->stride, d->dilation, d->pad_top, d->pad_left,
-         d->flags, d->n * d->oh * d->ow};
+         flags, d->n * d->oh * d->ow};
   hipLaunchKernelGGL(conv_f32_mfma_kernel, dim3(ocr_cdiv(p.P, kFM), ocr_cdiv(p.cout, kFN)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), p, static_cast<const float*>(x), static_cast<const float*>(w_hwio),
-                     static_cast<const float*>(bias), static_cast<float*>(y));
+                     ep, static_cast<float*>(y));
   return ocr_launch_status();
+}
+
+}  // namespace
+
+// flags: OCR_CONV_BIAS, OCR_CONV_RELU, OCR_CONV_ACCUM_F16 (here: y += conv, f32).  x f32 NHWC, w f32 HWIO (the TF master
+// layout, no packing), y f32 NHWC.  A thin caller of the kernel of ocr_conv2d_f32_mfma_ep: these three flags, nothing else.
+extern "C" int ocr_conv2d_f32_mfma(const ocr_conv_desc* d, const void* x, const void* w_hwio, const void* bias, void* y,
+                                   void* stream) {
+  OCR_CHECK_ARG(d);
+  OCR_CHECK_ARG(!(d->flags & OCR_CONV_BIAS) || bias);
+  return launch_f32_mfma(d, d->flags & kF32PlainFlags, x, w_hwio,
+                         F32Ep{static_cast<const float*>(bias), nullptr, nullptr, nullptr}, y, stream);
+}
+
+// ... with the whole epilogue of f32_conv_ep.h (OCR_CONV_AFFINE, OCR_CONV_RESIDUAL, OCR_CONV_ACCUM_IN as well)
+extern "C" int ocr_conv2d_f32_mfma_ep(const ocr_conv_desc* d, const void* x, const void* w_hwio,
+                                      const ocr_conv_f32_epilogue* epilogue, void* y, void* stream) {
+  OCR_CHECK_ARG(d);
+  F32Ep ep;
+  OCR_CHECK_ARG(f32_ep_args(d->flags, epilogue, &ep));
+  return launch_f32_mfma(d, d->flags & kF32EpFlags, x, w_hwio, ep, y, stream);
 }
 
 extern "C" int ocr_channel_stats_f32_num_partials(int64_t npix, int c) {
@@ -312,6 +345,20 @@ extern "C" int ocr_maxpool_f32(const void* x, int n, int h, int w, int c, int k,
   hipLaunchKernelGGL(maxpool_f32_kernel, dim3(vgrid((size_t)n * oh * ow * c)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const float*>(x), n, h, w, c, k, stride,
                      pad_top, pad_left, oh, ow, static_cast<float*>(y));
+  return ocr_launch_status();
+}
+
+extern "C" int ocr_subsample_f32(const void* x, int n, int h, int w, int c, int stride, void* y, void* stream) {
+  OCR_CHECK_ARG(x && y && n > 0 && h > 0 && w > 0 && c > 0 && stride > 0);
+  const int oh = ocr_cdiv(h, stride), ow = ocr_cdiv(w, stride);
+  const bool v4 = (c & 3) == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+  const size_t total = (size_t)n * oh * ow * (v4 ? c / 4 : c);
+  if (v4)
+    hipLaunchKernelGGL(subsample_f32_kernel<4>, dim3(vgrid(total)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const float*>(x), h, w, c, stride, oh, ow, total, static_cast<float*>(y));
+  else
+    hipLaunchKernelGGL(subsample_f32_kernel<1>, dim3(vgrid(total)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const float*>(x), h, w, c, stride, oh, ow, total, static_cast<float*>(y));
   return ocr_launch_status();
 }
 

@@ -210,7 +210,7 @@ class Graph:
     """One tower: variable store + tape + scratch.  `loss_scale` multiplies the loss gradient so
     that f16 activation gradients stay in range; the optimiser divides it out."""
 
-    def __init__(self, device="cuda:0", loss_scale=1024.0, seed=1, precision="f16"):
+    def __init__(self, device="cuda:0", loss_scale=1024.0, seed=1, precision="f16", fold_bn=False):
         """precision: "f16" = the product path (f16 storage, f32 accumulate, MFMA kernels);
         "f32" = forward-only f32 INFERENCE precision (f32 storage and arithmetic, the convolutions on the matrix
         cores with v_mfma_f32_32x32x2_f32: layers_f32.py, csrc/f32_infer.hip): whole-graph outputs within 1e-3 of the
@@ -221,9 +221,16 @@ class Graph:
         faster.  Operand range: |x|, |w| < 65504; larger values saturate (finite, wrong); NaN stays NaN.
         `precision` holds the STORAGE family the layer modules dispatch on ("f16" | "f32"; "f16x2" is stored as "f32"),
         `precision_name` the name given here, `f32_conv_route` the ops.conv2d_f32 route of the f32 family (None: the
-        process default ops.F32_CONV; "split")."""
+        process default ops.F32_CONV; "split").
+        fold_bn ("f32" / "f16x2" only): a layer whose batch norm runs in inference mode (moving statistics) launches ONE
+        convolution that applies the normalisation, the bottleneck's residual add and the ReLU in its epilogue, and
+        conv2d_same layers run at their real stride (layers_f32.py; ocr_conv2d_f32_mfma_ep / ocr_conv2d_f32_split_ep).
+        False: every graph launches what it always launched."""
         if precision not in ("f16", "f32", "f16x2"):
             raise ValueError("precision must be 'f16', 'f32' or 'f16x2'")
+        if fold_bn and precision not in ("f32", "f16x2"):
+            raise ValueError("fold_bn needs precision 'f32' or 'f16x2' (the f16 path carries its batch norm already)")
+        self.fold_bn = bool(fold_bn)
         self.precision_name = precision
         self.precision = "f32" if precision == "f16x2" else precision
         self.f32_conv_route = "split" if precision == "f16x2" else None

@@ -1132,21 +1132,82 @@ def conv2d_f32_split_workspace(d):
     return L.call_size("ocr_conv2d_f32_split_workspace", byref(d))
 
 
-def conv2d_f32(d, x, w_hwio, y, bias=None, route=None, workspace=None):
+class ConvF32Epilogue(ctypes.Structure):
+    """ocr_conv_f32_epilogue (include/ocr_hip.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("bias", "scale", "shift", "residual")]
+
+
+def conv2d_same_geometry(size, k, stride, rate=1):
+    """One spatial dim of resnet_utils.conv2d_same (nets/resnet_utils.py:74-123) -> (out, pad_before): explicit padding of
+    k_eff - 1 (the smaller half first), then a VALID convolution at `stride`: out = ceil(size / stride).  At stride 1 this
+    is TF 'SAME'; at stride s it is the [::s] subsample of the stride-1 SAME convolution, computed directly.  Pure host
+    arithmetic (tests/test_fold_bn_host.py)."""
+    k_eff = (k - 1) * rate + 1
+    return -(-size // stride), (k_eff - 1) // 2
+
+
+def conv2d_same_desc(x_shape, cout, k, stride=1, rate=1):
+    """The descriptor of conv2d_same at its real stride."""
+    _, h, w, _ = x_shape
+    oh, pt = conv2d_same_geometry(h, k, stride, rate)
+    ow, pl = conv2d_same_geometry(w, k, stride, rate)
+    return conv_desc(x_shape, cout, k, k, stride, rate, pad=(pt, pl), out_hw=(oh, ow))
+
+
+def conv2d_f32(d, x, w_hwio, y, bias=None, route=None, workspace=None, scale=None, shift=None, residual=None,
+               accum_in=False):
     """route: None -> F32_CONV (OCR_F32_CONV: "mfma" | "direct" | "split"); "mfma" = v_mfma_f32_32x32x2_f32 (f32_infer.hip);
     "direct" = the checker of libocr_verify.so; "split" = split-f16 operands on v_mfma_f32_16x16x32_f16 (f16x2_infer.hip),
     the convolution of Graph(precision="f16x2").  workspace (split route only): a callable returning the caller's
     stream-ordered `Workspace` for the packed weights (Graph.split_workspace: one arena per tower, like its other scratch);
-    without one the call takes a buffer of its own from the allocator."""
+    without one the call takes a buffer of its own from the allocator.
+    Epilogue (ocr_conv2d_f32_mfma_ep / ocr_conv2d_f32_split_ep; the flags are added to d.flags for the call, `d` itself is
+    left alone): accum_in -> OCR_CONV_ACCUM_IN (conv += y first), scale + shift [cout] -> OCR_CONV_AFFINE, residual
+    [n,oh,ow,cout] -> OCR_CONV_RESIDUAL; order: accum_in, affine, bias, residual, ReLU, OCR_CONV_ACCUM_F16.  The "direct"
+    route computes the same unfused — its convolution, then the element-wise f32 kernels — for the combinations the layers
+    use (affine [+ accum_in] [+ ReLU]; affine + residual + ReLU) and raises on any other."""
     route = route or F32_CONV
+    if (scale is None) != (shift is None):
+        raise ValueError("scale and shift come together")
+    flags = d.flags | (L.CONV_AFFINE if scale is not None else 0) | (L.CONV_RESIDUAL if residual is not None else 0) | \
+        (L.CONV_ACCUM_IN if accum_in else 0)
+    if route == "direct":
+        return _conv2d_f32_direct(d, flags, x, w_hwio, y, bias, scale, shift, residual)
+    de = L.ConvDesc.from_buffer_copy(d)
+    de.flags = flags
+    ep = ConvF32Epilogue(_dp(bias), _dp(scale), _dp(shift), _dp(residual))
     if route == "split":
-        nbytes = conv2d_f32_split_workspace(d)
+        nbytes = conv2d_f32_split_workspace(de)
         buf = workspace().get(nbytes) if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        L.call("ocr_conv2d_f32_split", byref(d), ptr(x), ptr(w_hwio), ptr(bias), ptr(y), ptr(buf), c_size_t(nbytes), _st())
-    elif route == "direct":
-        L.call_verify("ocr_conv2d_f32", byref(d), ptr(x), ptr(w_hwio), ptr(bias), ptr(y), _st())
+        L.call("ocr_conv2d_f32_split_ep", byref(de), ptr(x), ptr(w_hwio), byref(ep), ptr(y), ptr(buf), c_size_t(nbytes),
+               _st())
     else:
-        L.call("ocr_conv2d_f32_mfma", byref(d), ptr(x), ptr(w_hwio), ptr(bias), ptr(y), _st())
+        L.call("ocr_conv2d_f32_mfma_ep", byref(de), ptr(x), ptr(w_hwio), byref(ep), ptr(y), _st())
+
+
+def _conv2d_f32_direct(d, flags, x, w_hwio, y, bias, scale, shift, residual):
+    new = flags & (L.CONV_AFFINE | L.CONV_RESIDUAL | L.CONV_ACCUM_IN)
+    if not new:
+        L.call_verify("ocr_conv2d_f32", byref(d), ptr(x), ptr(w_hwio), ptr(bias), ptr(y), _st())
+        return
+    relu = bool(flags & L.CONV_RELU)
+    tail = new == (L.CONV_AFFINE | L.CONV_RESIDUAL) and relu
+    if not (new in (L.CONV_AFFINE, L.CONV_AFFINE | L.CONV_ACCUM_IN) or tail) or \
+            flags & (L.CONV_BIAS | L.CONV_ACCUM_F16):
+        raise NotImplementedError("conv2d_f32 route 'direct': no unfused form of flags %d" % flags)
+    dr = L.ConvDesc.from_buffer_copy(d)
+    dr.flags = L.CONV_ACCUM_F16 if flags & L.CONV_ACCUM_IN else 0
+    raw = y.clone() if flags & L.CONV_ACCUM_IN else torch.empty_like(y)
+    L.call_verify("ocr_conv2d_f32", byref(dr), ptr(x), ptr(w_hwio), ptr(None), ptr(raw), _st())
+    if tail:
+        bn_add_relu_f32(raw, scale, shift, residual, y)
+    else:
+        bn_relu_f32(raw, scale, shift, relu, 0, y, None)
+
+
+def subsample_f32(x, stride, y):
+    n, h, w, c = x.shape
+    L.call("ocr_subsample_f32", ptr(x), c_int(n), c_int(h), c_int(w), c_int(c), c_int(stride), ptr(y), _st())
 
 
 def channel_stats_f32_num_partials(npix, c):

@@ -411,6 +411,9 @@ def bottleneck(g, x, depth, depth_bottleneck, stride, scope, is_training=True):
         if not projection:
             if stride == 1:
                 return x
+            if g.precision == "f32" and g.fold_bn and not is_training:
+                from . import layers_f32
+                return layers_f32.subsample(g, x, stride)
             return max_pool2d(g, x, 1, stride, scope="shortcut")
         if stride != 1:
             raise NotImplementedError("strided projection shortcut")

@@ -30,7 +30,23 @@ def parse():
                     "precision (f32 storage, matrix-core f32 convolutions): score maps within 1e-3 of the f32 reference, ~10x the time; "
                     "f16x2: the same f32 graph with split-f16 operands (hi + scaled residual) on the 16-bit matrix cores: "
                     "the accuracy of f32, faster")
+    ap.add_argument('--fold-bn', dest='fold_bn', action=argparse.BooleanOptionalAction, default=None,
+                    help="f32 / f16x2 only (ignored with f16): run each convolution, its frozen batch norm, the residual add and the "
+                    "ReLU as one kernel (Graph(fold_bn=True)).  Default per precision: FOLD_BN_DEFAULT")
     return ap.parse_args()
+
+
+# --fold-bn when the flag is not given: on where the folded graph measured faster than the unfolded one at this script's
+# case (512^2, batch 1) by more than the spread of the alternating repeats (profiles/fold_bn_forward.json)
+FOLD_BN_DEFAULT = {'f32': True, 'f16x2': True}
+
+
+def graph_kwargs(precision, fold_bn):
+    """Graph(...) keywords of this script: no fold_bn at all with f16."""
+    kw = {'precision': precision}
+    if precision != 'f16':
+        kw['fold_bn'] = FOLD_BN_DEFAULT[precision] if fold_bn is None else bool(fold_bn)
+    return kw
 
 
 def order_points(pts):
@@ -125,7 +141,7 @@ def main():
     from tensorflow_ocr_amd.nets import model
     from tensorflow_ocr_amd.tool import pixellink_fn
     os.makedirs(FLAGS.output_dir, exist_ok=True)
-    g = Graph('cuda:0', precision=FLAGS.precision)
+    g = Graph('cuda:0', **graph_kwargs(FLAGS.precision, FLAGS.fold_bn))
     restored = False
 
     def network(gr, im):      # sess.run([f_score, f_geometry]) + the two softmaxes: one HIP graph per image shape
