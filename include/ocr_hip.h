@@ -28,7 +28,8 @@ extern "C" {
  * library whose ocr_abi_version() differs from the value it was written against (_lib.ABI_VERSION).
  * New entry points do not bump it: ocr_conv2d_f32_split / ocr_conv2d_f32_split_workspace (the f16x2 precision) joined at 7,
  * and so did ocr_conv2d_f32_mfma_ep / ocr_conv2d_f32_split_ep / ocr_subsample_f32 (the folded inference batch norm) with
- * their flags OCR_CONV_AFFINE, OCR_CONV_RESIDUAL, OCR_CONV_ACCUM_IN: every older entry point ignores those bits. */
+ * their flags OCR_CONV_AFFINE, OCR_CONV_RESIDUAL, OCR_CONV_ACCUM_IN: every older entry point ignores those bits; the dynamic
+ * loss scale (ocr_loss_scale_init, ocr_grad_check_f32, the *_dyn optimiser steps and loss seeds) joined at 7 too. */
 #define OCR_ABI_VERSION 7
 
 enum {
@@ -545,6 +546,11 @@ int ocr_dice_loss_fwd(const void* y_true_pixel, const void* y_pred_pixel, int pc
 int ocr_dice_loss_bwd(const void* y_true_pixel, int pc, const void* y_true_link, int G,
                       const void* training_mask, int P, const void* sums27, float grad_scale,
                       void* d_pred_pixel, void* d_pred_link, void* stream);
+/* The same kernels with the f16 loss scale read ON THE DEVICE: the seed is grad_scale * *loss_scale, loss_scale pointing
+ * at the `scale` word of an ocr_loss_scale_state (dynamic loss scaling, below the optimisers).  No extra pass or launch. */
+int ocr_dice_loss_bwd_dyn(const void* y_true_pixel, int pc, const void* y_true_link, int G,
+                          const void* training_mask, int P, const void* sums27, float grad_scale,
+                          const float* loss_scale, void* d_pred_pixel, void* d_pred_link, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Softmax cross-entropy losses with online hard negative mining / focal links.
@@ -582,6 +588,11 @@ int ocr_softmax_loss_bwd(const ocr_softmax_loss_desc* d, const void* pixel_logit
                          const void* link_logits, const void* pixel_labels, const void* link_labels,
                          const void* ohnm_threshold, const void* sums34, float grad_scale,
                          void* d_pixel_logits, void* d_link_logits, void* stream);
+/* seed = grad_scale * *loss_scale, read on the device (see ocr_dice_loss_bwd_dyn) */
+int ocr_softmax_loss_bwd_dyn(const ocr_softmax_loss_desc* d, const void* pixel_logits,
+                             const void* link_logits, const void* pixel_labels, const void* link_labels,
+                             const void* ohnm_threshold, const void* sums34, float grad_scale,
+                             const float* loss_scale, void* d_pixel_logits, void* d_link_logits, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * f32 INFERENCE PRECISION (round 4; csrc/f32_infer.hip): the forward graph with f32 storage and arithmetic, the
@@ -743,6 +754,10 @@ int ocr_link_ce_fwd(const void* link_gt, int gt_stride, const void* link_pred, i
                     int64_t count, void* sums4, void* loss1, void* workspace, size_t ws_bytes, void* stream);
 int ocr_link_ce_bwd(const void* link_gt, int gt_stride, const void* link_pred, int pred_stride, const void* w_pixel,
                     int64_t count, const void* sums4, float grad_scale, void* d_link_pred, int d_stride, void* stream);
+/* seed = grad_scale * *loss_scale, read on the device (see ocr_dice_loss_bwd_dyn) */
+int ocr_link_ce_bwd_dyn(const void* link_gt, int gt_stride, const void* link_pred, int pred_stride, const void* w_pixel,
+                        int64_t count, const void* sums4, float grad_scale, const float* loss_scale, void* d_link_pred,
+                        int d_stride, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * PixelLink decode (test_pixellink_fast.py:53-64,110-178; tool/pixellink_fn.py:120-158).
@@ -924,6 +939,50 @@ int ocr_sum_squares_f32(const void* x, int64_t n, float scale, void* out_f32, vo
                         size_t ws_bytes, void* stream);
 int ocr_scale_f32(void* x, int64_t n, float s, void* stream);
 int ocr_fill_f32(void* x, int64_t n, float value, void* stream);   /* n 4-byte words */
+
+/* ------------------------------------------------------------------------- *
+ * Dynamic loss scaling for f16 training, decided ON THE DEVICE (graph.DynamicLossScale).
+ * The scale, the overflow flag and the skip decision live in one small device block that
+ * kernels read and write; no host read happens anywhere on the path, so every call below
+ * is capturable in a HIP graph and a recorded step plan never changes.
+ *
+ * Per step:  loss backward (_dyn: seed = grad_scale * state.scale)  ->  backward  ->
+ * [all-reduce]  ->  ocr_grad_check_f32 (sets skip, inv_scale_used, the NEXT scale)  ->
+ * ocr_adam_step_dyn / ocr_momentum_step_dyn (no write at all when skip == 1).
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  float    scale;           /* what the next loss backward multiplies its seed with */
+  float    inv_scale_used;  /* 1 / (the scale the gradients just checked were produced with) */
+  uint32_t skip;            /* 1: the gradients just checked hold inf / NaN, the optimiser leaves everything as it is */
+  uint32_t good_steps;      /* clean steps since the last change of scale */
+  uint32_t skipped_total;   /* steps skipped since ocr_loss_scale_init */
+  uint32_t found;           /* per-step non-finite flag; 0 between calls */
+  uint32_t ticket;          /* workgroups of the running check that have finished; 0 between calls */
+  uint32_t reserved;
+} ocr_loss_scale_state;     /* 8 x 32-bit words; 4-byte aligned device memory */
+/* scale = init_scale (finite, > 0), inv_scale_used = 1 / init_scale, every counter 0 */
+int ocr_loss_scale_init(void* state, float init_scale, void* stream);
+/* One streaming pass over the flat f32 gradient buffer (16-byte loads): an element whose exponent field is all ones
+ * (inf, NaN) sets `found`.  The workgroup that finishes LAST (an atomic ticket counter behind __threadfence(); it puts
+ * the counter back to 0) performs the transition:
+ *   inv_scale_used = 1 / scale
+ *   found:  skip = 1, scale = max(scale * backoff_factor, min_scale), good_steps = 0, skipped_total += 1
+ *   else:   skip = 0, good_steps += 1; at good_steps == growth_interval: scale = min(scale * growth_factor, max_scale),
+ *           good_steps = 0
+ *   found = 0
+ * grad needs 4-byte alignment only: the elements in front of the first 16-byte boundary and the n & 3 tail are read
+ * one by one.  Calls that share a state must be ordered on their stream(s). */
+int ocr_grad_check_f32(const void* grad, int64_t n, void* state, float growth_factor, float backoff_factor,
+                       int growth_interval, float min_scale, float max_scale, void* stream);
+/* ocr_adam_step / ocr_momentum_step guarded by the state: nothing is written when state->skip == 1; otherwise
+ * g is multiplied by grad_scale * state->inv_scale_used (grad_scale: the reducer's host factor, 1 or 1/world) and
+ * the update is the same expression in the same order. */
+int ocr_adam_step_dyn(void* w, const void* g, void* m, void* v, void* ema, int64_t n,
+                      int64_t n_regularized, float lr_t, float beta1, float beta2, float eps,
+                      float weight_decay, float grad_scale, float ema_decay, const void* state, void* stream);
+int ocr_momentum_step_dyn(void* w, const void* g, void* accum, void* ema, int64_t n,
+                          int64_t n_regularized, float lr, float momentum, float weight_decay,
+                          float grad_scale, float ema_decay, const void* state, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Data-parallel exchange.  Replaces `average_gradients`

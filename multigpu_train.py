@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--input_size', type=int, default=512)
     ap.add_argument('--batch_size_per_gpu', type=int, default=14)
@@ -37,7 +37,18 @@ def parse():
     ap.add_argument('--pretrained_model_path', type=str, default=None)
     ap.add_argument('--training_data_path', type=str, default='/data/ocr/icdar2015/')
     ap.add_argument('--net', choices=['model', 'model_vgg', 'east', 'pixellink'], default='model')
-    return ap.parse_args()
+    # not a reference flag (TF-1.4 trains in f32): the f16 loss scale, a number or "dynamic" (graph.DynamicLossScale:
+    # a step whose gradients overflow is skipped and the scale backs off; it grows again after a run of clean steps)
+    ap.add_argument('--loss_scale', type=_loss_scale_arg, default=1024.0)
+    return ap.parse_args(argv)
+
+
+def _loss_scale_arg(text):
+    from tensorflow_ocr_amd.graph import parse_loss_scale
+    try:
+        return parse_loss_scale(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def build_forward_loss(net):
@@ -84,7 +95,7 @@ def main():
     if rank == 0:
         os.makedirs(FLAGS.checkpoint_path, exist_ok=True)
 
-    g = Graph(device, seed=1)
+    g = Graph(device, loss_scale=FLAGS.loss_scale, seed=1)
     step = TrainStep(g, build_forward_loss(FLAGS.net),
                      lambda gr: AdamOptimizer(gr, learning_rate=FLAGS.learning_rate,
                                               moving_average_decay=FLAGS.moving_average_decay),
@@ -162,6 +173,9 @@ def _train_loop(FLAGS, g, step, feeder, rng, rank, world, device, start):
                 tl = ml + opt.regularization_loss().item()
                 print('Step {:06d}, model loss {:.4f}, total loss {:.4f}, {:.2f} seconds/step, {:.2f} examples/second'.format(
                     it, ml, tl, avg_time_per_step, avg_examples_per_second), flush=True)
+                if g.loss_scaler is not None:       # (the loss was just read: one more device read costs nothing here)
+                    print('loss scale {:g}, {:d} steps skipped'.format(g.loss_scaler.scale(), g.loss_scaler.skipped_steps()),
+                          flush=True)
         if rank == 0 and it % FLAGS.save_checkpoint_steps == 0:     # step 0 included (multigpu_train.py:185-186)
             # saver.save(sess, FLAGS.checkpoint_path + 'model.ckpt', global_step=global_step) (:186-187):
             # a TensorFlow V2 bundle of Saver(tf.global_variables()) — variables, EMA shadows, Adam slots

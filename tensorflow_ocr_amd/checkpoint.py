@@ -106,6 +106,8 @@ def save_tf_checkpoint(checkpoint_dir, global_step, tf_state_dict, ema_state_dic
 
 
 SLOT_SUFFIXES = ("/Adam", "/Adam_1", "/Momentum")
+# graph.DynamicLossScale.state_dict(), saved beside the optimiser's scalars (no reference counterpart: TF-1.4 trains in f32)
+LOSS_SCALE_KEYS = {"loss_scale/scale": "scale", "loss_scale/good_steps": "good_steps"}
 
 
 def _read_raw(path):
@@ -127,16 +129,24 @@ def save_training_state(checkpoint_dir, graph, opt, basename="model.ckpt"):
     global step: variables (incl. BN moving statistics), EMA shadows, optimiser slots and scalars."""
     ema = internal_to_tf(opt.shadow_state_dict()) if opt.ema is not None else None
     slots = {k: internal_to_tf(v) for k, v in opt.slot_state_dict().items()}
+    scalars = dict(opt.scalar_state_dict())
+    if getattr(graph, "loss_scaler", None) is not None:
+        sd = graph.loss_scaler.state_dict()               # (reads the device)
+        scalars.update({k: sd[f] for k, f in LOSS_SCALE_KEYS.items()})
     return save_tf_checkpoint(checkpoint_dir, opt.global_step, internal_to_tf(graph.store.state_dict()), ema,
-                              basename, slots=slots, scalars=opt.scalar_state_dict())
+                              basename, slots=slots, scalars=scalars)
 
 
 def restore_training_state(path, graph, opt, strict=False):
     """`saver.restore(sess, latest_checkpoint)` (multigpu_train.py:153-158) for a tower whose variables
-    and optimiser exist (train.TrainStep.build): variables, EMA shadows, optimiser slots, global step.
+    and optimiser exist (train.TrainStep.build): variables, EMA shadows, optimiser slots, global step — and the
+    scale / clean-step count of a dynamic loss scale (graph.DynamicLossScale; `init_scale` when the file has none).
     Returns the restored global step (None when the file has none, e.g. an ImageNet backbone)."""
     raw = _read_raw(path)
     step = int(raw.pop("global_step")) if "global_step" in raw else None
+    scaler_sd = {f: raw.pop(k) for k, f in LOSS_SCALE_KEYS.items() if k in raw}
+    if getattr(graph, "loss_scaler", None) is not None:
+        graph.loss_scaler.load_state_dict(scaler_sd)      # a checkpoint without them: back to init_scale
     names = graph.store.order
     plain, ema, slots = {}, {}, {sfx[1:]: {} for sfx in SLOT_SUFFIXES}
     for k, v in raw.items():
@@ -165,7 +175,7 @@ def load_tf_checkpoint(path, use_moving_averages=False):
     raw = _read_raw(path)
     step = int(raw.pop("global_step")) if "global_step" in raw else None
     sd = {k: v for k, v in raw.items() if not k.endswith(EMA_SUFFIX) and not k.endswith(SLOT_SUFFIXES)
-          and k not in ("beta1_power", "beta2_power")}
+          and k not in ("beta1_power", "beta2_power") and k not in LOSS_SCALE_KEYS}
     if use_moving_averages:
         for k, v in raw.items():
             if k.endswith(EMA_SUFFIX):

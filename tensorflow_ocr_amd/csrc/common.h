@@ -150,6 +150,19 @@ static inline int ocr_launch_status() {
 
 static inline int ocr_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// The backward seed d(loss)/d(loss): the host's factor of the loss kernels (static loss scale: the kernels the static entry points
+// launch are what they always were), or that factor times the device-resident scale of dynamic loss scaling
+// (ocr_loss_scale_state.scale, include/ocr_hip.h), read by the kernel itself.
+struct SeedStatic {
+  float s;
+  __device__ __forceinline__ float get() const { return s; }
+};
+struct SeedDevice {
+  float s;
+  const float* scale;
+  __device__ __forceinline__ float get() const { return s * *scale; }
+};
+
 // wave64 all-lane sum through DPP-free shuffles (width 64).
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -197,14 +197,15 @@ __global__ __launch_bounds__(256) void dice_reduce11_kernel(DiceP d, const float
         red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
+template <class Seed>
 __global__ void dice_bwd11_kernel(DiceP d, const float* __restrict__ ytp, const float* __restrict__ ytl,
-                                  const float* __restrict__ mask, const float* __restrict__ sums, float gscale,
+                                  const float* __restrict__ mask, const float* __restrict__ sums, Seed seed,
                                   float* __restrict__ dpp, float* __restrict__ dpl) {
   __shared__ float cI[9], cU[9];
   if (threadIdx.x < 9) {
     const int k = threadIdx.x;
     const float I = sums[3 * k], U = sums[3 * k + 1] + sums[3 * k + 2] + 1e-5f;
-    const float wk = (k == 0 ? 2.f : 1.f) * gscale;
+    const float wk = (k == 0 ? 2.f : 1.f) * seed.get();
     cU[k] = -2.f * wk / U;
     cI[k] = 2.f * wk * I / (U * U);
   }
@@ -223,15 +224,16 @@ __global__ void dice_bwd11_kernel(DiceP d, const float* __restrict__ ytp, const 
   }
 }
 
+template <class Seed>
 __global__ void dice_bwd_kernel(DiceP d, const float* __restrict__ ytp,
                                 const float* __restrict__ ytl, const float* __restrict__ mask,
-                                const float* __restrict__ sums, float gscale,
+                                const float* __restrict__ sums, Seed seed,
                                 float* __restrict__ dpp, float* __restrict__ dpl) {
   __shared__ float cI[9], cU[9];
   if (threadIdx.x < 9) {
     const int k = threadIdx.x;
     const float I = sums[3 * k], U = sums[3 * k + 1] + sums[3 * k + 2] + 1e-5f;
-    const float wk = (k == 0 ? 2.f : 1.f) * gscale;
+    const float wk = (k == 0 ? 2.f : 1.f) * seed.get();
     // d/dp [1 - 2I/U] = -2 (y m U - I m) / U^2 = m * (-2 y / U + 2 I / U^2)
     cU[k] = -2.f * wk / U;
     cI[k] = 2.f * wk * I / (U * U);
@@ -249,14 +251,15 @@ __global__ void dice_bwd_kernel(DiceP d, const float* __restrict__ ytp,
   }
 }
 
+template <class Seed>
 __global__ void dice_bwd22_kernel(DiceP d, const float* __restrict__ ytp, const float* __restrict__ ytl,
-                                  const float* __restrict__ mask, const float* __restrict__ sums, float gscale,
+                                  const float* __restrict__ mask, const float* __restrict__ sums, Seed seed,
                                   float* __restrict__ dpp, float* __restrict__ dpl) {
   __shared__ float cI[9], cU[9];
   if (threadIdx.x < 9) {
     const int k = threadIdx.x;
     const float I = sums[3 * k], U = sums[3 * k + 1] + sums[3 * k + 2] + 1e-5f;
-    const float wk = (k == 0 ? 2.f : 1.f) * gscale;
+    const float wk = (k == 0 ? 2.f : 1.f) * seed.get();
     cU[k] = -2.f * wk / U;
     cI[k] = 2.f * wk * I / (U * U);
   }
@@ -309,18 +312,35 @@ extern "C" int ocr_dice_loss_fwd(const void* y_true_pixel, const void* y_pred_pi
   return ocr_launch_status();
 }
 
+namespace {
+template <class Seed>
+int dice_bwd_launch(const void* y_true_pixel, int pc, const void* y_true_link, int G, const void* training_mask, int P,
+                    const void* sums27, Seed seed, void* d_pred_pixel, void* d_pred_link, void* stream) {
+  OCR_CHECK_ARG(y_true_pixel && y_true_link && training_mask && sums27 && d_pred_pixel && d_pred_link);
+  OCR_CHECK_ARG(P > 0 && pc >= 1 && G >= 1);
+  DiceP d{P, pc, G};
+  hipLaunchKernelGGL(pc == 2 && G == 2 ? dice_bwd22_kernel<Seed> : pc == 1 && G == 1 ? dice_bwd11_kernel<Seed> : dice_bwd_kernel<Seed>,
+                     dim3(dice_blocks(P) * 2), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), d, static_cast<const float*>(y_true_pixel),
+                     static_cast<const float*>(y_true_link), static_cast<const float*>(training_mask),
+                     static_cast<const float*>(sums27), seed,
+                     static_cast<float*>(d_pred_pixel), static_cast<float*>(d_pred_link));
+  return ocr_launch_status();
+}
+}  // namespace
+
 extern "C" int ocr_dice_loss_bwd(const void* y_true_pixel, int pc, const void* y_true_link, int G,
                                  const void* training_mask, int P, const void* sums27,
                                  float grad_scale, void* d_pred_pixel, void* d_pred_link,
                                  void* stream) {
-  OCR_CHECK_ARG(y_true_pixel && y_true_link && training_mask && sums27 && d_pred_pixel && d_pred_link);
-  OCR_CHECK_ARG(P > 0 && pc >= 1 && G >= 1);
-  DiceP d{P, pc, G};
-  hipLaunchKernelGGL(pc == 2 && G == 2 ? dice_bwd22_kernel : pc == 1 && G == 1 ? dice_bwd11_kernel : dice_bwd_kernel,
-                     dim3(dice_blocks(P) * 2), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), d, static_cast<const float*>(y_true_pixel),
-                     static_cast<const float*>(y_true_link), static_cast<const float*>(training_mask),
-                     static_cast<const float*>(sums27), grad_scale,
-                     static_cast<float*>(d_pred_pixel), static_cast<float*>(d_pred_link));
-  return ocr_launch_status();
+  return dice_bwd_launch(y_true_pixel, pc, y_true_link, G, training_mask, P, sums27, SeedStatic{grad_scale},
+                         d_pred_pixel, d_pred_link, stream);
+}
+
+extern "C" int ocr_dice_loss_bwd_dyn(const void* y_true_pixel, int pc, const void* y_true_link, int G,
+                                     const void* training_mask, int P, const void* sums27, float grad_scale,
+                                     const float* loss_scale, void* d_pred_pixel, void* d_pred_link, void* stream) {
+  OCR_CHECK_ARG(loss_scale != nullptr);
+  return dice_bwd_launch(y_true_pixel, pc, y_true_link, G, training_mask, P, sums27, SeedDevice{grad_scale, loss_scale},
+                         d_pred_pixel, d_pred_link, stream);
 }

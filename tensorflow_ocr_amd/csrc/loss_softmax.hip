@@ -229,14 +229,16 @@ __global__ void sl_finalize_kernel(SlP p, const float* __restrict__ partial, int
   }
 }
 
+template <class Seed>
 __global__ __launch_bounds__(256) void sl_bwd_kernel(SlP p, const float* __restrict__ pl,
                                                      const float* __restrict__ ll,
                                                      const float* __restrict__ plab,
                                                      const float* __restrict__ llab,
                                                      const float* __restrict__ thr,
-                                                     const float* __restrict__ sums, float gscale,
+                                                     const float* __restrict__ sums, Seed seed,
                                                      float* __restrict__ dpl, float* __restrict__ dll) {
   __shared__ float c_pix, c_pos[8], c_neg[8];
+  const float gscale = seed.get();
   if (threadIdx.x == 0) {
     if (p.pixel_rule == 2) c_pix = 2.f * gscale / ((float)p.n * (float)p.hw);
     else if (p.pixel_rule == 0) c_pix = sums[1] > 0.f ? 2.f * gscale / sums[1] : 0.f;
@@ -416,10 +418,12 @@ __global__ void link_ce_finalize_kernel(const float* __restrict__ partial, int T
   __syncthreads();
   if (threadIdx.x == 0) loss[0] = sums4[0] / sums4[1] + sums4[2] / sums4[3];
 }
+template <class Seed>
 __global__ __launch_bounds__(256) void link_ce_bwd_kernel(const float* __restrict__ gt, int gs, const float* __restrict__ pred,
                                                           int ps, const float* __restrict__ W, size_t P,
-                                                          const float* __restrict__ sums4, float gscale,
+                                                          const float* __restrict__ sums4, Seed seed,
                                                           float* __restrict__ dpred, int ds) {
+  const float gscale = seed.get();
   const float cp = gscale / sums4[1], cn = gscale / sums4[3];
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < P; i += (size_t)gridDim.x * 256) {
     const float y = gt[i * gs], w = W[i];
@@ -499,24 +503,44 @@ extern "C" int ocr_softmax_loss_selected(const ocr_softmax_loss_desc* d, const v
   return ocr_launch_status();
 }
 
-extern "C" int ocr_softmax_loss_bwd(const ocr_softmax_loss_desc* d, const void* pixel_logits,
-                                    const void* link_logits, const void* pixel_labels,
-                                    const void* link_labels, const void* ohnm_threshold,
-                                    const void* sums34, float grad_scale, void* d_pixel_logits,
-                                    void* d_link_logits, void* stream) {
+namespace {
+template <class Seed>
+int sl_bwd_launch(const ocr_softmax_loss_desc* d, const void* pixel_logits, const void* link_logits, const void* pixel_labels,
+                  const void* link_labels, const void* ohnm_threshold, const void* sums34, Seed seed, void* d_pixel_logits,
+                  void* d_link_logits, void* stream) {
   SlP p;
   int rc = fill(d, &p);
   if (rc != OCR_OK) return rc;
   OCR_CHECK_ARG(pixel_logits && link_logits && pixel_labels && link_labels && ohnm_threshold);
   OCR_CHECK_ARG(sums34 && d_pixel_logits && d_link_logits);
   const int T = sl_blocks((size_t)p.n * p.hw) * 2;
-  hipLaunchKernelGGL(sl_bwd_kernel, dim3(T), dim3(256), 0, static_cast<hipStream_t>(stream), p,
+  hipLaunchKernelGGL(sl_bwd_kernel<Seed>, dim3(T), dim3(256), 0, static_cast<hipStream_t>(stream), p,
                      static_cast<const float*>(pixel_logits), static_cast<const float*>(link_logits),
                      static_cast<const float*>(pixel_labels), static_cast<const float*>(link_labels),
                      static_cast<const float*>(ohnm_threshold), static_cast<const float*>(sums34),
-                     grad_scale, static_cast<float*>(d_pixel_logits),
+                     seed, static_cast<float*>(d_pixel_logits),
                      static_cast<float*>(d_link_logits));
   return ocr_launch_status();
+}
+}  // namespace
+
+extern "C" int ocr_softmax_loss_bwd(const ocr_softmax_loss_desc* d, const void* pixel_logits,
+                                    const void* link_logits, const void* pixel_labels,
+                                    const void* link_labels, const void* ohnm_threshold,
+                                    const void* sums34, float grad_scale, void* d_pixel_logits,
+                                    void* d_link_logits, void* stream) {
+  return sl_bwd_launch(d, pixel_logits, link_logits, pixel_labels, link_labels, ohnm_threshold, sums34,
+                       SeedStatic{grad_scale}, d_pixel_logits, d_link_logits, stream);
+}
+
+extern "C" int ocr_softmax_loss_bwd_dyn(const ocr_softmax_loss_desc* d, const void* pixel_logits,
+                                        const void* link_logits, const void* pixel_labels,
+                                        const void* link_labels, const void* ohnm_threshold,
+                                        const void* sums34, float grad_scale, const float* loss_scale,
+                                        void* d_pixel_logits, void* d_link_logits, void* stream) {
+  OCR_CHECK_ARG(loss_scale != nullptr);
+  return sl_bwd_launch(d, pixel_logits, link_logits, pixel_labels, link_labels, ohnm_threshold, sums34,
+                       SeedDevice{grad_scale, loss_scale}, d_pixel_logits, d_link_logits, stream);
 }
 
 extern "C" int ocr_label_masks(const void* labels, int64_t count, int label_rule, void* pos_u8, void* neg_u8, void* stream) {
@@ -554,14 +578,31 @@ extern "C" int ocr_link_ce_fwd(const void* link_gt, int gt_stride, const void* l
   return ocr_launch_status();
 }
 
+namespace {
+template <class Seed>
+int link_ce_bwd_launch(const void* link_gt, int gt_stride, const void* link_pred, int pred_stride, const void* w_pixel,
+                       int64_t count, const void* sums4, Seed seed, void* d_link_pred, int d_stride, void* stream) {
+  OCR_CHECK_ARG(link_gt && link_pred && w_pixel && sums4 && d_link_pred && count > 0 && gt_stride >= 1 && pred_stride >= 2 &&
+                d_stride >= 2);
+  hipLaunchKernelGGL(link_ce_bwd_kernel<Seed>, dim3(sl_blocks((size_t)count) * 2), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const float*>(link_gt), gt_stride, static_cast<const float*>(link_pred), pred_stride,
+                     static_cast<const float*>(w_pixel), (size_t)count, static_cast<const float*>(sums4), seed,
+                     static_cast<float*>(d_link_pred), d_stride);
+  return ocr_launch_status();
+}
+}  // namespace
+
 extern "C" int ocr_link_ce_bwd(const void* link_gt, int gt_stride, const void* link_pred, int pred_stride, const void* w_pixel,
                                int64_t count, const void* sums4, float grad_scale, void* d_link_pred, int d_stride,
                                void* stream) {
-  OCR_CHECK_ARG(link_gt && link_pred && w_pixel && sums4 && d_link_pred && count > 0 && gt_stride >= 1 && pred_stride >= 2 &&
-                d_stride >= 2);
-  hipLaunchKernelGGL(link_ce_bwd_kernel, dim3(sl_blocks((size_t)count) * 2), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const float*>(link_gt), gt_stride, static_cast<const float*>(link_pred), pred_stride,
-                     static_cast<const float*>(w_pixel), (size_t)count, static_cast<const float*>(sums4), grad_scale,
-                     static_cast<float*>(d_link_pred), d_stride);
-  return ocr_launch_status();
+  return link_ce_bwd_launch(link_gt, gt_stride, link_pred, pred_stride, w_pixel, count, sums4, SeedStatic{grad_scale},
+                            d_link_pred, d_stride, stream);
+}
+
+extern "C" int ocr_link_ce_bwd_dyn(const void* link_gt, int gt_stride, const void* link_pred, int pred_stride,
+                                   const void* w_pixel, int64_t count, const void* sums4, float grad_scale,
+                                   const float* loss_scale, void* d_link_pred, int d_stride, void* stream) {
+  OCR_CHECK_ARG(loss_scale != nullptr);
+  return link_ce_bwd_launch(link_gt, gt_stride, link_pred, pred_stride, w_pixel, count, sums4,
+                            SeedDevice{grad_scale, loss_scale}, d_link_pred, d_stride, stream);
 }

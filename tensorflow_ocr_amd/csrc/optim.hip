@@ -18,12 +18,36 @@ struct AdamP {
   long long n, n_reg;
 };
 
-__global__ void adam_kernel(AdamP a, float* __restrict__ w, const float* __restrict__ g,
+// Dynamic loss scaling (ocr_loss_scale_state, include/ocr_hip.h): the *_dyn entry points instantiate the SAME kernel
+// bodies with a parameter block that carries the state pointer.  step_guard() is where the two differ: the static
+// block hands back its host factor (the instantiation the static entry points launch is what it always was), the
+// dynamic one reads the skip decision and 1 / scale that ocr_grad_check_f32 left on the device.
+struct AdamDynP : AdamP {
+  const ocr_loss_scale_state* st;     // inv_scale holds the reducer's host factor (1 or 1 / world)
+};
+
+template <class P>
+__device__ __forceinline__ bool step_guard(const P& a, float* inv_scale) {
+  *inv_scale = a.inv_scale;
+  return false;
+}
+template <class P>
+__device__ __forceinline__ bool step_guard_dyn(const P& a, float* inv_scale) {
+  if (a.st->skip) return true;                          // uniform: every workgroup leaves before its first store
+  *inv_scale = a.inv_scale * a.st->inv_scale_used;
+  return false;
+}
+__device__ __forceinline__ bool step_guard(const AdamDynP& a, float* inv_scale) { return step_guard_dyn(a, inv_scale); }
+
+template <class P>
+__global__ void adam_kernel(P a, float* __restrict__ w, const float* __restrict__ g,
                             float* __restrict__ m, float* __restrict__ v,
                             float* __restrict__ ema) {
+  float inv_scale;
+  if (step_guard(a, &inv_scale)) return;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long long)gridDim.x * 256) {
     float wi = w[i];
-    float gi = g[i] * a.inv_scale;
+    float gi = g[i] * inv_scale;
     if (i < a.n_reg) gi += a.wd * wi;
     const float mi = a.beta1 * m[i] + (1.f - a.beta1) * gi;
     const float vi = a.beta2 * v[i] + (1.f - a.beta2) * gi * gi;
@@ -43,11 +67,19 @@ struct MomP {
   long long n, n_reg;
 };
 
-__global__ void momentum_kernel(MomP a, float* __restrict__ w, const float* __restrict__ g,
+struct MomDynP : MomP {
+  const ocr_loss_scale_state* st;
+};
+__device__ __forceinline__ bool step_guard(const MomDynP& a, float* inv_scale) { return step_guard_dyn(a, inv_scale); }
+
+template <class P>
+__global__ void momentum_kernel(P a, float* __restrict__ w, const float* __restrict__ g,
                                 float* __restrict__ acc, float* __restrict__ ema) {
+  float inv_scale;
+  if (step_guard(a, &inv_scale)) return;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long long)gridDim.x * 256) {
     float wi = w[i];
-    float gi = g[i] * a.inv_scale;
+    float gi = g[i] * inv_scale;
     if (i < a.n_reg) gi += a.wd * wi;
     const float ai = a.momentum * acc[i] + gi;
     acc[i] = ai;
@@ -182,6 +214,73 @@ __global__ void sumsq_final_kernel(const double* __restrict__ partial, int g, do
   if (threadIdx.x == 0) out[0] = (float)(scale * t);
 }
 
+// ---- dynamic loss scaling: the device-side state machine (ocr_loss_scale_state, include/ocr_hip.h) ----------------
+__global__ void loss_scale_init_kernel(ocr_loss_scale_state* st, float init_scale) {
+  if (threadIdx.x == 0) {
+    st->scale = init_scale;
+    st->inv_scale_used = 1.f / init_scale;
+  } else if (threadIdx.x >= 2 && threadIdx.x < 8) {
+    reinterpret_cast<uint32_t*>(st)[threadIdx.x] = 0u;           // skip .. reserved (words 0 and 1 are thread 0's)
+  }
+}
+
+struct GradCheckP {
+  float growth, backoff, min_scale, max_scale;
+  unsigned interval;
+  long long head, n4, tail;     // elements in front of the first 16-byte boundary, float4 groups, n & 3 leftovers
+};
+
+__device__ __forceinline__ unsigned nonfinite(float v) {          // exponent field all ones: inf or NaN
+  return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
+}
+
+// One HBM-bound read of the flat gradient buffer, shaped like sumsq_partial_kernel.  A workgroup that saw a
+// non-finite element ORs `found` (one agent-scope atomic) and fences before it draws its ticket; clean workgroups
+// have nothing to publish and only draw.  All ticket operations are read-modify-writes on one word, so the
+// workgroup that draws the last one is ordered behind every release above and, after its own fence, reads the final
+// `found`.  It alone touches the rest of the state, and it puts `found` and the ticket counter back to 0: the next
+// launch on the stream starts clean with no memset in front of it (ocr_loss_scale_init zeroes them once).
+__global__ __launch_bounds__(256) void grad_check_kernel(const float* __restrict__ x, GradCheckP p,
+                                                         ocr_loss_scale_state* __restrict__ st) {
+  unsigned bad = 0;
+  const float4* x4 = reinterpret_cast<const float4*>(x + p.head);
+#pragma unroll 4
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < p.n4; i += (long long)gridDim.x * 256) {
+    const float4 v = x4[i];
+    bad |= nonfinite(v.x) | nonfinite(v.y) | nonfinite(v.z) | nonfinite(v.w);
+  }
+  if (blockIdx.x == 0) {
+    if (threadIdx.x < p.head) bad |= nonfinite(x[threadIdx.x]);
+    if (threadIdx.x < p.tail) bad |= nonfinite(x[p.head + (p.n4 << 2) + threadIdx.x]);
+  }
+  bad = __syncthreads_or((int)bad);
+  if (threadIdx.x != 0) return;
+  if (bad) {
+    __hip_atomic_fetch_or(&st->found, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence();
+  }
+  const unsigned t = __hip_atomic_fetch_add(&st->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (t != gridDim.x - 1) return;
+  __threadfence();
+  const unsigned found = __hip_atomic_load(&st->found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  float scale = st->scale;
+  unsigned good = st->good_steps;
+  __hip_atomic_store(&st->inv_scale_used, 1.f / scale, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (found) {
+    scale = fmaxf(scale * p.backoff, p.min_scale);
+    good = 0;
+    __hip_atomic_store(&st->skipped_total, st->skipped_total + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else if (++good == p.interval) {
+    scale = fminf(scale * p.growth, p.max_scale);
+    good = 0;
+  }
+  __hip_atomic_store(&st->skip, found ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&st->scale, scale, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&st->good_steps, good, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&st->found, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 unsigned sumsq_grid(long long n) {
   long long b = (n / 4 + 255) / 256;
   if (b > 1024) b = 1024;
@@ -204,7 +303,7 @@ extern "C" int ocr_adam_step(void* w, const void* g, void* m, void* v, void* ema
                              void* stream) {
   OCR_CHECK_ARG(w && g && m && v && n > 0 && n_regularized >= 0 && n_regularized <= n);
   AdamP a{lr_t, beta1, beta2, eps, weight_decay, inv_loss_scale, ema_decay, n, n_regularized};
-  hipLaunchKernelGGL(adam_kernel, dim3(ogrid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), a,
+  hipLaunchKernelGGL(adam_kernel<AdamP>, dim3(ogrid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), a,
                      static_cast<float*>(w), static_cast<const float*>(g), static_cast<float*>(m),
                      static_cast<float*>(v), static_cast<float*>(ema));
   return ocr_launch_status();
@@ -215,7 +314,7 @@ extern "C" int ocr_momentum_step(void* w, const void* g, void* accum, void* ema,
                                  float inv_loss_scale, float ema_decay, void* stream) {
   OCR_CHECK_ARG(w && g && accum && n > 0 && n_regularized >= 0 && n_regularized <= n);
   MomP a{lr, momentum, weight_decay, inv_loss_scale, ema_decay, n, n_regularized};
-  hipLaunchKernelGGL(momentum_kernel, dim3(ogrid(n)), dim3(256), 0,
+  hipLaunchKernelGGL(momentum_kernel<MomP>, dim3(ogrid(n)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), a, static_cast<float*>(w),
                      static_cast<const float*>(g), static_cast<float*>(accum),
                      static_cast<float*>(ema));
@@ -298,5 +397,53 @@ extern "C" int ocr_fill_f32(void* x, int64_t n, float value, void* stream) {
   OCR_CHECK_ARG(x && n > 0);
   hipLaunchKernelGGL(fill_kernel, dim3(ogrid(n)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<float*>(x), (long long)n, value);
+  return ocr_launch_status();
+}
+
+extern "C" int ocr_loss_scale_init(void* state, float init_scale, void* stream) {
+  OCR_CHECK_ARG(state && ((uintptr_t)state & 3) == 0 && init_scale > 0.f && init_scale <= 3.4028234664e38f);
+  hipLaunchKernelGGL(loss_scale_init_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream),
+                     static_cast<ocr_loss_scale_state*>(state), init_scale);
+  return ocr_launch_status();
+}
+
+extern "C" int ocr_grad_check_f32(const void* grad, int64_t n, void* state, float growth_factor, float backoff_factor,
+                                  int growth_interval, float min_scale, float max_scale, void* stream) {
+  OCR_CHECK_ARG(grad && state && n > 0 && ((uintptr_t)grad & 3) == 0 && ((uintptr_t)state & 3) == 0);
+  OCR_CHECK_ARG(growth_factor >= 1.f && backoff_factor > 0.f && backoff_factor <= 1.f && growth_interval > 0);
+  OCR_CHECK_ARG(min_scale > 0.f && min_scale <= max_scale && max_scale <= 3.4028234664e38f);
+  GradCheckP p{growth_factor, backoff_factor, min_scale, max_scale, (unsigned)growth_interval, 0, 0, 0};
+  p.head = (long long)(((16 - ((uintptr_t)grad & 15)) & 15) >> 2);       // 0..3 elements up to the 16-byte boundary
+  if (p.head > n) p.head = n;
+  p.n4 = (n - p.head) >> 2;
+  p.tail = (n - p.head) & 3;
+  hipLaunchKernelGGL(grad_check_kernel, dim3(ogrid(p.n4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const float*>(grad), p, static_cast<ocr_loss_scale_state*>(state));
+  return ocr_launch_status();
+}
+
+extern "C" int ocr_adam_step_dyn(void* w, const void* g, void* m, void* v, void* ema, int64_t n,
+                                 int64_t n_regularized, float lr_t, float beta1, float beta2, float eps,
+                                 float weight_decay, float grad_scale, float ema_decay, const void* state,
+                                 void* stream) {
+  OCR_CHECK_ARG(w && g && m && v && state && n > 0 && n_regularized >= 0 && n_regularized <= n);
+  AdamDynP a{{lr_t, beta1, beta2, eps, weight_decay, grad_scale, ema_decay, n, n_regularized},
+             static_cast<const ocr_loss_scale_state*>(state)};
+  hipLaunchKernelGGL(adam_kernel<AdamDynP>, dim3(ogrid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), a,
+                     static_cast<float*>(w), static_cast<const float*>(g), static_cast<float*>(m),
+                     static_cast<float*>(v), static_cast<float*>(ema));
+  return ocr_launch_status();
+}
+
+extern "C" int ocr_momentum_step_dyn(void* w, const void* g, void* accum, void* ema, int64_t n,
+                                     int64_t n_regularized, float lr, float momentum, float weight_decay,
+                                     float grad_scale, float ema_decay, const void* state, void* stream) {
+  OCR_CHECK_ARG(w && g && accum && state && n > 0 && n_regularized >= 0 && n_regularized <= n);
+  MomDynP a{{lr, momentum, weight_decay, grad_scale, ema_decay, n, n_regularized},
+            static_cast<const ocr_loss_scale_state*>(state)};
+  hipLaunchKernelGGL(momentum_kernel<MomDynP>, dim3(ogrid(n)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), a, static_cast<float*>(w),
+                     static_cast<const float*>(g), static_cast<float*>(accum),
+                     static_cast<float*>(ema));
   return ocr_launch_status();
 }

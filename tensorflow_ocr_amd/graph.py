@@ -206,6 +206,138 @@ class Act:
         return tuple(self._data.shape)
 
 
+class DynamicLossScale:
+    """Dynamic loss scaling for f16 training, decided ON THE DEVICE: `Graph(..., loss_scale=DynamicLossScale(...))`.
+
+    The scale, the per-step overflow flag and the skip decision live in one small device block (`ocr_loss_scale_state`,
+    include/ocr_hip.h).  The loss kernels read the scale from it (`ops.*_bwd_dyn`), `ops.grad_check` — one pass over the
+    flat gradient buffer behind the all-reduce — looks for inf / NaN and moves the state, and the optimiser kernel
+    (`ops.adam_step_dyn` / `ops.momentum_step_dyn`) returns without a single store when the step is to be skipped.  No
+    host read happens anywhere on that path, so a recorded step plan (train.TrainStep) never changes.
+
+    State machine, once per step: an overflow skips the step, multiplies the scale by `backoff_factor` (not below
+    `min_scale`) and clears the run of clean steps; `growth_interval` clean steps in a row multiply it by `growth_factor`
+    (not above `max_scale`).
+
+    HOST counters do not know about skips: `global_step` — hence the learning-rate staircase, Adam's bias correction and
+    the EMA warm-up — advances on a skipped step too, as a learning-rate schedule usually does under dynamic scaling (the
+    alternative is a device-to-host sync in every step; skips are rare).  `store.version` advances as well; the re-pack
+    that follows re-creates the same operand copies.
+
+    `scale()`, `skipped_steps()`, `good_steps()` and `state_dict()` READ THE DEVICE (a sync): for logging and
+    checkpoints, never inside a step.  The Graph works on its own bound copy (`graph.loss_scaler`), so one instance can
+    configure several graphs."""
+
+    def __init__(self, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, min_scale=1.0,
+                 max_scale=2.0 ** 24):
+        vals = dict(init_scale=init_scale, growth_factor=growth_factor, backoff_factor=backoff_factor, min_scale=min_scale,
+                    max_scale=max_scale)
+        for k, v in vals.items():
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v <= 0:
+                raise ValueError("%s must be a positive finite number, got %r" % (k, v))
+        if not (backoff_factor < 1.0 < growth_factor):
+            raise ValueError("need backoff_factor < 1 < growth_factor, got %r, %r" % (backoff_factor, growth_factor))
+        if not (min_scale <= init_scale <= max_scale):
+            raise ValueError("need min_scale <= init_scale <= max_scale, got %r, %r, %r" % (min_scale, init_scale, max_scale))
+        if isinstance(growth_interval, bool) or int(growth_interval) != growth_interval or growth_interval < 1:
+            raise ValueError("growth_interval must be a positive integer, got %r" % (growth_interval,))
+        f32 = lambda v: float(np.float32(v))           # what the kernels will see
+        self.init_scale, self.growth_factor, self.backoff_factor = f32(init_scale), f32(growth_factor), f32(backoff_factor)
+        self.min_scale, self.max_scale = f32(min_scale), f32(max_scale)
+        self.growth_interval = int(growth_interval)
+        self.device = None
+        self._state = None                                      # int32 [8] on the device, created on first use
+        self._host = {"scale": self.init_scale, "good_steps": 0, "skipped_total": 0}    # the values until then
+
+    def bind(self, device):
+        """A copy of the configuration with device state of its own (Graph.__init__)."""
+        b = DynamicLossScale(self.init_scale, self.growth_factor, self.backoff_factor, self.growth_interval, self.min_scale,
+                             self.max_scale)
+        b.device = torch.device(device)
+        return b
+
+    @property
+    def state(self):
+        """The device block (ops.LOSS_SCALE_WORDS 32-bit words).  Created outside any recording: the initialising launch
+        must not become part of a replayed plan."""
+        if self._state is None:
+            if self.device is None:
+                raise RuntimeError("this DynamicLossScale is a configuration only: Graph(loss_scale=...) binds a copy to its device")
+            st = torch.empty(ops.LOSS_SCALE_WORDS, dtype=torch.int32, device=self.device)
+            rec, L.RECORDER = L.RECORDER, None
+            try:
+                ops.loss_scale_init(st, self._host["scale"])
+            finally:
+                L.RECORDER = rec
+            if self._host["good_steps"] or self._host["skipped_total"]:
+                st[ops.LS_GOOD_STEPS:ops.LS_SKIPPED_TOTAL + 1].copy_(
+                    torch.tensor([self._host["good_steps"], self._host["skipped_total"]], dtype=torch.int32))
+            self._state = st
+        return self._state
+
+    @property
+    def scale_ptr(self):
+        """1-element f32 view of the state's `scale` word: what the *_bwd_dyn loss kernels take."""
+        return self.state[ops.LS_SCALE:ops.LS_SCALE + 1].view(torch.float32)
+
+    def _words(self):
+        if self._state is None:
+            return None
+        return self._state.cpu().numpy()
+
+    def scale(self):
+        """The scale the NEXT backward pass will use (device read: a sync)."""
+        w = self._words()
+        return self._host["scale"] if w is None else float(w[ops.LS_SCALE:ops.LS_SCALE + 1].view(np.float32)[0])
+
+    def skipped_steps(self):
+        w = self._words()
+        return self._host["skipped_total"] if w is None else int(w[ops.LS_SKIPPED_TOTAL])
+
+    def good_steps(self):
+        w = self._words()
+        return self._host["good_steps"] if w is None else int(w[ops.LS_GOOD_STEPS])
+
+    def check(self, grad):
+        """ops.grad_check on `grad` with this configuration (the optimisers call it behind the all-reduce)."""
+        ops.grad_check(grad, self.state, self.growth_factor, self.backoff_factor, self.growth_interval, self.min_scale,
+                       self.max_scale)
+
+    def state_dict(self):
+        return {"scale": np.float32(self.scale()), "good_steps": np.int64(self.good_steps())}
+
+    def load_state_dict(self, sd=None):
+        """Restore `scale` and `good_steps`; None / a dict without them (an older checkpoint) restores `init_scale`."""
+        sd = sd or {}
+        scale = float(np.float32(sd["scale"])) if "scale" in sd else self.init_scale
+        good = int(sd["good_steps"]) if "good_steps" in sd and "scale" in sd else 0
+        if not (math.isfinite(scale) and scale > 0):
+            raise ValueError("loss scale must be positive and finite, got %r" % scale)
+        scale = min(max(scale, self.min_scale), self.max_scale)
+        good = max(0, min(good, self.growth_interval - 1))
+        self._host.update(scale=scale, good_steps=good, skipped_total=self.skipped_steps())
+        if self._state is not None:
+            host = np.zeros(2, dtype=np.int32)
+            host[:1].view(np.float32)[0] = scale
+            host[1:2].view(np.float32)[0] = np.float32(1.0) / np.float32(scale)
+            self._state[ops.LS_SCALE:ops.LS_INV_SCALE_USED + 1].copy_(torch.from_numpy(host))
+            self._state[ops.LS_GOOD_STEPS:ops.LS_GOOD_STEPS + 1].copy_(torch.tensor([good], dtype=torch.int32))
+
+
+def parse_loss_scale(text):
+    """The training scripts' `--loss_scale` value: "dynamic" -> DynamicLossScale() with its defaults, a number -> that
+    constant scale (a float)."""
+    if isinstance(text, str) and text.strip().lower() == "dynamic":
+        return DynamicLossScale()
+    try:
+        v = float(text)
+    except (TypeError, ValueError):
+        raise ValueError("loss_scale must be 'dynamic' or a number, got %r" % (text,))
+    if not (math.isfinite(v) and v > 0):
+        raise ValueError("loss_scale must be positive and finite, got %r" % (text,))
+    return v
+
+
 class Graph:
     """One tower: variable store + tape + scratch.  `loss_scale` multiplies the loss gradient so
     that f16 activation gradients stay in range; the optimiser divides it out."""
@@ -225,7 +357,10 @@ class Graph:
         fold_bn ("f32" / "f16x2" only): a layer whose batch norm runs in inference mode (moving statistics) launches ONE
         convolution that applies the normalisation, the bottleneck's residual add and the ReLU in its epilogue, and
         conv2d_same layers run at their real stride (layers_f32.py; ocr_conv2d_f32_mfma_ep / ocr_conv2d_f32_split_ep).
-        False: every graph launches what it always launched."""
+        False: every graph launches what it always launched.
+        loss_scale: a number = the constant f16 loss scale; a `DynamicLossScale` ("f16" only) = a scale kept on the device
+        that backs off when a gradient overflows (the step is skipped) and grows after a run of clean steps:
+        `loss_scaler` is then this graph's bound copy of it (None for a constant), `loss_scale` its initial value."""
         if precision not in ("f16", "f32", "f16x2"):
             raise ValueError("precision must be 'f16', 'f32' or 'f16x2'")
         if fold_bn and precision not in ("f32", "f16x2"):
@@ -238,7 +373,15 @@ class Graph:
         self.store = VariableStore(self.device)
         self.tape = []
         self.scope = []
-        self.loss_scale = float(loss_scale)
+        if isinstance(loss_scale, DynamicLossScale):
+            if precision != "f16":
+                raise ValueError("DynamicLossScale needs precision 'f16' (the %s inference precision has no backward pass)"
+                                 % precision)
+            self.loss_scaler = loss_scale.bind(self.device)
+            self.loss_scale = self.loss_scaler.init_scale
+        else:
+            self.loss_scaler = None
+            self.loss_scale = float(loss_scale)
         self.loss_div = 1.0          # train_pixellink.py:264: each clone's loss is divided by num_clones
         self.rng = np.random.default_rng(seed)
         self.ws = None

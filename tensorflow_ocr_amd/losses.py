@@ -47,8 +47,12 @@ def softmax_loss(g, pixel_logits, link_logits, pixel_labels, link_labels, *, pix
     def backward():
         pixel_logits.grad = g.empty(pixel_logits.data.shape, F32)
         link_logits.grad = g.empty(link_logits.data.shape, F32)
-        ops.softmax_loss_bwd(d, pixel_logits.data, link_logits.data, pl, ll, thr, sums, g.seed_scale(),
-                             pixel_logits.grad, link_logits.grad)
+        if g.loss_scaler is not None:       # dynamic loss scaling: the kernel reads the scale from the device state
+            ops.softmax_loss_bwd_dyn(d, pixel_logits.data, link_logits.data, pl, ll, thr, sums, 1.0 / g.loss_div,
+                                     g.loss_scaler.scale_ptr, pixel_logits.grad, link_logits.grad)
+        else:
+            ops.softmax_loss_bwd(d, pixel_logits.data, link_logits.data, pl, ll, thr, sums, g.seed_scale(),
+                                 pixel_logits.grad, link_logits.grad)
     g.record(backward)
     res = Scalar(out)
     res.ohnm_threshold = thr

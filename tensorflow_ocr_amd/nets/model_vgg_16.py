@@ -119,7 +119,11 @@ def loss(y_true_pixel, y_pred_pixel, y_true_link, y_pred_link, training_mask, gr
     def backward():
         y_pred_pixel.grad = g.empty(y_pred_pixel.data.shape, F32)
         y_pred_link.grad = g.empty(y_pred_link.data.shape, F32)
-        ops.dice_loss_bwd(ytp, ytl, m, sums, g.seed_scale(), y_pred_pixel.grad, y_pred_link.grad)
+        if g.loss_scaler is not None:       # dynamic loss scaling: the kernel reads the scale from the device state
+            ops.dice_loss_bwd_dyn(ytp, ytl, m, sums, 1.0 / g.loss_div, g.loss_scaler.scale_ptr, y_pred_pixel.grad,
+                                  y_pred_link.grad)
+        else:
+            ops.dice_loss_bwd(ytp, ytl, m, sums, g.seed_scale(), y_pred_pixel.grad, y_pred_link.grad)
     g.record(backward)
     res = Scalar(out)
     g.collections["losses"].append(res)
@@ -176,6 +180,9 @@ def cal_link_loss(link_gt, link_pred, W_pixel, graph=None):
     if handle is not None:
         def backward():
             handle.grad = g.empty(pr_t.shape, F32)
-            ops.link_ce_bwd(gt_t, gs, pr_t, ps, W, P, sums, g.seed_scale(), handle.grad, 2)
+            if g.loss_scaler is not None:
+                ops.link_ce_bwd_dyn(gt_t, gs, pr_t, ps, W, P, sums, 1.0 / g.loss_div, g.loss_scaler.scale_ptr, handle.grad, 2)
+            else:
+                ops.link_ce_bwd(gt_t, gs, pr_t, ps, W, P, sums, g.seed_scale(), handle.grad, 2)
         g.record(backward)
     return Scalar(out)

@@ -815,6 +815,15 @@ def dice_loss_bwd(yt_pixel, yt_link, mask, sums27, grad_scale, d_pixel, d_link):
            ptr(sums27), c_float(grad_scale), ptr(d_pixel), ptr(d_link), _st())
 
 
+def dice_loss_bwd_dyn(yt_pixel, yt_link, mask, sums27, grad_scale, loss_scale, d_pixel, d_link):
+    """dice_loss_bwd with the seed grad_scale * loss_scale[0], `loss_scale` a DEVICE f32 (LossScaleState.scale_ptr)."""
+    P = mask.numel()
+    pc = d_pixel.numel() // P
+    G = d_link.numel() // (8 * P)
+    L.call("ocr_dice_loss_bwd_dyn", ptr(yt_pixel), c_int(pc), ptr(yt_link), c_int(G), ptr(mask), c_int(P),
+           ptr(sums27), c_float(grad_scale), ptr(loss_scale), ptr(d_pixel), ptr(d_link), _st())
+
+
 def softmax_loss_fwd(desc, pixel_logits, link_logits, pixel_labels, link_labels, thr, sums34, loss10, ws):
     nbytes = L.call_size("ocr_softmax_loss_workspace", byref(desc))
     buf = ws.get(nbytes)
@@ -830,6 +839,12 @@ def softmax_loss_bwd(desc, pixel_logits, link_logits, pixel_labels, link_labels,
                      d_pixel, d_link):
     L.call("ocr_softmax_loss_bwd", byref(desc), ptr(pixel_logits), ptr(link_logits), ptr(pixel_labels),
            ptr(link_labels), ptr(thr), ptr(sums34), c_float(grad_scale), ptr(d_pixel), ptr(d_link), _st())
+
+
+def softmax_loss_bwd_dyn(desc, pixel_logits, link_logits, pixel_labels, link_labels, thr, sums34, grad_scale, loss_scale,
+                         d_pixel, d_link):
+    L.call("ocr_softmax_loss_bwd_dyn", byref(desc), ptr(pixel_logits), ptr(link_logits), ptr(pixel_labels),
+           ptr(link_labels), ptr(thr), ptr(sums34), c_float(grad_scale), ptr(loss_scale), ptr(d_pixel), ptr(d_link), _st())
 
 
 # ------------------------------------------------------------------ heads, batched (one launch per kernel kind)
@@ -955,6 +970,11 @@ def link_ce_fwd(gt, gt_stride, pred, pred_stride, w_pixel, count, sums4, loss1, 
 def link_ce_bwd(gt, gt_stride, pred, pred_stride, w_pixel, count, sums4, grad_scale, d_pred, d_stride):
     L.call("ocr_link_ce_bwd", ptr(gt), c_int(gt_stride), ptr(pred), c_int(pred_stride), ptr(w_pixel), c_int64(count),
            ptr(sums4), c_float(grad_scale), ptr(d_pred), c_int(d_stride), _st())
+
+
+def link_ce_bwd_dyn(gt, gt_stride, pred, pred_stride, w_pixel, count, sums4, grad_scale, loss_scale, d_pred, d_stride):
+    L.call("ocr_link_ce_bwd_dyn", ptr(gt), c_int(gt_stride), ptr(pred), c_int(pred_stride), ptr(w_pixel), c_int64(count),
+           ptr(sums4), c_float(grad_scale), ptr(loss_scale), ptr(d_pred), c_int(d_stride), _st())
 
 
 # ----------------------------------------------------------------------------- decode
@@ -1108,6 +1128,33 @@ def adam_step(w, g, m, v, ema, n_reg, lr_t, beta1, beta2, eps, wd, inv_scale, em
 def momentum_step(w, g, acc, ema, n_reg, lr, momentum, wd, inv_scale, ema_decay):
     L.call("ocr_momentum_step", ptr(w), ptr(g), ptr(acc), ptr(ema), c_int64(w.numel()), c_int64(n_reg),
            c_float(lr), c_float(momentum), c_float(wd), c_float(inv_scale), c_float(ema_decay), _st())
+
+
+# dynamic loss scaling: `state` is the 8-word device block ocr_loss_scale_state (include/ocr_hip.h) as an int32 tensor
+LOSS_SCALE_WORDS = 8
+LS_SCALE, LS_INV_SCALE_USED, LS_SKIP, LS_GOOD_STEPS, LS_SKIPPED_TOTAL, LS_FOUND, LS_TICKET = range(7)
+
+
+def loss_scale_init(state, init_scale):
+    assert state.numel() >= LOSS_SCALE_WORDS and state.element_size() == 4
+    L.call("ocr_loss_scale_init", ptr(state), c_float(init_scale), _st())
+
+
+def grad_check(grad, state, growth_factor, backoff_factor, growth_interval, min_scale, max_scale):
+    """One pass over the f32 buffer `grad` (any 4-byte aligned view): sets state.skip / inv_scale_used and moves the scale."""
+    L.call("ocr_grad_check_f32", ptr(grad), c_int64(grad.numel()), ptr(state), c_float(growth_factor), c_float(backoff_factor),
+           c_int(growth_interval), c_float(min_scale), c_float(max_scale), _st())
+
+
+def adam_step_dyn(w, g, m, v, ema, n_reg, lr_t, beta1, beta2, eps, wd, grad_scale, ema_decay, state):
+    L.call("ocr_adam_step_dyn", ptr(w), ptr(g), ptr(m), ptr(v), ptr(ema), c_int64(w.numel()),
+           c_int64(n_reg), c_float(lr_t), c_float(beta1), c_float(beta2), c_float(eps), c_float(wd),
+           c_float(grad_scale), c_float(ema_decay), ptr(state), _st())
+
+
+def momentum_step_dyn(w, g, acc, ema, n_reg, lr, momentum, wd, grad_scale, ema_decay, state):
+    L.call("ocr_momentum_step_dyn", ptr(w), ptr(g), ptr(acc), ptr(ema), c_int64(w.numel()), c_int64(n_reg),
+           c_float(lr), c_float(momentum), c_float(wd), c_float(grad_scale), c_float(ema_decay), ptr(state), _st())
 
 
 def scale_(x, s):

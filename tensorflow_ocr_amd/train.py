@@ -72,8 +72,17 @@ class AdamOptimizer:
         lr = self.learning_rate()
         lr_t = lr * math.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
         ema_d = min(self.mad, (1.0 + self.global_step) / (10.0 + self.global_step)) if self.mad else 0.0
-        ops.adam_step(st.flat, st.flat_grad, self.m, self.v, self.ema, st.n_reg, lr_t, self.b1, self.b2,
-                      self.eps, self.wd, grad_scale / self.g.loss_scale, ema_d)
+        scaler = self.g.loss_scaler
+        if scaler is not None:
+            # dynamic loss scaling (graph.DynamicLossScale): the check sees the REDUCED gradients (inf / NaN survive a sum
+            # all-reduce, so every rank decides alike), the guarded step writes nothing when it found one.  The host
+            # counters below advance either way: no device read in the step.
+            scaler.check(st.flat_grad)
+            ops.adam_step_dyn(st.flat, st.flat_grad, self.m, self.v, self.ema, st.n_reg, lr_t, self.b1, self.b2,
+                              self.eps, self.wd, grad_scale, ema_d, scaler.state)
+        else:
+            ops.adam_step(st.flat, st.flat_grad, self.m, self.v, self.ema, st.n_reg, lr_t, self.b1, self.b2,
+                          self.eps, self.wd, grad_scale / self.g.loss_scale, ema_d)
         st.version += 1
         self.global_step += 1
 
@@ -149,8 +158,14 @@ class MomentumOptimizer:
     def apply_gradients(self, grad_scale=1.0):
         st = self.g.store
         ema_d = min(self.mad, (1.0 + self.global_step) / (10.0 + self.global_step)) if self.mad else 0.0
-        ops.momentum_step(st.flat, st.flat_grad, self.acc, self.ema, st.n_reg, self.learning_rate(),
-                          self.momentum, self.wd, grad_scale / self.g.loss_scale, ema_d)
+        scaler = self.g.loss_scaler
+        if scaler is not None:               # as in AdamOptimizer.apply_gradients
+            scaler.check(st.flat_grad)
+            ops.momentum_step_dyn(st.flat, st.flat_grad, self.acc, self.ema, st.n_reg, self.learning_rate(),
+                                  self.momentum, self.wd, grad_scale, ema_d, scaler.state)
+        else:
+            ops.momentum_step(st.flat, st.flat_grad, self.acc, self.ema, st.n_reg, self.learning_rate(),
+                              self.momentum, self.wd, grad_scale / self.g.loss_scale, ema_d)
         st.version += 1
         self.global_step += 1
 

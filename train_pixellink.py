@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--train_with_ignored', action='store_true')
     ap.add_argument('--train_dir', type=str, default=None)
@@ -46,7 +46,18 @@ def parse():
     ap.add_argument('--dataset_dir', type=str, default=None)
     ap.add_argument('--train_image_width', type=int, default=512)
     ap.add_argument('--train_image_height', type=int, default=512)
-    return ap.parse_args()
+    # not a reference flag (TF-1.4 trains in f32): the f16 loss scale, a number or "dynamic" (graph.DynamicLossScale:
+    # a step whose gradients overflow is skipped and the scale backs off; it grows again after a run of clean steps)
+    ap.add_argument('--loss_scale', type=_loss_scale_arg, default=1024.0)
+    return ap.parse_args(argv)
+
+
+def _loss_scale_arg(text):
+    from tensorflow_ocr_amd.graph import parse_loss_scale
+    try:
+        return parse_loss_scale(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def staircase_lr(step, base, breakpoints, decays):
@@ -120,7 +131,7 @@ def main():
     if FLAGS.lr_policy != 'staircase':
         raise SystemExit('Unkonw lr_policy: {}'.format(FLAGS.lr_policy))
 
-    g = Graph(device, seed=1)
+    g = Graph(device, loss_scale=FLAGS.loss_scale, seed=1)
 
     def forward_loss(gr, im, pixel_labels, link_labels):
         net = pixellink.PixelLinkNet(im, graph=gr, input_norm=INPUT_NORM)   # raw images in
@@ -156,6 +167,8 @@ def main():
             if rank == 0:
                 print('global step %d: loss = %.4f (%.3f sec/step), lr %.6f' % (
                     it, v, dt, staircase_lr(it, FLAGS.learning_rate, bps, dcs)), flush=True)
+                if g.loss_scaler is not None:       # (the loss was just read: one more device read costs nothing here)
+                    print('loss scale %g, %d steps skipped' % (g.loss_scaler.scale(), g.loss_scaler.skipped_steps()), flush=True)
             if dist.any_rank(bool(np.isnan(v))):     # collective: no rank leaves the all-reduce alone
                 break
         if FLAGS.train_dir and rank == 0 and it > 0 and it % 1000 == 0:
