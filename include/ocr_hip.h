@@ -29,7 +29,8 @@ extern "C" {
  * New entry points do not bump it: ocr_conv2d_f32_split / ocr_conv2d_f32_split_workspace (the f16x2 precision) joined at 7,
  * and so did ocr_conv2d_f32_mfma_ep / ocr_conv2d_f32_split_ep / ocr_subsample_f32 (the folded inference batch norm) with
  * their flags OCR_CONV_AFFINE, OCR_CONV_RESIDUAL, OCR_CONV_ACCUM_IN: every older entry point ignores those bits; the dynamic
- * loss scale (ocr_loss_scale_init, ocr_grad_check_f32, the *_dyn optimiser steps and loss seeds) joined at 7 too. */
+ * loss scale (ocr_loss_scale_init, ocr_grad_check_f32, the *_dyn optimiser steps and loss seeds) joined at 7 too, and so
+ * did global-norm clipping (ocr_grad_clip_*, ocr_grad_check_clip_f32, the *_clip optimiser steps). */
 #define OCR_ABI_VERSION 7
 
 enum {
@@ -983,6 +984,63 @@ int ocr_adam_step_dyn(void* w, const void* g, void* m, void* v, void* ema, int64
 int ocr_momentum_step_dyn(void* w, const void* g, void* accum, void* ema, int64_t n,
                           int64_t n_regularized, float lr, float momentum, float weight_decay,
                           float grad_scale, float ema_decay, const void* state, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Global-norm gradient clipping, decided ON THE DEVICE (train.AdamOptimizer(clip_norm=c)).
+ * `base` is the factor the optimiser multiplies g with anyway: the host's grad_scale / loss_scale
+ * with a numeric loss scale, grad_scale * state.inv_scale_used with a dynamic one.
+ *   norm  = sqrt(sum_i (g[i] * base)^2)   product in f32 (the value the optimiser will use), square and sum
+ *                                         in f64 in a fixed order (bitwise reproducible), root in f64, stored f32
+ *   coef  = norm > clip_norm ? clip_norm / norm : 1.0f       (f32 division of the stored norm)
+ *   g_mul = base * coef                                      (what the *_clip steps multiply g with)
+ * A non-finite norm (an inf / NaN element, or a root above f32's range) sets skip = 1, coef = g_mul = 0 and counts in
+ * nonfinite_total: the *_clip steps then write nothing, with a numeric loss scale too.  Otherwise skip = 0, and
+ * clipped_total counts the steps with coef < 1.
+ *
+ * What is clipped is the gradient of the DATA loss.  The slim L2 term weight_decay * w is added inside the optimiser
+ * kernel, after the multiplication, and is not part of the norm: one read of the gradient buffer instead of two
+ * buffers, and the regulariser's share is about 1e-5 of |w|.
+ *
+ * Per step, numeric loss scale:  backward -> [all-reduce] -> ocr_grad_clip_f32 -> ocr_adam_step_clip /
+ * ocr_momentum_step_clip.  Dynamic: loss backward (_dyn) -> backward -> [all-reduce] -> ocr_grad_check_clip_f32 (ONE
+ * pass: the loss-scale transition of ocr_grad_check_f32, then the clip rule) -> the same *_clip step.  No host read
+ * anywhere; every call is capturable and a recorded plan never changes.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  float    g_mul;            /* base * coef: the optimiser's factor for this step */
+  float    norm;             /* global norm of g * base (inf / NaN when skip == 1) */
+  float    coef;             /* 1.0f exactly when the step was not clipped */
+  uint32_t skip;             /* 1: non-finite norm, the *_clip steps leave everything as it is */
+  uint32_t clipped_total;    /* steps with coef < 1 since ocr_grad_clip_init */
+  uint32_t nonfinite_total;  /* steps with skip == 1 since ocr_grad_clip_init */
+  uint32_t ticket;           /* workgroups of the running pass that have finished; 0 between calls */
+  uint32_t reserved;
+} ocr_grad_clip_state;       /* 8 x 32-bit words; 4-byte aligned device memory */
+/* every word 0 */
+int ocr_grad_clip_init(void* clip_state, void* stream);
+/* bytes of the f64 per-workgroup partials for a gradient buffer of n elements (any alignment of it) */
+size_t ocr_grad_clip_workspace(int64_t n);
+/* The static form: one streaming pass shaped like ocr_grad_check_f32 (16-byte loads; grad needs 4-byte alignment only,
+ * head and n & 3 tail are read one by one).  Every workgroup stores its partial in `workspace` (8-byte aligned,
+ * caller-owned: not shared with a call that may run concurrently); the one that draws the last ticket sums them,
+ * applies the rule above and puts the ticket back to 0.  clip_norm must be finite and > 0. */
+int ocr_grad_clip_f32(const void* grad, int64_t n, void* clip_state, float clip_norm, float base, void* workspace,
+                      size_t ws_bytes, void* stream);
+/* The dynamic form: ocr_grad_check_f32 and ocr_grad_clip_f32 in the same single pass, base = grad_scale * (1 / state.scale)
+ * (the scale is read before the workgroup draws its ticket; it moves only behind the last one).  `state` ends exactly
+ * as ocr_grad_check_f32 leaves it; when it says skip, so does clip_state.  The ticket is the clip state's. */
+int ocr_grad_check_clip_f32(const void* grad, int64_t n, void* state, float growth_factor, float backoff_factor,
+                            int growth_interval, float min_scale, float max_scale, void* clip_state, float clip_norm,
+                            float grad_scale, void* workspace, size_t ws_bytes, void* stream);
+/* ocr_adam_step / ocr_momentum_step guarded by the clip state: nothing is written when clip_state->skip == 1; otherwise
+ * g is multiplied by clip_state->g_mul (which carries grad_scale and, in the dynamic mode, 1 / scale: these entries
+ * serve both modes) and the update is the same expression in the same order. */
+int ocr_adam_step_clip(void* w, const void* g, void* m, void* v, void* ema, int64_t n,
+                       int64_t n_regularized, float lr_t, float beta1, float beta2, float eps,
+                       float weight_decay, float ema_decay, const void* clip_state, void* stream);
+int ocr_momentum_step_clip(void* w, const void* g, void* accum, void* ema, int64_t n,
+                           int64_t n_regularized, float lr, float momentum, float weight_decay,
+                           float ema_decay, const void* clip_state, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Data-parallel exchange.  Replaces `average_gradients`

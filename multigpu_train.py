@@ -40,7 +40,18 @@ def parse(argv=None):
     # not a reference flag (TF-1.4 trains in f32): the f16 loss scale, a number or "dynamic" (graph.DynamicLossScale:
     # a step whose gradients overflow is skipped and the scale backs off; it grows again after a run of clean steps)
     ap.add_argument('--loss_scale', type=_loss_scale_arg, default=1024.0)
+    # not a reference flag: clip the un-scaled gradients to this global L2 norm on the device (train.GradClip); a step whose
+    # norm is not finite is skipped.  Off by default.
+    ap.add_argument('--clip_norm', type=_clip_norm_arg, default=None)
     return ap.parse_args(argv)
+
+
+def _clip_norm_arg(text):
+    from tensorflow_ocr_amd.train import check_clip_norm
+    try:
+        return check_clip_norm(float(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def _loss_scale_arg(text):
@@ -98,7 +109,8 @@ def main():
     g = Graph(device, loss_scale=FLAGS.loss_scale, seed=1)
     step = TrainStep(g, build_forward_loss(FLAGS.net),
                      lambda gr: AdamOptimizer(gr, learning_rate=FLAGS.learning_rate,
-                                              moving_average_decay=FLAGS.moving_average_decay),
+                                              moving_average_decay=FLAGS.moving_average_decay,
+                                              clip_norm=FLAGS.clip_norm),
                      world_size=world)
     rng = np.random.default_rng(1000 + rank)
     feeder = None
@@ -176,6 +188,8 @@ def _train_loop(FLAGS, g, step, feeder, rng, rank, world, device, start):
                 if g.loss_scaler is not None:       # (the loss was just read: one more device read costs nothing here)
                     print('loss scale {:g}, {:d} steps skipped'.format(g.loss_scaler.scale(), g.loss_scaler.skipped_steps()),
                           flush=True)
+                if opt.clip is not None:
+                    print('grad norm {:.4g}, {:d} steps clipped'.format(opt.grad_norm(), opt.clipped_steps()), flush=True)
         if rank == 0 and it % FLAGS.save_checkpoint_steps == 0:     # step 0 included (multigpu_train.py:185-186)
             # saver.save(sess, FLAGS.checkpoint_path + 'model.ckpt', global_step=global_step) (:186-187):
             # a TensorFlow V2 bundle of Saver(tf.global_variables()) — variables, EMA shadows, Adam slots

@@ -39,6 +39,20 @@ __device__ __forceinline__ bool step_guard_dyn(const P& a, float* inv_scale) {
 }
 __device__ __forceinline__ bool step_guard(const AdamDynP& a, float* inv_scale) { return step_guard_dyn(a, inv_scale); }
 
+// Global-norm clipping (ocr_grad_clip_state, include/ocr_hip.h): a third parameter block for the same bodies.  The factor
+// comes whole from the device: g_mul = base * coef already carries the host factor and, in the dynamic mode, 1 / scale,
+// so one instantiation serves a numeric and a dynamic loss scale (inv_scale of the block is not read).
+struct AdamClipP : AdamP {
+  const ocr_grad_clip_state* cs;
+};
+template <class P>
+__device__ __forceinline__ bool step_guard_clip(const P& a, float* inv_scale) {
+  if (a.cs->skip) return true;                          // uniform, as in step_guard_dyn
+  *inv_scale = a.cs->g_mul;
+  return false;
+}
+__device__ __forceinline__ bool step_guard(const AdamClipP& a, float* inv_scale) { return step_guard_clip(a, inv_scale); }
+
 template <class P>
 __global__ void adam_kernel(P a, float* __restrict__ w, const float* __restrict__ g,
                             float* __restrict__ m, float* __restrict__ v,
@@ -71,6 +85,10 @@ struct MomDynP : MomP {
   const ocr_loss_scale_state* st;
 };
 __device__ __forceinline__ bool step_guard(const MomDynP& a, float* inv_scale) { return step_guard_dyn(a, inv_scale); }
+struct MomClipP : MomP {
+  const ocr_grad_clip_state* cs;
+};
+__device__ __forceinline__ bool step_guard(const MomClipP& a, float* inv_scale) { return step_guard_clip(a, inv_scale); }
 
 template <class P>
 __global__ void momentum_kernel(P a, float* __restrict__ w, const float* __restrict__ g,
@@ -234,6 +252,29 @@ __device__ __forceinline__ unsigned nonfinite(float v) {          // exponent fi
   return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
 }
 
+// The transition of the loss-scale state, run by the one thread behind the last ticket (and behind its fence):
+// grad_check_kernel and the fused grad_clip_kernel<true> both end in it.  Returns `found`; st->inv_scale_used then holds
+// 1 / (the scale the checked gradients were produced with).  The caller owns the ticket word it drew from.
+__device__ __forceinline__ unsigned loss_scale_transition(ocr_loss_scale_state* __restrict__ st, const GradCheckP& p) {
+  const unsigned found = __hip_atomic_load(&st->found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  float scale = st->scale;
+  unsigned good = st->good_steps;
+  __hip_atomic_store(&st->inv_scale_used, 1.f / scale, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (found) {
+    scale = fmaxf(scale * p.backoff, p.min_scale);
+    good = 0;
+    __hip_atomic_store(&st->skipped_total, st->skipped_total + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else if (++good == p.interval) {
+    scale = fminf(scale * p.growth, p.max_scale);
+    good = 0;
+  }
+  __hip_atomic_store(&st->skip, found ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&st->scale, scale, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&st->good_steps, good, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&st->found, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return found;
+}
+
 // One HBM-bound read of the flat gradient buffer, shaped like sumsq_partial_kernel.  A workgroup that saw a
 // non-finite element ORs `found` (one agent-scope atomic) and fences before it draws its ticket; clean workgroups
 // have nothing to publish and only draw.  All ticket operations are read-modify-writes on one word, so the
@@ -262,23 +303,102 @@ __global__ __launch_bounds__(256) void grad_check_kernel(const float* __restrict
   const unsigned t = __hip_atomic_fetch_add(&st->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (t != gridDim.x - 1) return;
   __threadfence();
-  const unsigned found = __hip_atomic_load(&st->found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  float scale = st->scale;
-  unsigned good = st->good_steps;
-  __hip_atomic_store(&st->inv_scale_used, 1.f / scale, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (found) {
-    scale = fmaxf(scale * p.backoff, p.min_scale);
-    good = 0;
-    __hip_atomic_store(&st->skipped_total, st->skipped_total + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else if (++good == p.interval) {
-    scale = fminf(scale * p.growth, p.max_scale);
-    good = 0;
-  }
-  __hip_atomic_store(&st->skip, found ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(&st->scale, scale, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(&st->good_steps, good, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(&st->found, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  loss_scale_transition(st, p);
   __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- global-norm gradient clipping: the device-side rule (ocr_grad_clip_state, include/ocr_hip.h) -------------------
+__global__ void grad_clip_init_kernel(ocr_grad_clip_state* cs) {
+  if (threadIdx.x < 8) reinterpret_cast<uint32_t*>(cs)[threadIdx.x] = 0u;
+}
+
+struct GradClipP {
+  GradCheckP c;                 // head / n4 / tail; the loss-scale constants are read by the fused form only
+  float clip_norm;
+  float base;                   // static form: the optimiser's host factor; fused form: grad_scale (base = grad_scale * (1 / scale))
+};
+
+// sum over one element: the product the optimiser will use, in f32; its square and the sum in f64
+__device__ __forceinline__ double clip_acc(double acc, float g, float base) {
+  const double a = (double)(g * base);
+  return fma(a, a, acc);
+}
+
+// grad_check_kernel's streaming pass with the squared norm of g * base summed beside it (FUSED: the non-finite test
+// stays, for the loss-scale transition; the static form needs none: inf and NaN survive the sum).  Every workgroup
+// stores its f64 partial write-through, releases, and draws a ticket from the CLIP state; the workgroup behind the
+// last ticket acquires, sums the partials (thread t takes t, t + 256, ... in rising order, then the fixed
+// block_sum_256 tree: the same bits on every call), and its thread 0 performs the transition(s).  FUSED reads
+// ls->scale in every thread before its workgroup draws: the scale moves only behind the last ticket.
+template <bool FUSED>
+__global__ __launch_bounds__(256) void grad_clip_kernel(const float* __restrict__ x, GradClipP p,
+                                                        ocr_grad_clip_state* __restrict__ cs,
+                                                        ocr_loss_scale_state* ls, double* partial) {
+  __shared__ double sh[4];
+  __shared__ unsigned last;
+  float base = p.base;
+  if (FUSED) base = p.base * (1.f / __hip_atomic_load(&ls->scale, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  unsigned bad = 0;
+  double acc = 0.0;
+  const float4* x4 = reinterpret_cast<const float4*>(x + p.c.head);
+#pragma unroll 4
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < p.c.n4; i += (long long)gridDim.x * 256) {
+    const float4 v = x4[i];
+    if (FUSED) bad |= nonfinite(v.x) | nonfinite(v.y) | nonfinite(v.z) | nonfinite(v.w);
+    acc = clip_acc(clip_acc(clip_acc(clip_acc(acc, v.x, base), v.y, base), v.z, base), v.w, base);
+  }
+  if (blockIdx.x == 0) {
+    if (threadIdx.x < p.c.head) {
+      const float v = x[threadIdx.x];
+      if (FUSED) bad |= nonfinite(v);
+      acc = clip_acc(acc, v, base);
+    }
+    if (threadIdx.x < p.c.tail) {
+      const float v = x[p.c.head + (p.c.n4 << 2) + threadIdx.x];
+      if (FUSED) bad |= nonfinite(v);
+      acc = clip_acc(acc, v, base);
+    }
+  }
+  const double t = block_sum_256(acc, sh);
+  if (FUSED) bad = __syncthreads_or((int)bad);
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(&partial[blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (FUSED && bad) __hip_atomic_fetch_or(&ls->found, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned k = __hip_atomic_fetch_add(&cs->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned l = k == gridDim.x - 1;
+    if (l) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    last = l;
+  }
+  __syncthreads();                    // (also: every thread is done with sh before the second sum writes it)
+  if (!last) return;
+  double s = 0.0;
+  for (unsigned i = threadIdx.x; i < gridDim.x; i += 256)
+    s += __hip_atomic_load(&partial[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  s = block_sum_256(s, sh);
+  if (threadIdx.x != 0) return;
+  unsigned found = 0;
+  if (FUSED) found = loss_scale_transition(ls, p.c);           // base above IS grad_scale * the inv_scale_used it stored
+  const float norm = (float)sqrt(s);                           // root in f64; above f32's range the store is inf
+  const unsigned skip = found | nonfinite(norm);
+  float coef = 0.f, g_mul = 0.f;
+  if (!skip) {
+    coef = norm > p.clip_norm ? p.clip_norm / norm : 1.f;
+    g_mul = base * coef;
+  }
+  __hip_atomic_store(&cs->norm, norm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&cs->coef, coef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&cs->g_mul, g_mul, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&cs->skip, skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (skip)
+    __hip_atomic_store(&cs->nonfinite_total, cs->nonfinite_total + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else if (coef < 1.f)
+    __hip_atomic_store(&cs->clipped_total, cs->clipped_total + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&cs->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 unsigned sumsq_grid(long long n) {
@@ -293,6 +413,23 @@ unsigned ogrid(long long n) {
   if (b > 4096) b = 4096;
   if (b < 1) b = 1;
   return (unsigned)b;
+}
+
+// grad_clip_kernel: at most 2048 workgroups (8 resident per CU on 256 CUs): each publishes one partial behind one
+// release, so fewer, longer-lived workgroups than grad_check_kernel's 4096
+unsigned clip_grid(long long n4) {
+  long long b = (n4 + 255) / 256;
+  if (b > 2048) b = 2048;
+  if (b < 1) b = 1;
+  return (unsigned)b;
+}
+
+GradCheckP split_head_tail(const void* grad, long long n, GradCheckP p) {
+  p.head = (long long)(((16 - ((uintptr_t)grad & 15)) & 15) >> 2);       // 0..3 elements up to the 16-byte boundary
+  if (p.head > n) p.head = n;
+  p.n4 = (n - p.head) >> 2;
+  p.tail = (n - p.head) & 3;
+  return p;
 }
 
 }  // namespace
@@ -412,11 +549,8 @@ extern "C" int ocr_grad_check_f32(const void* grad, int64_t n, void* state, floa
   OCR_CHECK_ARG(grad && state && n > 0 && ((uintptr_t)grad & 3) == 0 && ((uintptr_t)state & 3) == 0);
   OCR_CHECK_ARG(growth_factor >= 1.f && backoff_factor > 0.f && backoff_factor <= 1.f && growth_interval > 0);
   OCR_CHECK_ARG(min_scale > 0.f && min_scale <= max_scale && max_scale <= 3.4028234664e38f);
-  GradCheckP p{growth_factor, backoff_factor, min_scale, max_scale, (unsigned)growth_interval, 0, 0, 0};
-  p.head = (long long)(((16 - ((uintptr_t)grad & 15)) & 15) >> 2);       // 0..3 elements up to the 16-byte boundary
-  if (p.head > n) p.head = n;
-  p.n4 = (n - p.head) >> 2;
-  p.tail = (n - p.head) & 3;
+  const GradCheckP p = split_head_tail(grad, n, GradCheckP{growth_factor, backoff_factor, min_scale, max_scale,
+                                                           (unsigned)growth_interval, 0, 0, 0});
   hipLaunchKernelGGL(grad_check_kernel, dim3(ogrid(p.n4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<const float*>(grad), p, static_cast<ocr_loss_scale_state*>(state));
   return ocr_launch_status();
@@ -442,6 +576,79 @@ extern "C" int ocr_momentum_step_dyn(void* w, const void* g, void* accum, void* 
   MomDynP a{{lr, momentum, weight_decay, grad_scale, ema_decay, n, n_regularized},
             static_cast<const ocr_loss_scale_state*>(state)};
   hipLaunchKernelGGL(momentum_kernel<MomDynP>, dim3(ogrid(n)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), a, static_cast<float*>(w),
+                     static_cast<const float*>(g), static_cast<float*>(accum),
+                     static_cast<float*>(ema));
+  return ocr_launch_status();
+}
+
+// ---- global-norm gradient clipping -------------------------------------------------------------------------------
+extern "C" int ocr_grad_clip_init(void* clip_state, void* stream) {
+  OCR_CHECK_ARG(clip_state && ((uintptr_t)clip_state & 3) == 0);
+  hipLaunchKernelGGL(grad_clip_init_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream),
+                     static_cast<ocr_grad_clip_state*>(clip_state));
+  return ocr_launch_status();
+}
+
+// (the head in front of the 16-byte boundary only ever lowers the float4 count: n / 4 bounds the grid of any alignment)
+extern "C" size_t ocr_grad_clip_workspace(int64_t n) { return (size_t)clip_grid(n > 0 ? n / 4 : 0) * sizeof(double); }
+
+static int grad_clip_args(const void* grad, int64_t n, const void* clip_state, float clip_norm, const void* workspace,
+                          size_t ws_bytes) {
+  OCR_CHECK_ARG(grad && clip_state && workspace && n > 0);
+  OCR_CHECK_ARG(((uintptr_t)grad & 3) == 0 && ((uintptr_t)clip_state & 3) == 0 && ((uintptr_t)workspace & 7) == 0);
+  OCR_CHECK_ARG(clip_norm > 0.f && clip_norm <= 3.4028234664e38f);                  // (false for NaN)
+  if (ws_bytes < ocr_grad_clip_workspace(n)) return OCR_ERR_WORKSPACE;
+  return OCR_OK;
+}
+
+extern "C" int ocr_grad_clip_f32(const void* grad, int64_t n, void* clip_state, float clip_norm, float base,
+                                 void* workspace, size_t ws_bytes, void* stream) {
+  const int rc = grad_clip_args(grad, n, clip_state, clip_norm, workspace, ws_bytes);
+  if (rc != OCR_OK) return rc;
+  const GradClipP p{split_head_tail(grad, n, GradCheckP{}), clip_norm, base};
+  hipLaunchKernelGGL(grad_clip_kernel<false>, dim3(clip_grid(p.c.n4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const float*>(grad), p, static_cast<ocr_grad_clip_state*>(clip_state),
+                     static_cast<ocr_loss_scale_state*>(nullptr), static_cast<double*>(workspace));
+  return ocr_launch_status();
+}
+
+extern "C" int ocr_grad_check_clip_f32(const void* grad, int64_t n, void* state, float growth_factor, float backoff_factor,
+                                       int growth_interval, float min_scale, float max_scale, void* clip_state,
+                                       float clip_norm, float grad_scale, void* workspace, size_t ws_bytes, void* stream) {
+  OCR_CHECK_ARG(state && ((uintptr_t)state & 3) == 0 && state != clip_state);
+  OCR_CHECK_ARG(growth_factor >= 1.f && backoff_factor > 0.f && backoff_factor <= 1.f && growth_interval > 0);
+  OCR_CHECK_ARG(min_scale > 0.f && min_scale <= max_scale && max_scale <= 3.4028234664e38f);
+  const int rc = grad_clip_args(grad, n, clip_state, clip_norm, workspace, ws_bytes);
+  if (rc != OCR_OK) return rc;
+  const GradClipP p{split_head_tail(grad, n, GradCheckP{growth_factor, backoff_factor, min_scale, max_scale,
+                                                        (unsigned)growth_interval, 0, 0, 0}),
+                    clip_norm, grad_scale};
+  hipLaunchKernelGGL(grad_clip_kernel<true>, dim3(clip_grid(p.c.n4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const float*>(grad), p, static_cast<ocr_grad_clip_state*>(clip_state),
+                     static_cast<ocr_loss_scale_state*>(state), static_cast<double*>(workspace));
+  return ocr_launch_status();
+}
+
+extern "C" int ocr_adam_step_clip(void* w, const void* g, void* m, void* v, void* ema, int64_t n,
+                                  int64_t n_regularized, float lr_t, float beta1, float beta2, float eps,
+                                  float weight_decay, float ema_decay, const void* clip_state, void* stream) {
+  OCR_CHECK_ARG(w && g && m && v && clip_state && n > 0 && n_regularized >= 0 && n_regularized <= n);
+  AdamClipP a{{lr_t, beta1, beta2, eps, weight_decay, 0.f, ema_decay, n, n_regularized},
+              static_cast<const ocr_grad_clip_state*>(clip_state)};
+  hipLaunchKernelGGL(adam_kernel<AdamClipP>, dim3(ogrid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), a,
+                     static_cast<float*>(w), static_cast<const float*>(g), static_cast<float*>(m),
+                     static_cast<float*>(v), static_cast<float*>(ema));
+  return ocr_launch_status();
+}
+
+extern "C" int ocr_momentum_step_clip(void* w, const void* g, void* accum, void* ema, int64_t n,
+                                      int64_t n_regularized, float lr, float momentum, float weight_decay,
+                                      float ema_decay, const void* clip_state, void* stream) {
+  OCR_CHECK_ARG(w && g && accum && clip_state && n > 0 && n_regularized >= 0 && n_regularized <= n);
+  MomClipP a{{lr, momentum, weight_decay, 0.f, ema_decay, n, n_regularized},
+             static_cast<const ocr_grad_clip_state*>(clip_state)};
+  hipLaunchKernelGGL(momentum_kernel<MomClipP>, dim3(ogrid(n)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), a, static_cast<float*>(w),
                      static_cast<const float*>(g), static_cast<float*>(accum),
                      static_cast<float*>(ema));

@@ -1157,6 +1157,48 @@ def momentum_step_dyn(w, g, acc, ema, n_reg, lr, momentum, wd, grad_scale, ema_d
            c_float(lr), c_float(momentum), c_float(wd), c_float(grad_scale), c_float(ema_decay), ptr(state), _st())
 
 
+# global-norm gradient clipping: `clip_state` is the 8-word device block ocr_grad_clip_state (include/ocr_hip.h) as an
+# int32 tensor, `ws` a float64 tensor of grad_clip_workspace(n) bytes that belongs to the caller (no arena: a recorded
+# plan replays its address)
+GRAD_CLIP_WORDS = 8
+GC_G_MUL, GC_NORM, GC_COEF, GC_SKIP, GC_CLIPPED_TOTAL, GC_NONFINITE_TOTAL, GC_TICKET = range(7)
+
+
+def grad_clip_init(clip_state):
+    assert clip_state.numel() >= GRAD_CLIP_WORDS and clip_state.element_size() == 4
+    L.call("ocr_grad_clip_init", ptr(clip_state), _st())
+
+
+def grad_clip_workspace(n):
+    """Bytes of the f64 partials for a gradient buffer of n elements."""
+    return L.call_size("ocr_grad_clip_workspace", c_int64(n))
+
+
+def grad_clip(grad, clip_state, clip_norm, base, ws):
+    """One pass over the f32 buffer `grad`: norm of grad * base, coef, g_mul = base * coef and skip into `clip_state`."""
+    L.call("ocr_grad_clip_f32", ptr(grad), c_int64(grad.numel()), ptr(clip_state), c_float(clip_norm), c_float(base),
+           ptr(ws), c_size_t(ws.numel() * ws.element_size()), _st())
+
+
+def grad_check_clip(grad, state, growth_factor, backoff_factor, growth_interval, min_scale, max_scale, clip_state, clip_norm,
+                    grad_scale, ws):
+    """grad_check and grad_clip in the same single pass, base = grad_scale / (the scale the gradients were produced with)."""
+    L.call("ocr_grad_check_clip_f32", ptr(grad), c_int64(grad.numel()), ptr(state), c_float(growth_factor),
+           c_float(backoff_factor), c_int(growth_interval), c_float(min_scale), c_float(max_scale), ptr(clip_state),
+           c_float(clip_norm), c_float(grad_scale), ptr(ws), c_size_t(ws.numel() * ws.element_size()), _st())
+
+
+def adam_step_clip(w, g, m, v, ema, n_reg, lr_t, beta1, beta2, eps, wd, ema_decay, clip_state):
+    L.call("ocr_adam_step_clip", ptr(w), ptr(g), ptr(m), ptr(v), ptr(ema), c_int64(w.numel()),
+           c_int64(n_reg), c_float(lr_t), c_float(beta1), c_float(beta2), c_float(eps), c_float(wd),
+           c_float(ema_decay), ptr(clip_state), _st())
+
+
+def momentum_step_clip(w, g, acc, ema, n_reg, lr, momentum, wd, ema_decay, clip_state):
+    L.call("ocr_momentum_step_clip", ptr(w), ptr(g), ptr(acc), ptr(ema), c_int64(w.numel()), c_int64(n_reg),
+           c_float(lr), c_float(momentum), c_float(wd), c_float(ema_decay), ptr(clip_state), _st())
+
+
 def scale_(x, s):
     L.call("ocr_scale_f32", ptr(x), c_int64(x.numel()), c_float(s), _st())
 

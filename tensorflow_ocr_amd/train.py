@@ -46,12 +46,85 @@ def _regularization_loss(opt):
     return opt._reg_out
 
 
-class AdamOptimizer:
+class GradClip:
+    """Global-norm gradient clipping decided on the device (ocr_grad_clip_state, include/ocr_hip.h): the optimisers'
+    `clip_norm=c`.  Per step one pass over the reduced flat gradient buffer leaves norm = |g * base|, coef =
+    min(1, c / norm) and g_mul = base * coef in an 8-word device block — fused into the dynamic loss scale's check pass
+    where one runs, a pass of its own with a numeric loss scale — and the `_clip` optimiser kernel multiplies g with
+    g_mul, or writes nothing when the norm is not finite.  `base` is the factor the optimiser applies anyway (grad_scale /
+    loss_scale), so the clipped quantity is the un-scaled gradient of the DATA loss; the L2 term weight_decay * w is
+    added inside the optimiser kernel and is not part of the norm.  No host read on the path.
+
+    The state block and the f64 partials are allocated here, once: a recorded plan replays their addresses.  Nothing of
+    this is checkpointed: `clip_norm` is a flag, the counters are diagnostics."""
+
+    def __init__(self, clip_norm, flat_grad):
+        self.clip_norm = check_clip_norm(clip_norm)
+        self.state = torch.zeros(ops.GRAD_CLIP_WORDS, dtype=torch.int32, device=flat_grad.device)     # = ocr_grad_clip_init
+        self.ws = torch.empty(max(1, ops.grad_clip_workspace(flat_grad.numel()) // 8), dtype=torch.float64,
+                              device=flat_grad.device)
+
+    def run(self, graph, grad, grad_scale):
+        """The clip pass on `grad`; afterwards the `_clip` step reads `self.state`."""
+        sc = graph.loss_scaler
+        if sc is not None:
+            ops.grad_check_clip(grad, sc.state, sc.growth_factor, sc.backoff_factor, sc.growth_interval, sc.min_scale,
+                                sc.max_scale, self.state, self.clip_norm, grad_scale, self.ws)
+        else:
+            ops.grad_clip(grad, self.state, self.clip_norm, grad_scale / graph.loss_scale, self.ws)
+
+    def _words(self):
+        return self.state.cpu().numpy()
+
+    def grad_norm(self):
+        return float(self._words()[ops.GC_NORM:ops.GC_NORM + 1].view(np.float32)[0])
+
+    def clipped_steps(self):
+        return int(self._words()[ops.GC_CLIPPED_TOTAL])
+
+    def nonfinite_steps(self):
+        return int(self._words()[ops.GC_NONFINITE_TOTAL])
+
+
+def check_clip_norm(clip_norm):
+    """A finite number > 0 as a float, ValueError otherwise."""
+    v = clip_norm
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v <= 0:
+        raise ValueError("clip_norm must be a positive finite number (or None: no clipping), got %r" % (clip_norm,))
+    if float(v) > float(np.finfo(np.float32).max) or float(v) < float(np.finfo(np.float32).tiny):
+        raise ValueError("clip_norm %r is outside float32's range" % (clip_norm,))
+    return float(v)
+
+
+class _ClipReadout:
+    """grad_norm() / clipped_steps() / nonfinite_steps() of an optimiser built with clip_norm: each READS THE DEVICE (a
+    sync), for logging only."""
+
+    def _clip_or_raise(self):
+        if self.clip is None:
+            raise RuntimeError("this optimiser was built without clip_norm")
+        return self.clip
+
+    def grad_norm(self):
+        """Global norm of the un-scaled gradients of the LAST step (inf / NaN: that step was skipped)."""
+        return self._clip_or_raise().grad_norm()
+
+    def clipped_steps(self):
+        return self._clip_or_raise().clipped_steps()
+
+    def nonfinite_steps(self):
+        return self._clip_or_raise().nonfinite_steps()
+
+
+class AdamOptimizer(_ClipReadout):
     """tf.train.AdamOptimizer + ExponentialMovingAverage(decay, num_updates=global_step) + slim L2
     regulariser gradient, as ONE fused launch over the tower's flat parameter buffer."""
 
     def __init__(self, graph, learning_rate=1e-4, decay_steps=5000, decay_rate=0.94,
-                 moving_average_decay=0.997, weight_decay=1e-5, beta1=0.9, beta2=0.999, epsilon=1e-8):
+                 moving_average_decay=0.997, weight_decay=1e-5, beta1=0.9, beta2=0.999, epsilon=1e-8,
+                 clip_norm=None):
+        if clip_norm is not None:
+            check_clip_norm(clip_norm)               # before anything is allocated
         self.g = graph
         graph.ensure_materialised()
         st = graph.store
@@ -61,6 +134,7 @@ class AdamOptimizer:
         self.lr0, self.decay_steps, self.decay_rate = learning_rate, decay_steps, decay_rate
         self.mad, self.wd = moving_average_decay, weight_decay
         self.b1, self.b2, self.eps = beta1, beta2, epsilon
+        self.clip = GradClip(clip_norm, st.flat_grad) if clip_norm is not None else None
         self.global_step = 0
 
     def learning_rate(self):
@@ -73,7 +147,13 @@ class AdamOptimizer:
         lr_t = lr * math.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
         ema_d = min(self.mad, (1.0 + self.global_step) / (10.0 + self.global_step)) if self.mad else 0.0
         scaler = self.g.loss_scaler
-        if scaler is not None:
+        if self.clip is not None:
+            # global-norm clipping (GradClip): with a scaler its check pass also sums the norm, two launches as without
+            # clipping; with a numeric loss scale the clip pass is one launch more.  The step reads g_mul / skip.
+            self.clip.run(self.g, st.flat_grad, grad_scale)
+            ops.adam_step_clip(st.flat, st.flat_grad, self.m, self.v, self.ema, st.n_reg, lr_t, self.b1, self.b2,
+                               self.eps, self.wd, ema_d, self.clip.state)
+        elif scaler is not None:
             # dynamic loss scaling (graph.DynamicLossScale): the check sees the REDUCED gradients (inf / NaN survive a sum
             # all-reduce, so every rank decides alike), the guarded step writes nothing when it found one.  The host
             # counters below advance either way: no device read in the step.
@@ -117,16 +197,19 @@ class AdamOptimizer:
         return _regularization_loss(self)
 
 
-class MomentumOptimizer:
+class MomentumOptimizer(_ClipReadout):
     """tf.train.MomentumOptimizer(lr, 0.9) with the PixelLink schedule (train_pixellink.py:222-243)."""
 
-    def __init__(self, graph, base_lr=0.01, momentum=0.9, weight_decay=5e-4, moving_average_decay=None):
+    def __init__(self, graph, base_lr=0.01, momentum=0.9, weight_decay=5e-4, moving_average_decay=None, clip_norm=None):
+        if clip_norm is not None:
+            check_clip_norm(clip_norm)
         self.g = graph
         graph.ensure_materialised()
         st = graph.store
         self.acc = torch.zeros_like(st.flat)
         self.ema = st.flat.clone() if moving_average_decay else None
         self.base_lr, self.momentum, self.wd, self.mad = base_lr, momentum, weight_decay, moving_average_decay
+        self.clip = GradClip(clip_norm, st.flat_grad) if clip_norm is not None else None
         self.global_step = 0
 
     def learning_rate(self):
@@ -159,7 +242,11 @@ class MomentumOptimizer:
         st = self.g.store
         ema_d = min(self.mad, (1.0 + self.global_step) / (10.0 + self.global_step)) if self.mad else 0.0
         scaler = self.g.loss_scaler
-        if scaler is not None:               # as in AdamOptimizer.apply_gradients
+        if self.clip is not None:            # as in AdamOptimizer.apply_gradients
+            self.clip.run(self.g, st.flat_grad, grad_scale)
+            ops.momentum_step_clip(st.flat, st.flat_grad, self.acc, self.ema, st.n_reg, self.learning_rate(),
+                                   self.momentum, self.wd, ema_d, self.clip.state)
+        elif scaler is not None:             # as in AdamOptimizer.apply_gradients
             scaler.check(st.flat_grad)
             ops.momentum_step_dyn(st.flat, st.flat_grad, self.acc, self.ema, st.n_reg, self.learning_rate(),
                                   self.momentum, self.wd, grad_scale, ema_d, scaler.state)

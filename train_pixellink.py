@@ -49,7 +49,18 @@ def parse(argv=None):
     # not a reference flag (TF-1.4 trains in f32): the f16 loss scale, a number or "dynamic" (graph.DynamicLossScale:
     # a step whose gradients overflow is skipped and the scale backs off; it grows again after a run of clean steps)
     ap.add_argument('--loss_scale', type=_loss_scale_arg, default=1024.0)
+    # not a reference flag: clip the un-scaled gradients to this global L2 norm on the device (train.GradClip); a step whose
+    # norm is not finite is skipped.  Off by default.
+    ap.add_argument('--clip_norm', type=_clip_norm_arg, default=None)
     return ap.parse_args(argv)
+
+
+def _clip_norm_arg(text):
+    from tensorflow_ocr_amd.train import check_clip_norm
+    try:
+        return check_clip_norm(float(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def _loss_scale_arg(text):
@@ -140,7 +151,8 @@ def main():
     def make_opt(gr):
         opt = MomentumOptimizer(gr, base_lr=FLAGS.learning_rate, momentum=FLAGS.momentum,
                                 weight_decay=FLAGS.weight_decay,
-                                moving_average_decay=FLAGS.moving_average_decay if FLAGS.using_moving_average else None)
+                                moving_average_decay=FLAGS.moving_average_decay if FLAGS.using_moving_average else None,
+                                clip_norm=FLAGS.clip_norm)
         opt.learning_rate = lambda: staircase_lr(opt.global_step, FLAGS.learning_rate, bps, dcs)
         return opt
     step = TrainStep(g, forward_loss, make_opt, world_size=world, grad_op="sum")
@@ -169,6 +181,8 @@ def main():
                     it, v, dt, staircase_lr(it, FLAGS.learning_rate, bps, dcs)), flush=True)
                 if g.loss_scaler is not None:       # (the loss was just read: one more device read costs nothing here)
                     print('loss scale %g, %d steps skipped' % (g.loss_scaler.scale(), g.loss_scaler.skipped_steps()), flush=True)
+                if step.opt.clip is not None:
+                    print('grad norm {:.4g}, {:d} steps clipped'.format(step.opt.grad_norm(), step.opt.clipped_steps()), flush=True)
             if dist.any_rank(bool(np.isnan(v))):     # collective: no rank leaves the all-reduce alone
                 break
         if FLAGS.train_dir and rank == 0 and it > 0 and it % 1000 == 0:
