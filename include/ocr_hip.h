@@ -30,7 +30,8 @@ extern "C" {
  * and so did ocr_conv2d_f32_mfma_ep / ocr_conv2d_f32_split_ep / ocr_subsample_f32 (the folded inference batch norm) with
  * their flags OCR_CONV_AFFINE, OCR_CONV_RESIDUAL, OCR_CONV_ACCUM_IN: every older entry point ignores those bits; the dynamic
  * loss scale (ocr_loss_scale_init, ocr_grad_check_f32, the *_dyn optimiser steps and loss seeds) joined at 7 too, and so
- * did global-norm clipping (ocr_grad_clip_*, ocr_grad_check_clip_f32, the *_clip optimiser steps). */
+ * did global-norm clipping (ocr_grad_clip_*, ocr_grad_check_clip_f32, the *_clip optimiser steps) and the batched training
+ * augmentation (ocr_augment_u8_batch, ocr_augment_desc). */
 #define OCR_ABI_VERSION 7
 
 enum {
@@ -912,6 +913,28 @@ int ocr_weights_s2d_grad_f32(const void* dw22_f32, int cin, int cout, void* dw33
  * datasets/icdar.py:615,630.  src uint8 [H][W][cn] -> dst f32 [dh][dw][cn]. */
 int ocr_resize_linear_u8(const void* src_u8, int H, int W, int cn, void* dst_f32, int dh, int dw,
                          void* stream);
+
+/* Training augmentation of a whole batch in ONE launch (the flow datasets/icdar.py:576-615 keeps under `if (0)`: random
+ * scale, crop_area :138-199, pad to a square, resize; plus rotations and colour distortion): an inverse-affine warp with a
+ * colour matrix from n uint8 RGB images of any size inside one slab to dst f32 [n][S][S][3].  `desc` is a DEVICE table of n
+ * records (8-byte aligned).  Per output pixel (dx, dy) of image b, all geometry in integers:
+ *     X16 = A[0]*dx + A[1]*dy + A[2],  Y16 = A[3]*dx + A[4]*dy + A[5]            (int64, 16.16 source coordinates)
+ *     X5 = (X16 + 1024) >> 11,  Y5 likewise                                      (arithmetic shift: floor)
+ *     sx = X5 >> 5, fx = X5 & 31, sy = Y5 >> 5, fy = Y5 & 31
+ *     taps (sx,sy) (sx+1,sy) (sx,sy+1) (sx+1,sy+1), weights (32-fx)(32-fy), fx(32-fy), (32-fx)fy, fx*fy (sum 1024);
+ *     a tap outside [0,W) x [0,H) contributes 0 and is not loaded: no address outside [src_off, src_off + 3*H*W) is formed
+ *     v_c = sum w*s_c (int),  p_c = (float)v_c * (1.0f/1024)                      (exact)
+ *     out_c = min(max(((col[c][0]*p_r + col[c][1]*p_g) + col[c][2]*p_b) + col[c][3], 0.f), 255.f)   (f32, in this order, no FMA)
+ * The half-pixel convention u = M(d + 0.5) - 0.5 is folded into A[2], A[5] by the host (datasets/augment.py).  float4 stores
+ * when S is a multiple of 4 and dst is 16-byte aligned, element stores otherwise.  OCR_ERR_INVALID_ARG for n <= 0, S <= 0
+ * or a null pointer; OCR_ERR_UNSUPPORTED for n > 65535 or S > 32768. */
+typedef struct {
+  int64_t src_off;            /* byte offset of the image (uint8 [H][W][3], RGB) in the slab */
+  int32_t H, W;
+  int64_t A[6];               /* inverse map, output pixel -> source pixel, 16.16 fixed point */
+  float col[3][4];            /* colour matrix and offset, applied to 0..255 values */
+} ocr_augment_desc;
+int ocr_augment_u8_batch(const void* slab_u8, const void* desc, int n, int S, void* dst_f32, void* stream);
 
 /* cv2.resize(plane, (dw, dh), interpolation=cv2.INTER_CUBIC) on float32 score maps, the up-sampling
  * of the full-resolution decode (test_pixellink.py:97-98 `b_score * 255` then resize = pre_scale 255;

@@ -11,7 +11,9 @@ PixelLink heads + OHNM loss, the one the reference script imports; `model_vgg` /
 `pixellink` the others).  Data: `--training_data_path` (the reference's icdar.py flag) feeds ICDAR
 images + gt_*.txt through datasets/icdar.get_batch — host decode in `--num_readers` processes,
 upload + resize + label maps on the feeder's HIP stream, overlapped with the step; without it (or
-with an empty directory) batches are synthetic (`tensorflow_ocr_amd.synthetic`).  The stdout line
+with an empty directory) batches are synthetic (`tensorflow_ocr_amd.synthetic`).  `--augment east`
+(or `pixellink`, or key=value,...) turns on the augmentation the reference keeps disabled
+(datasets/icdar.py:576-615), warped on the device in one launch per batch.  The stdout line
 format is the reference's (:183-184)."""
 import argparse
 import os
@@ -43,7 +45,18 @@ def parse(argv=None):
     # not a reference flag: clip the un-scaled gradients to this global L2 norm on the device (train.GradClip); a step whose
     # norm is not finite is skipped.  Off by default.
     ap.add_argument('--clip_norm', type=_clip_norm_arg, default=None)
+    # the augmentation the reference keeps disabled (datasets/icdar.py:576-615), on the device: none | east | pixellink |
+    # key=value,... (datasets/augment.py: Augment.parse).  Only with --training_data_path; synthetic batches have none.
+    ap.add_argument('--augment', type=_augment_arg, default=None, metavar='SPEC')
     return ap.parse_args(argv)
+
+
+def _augment_arg(text):
+    from tensorflow_ocr_amd.datasets.augment import Augment
+    try:
+        return Augment.parse(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def _clip_norm_arg(text):
@@ -120,7 +133,7 @@ def main():
             # multigpu_train.py:164-167: icdar.get_batch(num_workers, input_size, batch_size)
             feeder = icdar.get_batch(num_workers=FLAGS.num_readers, training_data_path=FLAGS.training_data_path,
                                      input_size=FLAGS.input_size, batch_size=FLAGS.batch_size_per_gpu,
-                                     graph=g, seed=1000 + rank)
+                                     graph=g, seed=1000 + rank, augment=FLAGS.augment)
     start = time.time()
     try:
         _train_loop(FLAGS, g, step, feeder, rng, rank, world, device, start)

@@ -82,8 +82,11 @@ def txt_name(im_fn):
 
 def load_sample(args):
     """One sample (icdar.py:559-571,616-619): decode, parse, validate, scale the polygons to the training size.
-    Returns None for a sample the reference skips, else (im_fn, image uint8 [H,W,3], polys float32 [k,4,2], tags bool [k])."""
-    im_fn, input_size = args
+    Returns None for a sample the reference skips, else (im_fn, image uint8 [H,W,3], polys float32 [k,4,2], tags bool [k]).
+    An optional third field of the job, when true, leaves the polygons in SOURCE pixels (the augmentation plan moves them:
+    datasets/augment.py)."""
+    im_fn, input_size = args[0], args[1]
+    raw = len(args) > 2 and bool(args[2])
     tf = txt_name(im_fn)
     if not os.path.exists(tf):
         return None
@@ -94,8 +97,9 @@ def load_sample(args):
         text_polys, text_tags = check_and_validate_polys(text_polys, text_tags, (h, w))
         if text_polys.shape[0] == 0:
             return None
-        text_polys[:, :, 0] *= input_size / float(w)
-        text_polys[:, :, 1] *= input_size / float(h)
+        if not raw:
+            text_polys[:, :, 0] *= input_size / float(w)
+            text_polys[:, :, 1] *= input_size / float(h)
     except Exception:                       # the reference prints the traceback and moves on (:646-649)
         import traceback
         traceback.print_exc()
@@ -131,8 +135,8 @@ def _worker_main(path, slots, slot_bytes):
         job = _recv(fin)
         if job is None:
             return
-        im_fn, input_size, slot = job
-        smp = load_sample((im_fn, input_size))
+        im_fn, input_size, slot = job[:3]
+        smp = load_sample((im_fn, input_size) + tuple(job[3:]))
         if smp is None:
             _send(fout, None)
             continue
@@ -230,9 +234,9 @@ class DecodePool:
             item = self.jobs.get()
             if item is None:
                 return
-            fut, im_fn, input_size, slot = item
+            fut, im_fn, input_size, slot, extra = item
             try:
-                _send(proc.stdin, (im_fn, input_size, slot))
+                _send(proc.stdin, (im_fn, input_size, slot) + extra)
                 res = _recv(proc.stdout)
                 if res is None:
                     self.free.put(slot)
@@ -250,12 +254,13 @@ class DecodePool:
                 fut.set_exception(e)
                 return
 
-    def submit(self, im_fn, input_size):
-        """Blocks while every slot is in use (back-pressure: at most `slots` decoded images wait for the consumer)."""
+    def submit(self, im_fn, input_size, *extra):
+        """Blocks while every slot is in use (back-pressure: at most `slots` decoded images wait for the consumer).
+        `extra`: the optional fields of a load_sample job, passed through."""
         from concurrent.futures import Future
         slot = self.free.get()
         fut = Future()
-        self.jobs.put((fut, im_fn, input_size, slot))
+        self.jobs.put((fut, im_fn, input_size, slot, tuple(extra)))
         return fut
 
     def release(self, slot):

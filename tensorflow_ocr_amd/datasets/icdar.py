@@ -7,8 +7,11 @@ Same function names and argument order as the reference where it has them:
   check_and_validate_polys  icdar.py:108-135
   generate_rbox             icdar.py:486-539 (one image, full resolution, NumPy results)
   generator / get_batch     icdar.py:542-668 (resize to input_size, BGR->RGB float, labels at 1/4)
-plus the batched device entry point the feeder uses:
+plus the batched device entry points the feeder uses:
   generate_rbox_batch       all images of a batch in two launches; device tensors at 1/4 resolution
+  augment_images            the augmentation the reference keeps disabled (icdar.py:576-615: random scale, crop_area,
+                            pad, resize) plus rotations and colour distortion: the policy draws a plan per sample on the
+                            host (datasets/augment.py), ONE launch warps the batch (ocr_augment_u8_batch)
 
 The reference rasterises with cv2.fillPoly and resizes with cv2.resize; here both run as HIP kernels
 (ocr_poly_cover / ocr_icdar_labels / ocr_resize_linear_u8) that reproduce OpenCV's rasters bit for bit
@@ -129,15 +132,47 @@ def resize_images(images_u8, input_size, graph=None):
     return out
 
 
+def augment_images(images_u8, plans, input_size, graph=None):
+    """The augmented counterpart of resize_images: a list of uint8 [H,W,3] images of any size and their plans
+    (datasets/augment.py: Augment.plan) -> device float32 [n,S,S,3] in ONE launch (ocr_augment_u8_batch).  Pixels and the
+    descriptor table share one pinned slab and cross PCIe in one asynchronous copy."""
+    from .augment import DESC_DTYPE, pack_desc
+    g = graph or get_default_graph()
+    n = len(images_u8)
+    out = torch.empty((n, input_size, input_size, 3), dtype=F32, device=g.device)
+    if n == 0:
+        return out
+    shapes = [tuple(im.shape) for im in images_u8]
+    sizes = [int(np.prod(s)) for s in shapes]
+    offs = [int(o) for o in np.cumsum([0] + sizes[:-1])]
+    pix = sum(sizes)
+    desc_off = (pix + 7) & ~7                                  # the table holds int64 fields
+    desc = pack_desc(offs, shapes, plans, pix)
+    slab = torch.empty(desc_off + DESC_DTYPE.itemsize * n, dtype=torch.uint8, pin_memory=(g.device.type == "cuda"))
+    host = slab.numpy()
+    for im, off, sz in zip(images_u8, offs, sizes):
+        host[off:off + sz] = np.asarray(im, dtype=np.uint8).reshape(-1)
+    host[pix:desc_off] = 0
+    host[desc_off:] = desc.view(np.uint8)
+    dev = slab.to(g.device, non_blocking=True)
+    ops.augment_u8_batch(dev[:pix], dev[desc_off:], n, input_size, out)
+    return out
+
+
 def generator(training_data_path, input_size=512, batch_size=32, graph=None, shuffle=True, seed=None,
-              num_workers=0, worker_kind=None):
+              num_workers=0, worker_kind=None, augment=None):
     """icdar.py:542-649 with the branches the reference has live (no random scale / crop: `if (0)`):
     read image + gt, validate polygons, resize to input_size x input_size, scale the polygons,
     labels at 1/4 resolution.  Yields (images [B,S,S,3] float32 RGB, image_fns, score_maps, geo_maps,
     training_masks) as DEVICE tensors (the reference yields lists of NumPy arrays).  num_workers > 0:
     that many decode workers run ahead (the reference's GeneratorEnqueuer workers) — worker_kind "process" (default;
     OCR_DECODE_WORKERS): plain interpreters that import NumPy + PIL only and hand the pixels over through a shared slab
-    (datasets/_decode.py: DecodePool); "thread": threads of this process (their Python parts serialise on the GIL)."""
+    (datasets/_decode.py: DecodePool); "thread": threads of this process (their Python parts serialise on the GIL).
+    augment: None = the path above, launch for launch; an augment.Augment = the flow the reference keeps disabled (:576-615)
+    and more: the decode jobs leave the polygons in source pixels, the plan of each sample (inverse map, colour matrix,
+    moved polygons) is drawn HERE, from the generator's own RandomState in sample order, so a batch does not depend on
+    num_workers or worker_kind; one launch warps the whole batch (augment_images) and the labels come from the planned
+    polygons.  A sample whose plan is None (the reference's `continue`) is skipped."""
     image_list = np.array(sorted(get_images(training_data_path)))
     print('{} training images in {}'.format(image_list.shape[0], training_data_path))
     if len(image_list) == 0:
@@ -186,19 +221,35 @@ def generator(training_data_path, input_size=512, batch_size=32, graph=None, shu
         while True:
             if shuffle:
                 rng.shuffle(index)
-            jobs = [(str(image_list[i]), input_size) for i in index]
+            jobs = [(str(image_list[i]), input_size) + ((True,) if augment is not None else ()) for i in index]
+            plans = []
             ims, fns, polys_l, tags_l, slots = [], [], [], [], []
             produced = False
             for smp in samples_of(jobs):
                 if smp is None:
                     continue
+                if augment is not None:
+                    h, w = smp[1].shape[:2]
+                    plan = augment.plan(rng, h, w, smp[2], smp[3], input_size)
+                    if plan is None:
+                        if dpool is not None:
+                            dpool.release(smp[4])
+                        continue
+                    plans.append(plan)
+                    smp = (smp[0], smp[1], plan[2], plan[3], smp[4])
                 fns.append(smp[0])
                 ims.append(smp[1])
                 polys_l.append(smp[2])
                 tags_l.append(smp[3])
                 slots.append(smp[4])
                 if len(ims) == batch_size:
-                    images = resize_images(ims, input_size, graph=graph)      # copies the pixels out of their slots
+                    if augment is None:
+                        images = resize_images(ims, input_size, graph=graph)  # copies the pixels out of their slots
+                    else:
+                        images = augment_images(ims, plans, input_size, graph=graph)
+                        if augment.log is not None:
+                            augment.log.extend((fn,) + pl for fn, pl in zip(fns, plans))
+                        plans = []
                     for sl in slots:
                         if dpool is not None:
                             dpool.release(sl)

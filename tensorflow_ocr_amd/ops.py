@@ -1102,6 +1102,14 @@ def resize_linear_u8(src_u8, dst_f32):
            c_int(dw), _st())
 
 
+def augment_u8_batch(slab, desc, n, S, dst):
+    """One launch for a batch (include/ocr_hip.h: ocr_augment_u8_batch): slab uint8 [bytes] holding the n source images,
+    desc uint8 [n * sizeof(ocr_augment_desc)] (datasets/augment.py: DESC_DTYPE), dst f32 [n,S,S,3]; all on the device."""
+    assert slab.dtype == torch.uint8 and desc.dtype == torch.uint8 and dst.dtype == torch.float32
+    assert desc.numel() >= 112 * n and tuple(dst.shape) == (n, S, S, 3) and dst.is_contiguous()
+    L.call("ocr_augment_u8_batch", ptr(slab), ptr(desc), c_int(n), c_int(S), ptr(dst), _st())
+
+
 def resize_cubic_f32(src_f32, dst_f32, pre_scale=1.0, post_scale=1.0):
     """src f32 [planes,h,w] -> dst f32 [planes,dh,dw] (cv2.resize INTER_CUBIC per plane)."""
     planes, h, w = src_f32.shape
