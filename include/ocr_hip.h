@@ -30,8 +30,9 @@ extern "C" {
  * and so did ocr_conv2d_f32_mfma_ep / ocr_conv2d_f32_split_ep / ocr_subsample_f32 (the folded inference batch norm) with
  * their flags OCR_CONV_AFFINE, OCR_CONV_RESIDUAL, OCR_CONV_ACCUM_IN: every older entry point ignores those bits; the dynamic
  * loss scale (ocr_loss_scale_init, ocr_grad_check_f32, the *_dyn optimiser steps and loss seeds) joined at 7 too, and so
- * did global-norm clipping (ocr_grad_clip_*, ocr_grad_check_clip_f32, the *_clip optimiser steps) and the batched training
- * augmentation (ocr_augment_u8_batch, ocr_augment_desc). */
+ * did global-norm clipping (ocr_grad_clip_*, ocr_grad_check_clip_f32, the *_clip optimiser steps), the batched training
+ * augmentation (ocr_augment_u8_batch, ocr_augment_desc) and gradient accumulation (ocr_grad_accum_init, ocr_grad_accum_f32,
+ * ocr_grad_accum_advance, ocr_grad_accum_state). */
 #define OCR_ABI_VERSION 7
 
 enum {
@@ -1064,6 +1065,46 @@ int ocr_adam_step_clip(void* w, const void* g, void* m, void* v, void* ema, int6
 int ocr_momentum_step_clip(void* w, const void* g, void* accum, void* ema, int64_t n,
                            int64_t n_regularized, float lr, float momentum, float weight_decay,
                            float ema_decay, const void* clip_state, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Gradient accumulation: one optimiser step per window of K micro-batches
+ * (train.TrainStep(accumulate_steps=K)), the phase kept ON THE DEVICE.
+ * `grad` is the flat f32 gradient buffer backward has just written (or a bucket's slice of it), `acc` a
+ * second buffer of the same layout (the same slice of it).  ocr_grad_accum_f32 reads micro and k from the
+ * state and applies ONE of three rules to all n elements:
+ *   micro == 0 && k > 1:   acc[i]  = grad[i]            writes acc only; acc is not read, so nothing is zeroed between
+ *                                                       windows and a skipped window leaves nothing behind
+ *   0 < micro < k - 1:     acc[i]  = acc[i] + grad[i]   writes acc only
+ *   micro == k - 1:        grad[i] = acc[i] + grad[i]   writes grad only (k == 1: acc is not read, the call changes nothing)
+ * Plain f32 IEEE adds in this order: a window's total is ((g1 + g2) + g3) + ... + gK; inf and NaN propagate.  The
+ * total ends up in `grad`, so the exchange, ocr_grad_check_f32, ocr_grad_clip_f32, ocr_grad_check_clip_f32 and every
+ * optimiser step run unchanged on it; the mean's 1 / K goes into their host factor (inv_loss_scale / grad_scale / base).
+ *
+ * Because the device picks the rule, a recorded plan holds one accumulate entry per bucket that is right in every
+ * phase.  The kernel writes nothing to the state, uses no atomics and no ticket; ocr_grad_accum_advance is a launch of
+ * its own, ordered on the stream behind every accumulate call of the step, so the per-bucket calls of one step all
+ * see the same micro.  No host read anywhere.
+ *
+ * Per micro-step:  backward -> ocr_grad_accum_f32 (per bucket, in front of its all-reduce; or once over the whole
+ * buffer) -> ocr_grad_accum_advance;  on the closing one (micro == k - 1) then [all-reduce] -> [check / clip] ->
+ * optimiser step as before.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  uint32_t micro;          /* index of the running micro-step inside the window, 0 .. k-1 */
+  uint32_t k;              /* window length, >= 1 */
+  uint32_t windows_total;  /* windows closed since ocr_grad_accum_init */
+  uint32_t reserved[5];
+} ocr_grad_accum_state;    /* 8 x 32-bit words; 4-byte aligned device memory */
+/* micro = 0, windows_total = 0, reserved = 0; k < 1 -> OCR_ERR_INVALID_ARG */
+int ocr_grad_accum_init(void* state, int k, void* stream);
+/* One streaming pass over n f32 elements (16-byte loads and stores, grid-stride over a capped grid).  grad and acc need
+ * 4-byte alignment only (bucket slices start anywhere): the elements in front of the first 16-byte boundary and the
+ * n & 3 tail go one by one.  Both are slices at the same offset of their flat buffers, so one head length serves both:
+ * a pair whose addresses differ modulo 16 is refused (OCR_ERR_INVALID_ARG), and so are n <= 0, a null pointer and
+ * grad == acc.  The ranges must not overlap. */
+int ocr_grad_accum_f32(void* grad, void* acc, int64_t n, const void* state, void* stream);
+/* micro = (micro + 1) % k; windows_total += 1 on the wrap.  One thread. */
+int ocr_grad_accum_advance(void* state, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Data-parallel exchange.  Replaces `average_gradients`

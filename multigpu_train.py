@@ -45,6 +45,10 @@ def parse(argv=None):
     # not a reference flag: clip the un-scaled gradients to this global L2 norm on the device (train.GradClip); a step whose
     # norm is not finite is skipped.  Off by default.
     ap.add_argument('--clip_norm', type=_clip_norm_arg, default=None)
+    # not a reference flag: gradient accumulation (train.TrainStep(accumulate_steps=K)): one optimiser step on the mean gradient
+    # of K micro-batches of --batch_size_per_gpu, so one card reaches the effective batch of K.  The step counters
+    # below (--max_steps, --save_checkpoint_steps, --save_summary_steps, the staircase) count OPTIMISER steps.  1 = off.
+    ap.add_argument('--accumulate_steps', type=_accumulate_steps_arg, default=1)
     # the augmentation the reference keeps disabled (datasets/icdar.py:576-615), on the device: none | east | pixellink |
     # key=value,... (datasets/augment.py: Augment.parse).  Only with --training_data_path; synthetic batches have none.
     ap.add_argument('--augment', type=_augment_arg, default=None, metavar='SPEC')
@@ -55,6 +59,14 @@ def _augment_arg(text):
     from tensorflow_ocr_amd.datasets.augment import Augment
     try:
         return Augment.parse(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def _accumulate_steps_arg(text):
+    from tensorflow_ocr_amd.train import check_accumulate_steps
+    try:
+        return check_accumulate_steps(int(text))
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e))
 
@@ -124,7 +136,7 @@ def main():
                      lambda gr: AdamOptimizer(gr, learning_rate=FLAGS.learning_rate,
                                               moving_average_decay=FLAGS.moving_average_decay,
                                               clip_norm=FLAGS.clip_norm),
-                     world_size=world)
+                     world_size=world, accumulate_steps=FLAGS.accumulate_steps)
     rng = np.random.default_rng(1000 + rank)
     feeder = None
     if os.path.isdir(FLAGS.training_data_path):
@@ -149,6 +161,17 @@ def _next_batch(FLAGS, feeder, rng, device):
         return [images, score_maps, geo_maps, training_masks]
     data = synthetic.make_batch(rng, FLAGS.batch_size_per_gpu, FLAGS.input_size)
     return [torch.from_numpy(a).to(device, non_blocking=True) for a in data]
+
+
+def _window(step, K, next_batch):
+    """One optimiser step: K calls of `step`, each on a batch of its own.  Returns the mean of the micro-step losses as a
+    device tensor (summed on the device: no read here)."""
+    total = None
+    for _ in range(K):
+        loss = step(*next_batch())
+        if K > 1:
+            total = loss.clone() if total is None else total + loss
+    return loss if K == 1 else total / K
 
 
 def _train_loop(FLAGS, g, step, feeder, rng, rank, world, device, start):
@@ -178,10 +201,13 @@ def _train_loop(FLAGS, g, step, feeder, rng, rank, world, device, start):
                 print('loaded ' + src)
     # `for step in range(FLAGS.max_steps)` (multigpu_train.py:168): the loop counter is separate from the restored
     # `global_step` (which the optimiser continues from), so a resumed run takes max_steps MORE steps
+    K = FLAGS.accumulate_steps
+    first = [batch]
+
+    def next_batch():
+        return first.pop() if first else _next_batch(FLAGS, feeder, rng, device)
     for it in range(FLAGS.max_steps):
-        if it > 0:
-            batch = _next_batch(FLAGS, feeder, rng, device)
-        loss = step(*batch)
+        loss = _window(step, K, next_batch)
         if it % 10 == 0:
             ml = loss.item()
             # the stop decision is collective: a rank leaving alone would strand the others in the
@@ -191,7 +217,7 @@ def _train_loop(FLAGS, g, step, feeder, rng, rank, world, device, start):
                     print('Loss diverged, stop training')
                 break
             avg_time_per_step = (time.time() - start) / 10
-            avg_examples_per_second = (10 * FLAGS.batch_size_per_gpu * world) / (time.time() - start)
+            avg_examples_per_second = (10 * K * FLAGS.batch_size_per_gpu * world) / (time.time() - start)
             start = time.time()
             if rank == 0:
                 # total_loss = model_loss + sum(REGULARIZATION_LOSSES) (multigpu_train.py:36)

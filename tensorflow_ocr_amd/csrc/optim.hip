@@ -401,6 +401,62 @@ __global__ __launch_bounds__(256) void grad_clip_kernel(const float* __restrict_
   __hip_atomic_store(&cs->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- gradient accumulation: K micro-batch gradients into one optimiser step (ocr_grad_accum_state, include/ocr_hip.h) --
+__global__ void grad_accum_init_kernel(ocr_grad_accum_state* st, unsigned k) {
+  if (threadIdx.x < 8) reinterpret_cast<uint32_t*>(st)[threadIdx.x] = threadIdx.x == 1 ? k : 0u;
+}
+
+__global__ void grad_accum_advance_kernel(ocr_grad_accum_state* st) {
+  if (threadIdx.x != 0) return;
+  unsigned m = st->micro + 1u;
+  if (m >= st->k) {
+    m = 0u;
+    st->windows_total = st->windows_total + 1u;
+  }
+  st->micro = m;
+}
+
+// grad_check_kernel's streaming shape with a second buffer.  The rule is uniform over the launch: every thread reads
+// micro and k (one scalar load each; the block is written by grad_accum_advance_kernel only, a launch of its own behind
+// every accumulate call of the step) and the loop bodies differ in which buffer is read and which is written:
+//   STORE  micro == 0      acc  = grad          (acc is not read: nothing to zero between windows)
+//   ADD    0 < micro < k-1 acc  = acc + grad
+//   CLOSE  micro == k-1    grad = acc + grad    (k == 1: grad = grad, nothing is launched into the loops at all)
+// p.head / p.n4 / p.tail come from grad's address; acc has the same address modulo 16 (checked by the entry point).
+template <int RULE>
+__device__ __forceinline__ void grad_accum_body(float* __restrict__ grad, float* __restrict__ acc, const GradCheckP& p) {
+  float4* g4 = reinterpret_cast<float4*>(grad + p.head);
+  float4* a4 = reinterpret_cast<float4*>(acc + p.head);
+#pragma unroll 4
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < p.n4; i += (long long)gridDim.x * 256) {
+    const float4 g = g4[i];
+    if (RULE == 0) {
+      a4[i] = g;
+    } else {
+      const float4 a = a4[i];
+      const float4 s = make_float4(a.x + g.x, a.y + g.y, a.z + g.z, a.w + g.w);
+      if (RULE == 1) a4[i] = s; else g4[i] = s;
+    }
+  }
+  if (blockIdx.x != 0) return;
+  long long j = -1;
+  if (threadIdx.x < p.head) j = threadIdx.x;
+  else if (threadIdx.x >= 4 && threadIdx.x - 4 < p.tail) j = p.head + (p.n4 << 2) + (threadIdx.x - 4);
+  if (j < 0) return;
+  if (RULE == 0) acc[j] = grad[j];
+  else if (RULE == 1) acc[j] = acc[j] + grad[j];
+  else grad[j] = acc[j] + grad[j];
+}
+
+__global__ __launch_bounds__(256) void grad_accum_kernel(float* __restrict__ grad, float* __restrict__ acc, GradCheckP p,
+                                                         const ocr_grad_accum_state* __restrict__ st) {
+  const unsigned micro = st->micro, k = st->k;
+  if (k <= 1u) return;
+  if (micro + 1u >= k) grad_accum_body<2>(grad, acc, p);
+  else if (micro == 0u) grad_accum_body<0>(grad, acc, p);
+  else grad_accum_body<1>(grad, acc, p);
+}
+
 unsigned sumsq_grid(long long n) {
   long long b = (n / 4 + 255) / 256;
   if (b > 1024) b = 1024;
@@ -652,5 +708,31 @@ extern "C" int ocr_momentum_step_clip(void* w, const void* g, void* accum, void*
                      static_cast<hipStream_t>(stream), a, static_cast<float*>(w),
                      static_cast<const float*>(g), static_cast<float*>(accum),
                      static_cast<float*>(ema));
+  return ocr_launch_status();
+}
+
+// ---- gradient accumulation ---------------------------------------------------------------------------------------
+extern "C" int ocr_grad_accum_init(void* state, int k, void* stream) {
+  OCR_CHECK_ARG(state && ((uintptr_t)state & 3) == 0 && k >= 1);
+  hipLaunchKernelGGL(grad_accum_init_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream),
+                     static_cast<ocr_grad_accum_state*>(state), (unsigned)k);
+  return ocr_launch_status();
+}
+
+extern "C" int ocr_grad_accum_f32(void* grad, void* acc, int64_t n, const void* state, void* stream) {
+  OCR_CHECK_ARG(grad && acc && state && n > 0 && grad != acc);
+  OCR_CHECK_ARG(((uintptr_t)grad & 3) == 0 && ((uintptr_t)acc & 3) == 0 && ((uintptr_t)state & 3) == 0);
+  OCR_CHECK_ARG((((uintptr_t)grad ^ (uintptr_t)acc) & 15) == 0);       // one head length serves both buffers
+  const GradCheckP p = split_head_tail(grad, n, GradCheckP{});
+  hipLaunchKernelGGL(grad_accum_kernel, dim3(clip_grid(p.n4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<float*>(grad), static_cast<float*>(acc), p,
+                     static_cast<const ocr_grad_accum_state*>(state));
+  return ocr_launch_status();
+}
+
+extern "C" int ocr_grad_accum_advance(void* state, void* stream) {
+  OCR_CHECK_ARG(state && ((uintptr_t)state & 3) == 0);
+  hipLaunchKernelGGL(grad_accum_advance_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream),
+                     static_cast<ocr_grad_accum_state*>(state));
   return ocr_launch_status();
 }

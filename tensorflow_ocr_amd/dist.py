@@ -185,7 +185,7 @@ def exchange_mode(world, cuda, force=False):
 
 class GradientAllReduce:
     def __init__(self, store, world_size, bucket_bytes=32 << 20, op="mean", group=None, fold_mean=False,
-                 force=False, mode=None, comm=None, proxy=None, overlap=None):
+                 force=False, mode=None, comm=None, proxy=None, overlap=None, accum=None):
         """op: "mean" = `average_gradients` (multigpu_train.py:70-85); "sum" = `sum_gradients`
         (train_pixellink.py:179-194: the caller has already divided its loss by num_clones).
         fold_mean: leave the SUM in the buffer and let the optimiser apply `grad_scale` (= 1/world)
@@ -207,7 +207,15 @@ class GradientAllReduce:
         the conv kernels; the whole exchange is exposed).  Default: OCR_EXCHANGE_OVERLAP (1).  Why the choice exists:
         DESIGN.md section 3.4 — the weight-gradient, persistent and 256-tile conv launches fill the chip in exactly one
         round of workgroups, so a comm kernel that holds even a few CUs sends their tiles into a second round.  With
-        `proxy` (world 1, a measurement aid) the plan holds BOTH placements and a replay runs the one `self.overlap` names."""
+        `proxy` (world 1, a measurement aid) the plan holds BOTH placements and a replay runs the one `self.overlap` names.
+        accum: a `train.GradAccum` over store.flat_grad (gradient accumulation), or None.  `_fire` then runs the bucket's
+        accumulate call on the compute stream immediately before the bucket is handed to the comm stream — once per step
+        and bucket, whichever placements the plan holds — so the all-reduce moves the window's sum and the overlap with
+        backward is kept.  `closing` is set by the caller before every step: False on a micro-step inside its window,
+        whose buckets are accumulated as they become ready (the same calls, in the same places, as on the closing one)
+        and not exchanged."""
+        self.accum = accum
+        self.closing = True
         self.store = store
         self.active = world_size > 1 or force
         self.enabled = True
@@ -294,6 +302,10 @@ class GradientAllReduce:
         self.left = list(self.need)
         self.handles = []
         self.fired = [False] * len(self.buckets)
+        self.accumulated = [False] * len(self.buckets)
+
+    def _exchanging(self):
+        return self.enabled and self.closing
 
     def bucket_nbytes(self):
         return [(e - s) * 4 for s, e in self.buckets]
@@ -308,7 +320,7 @@ class GradientAllReduce:
         rec = _lib.RECORDER
         if rec is not None and self.mode == "torch" and not self._replaying:
             rec.py(lambda vs=tuple(variables): self._replayed(self.on_grads_ready, vs))
-        if not self.enabled:
+        if not self.enabled and self.accum is None:
             return
         for v in variables:
             bi = self.bucket_of.get(v.name)
@@ -331,6 +343,13 @@ class GradientAllReduce:
         self.fired[bi] = True
         s, e = self.buckets[bi]
         buf = self.store.flat_grad[s:e]
+        if self.accum is not None and not self.accumulated[bi]:
+            # abi mode: a C entry of the plan, tagged ("accum",), replayed in every phase; torch mode: the recorded host
+            # callback re-runs this call, so it must not ALSO enter the plan (as the scale in `finish`)
+            self.accumulated[bi] = True
+            self.accum.run(s, e, record=self.mode == "abi")
+        if not self._exchanging():
+            return
         if self.mode == "abi":
             import ctypes
             from . import _lib as L
@@ -379,12 +398,15 @@ class GradientAllReduce:
         rec = _lib.RECORDER
         if rec is not None and not self._replaying and (self.mode == "torch" or not self.active):
             rec.py(lambda: self._replayed(self.finish))
-        if not self.active or not self.enabled:
+        if not self.active or (not self.enabled and self.accum is None):
             self.reset()
             return
         for bi in range(len(self.buckets)):
             if not self.fired[bi] or self.both_placements:
                 self._fire(bi, "late")
+        if not self._exchanging():          # buckets accumulated, nothing in flight
+            self.reset()
+            return
         if self.mode == "abi":
             cur = _lib.stream_ptr()
             for bi, _ in self.handles:

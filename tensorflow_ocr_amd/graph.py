@@ -476,6 +476,17 @@ class Graph:
         for v, kind, e, _ in ents:
             v.packed[kind] = (self.store.version, e[1])
 
+    def stale_lazy_packs(self):
+        """Mark the pack kinds that `repack_all` leaves lazy as out of date (their buffers stay): the next forward and
+        backward refresh them again.  A step recorded with gradient accumulation needs it: the call in front of the
+        recorded one ran at the same store version and left them current, and a plan recorded without their refresh
+        would replay stale weights for ever (train.TrainStep._eager)."""
+        for v in self.store.vars.values():
+            pk = getattr(v, "packed", None)
+            for kind in list(pk or ()):
+                if kind not in ("kc_ck", "small"):
+                    pk[kind] = (None, pk[kind][1])
+
     # --- tape ---
     def record(self, fn, produces=()):
         """`produces`: the variables whose gradients are complete once `fn` has run."""

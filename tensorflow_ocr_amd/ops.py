@@ -1207,6 +1207,27 @@ def momentum_step_clip(w, g, acc, ema, n_reg, lr, momentum, wd, ema_decay, clip_
            c_float(lr), c_float(momentum), c_float(wd), c_float(ema_decay), ptr(clip_state), _st())
 
 
+# gradient accumulation: `state` is the 8-word device block ocr_grad_accum_state (include/ocr_hip.h) as an int32 tensor
+GRAD_ACCUM_WORDS = 8
+GA_MICRO, GA_K, GA_WINDOWS_TOTAL = range(3)
+
+
+def grad_accum_init(state, k):
+    assert state.numel() >= GRAD_ACCUM_WORDS and state.element_size() == 4
+    L.call("ocr_grad_accum_init", ptr(state), c_int(k), _st())
+
+
+def grad_accum(grad, acc, state):
+    """One pass over the f32 buffers `grad` and `acc` (equal length, equal address modulo 16): store, add or close the
+    window, as state.micro and state.k say."""
+    assert grad.numel() == acc.numel()
+    L.call("ocr_grad_accum_f32", ptr(grad), ptr(acc), c_int64(grad.numel()), ptr(state), _st())
+
+
+def grad_accum_advance(state):
+    L.call("ocr_grad_accum_advance", ptr(state), _st())
+
+
 def scale_(x, s):
     L.call("ocr_scale_f32", ptr(x), c_int64(x.numel()), c_float(s), _st())
 

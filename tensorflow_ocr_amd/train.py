@@ -96,6 +96,92 @@ def check_clip_norm(clip_norm):
     return float(v)
 
 
+def check_accumulate_steps(k):
+    """An int >= 1, ValueError otherwise."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError("accumulate_steps must be an integer >= 1, got %r" % (k,))
+    return int(k)
+
+
+class GradAccum:
+    """Gradient accumulation decided on the device (ocr_grad_accum_state, include/ocr_hip.h): `TrainStep(accumulate_steps=K)`.
+    `acc` mirrors the flat gradient buffer; `run(s, e)` applies to the slice [s, e) of both the rule of the running
+    micro-step — store on the first, add in between, and on the closing one grad = acc + grad, so that the window's sum
+    ((g1 + g2) + ...) + gK stands where the exchange and the optimiser read it — and `advance()` moves the phase, once per
+    step behind every `run` of it.  The kernel reads the phase from the 8-word device block: a recorded plan holds one
+    entry that is right in every phase.  `micro` is the host's mirror of it (no device read in a step); with the buffers
+    on the CPU (the gloo path) the same three rules run as torch operators on the mirror.
+
+    The buffer and the block are allocated here, once: a recorded plan replays their addresses.  Nothing of this is
+    checkpointed: a restored run starts a fresh window (`TrainStep.reset_window`)."""
+
+    def __init__(self, k, flat_grad):
+        self.k = check_accumulate_steps(k)
+        self.grad = flat_grad
+        self.acc = torch.zeros_like(flat_grad)
+        self.state = torch.zeros(ops.GRAD_ACCUM_WORDS, dtype=torch.int32, device=flat_grad.device)
+        self.micro = 0
+        self.reset()
+
+    @property
+    def closing(self):
+        return self.micro == self.k - 1
+
+    def _unrecorded(self, fn, *args):
+        from . import _lib
+        rec, _lib.RECORDER = _lib.RECORDER, None           # an initialising launch is no part of a replayed plan
+        try:
+            fn(*args)
+        finally:
+            _lib.RECORDER = rec
+
+    def reset(self):
+        """micro = 0, windows_total = 0 on the device and in the mirror."""
+        self.micro = 0
+        if self.state.is_cuda:
+            self._unrecorded(ops.grad_accum_init, self.state, self.k)
+        else:
+            self.state.zero_()
+            self.state[ops.GA_K] = self.k
+
+    def run(self, s=0, e=None, record=True):
+        """The running micro-step's rule on grad[s:e] / acc[s:e]; in a recording the entry is tagged ("accum",).
+        record=False: the caller's host callback re-runs this call on every replay (dist: torch mode)."""
+        e = self.grad.numel() if e is None else e
+        g, a = self.grad[s:e], self.acc[s:e]
+        if g.is_cuda:
+            if not record:
+                return self._unrecorded(ops.grad_accum, g, a, self.state)
+            from . import _lib
+            ops.grad_accum(g, a, self.state)
+            if _lib.RECORDER is not None:
+                _lib.RECORDER.tag_last(("accum",))
+        elif self.k == 1:
+            pass
+        elif self.micro >= self.k - 1:
+            g.add_(a)                          # (f32 addition commutes: the bits of acc + grad)
+        elif self.micro == 0:
+            a.copy_(g)
+        else:
+            a.add_(g)
+
+    def advance(self):
+        if self.state.is_cuda:
+            from . import _lib
+            ops.grad_accum_advance(self.state)
+            if _lib.RECORDER is not None:
+                _lib.RECORDER.tag_last(("accum", "advance"))
+        else:
+            self.state[ops.GA_MICRO] = (self.micro + 1) % self.k
+            if self.micro + 1 >= self.k:
+                self.state[ops.GA_WINDOWS_TOTAL] += 1
+        self.micro = (self.micro + 1) % self.k
+
+    def windows(self):
+        """Windows closed since the last reset (READS THE DEVICE: a sync)."""
+        return int(self.state.cpu().numpy()[ops.GA_WINDOWS_TOTAL])
+
+
 class _ClipReadout:
     """grad_norm() / clipped_steps() / nonfinite_steps() of an optimiser built with clip_norm: each READS THE DEVICE (a
     sync), for logging only."""
@@ -338,6 +424,8 @@ def schedule_guests(entries, cover=None, min_us=None, xchg_at_fork=None, balance
 
     def travels(e):            # an exchange entry that belongs to the weight gradient in front of it
         t = tag(e)
+        if t[0] == "accum":    # a bucket's accumulate call (GradAccum.run): in front of its exchange entries, and like them
+            return len(t) < 2  # it reads every weight gradient recorded before it; the step's one advance call does not travel
         return t[0] == "xchg" and (len(t) < 2 or t[1] != "finish") and (len(t) < 3 or t[2] in (None, "early"))
 
     def guest_ahead(i0):             # is there a guest behind entry i0, before anything that needs the gradients?
@@ -346,7 +434,7 @@ def schedule_guests(entries, cover=None, min_us=None, xchg_at_fork=None, balance
             tq = tag(eq)
             if tq[0] == "guest":
                 return True
-            if eq[0] != "c" or (tq[0] == "xchg" and not travels(eq)):
+            if eq[0] != "c" or (tq[0] in ("xchg", "accum") and not travels(eq)):
                 return False
         return False
 
@@ -404,7 +492,7 @@ def schedule_guests(entries, cover=None, min_us=None, xchg_at_fork=None, balance
                 # a host that carries exchange entries (its weight gradient completed a bucket) may only go once every
                 # weight gradient recorded before it has gone: the bucket's all-reduce reads all of them
                 def closes_bucket(k):
-                    return any(tag(x)[0] == "xchg" for x in pending[k][1])
+                    return any(tag(x)[0] in ("xchg", "accum") for x in pending[k][1])
                 take, acc, skipped = [], 0.0, False
                 if balance and len(pending) <= 12:
                     # what is exposed of a guest is what its hosts do not cover, and every host a guest can use the later
@@ -465,10 +553,11 @@ def schedule_guests(entries, cover=None, min_us=None, xchg_at_fork=None, balance
             out.append(e)
             i += 1
             continue
-        if e[0] != "c" or t[0] == "xchg":
+        if e[0] != "c" or t[0] in ("xchg", "accum"):
             # host callbacks (optimiser, torch-mode exchange), the exchange's closing entries — and an exchange entry that
             # TRAVELS behind a weight gradient which stayed in place (one that cannot host, or conv1_1's sums form): its
-            # bucket's all-reduce reads every weight gradient recorded before it, the held-back ones included
+            # bucket's all-reduce reads every weight gradient recorded before it, the held-back ones included.  An accumulate
+            # call (GradAccum.run) reads them too: the whole-buffer one behind backward, a bucket's in front of its exchange
             flush()
         out.append(e)
         i += 1
@@ -491,16 +580,28 @@ class TrainStep:
     Everything between the batch tensors and the loss must therefore be C-ABI calls: input
     preprocessing written with torch operators belongs in the input pipeline, before the step (where
     the reference has it too — its queues deliver preprocessed images).  The recording runs under an
-    audit that raises if a torch operator touched device memory inside `forward_loss`."""
+    audit that raises if a torch operator touched device memory inside `forward_loss`.
+
+    `accumulate_steps=K` (gradient accumulation, `GradAccum`): one optimiser step per WINDOW of K calls, on the mean of
+    the K micro-batch gradients.  A call that does not close its window runs forward, loss, backward, the accumulate
+    calls and the phase's advance, and nothing else: no exchange, no check or clip pass, no optimiser, no re-pack.  The
+    closing call adds the window's sum into the flat gradient buffer and then runs everything on it, with 1 / K in the
+    optimiser's factor.  The step is recorded on a closing call, and a non-closing replay skips the plan's exchange,
+    optimiser and re-pack entries by their tags; the accumulate entries are the same in every phase (the device picks
+    the rule).  K = 1, the default, allocates and launches nothing of this."""
 
     def __init__(self, graph, forward_loss, optimizer_factory, world_size=1, bucket_bytes=32 << 20,
-                 replay=True, grad_op="mean", force_reduce=False, comm_proxy=None):
+                 replay=True, grad_op="mean", force_reduce=False, comm_proxy=None, accumulate_steps=1):
         """grad_op: "mean" = multigpu_train.py's `average_gradients` (each tower differentiates its own
         loss, the gradients are averaged); "sum" = train_pixellink.py's `sum_gradients`: each clone
         differentiates loss / num_clones (:264) and the gradients are summed (:179-194).
         force_reduce: run the bucketed exchange at world 1 too (needs a one-rank process group)."""
         if grad_op not in ("mean", "sum"):
             raise ValueError("grad_op must be 'mean' or 'sum'")
+        self.accumulate_steps = check_accumulate_steps(accumulate_steps)        # before anything is allocated
+        self.accum = None                 # GradAccum, created with the optimiser and the reducer when accumulate_steps > 1
+        self.window_pos = 0               # calls since the first window opened (or since reset_window)
+        self.closes_window = False        # whether the call just made stepped the optimiser
         self.g = graph
         self.grad_op = grad_op
         self.force_reduce = force_reduce
@@ -529,7 +630,6 @@ class TrainStep:
         (the reference restores before its first `sess.run(train_op)`, multigpu_train.py:153-158)."""
         if self.opt is not None:
             return self
-        from .dist import GradientAllReduce
         g = self.g
         g.reset_tape()
         # the dry-run forward updates the BN moving statistics: put back what was there BEFORE it (variables that
@@ -541,9 +641,33 @@ class TrainStep:
         g.store.reset_non_trainable()
         for n, t in before.items():
             g.store.vars[n].data.copy_(t)
-        self.reducer = GradientAllReduce(g.store, self.world, self.bucket_bytes, op=self.grad_op,
-                                         fold_mean=True, force=self.force_reduce, proxy=self.comm_proxy)
+        self._make_reducer()
         return self
+
+    def _make_reducer(self):
+        from .dist import GradientAllReduce
+        if self.accumulate_steps > 1:
+            self.accum = GradAccum(self.accumulate_steps, self.g.store.flat_grad)
+        self.reducer = GradientAllReduce(self.g.store, self.world, self.bucket_bytes, op=self.grad_op,
+                                         fold_mean=True, force=self.force_reduce, proxy=self.comm_proxy, accum=self.accum)
+
+    @property
+    def micro_step(self):
+        """Host mirror of the phase: the index, inside its window, of the NEXT call (0 .. accumulate_steps - 1)."""
+        return self.window_pos % self.accumulate_steps
+
+    def reset_window(self):
+        """Start a fresh window with the next call (after restoring a checkpoint mid-run): the device block and the
+        host mirror go back to micro-step 0; whatever the abandoned window had accumulated is overwritten by the
+        first micro-step's store rule."""
+        self.window_pos = 0
+        if self.accum is not None:
+            self.accum.reset()
+
+    def _grad_scale(self):
+        """The optimiser's host factor: the reducer's (1 or 1 / world), over K for the window's mean."""
+        gs = self.reducer.grad_scale
+        return gs if self.accumulate_steps == 1 else gs / self.accumulate_steps
 
     # -- eager / recording path --------------------------------------------------------------
     def _eager(self, batch, record):
@@ -554,6 +678,10 @@ class TrainStep:
             rec = _lib.Recorder()
             _lib.RECORDER = rec
             g.keepalive = []
+            if self.accumulate_steps > 1:
+                # the call before this one ran at the same store version and refreshed the lazily packed operands (conv1_1's
+                # among them); recorded as it stands, this step would hold no refresh of them and replay stale weights
+                g.stale_lazy_packs()
         audit = _record_audit() if record else __import__("contextlib").nullcontext()
         try:
             with audit:
@@ -563,20 +691,28 @@ class TrainStep:
                     "torch operators inside the recorded step would not be replayed: %s — move them "
                     "before the step (input pipeline) or use replay=False" % sorted(set(audit.offenders)))
             if self.opt is None:
-                from .dist import GradientAllReduce
                 self.opt = self.optimizer_factory(g)           # materialises the flat buffers
-                self.reducer = GradientAllReduce(g.store, self.world, self.bucket_bytes, op=self.grad_op,
-                                                 fold_mean=True, force=self.force_reduce, proxy=self.comm_proxy)
+                self._make_reducer()
+            closing = self.accum is None or self.accum.closing
+            self.reducer.closing = closing
             g.backward(self.reducer.on_grads_ready if self.reducer.active else None)
+            if self.accum is not None and not self.reducer.active:
+                self.accum.run()            # no buckets: one call over the whole buffer (an active reducer: per bucket, _fire)
             self.reducer.finish()           # records itself: host callback (torch mode) or C-ABI stream waits (abi mode)
+            if self.accum is not None:
+                self.accum.advance()        # behind every accumulate call of the step
         finally:
             _lib.RECORDER = None
-        self.opt.apply_gradients(self.reducer.grad_scale)
+        self.loss = loss
+        if not closing:                     # (never a recording step)
+            return loss
+        self.opt.apply_gradients(self._grad_scale())
         self._repack()                      # the conv operand packs of the new weights, one launch
         if record:
-            rec.py(lambda: self.opt.apply_gradients(self.reducer.grad_scale))
+            rec.py(lambda: self.opt.apply_gradients(self._grad_scale()))
             rec.entries[-1].append("opt")
             rec.py(self._repack)
+            rec.entries[-1].append("repack")
             self.recorded = rec.entries                       # (kept: reschedule() derives another plan from the same recording)
             self.plan = schedule_guests(rec.entries) if USE_GUESTS else rec.entries
             self.static_batch = list(batch)
@@ -609,6 +745,8 @@ class TrainStep:
         timing = ops.KERNEL_TIMING
         main = torch.cuda.current_stream()
         bwd_marked = False
+        closing = self.accum is None or self.accum.closing
+        self.reducer.closing = closing      # (torch mode: the exchange's host callbacks ask it)
         for e in self.plan:
             if e[0] == "fork":
                 # a weight gradient and the guest pass paired with it (schedule_guests): the guest stream starts here
@@ -630,8 +768,8 @@ class TrainStep:
                         _lib.check(rc, e[3])
                     continue
                 if tag is not None and tag[0] == "xchg":
-                    # the gradient exchange as C-ABI calls (dist.GradientAllReduce, abi mode)
-                    if self.reducer.enabled:
+                    # the gradient exchange as C-ABI calls (dist.GradientAllReduce, abi mode); once per window
+                    if self.reducer.enabled and closing:
                         kind = tag[1] if len(tag) > 1 else None
                         when = tag[2] if len(tag) > 2 else None
                         # a bucket's comm-stream launch: the RCCL all-reduce OR its one-GPU stand-in (dist: proxy)
@@ -660,15 +798,25 @@ class TrainStep:
                 if rc != 0:
                     _lib.check(rc, e[3])
             else:
+                if not closing and len(e) > 2 and e[2] in ("opt", "repack"):
+                    continue                                      # a micro-step inside its window: gradients only
                 if len(e) > 2 and e[2] == "opt" and self.backward_end_event is not None and not bwd_marked:
                     self.backward_end_event.record(main)          # (no exchange in this step: backward ends here)
                     bwd_marked = True
                 e[1]()
+        if self.accum is not None:
+            self.accum.micro = (self.accum.micro + 1) % self.accum.k      # the plan's advance entry has moved the device's
         return self.loss
 
     def __call__(self, *batch):
         self.steps += 1
+        closing = self.micro_step == self.accumulate_steps - 1
         if self.plan is not None:
-            return self._replay(batch)
-        # step 1 creates variables, step 2 runs with the flat buffers; step 3 is steady state
-        return self._eager(batch, record=self.replay and self.steps >= 3)
+            loss = self._replay(batch)
+        else:
+            # step 1 creates variables, step 2 runs with the flat buffers; step 3 is steady state.  With accumulation the
+            # recording waits for a call that closes its window: every entry of the plan is then executed as it is recorded
+            loss = self._eager(batch, record=self.replay and self.steps >= 3 and closing)
+        self.window_pos += 1
+        self.closes_window = closing
+        return loss

@@ -52,7 +52,19 @@ def parse(argv=None):
     # not a reference flag: clip the un-scaled gradients to this global L2 norm on the device (train.GradClip); a step whose
     # norm is not finite is skipped.  Off by default.
     ap.add_argument('--clip_norm', type=_clip_norm_arg, default=None)
+    # not a reference flag: gradient accumulation (train.TrainStep(accumulate_steps=K)): one optimiser step on the mean gradient
+    # of K micro-batches of --batch_size, so one card reaches the effective batch of K.  The step counters
+    # below (--max_number_of_steps, --log_every_n_steps, the checkpoint interval, the staircase) count OPTIMISER steps.  1 = off.
+    ap.add_argument('--accumulate_steps', type=_accumulate_steps_arg, default=1)
     return ap.parse_args(argv)
+
+
+def _accumulate_steps_arg(text):
+    from tensorflow_ocr_amd.train import check_accumulate_steps
+    try:
+        return check_accumulate_steps(int(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def _clip_norm_arg(text):
@@ -120,6 +132,17 @@ def dataset_batches(FLAGS, g, batch, rank):
                 ims, xs_l, ys_l, bb_l, ig_l = [], [], [], [], []
 
 
+def _window(step, K, next_batch):
+    """One optimiser step: K calls of `step`, each on a batch of its own.  Returns the mean of the micro-step losses as a
+    device tensor (summed on the device: no read here)."""
+    total = None
+    for _ in range(K):
+        loss = step(*next_batch())
+        if K > 1:
+            total = loss.clone() if total is None else total + loss
+    return loss if K == 1 else total / K
+
+
 def main():
     FLAGS = parse()
     from tensorflow_ocr_amd import launch
@@ -155,7 +178,7 @@ def main():
                                 clip_norm=FLAGS.clip_norm)
         opt.learning_rate = lambda: staircase_lr(opt.global_step, FLAGS.learning_rate, bps, dcs)
         return opt
-    step = TrainStep(g, forward_loss, make_opt, world_size=world, grad_op="sum")
+    step = TrainStep(g, forward_loss, make_opt, world_size=world, grad_op="sum", accumulate_steps=FLAGS.accumulate_steps)
 
     feeder = None
     if FLAGS.dataset_dir and os.path.isdir(FLAGS.dataset_dir):
@@ -165,13 +188,13 @@ def main():
     if FLAGS.train_dir and rank == 0:
         os.makedirs(FLAGS.train_dir, exist_ok=True)
     start = time.time()
-    for it in range(FLAGS.max_number_of_steps):
+    def next_batch():
         if feeder is not None:
-            images, pixel, link = next(feeder)
-        else:
-            im, px, lk, _ = synthetic.make_batch(rng, batch_size_per_gpu, FLAGS.train_image_height)
-            images, pixel, link = [torch.from_numpy(a).to(device, non_blocking=True) for a in (im, px[..., 0], lk)]
-        loss = step(images, pixel, link)
+            return next(feeder)
+        im, px, lk, _ = synthetic.make_batch(rng, batch_size_per_gpu, FLAGS.train_image_height)
+        return [torch.from_numpy(a).to(device, non_blocking=True) for a in (im, px[..., 0], lk)]
+    for it in range(FLAGS.max_number_of_steps):
+        loss = _window(step, FLAGS.accumulate_steps, next_batch)
         if it % FLAGS.log_every_n_steps == 0:
             v = loss.item()
             dt = (time.time() - start) / FLAGS.log_every_n_steps
