@@ -32,7 +32,7 @@ extern "C" {
  * loss scale (ocr_loss_scale_init, ocr_grad_check_f32, the *_dyn optimiser steps and loss seeds) joined at 7 too, and so
  * did global-norm clipping (ocr_grad_clip_*, ocr_grad_check_clip_f32, the *_clip optimiser steps), the batched training
  * augmentation (ocr_augment_u8_batch, ocr_augment_desc) and gradient accumulation (ocr_grad_accum_init, ocr_grad_accum_f32,
- * ocr_grad_accum_advance, ocr_grad_accum_state). */
+ * ocr_grad_accum_advance, ocr_grad_accum_state) and ocr_conv2d_wgrad_variant (the name of the weight-gradient launch). */
 #define OCR_ABI_VERSION 7
 
 enum {
@@ -224,8 +224,16 @@ int ocr_conv2d_first_num_mtiles(int n, int h, int w);
 
 /* Weight gradient: dw[ky,kx,ci,co] = sum_{n,y,x} x[n, y*s+ky*d-pt, x*s+kx*d-pl, ci]
  * * dy[n,y,x,co], f16 operands, f32 result (HWIO).  `workspace` holds split-K
- * partial slabs; its size comes from ocr_conv2d_wgrad_workspace.  When
- * `accumulate` != 0 the result is added to dw. */
+ * partial slabs [slabs][kh][kw][cin][cout] f32; its size comes from ocr_conv2d_wgrad_workspace
+ * (0 for a shape no kernel family takes).
+ * Contract of the outputs, in every kernel family: the slab launch STORES every element of every one of its slabs —
+ * partial channel blocks, pixel tiles over a ragged edge and a short last split included — and the slab sum STORES
+ * every element of dw, nothing is added to what was there; so neither buffer needs initialising, and nothing outside
+ * the ocr_conv2d_wgrad_workspace bytes and dw is written (tests/test_gpu_wgrad_matrix.py).
+ * Status: OCR_ERR_INVALID_ARG for a null pointer or a descriptor with a non-positive extent, OCR_ERR_UNSUPPORTED for a
+ * shape no family takes (cin or cout not a multiple of 32, more than 9 taps, an undilated filter of several taps at
+ * stride 2: the halo tile of the tap-sweeping kernels outgrows LDS), OCR_ERR_WORKSPACE for ws_bytes below ocr_conv2d_wgrad_workspace; nothing is
+ * launched in any of them. */
 int ocr_conv2d_wgrad_f16(const ocr_conv_desc* d, const void* x, const void* dy,
                          void* dw_hwio_f32, void* workspace, size_t ws_bytes,
                          void* stream);
@@ -234,7 +242,8 @@ size_t ocr_conv2d_wgrad_workspace(const ocr_conv_desc* d);
  * slabs into dw — so that the recorded step can issue the first as the host of a guest pass (ocr_bn_relu_bwd_apply_
  * affine_f16 ...) and the second behind the join: the slab sum is bandwidth- and cache-sensitive (13 us alone, 60-370 us
  * beside an HBM-streaming guest).  `workspace` (ocr_conv2d_wgrad_workspace bytes) must stay the launch's own until the
- * reduce has run.  Results are those of ocr_conv2d_wgrad_f16 bit for bit. */
+ * reduce has run.  Results are those of ocr_conv2d_wgrad_f16 bit for bit (the same kernels in the same order), under the
+ * same contract and with the same status codes: the slab call stores every slab element, the reduce call stores dw. */
 int ocr_conv2d_wgrad_slabs_f16(const ocr_conv_desc* d, const void* x, const void* dy, void* workspace, size_t ws_bytes,
                                void* stream);
 int ocr_conv2d_wgrad_reduce_f32(const ocr_conv_desc* d, const void* workspace, void* dw_hwio_f32, void* stream);
@@ -242,6 +251,13 @@ int ocr_conv2d_wgrad_reduce_f32(const ocr_conv_desc* d, const void* workspace, v
  * wgrad3_kernel<9,128>, 248 beside <9,64>, 80 beside the 256 x 256 pointwise tile; 0 = none / unknown): whether a guest
  * pass (<= 56) can be placed beside it.  The recorded step holds back only weight gradients that can host. */
 int ocr_conv2d_wgrad_guest_room(const ocr_conv_desc* d);
+/* What ocr_conv2d_wgrad_slabs_f16 / ocr_conv2d_wgrad_reduce_f32 launch for `d`, from the selection the launch itself reads:
+ * "<kernel> slabs=<S> grid=<G> xcd=<0|1> reduce=slab_reduce_kernel<SL>" — the slab kernel's instantiation as it appears
+ * (mangled) in rocprofv3 kernel traces (wgrad_pw_kernel<CIB,COB,NWCI>, wgrad3_kernel<9,COB>, wgrad2_kernel<COB,TAPS>,
+ * wgrad_kernel<TAPS>), the number of slabs it writes, its workgroups, whether they run in the XCD-aware order, and the
+ * instantiation of the slab sum.  The status is the one ocr_conv2d_wgrad_f16 gives for `d` (nothing is written then);
+ * OCR_ERR_INVALID_ARG also when `cap` is too small.  Measurement and tests only. */
+int ocr_conv2d_wgrad_variant(const ocr_conv_desc* d, char* out, size_t cap);
 
 /* First-layer weight gradient (cin=3 from the [n,h,w,4] f16 image). dw [3,3,3,cout] f32. */
 int ocr_conv2d_first_wgrad_f16(int n, int h, int w, int cout, const void* x4,

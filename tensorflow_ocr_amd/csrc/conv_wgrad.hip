@@ -17,12 +17,13 @@
 // Partial blocks go to a [split][tap][ci][co] f32 slab; a second kernel sums the
 // slabs in fixed order, so the result is bitwise reproducible (no atomics).
 #include "common.h"
+#include <stdio.h>
 #include <stdlib.h>
 
 namespace ocr_detail {   // conv_wgrad_pw.hip: GEMM-tiled path for 1x1 convolutions
-int wgrad_pw_splits(const ocr_conv_desc* d);
 int wgrad_pw_launch(const ocr_conv_desc* d, const void* x, const void* dy, void* slab, hipStream_t st);
 bool wgrad_pw_is_256x256(const ocr_conv_desc* d);     // the 256 x 256-tile instantiation (the one whose register room is tabulated)
+bool wgrad_pw_describe(const ocr_conv_desc* d, char* name, size_t cap, int* splits, int* grid, int* xcd);   // false: not a pointwise shape
 }
 
 namespace {
@@ -218,10 +219,16 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
   if (sl == 0 && i < elems4) reinterpret_cast<f32x4*>(dw)[i] = a;
 }
 
-static void launch_slab_reduce(const float* slab, float* dw, size_t elems4, int splits, hipStream_t st) {
-  // enough workgroups to fill the chip, but never more split lanes than slabs
+// lanes that share one output of the slab sum (the SL of slab_reduce_kernel): enough workgroups to fill the chip, but
+// never more split lanes than slabs
+static int slab_reduce_lanes(size_t elems4, int splits) {
   int sl = 1;
   while (sl < 64 && sl * 4 <= splits && (elems4 * sl) / 256 < 2048) sl *= 4;
+  return sl;
+}
+
+static void launch_slab_reduce(const float* slab, float* dw, size_t elems4, int splits, hipStream_t st) {
+  const int sl = slab_reduce_lanes(elems4, splits);
   const unsigned grid = (unsigned)((elems4 * sl + 255) / 256);
   switch (sl) {
     case 1: hipLaunchKernelGGL(slab_reduce_kernel<1>, dim3(grid), dim3(256), 0, st, slab, dw, elems4, splits); break;
@@ -754,9 +761,8 @@ int fill2(const ocr_conv_desc* d, Wg2P* p, int* cob) {
   return OCR_OK;
 }
 
+// (wgrad_select has checked the descriptor's extents)
 int fill(const ocr_conv_desc* d, WgP* p) {
-  OCR_CHECK_ARG(d != nullptr);
-  OCR_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->oh > 0 && d->ow > 0);
   OCR_CHECK_SHAPE(d->cin % 64 == 0 && d->cout % 64 == 0);
   OCR_CHECK_SHAPE(d->kh * d->kw <= 9);
   p->n = d->n; p->h = d->h; p->w = d->w; p->cin = d->cin;
@@ -796,79 +802,108 @@ static int launch_wg(K kern, const P& p, unsigned grid, size_t lds, const void* 
   return ocr_launch_status();
 }
 
+// The tap-sweeping instantiations, each ONE row: what selects it, its name as a kernel trace prints it (what
+// ocr_conv2d_wgrad_variant reports) and the kernel the launch starts.
+typedef void (*Tap2Kernel)(Wg2P, const half_t*, const half_t*, float*);
+typedef void (*GenericKernel)(WgP, const half_t*, const half_t*, float*);
+struct Tap2Row { bool v3; int cob, taps; const char* name; Tap2Kernel kern; unsigned threads; };   // taps: the MAXTAPS of the instantiation
+static const Tap2Row TAP2_ROWS[] = {
+    {true, 128, 9, "wgrad3_kernel<9,128>", wgrad3_kernel<9, 128>, 256},
+    {true, 64, 9, "wgrad3_kernel<9,64>", wgrad3_kernel<9, 64>, 256},
+    {false, 128, 1, "wgrad2_kernel<128,1>", wgrad2_kernel<128, 1>, 512},
+    {false, 128, 9, "wgrad2_kernel<128,9>", wgrad2_kernel<128, 9>, 512},
+    {false, 64, 1, "wgrad2_kernel<64,1>", wgrad2_kernel<64, 1>, 512},
+    {false, 64, 9, "wgrad2_kernel<64,9>", wgrad2_kernel<64, 9>, 512},
+};
+struct GenericRow { int taps; const char* name; GenericKernel kern; };
+static const GenericRow GENERIC_ROWS[] = {
+    {1, "wgrad_kernel<1>", wgrad_kernel<1>},
+    {9, "wgrad_kernel<9>", wgrad_kernel<9>},
+};
+
 // Which kernel family computes the weight gradient of `d`, with its plan — the ONE place this is decided: the launch
-// (wgrad_slabs), the slab count the reduction sums (wgrad_slab_count) and the register room a guest finds beside the
-// kernel (ocr_conv2d_wgrad_guest_room) all read it.
+// (wgrad_slabs), the slab count the reduction sums (ocr_conv2d_wgrad_reduce_f32), the register room a guest finds beside the
+// kernel (ocr_conv2d_wgrad_guest_room) and the name ocr_conv2d_wgrad_variant reports all read it.
 struct WgradSel {
   enum Family { NONE, PW, TAP3, TAP2, GENERIC } family = NONE;
+  int rc = OCR_ERR_UNSUPPORTED;   // NONE: why — OCR_ERR_INVALID_ARG for a malformed descriptor, else fill()'s own code
   int splits = 0;       // slabs written
   int cob = 0;          // TAP3 / TAP2: cout block (64 | 128)
+  unsigned grid = 0;    // workgroups of the slab kernel
+  int xcd = 0;          // XCD-aware workgroup order (conv_igemm.hip): PW / TAP3 / TAP2 grids that are a multiple of 8
+  char name[48] = "";   // the instantiation as a kernel trace prints it
   Wg2P p2{};            // TAP3 / TAP2
+  const Tap2Row* k2 = nullptr;
   WgP p{};              // GENERIC
+  const GenericRow* kg = nullptr;
 };
 static WgradSel wgrad_select(const ocr_conv_desc* d) {
   WgradSel s;
-  if ((s.splits = ocr_detail::wgrad_pw_splits(d)) > 0) {
+  // the ONE check of the descriptor's extents: the plans below divide by them, and no caller repeats it
+  if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh <= 0 || d->ow <= 0 || d->cin <= 0 || d->cout <= 0 || d->kh <= 0 ||
+      d->kw <= 0 || d->stride <= 0 || d->dilation <= 0) {
+    s.rc = OCR_ERR_INVALID_ARG;
+    return s;
+  }
+  const int taps = d->kh * d->kw == 1 ? 1 : 9;
+  int pw_grid = 0;
+  if (ocr_detail::wgrad_pw_describe(d, s.name, sizeof s.name, &s.splits, &pw_grid, &s.xcd)) {
     s.family = WgradSel::PW;
+    s.grid = (unsigned)pw_grid;
     return s;
   }
   if (fill2(d, &s.p2, &s.cob) == OCR_OK) {
     static const int v3 = [] { const char* e = getenv("OCR_WGRAD3"); return e ? atoi(e) : 1; }();   // 0: the wgrad2 family (tests)
     const bool small = (size_t)d->n * d->h * d->w * d->cin < (1u << 30) && (size_t)d->n * d->oh * d->ow * d->cout < (1u << 30);   // < 2 GiB each
     const bool use3 = d->kh * d->kw == 9 && v3 && small && d->cin % 64 == 0 && d->kw == 3 && d->stride == 1 && d->dilation == 1;
+    for (const Tap2Row& r : TAP2_ROWS)
+      if (r.v3 == use3 && r.cob == s.cob && r.taps == taps) s.k2 = &r;
+    if (!s.k2) return s;
     s.family = use3 ? WgradSel::TAP3 : WgradSel::TAP2;
     s.splits = s.p2.splits * (s.cob == 64 && !use3 ? 2 : 1);       // (wgrad2<64> splits K once more inside the workgroup)
+    s.grid = (unsigned)(s.p2.splits * s.p2.nci * s.p2.nco);
+    s.xcd = s.p2.xcd_swizzle = s.grid % 8 == 0;
+    snprintf(s.name, sizeof s.name, "%s", s.k2->name);
     return s;
   }
-  if (fill(d, &s.p) == OCR_OK) {
+  if ((s.rc = fill(d, &s.p)) == OCR_OK) {
+    for (const GenericRow& r : GENERIC_ROWS)
+      if (r.taps == taps) s.kg = &r;
     s.family = WgradSel::GENERIC;
     s.splits = s.p.splits * 2;
+    s.grid = (unsigned)(s.p.splits * s.p.nci * s.p.nco);
+    snprintf(s.name, sizeof s.name, "%s", s.kg->name);
   }
   return s;
 }
 
 extern "C" size_t ocr_conv2d_wgrad_workspace(const ocr_conv_desc* d) {
-  if (!d) return 0;
-  return (size_t)wgrad_select(d).splits * d->kh * d->kw * d->cin * d->cout * sizeof(float);
+  const WgradSel sel = wgrad_select(d);
+  if (sel.family == WgradSel::NONE) return 0;           // (a null or malformed descriptor included)
+  return (size_t)sel.splits * d->kh * d->kw * d->cin * d->cout * sizeof(float);
 }
 
 // The partial slabs [splits][kh][kw][cin][cout] of one weight gradient (every kernel family); *splits_out = their number.
 static int wgrad_slabs(const ocr_conv_desc* d, const void* x, const void* dy, void* workspace, size_t ws_bytes,
                        void* stream, int* splits_out) {
-  OCR_CHECK_ARG(d != nullptr);
-  OCR_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->oh > 0 && d->ow > 0);
   OCR_CHECK_ARG(x && dy && workspace);
+  const WgradSel sel = wgrad_select(d);                 // (checks d itself)
+  if (sel.family == WgradSel::NONE) return sel.rc;
   const size_t elems = (size_t)d->kh * d->kw * d->cin * d->cout;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int ntaps = d->kh * d->kw;
-  WgradSel sel = wgrad_select(d);
-  if (sel.family == WgradSel::NONE) return OCR_ERR_UNSUPPORTED;
   const int splits = sel.splits;
   if (ws_bytes < (size_t)splits * elems * sizeof(float)) return OCR_ERR_WORKSPACE;
   int rc;
   if (sel.family == WgradSel::PW) {
     rc = ocr_detail::wgrad_pw_launch(d, x, dy, workspace, st);
   } else if (sel.family == WgradSel::TAP3 || sel.family == WgradSel::TAP2) {
-    Wg2P& p2 = sel.p2;
-    const int cob = sel.cob;
-    const size_t lds = 2 * ((size_t)p2.HT * p2.WT * X2STR + 128 * (cob * 2 + 32));
-    const unsigned grid = (unsigned)(p2.splits * p2.nci * p2.nco);
-    p2.xcd_swizzle = grid % 8 == 0;           // XCD-aware workgroup order (conv_igemm.hip)
-    if (sel.family == WgradSel::TAP3)
-      rc = cob == 128 ? launch_wg(wgrad3_kernel<9, 128>, p2, grid, lds, x, dy, workspace, st, 256)
-                      : launch_wg(wgrad3_kernel<9, 64>, p2, grid, lds, x, dy, workspace, st, 256);
-    else if (cob == 128)
-      rc = ntaps == 1 ? launch_wg(wgrad2_kernel<128, 1>, p2, grid, lds, x, dy, workspace, st, 512)
-                      : launch_wg(wgrad2_kernel<128, 9>, p2, grid, lds, x, dy, workspace, st, 512);
-    else
-      rc = ntaps == 1 ? launch_wg(wgrad2_kernel<64, 1>, p2, grid, lds, x, dy, workspace, st, 512)
-                      : launch_wg(wgrad2_kernel<64, 9>, p2, grid, lds, x, dy, workspace, st, 512);
+    const Wg2P& p2 = sel.p2;
+    const size_t lds = 2 * ((size_t)p2.HT * p2.WT * X2STR + 128 * (sel.cob * 2 + 32));
+    rc = launch_wg(sel.k2->kern, p2, sel.grid, lds, x, dy, workspace, st, sel.k2->threads);
   } else {
     const WgP& p = sel.p;
     const size_t lds = (size_t)p.HT * p.WT * XSTR + 256 * DSTR;
-    const unsigned grid = (unsigned)(p.splits * p.nci * p.nco);
-    rc = ntaps == 1 ? launch_wg(wgrad_kernel<1>, p, grid, lds, x, dy, workspace, st, 512)
-                    : launch_wg(wgrad_kernel<9>, p, grid, lds, x, dy, workspace, st, 512);
+    rc = launch_wg(sel.kg->kern, p, sel.grid, lds, x, dy, workspace, st, 512);
   }
   if (rc != OCR_OK) return rc;
   *splits_out = splits;
@@ -896,9 +931,6 @@ extern "C" int ocr_conv2d_wgrad_slabs_f16(const ocr_conv_desc* d, const void* x,
   return wgrad_slabs(d, x, dy, workspace, ws_bytes, stream, &splits);
 }
 
-// the number of slabs wgrad_slabs writes for `d` (the same selection, nothing launched); <= 0: unsupported
-static int wgrad_slab_count(const ocr_conv_desc* d) { return wgrad_select(d).splits; }
-
 // Registers per lane a SIMD has LEFT beside the resident workgroup(s) of the kernel ocr_conv2d_wgrad_slabs_f16 selects for
 // `d` — what a guest wave may use (csrc/guest_bn.hip needs 56) — or 0 where the kernel fills the file / is not tabulated.
 // From -Rpass-analysis=kernel-resource-usage (allocation granule 8, AGPRs behind the VGPRs rounded to 4):
@@ -907,20 +939,29 @@ static int wgrad_slab_count(const ocr_conv_desc* d) { return wgrad_select(d).spl
 //   wgrad_pw_kernel<256,256,2>: 212 -> 216, two waves per SIMD (one WG of 512)       -> 80
 // tests/test_host_cpu.py::test_guest_kernels_fit_beside_the_weight_gradient re-derives the first from the compiler.
 extern "C" int ocr_conv2d_wgrad_guest_room(const ocr_conv_desc* d) {
-  if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh <= 0 || d->ow <= 0) return 0;
-  const WgradSel sel = wgrad_select(d);
+  const WgradSel sel = wgrad_select(d);                 // (NONE for a null or malformed descriptor)
   if (sel.family == WgradSel::PW) return ocr_detail::wgrad_pw_is_256x256(d) ? 80 : 0;
   if (sel.family != WgradSel::TAP3) return 0;
   return sel.cob == 128 ? 56 : 248;
 }
 
 extern "C" int ocr_conv2d_wgrad_reduce_f32(const ocr_conv_desc* d, const void* workspace, void* dw, void* stream) {
-  OCR_CHECK_ARG(d && workspace && dw);
-  OCR_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->oh > 0 && d->ow > 0);
-  const int splits = wgrad_slab_count(d);
-  if (splits <= 0) return OCR_ERR_UNSUPPORTED;
+  OCR_CHECK_ARG(workspace && dw);
+  const WgradSel sel = wgrad_select(d);                 // (checks d itself)
+  if (sel.family == WgradSel::NONE) return sel.rc;
+  const int splits = sel.splits;
   const size_t elems = (size_t)d->kh * d->kw * d->cin * d->cout;
   launch_slab_reduce(static_cast<const float*>(workspace), static_cast<float*>(dw), elems / 4, splits,
                      static_cast<hipStream_t>(stream));
   return ocr_launch_status();
+}
+
+extern "C" int ocr_conv2d_wgrad_variant(const ocr_conv_desc* d, char* out, size_t cap) {
+  const WgradSel sel = wgrad_select(d);
+  if (sel.family == WgradSel::NONE) return sel.rc;
+  OCR_CHECK_ARG(out && cap > 0);
+  const size_t elems4 = (size_t)d->kh * d->kw * d->cin * d->cout / 4;
+  const int len = snprintf(out, cap, "%s slabs=%d grid=%u xcd=%d reduce=slab_reduce_kernel<%d>", sel.name, sel.splits, sel.grid,
+                           sel.xcd, slab_reduce_lanes(elems4, sel.splits));
+  return len > 0 && (size_t)len < cap ? OCR_OK : OCR_ERR_INVALID_ARG;
 }

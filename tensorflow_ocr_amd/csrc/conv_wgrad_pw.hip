@@ -19,6 +19,7 @@
 // issued before the MFMAs of stage t.  Split-K partial blocks go to a [split][ci][co] f32 slab that
 // the caller reduces in fixed order (bitwise reproducible, no atomics).
 #include "common.h"
+#include <stdio.h>
 
 namespace {
 
@@ -182,7 +183,38 @@ __global__ __launch_bounds__(512) void wgrad_pw_kernel(PwP p, const half_t* __re
       for (int e = 0; e < 4; ++e) dst[(size_t)(i * 16 + e) * p.cout + j * 16] = acc[i][j][e];
 }
 
-struct PwCfg { int cib, cob; };
+template <int CIB, int COB, int NWCI>
+int pw_launch(const PwP& p, const void* x, const void* dy, void* slab, hipStream_t st) {
+  auto kern = wgrad_pw_kernel<CIB, COB, NWCI>;
+  const size_t lds = 2 * (size_t)PXS * ((CIB * 2 + 32) + (COB * 2 + 32));
+  static bool configured = false;
+  if (!configured) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024) != hipSuccess)
+      return OCR_ERR_HIP;
+    configured = true;
+  }
+  const unsigned grid = (unsigned)(p.splits * p.nci * p.nco * p.kh * p.kw);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, p,
+                     static_cast<const half_t*>(x), static_cast<const half_t*>(dy), static_cast<float*>(slab));
+  return ocr_launch_status();
+}
+
+// The instantiations, each ONE row: the tile that selects it, the ci waves of its 8 (the third template argument, printed in
+// the name ocr_conv2d_wgrad_variant reports) and its launcher.
+struct PwTile {
+  int cib, cob, nwci;
+  int (*launch)(const PwP&, const void*, const void*, void*, hipStream_t);
+};
+#define PW_TILE(CI, CO, NW) {CI, CO, NW, pw_launch<CI, CO, NW>}
+const PwTile PW_TILES[] = {
+    PW_TILE(256, 256, 2), PW_TILE(256, 128, 4), PW_TILE(256, 64, 4),
+    PW_TILE(128, 256, 2), PW_TILE(128, 128, 2), PW_TILE(128, 64, 4),
+    PW_TILE(64, 256, 1),  PW_TILE(64, 128, 1),  PW_TILE(64, 64, 2),
+};
+#undef PW_TILE
+
+struct PwCfg { int cib, cob; const PwTile* tile; };
 
 bool pw_plan(const ocr_conv_desc* d, PwP* p, PwCfg* c) {
   if (d->cin % 64 || d->cout % 64) return false;
@@ -192,6 +224,10 @@ bool pw_plan(const ocr_conv_desc* d, PwP* p, PwCfg* c) {
   if (!(d->kh * d->kw == 1 || (d->dilation > 1 && d->kh * d->kw <= 9))) return false;
   c->cib = d->cin % 256 == 0 ? 256 : d->cin % 128 == 0 ? 128 : 64;
   c->cob = d->cout % 256 == 0 ? 256 : d->cout % 128 == 0 ? 128 : 64;
+  c->tile = nullptr;
+  for (const PwTile& t : PW_TILES)
+    if (t.cib == c->cib && t.cob == c->cob) c->tile = &t;
+  if (!c->tile) return false;
   constexpr int wgs = 256;                       // one resident workgroup per CU
   p->n = d->n; p->h = d->h; p->w = d->w; p->cin = d->cin;
   p->oh = d->oh; p->ow = d->ow; p->cout = d->cout;
@@ -210,38 +246,13 @@ bool pw_plan(const ocr_conv_desc* d, PwP* p, PwCfg* c) {
   if (want < 1) want = 1;
   p->tiles_per_split = ocr_cdiv(p->m_tiles, want);
   p->splits = ocr_cdiv(p->m_tiles, p->tiles_per_split);
+  p->xcd_swizzle = blocks > 1 && (p->splits * blocks) % 8 == 0;
   return true;
-}
-
-template <int CIB, int COB, int NWCI>
-int pw_launch(const PwP& p, const void* x, const void* dy, void* slab, hipStream_t st) {
-  auto kern = wgrad_pw_kernel<CIB, COB, NWCI>;
-  const size_t lds = 2 * (size_t)PXS * ((CIB * 2 + 32) + (COB * 2 + 32));
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024) != hipSuccess)
-      return OCR_ERR_HIP;
-    configured = true;
-  }
-  PwP q = p;
-  const unsigned grid = (unsigned)(p.splits * p.nci * p.nco * p.kh * p.kw);
-  q.xcd_swizzle = p.nci * p.nco * p.kh * p.kw > 1 && grid % 8 == 0;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, q,
-                     static_cast<const half_t*>(x), static_cast<const half_t*>(dy), static_cast<float*>(slab));
-  return ocr_launch_status();
 }
 
 }  // namespace
 
 namespace ocr_detail {
-
-// Number of split-K slabs ([taps][cin][cout] f32 each) the pointwise path writes; 0 = shape not handled.
-int wgrad_pw_splits(const ocr_conv_desc* d) {
-  PwP p;
-  PwCfg c;
-  return pw_plan(d, &p, &c) ? p.splits : 0;
-}
 
 bool wgrad_pw_is_256x256(const ocr_conv_desc* d) {
   PwP p;
@@ -249,22 +260,25 @@ bool wgrad_pw_is_256x256(const ocr_conv_desc* d) {
   return pw_plan(d, &p, &c) && c.cib == 256 && c.cob == 256;
 }
 
+// What wgrad_pw_launch launches for `d` (nothing launched): the instantiation's name as a kernel trace prints it, the
+// number of split-K slabs ([taps][cin][cout] f32 each) it writes, the grid and whether the XCD-aware workgroup order is
+// on; false = shape not handled.
+bool wgrad_pw_describe(const ocr_conv_desc* d, char* name, size_t cap, int* splits, int* grid, int* xcd) {
+  PwP p;
+  PwCfg c;
+  if (!pw_plan(d, &p, &c)) return false;
+  snprintf(name, cap, "wgrad_pw_kernel<%d,%d,%d>", c.tile->cib, c.tile->cob, c.tile->nwci);
+  *splits = p.splits;
+  *grid = p.splits * p.nci * p.nco * p.kh * p.kw;
+  *xcd = p.xcd_swizzle;
+  return true;
+}
+
 int wgrad_pw_launch(const ocr_conv_desc* d, const void* x, const void* dy, void* slab, hipStream_t st) {
   PwP p;
   PwCfg c;
   if (!pw_plan(d, &p, &c)) return OCR_ERR_UNSUPPORTED;
-  switch (c.cib * 1000 + c.cob) {
-    case 256256: return pw_launch<256, 256, 2>(p, x, dy, slab, st);
-    case 256128: return pw_launch<256, 128, 4>(p, x, dy, slab, st);
-    case 256064: return pw_launch<256, 64, 4>(p, x, dy, slab, st);
-    case 128256: return pw_launch<128, 256, 2>(p, x, dy, slab, st);
-    case 128128: return pw_launch<128, 128, 2>(p, x, dy, slab, st);
-    case 128064: return pw_launch<128, 64, 4>(p, x, dy, slab, st);
-    case 64256: return pw_launch<64, 256, 1>(p, x, dy, slab, st);
-    case 64128: return pw_launch<64, 128, 1>(p, x, dy, slab, st);
-    case 64064: return pw_launch<64, 64, 2>(p, x, dy, slab, st);
-  }
-  return OCR_ERR_UNSUPPORTED;
+  return c.tile->launch(p, x, dy, slab, st);
 }
 
 }  // namespace ocr_detail

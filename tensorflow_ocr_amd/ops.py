@@ -306,6 +306,17 @@ def bn_relu_pool_bwd_idx_apply_affine(y, argmax, da_pool, coef, relu, dy):
         L.RECORDER.tag_last(("guest", 4.75 * n * h * w * c))          # y read + dy written + the pooled gradient and index
 
 
+def conv2d_wgrad_variant(d):
+    """What the weight gradient of `d` launches (ocr_conv2d_wgrad_variant): a dict with `kernel` (the slab kernel's
+    instantiation), `slabs`, `grid`, `xcd` (ints) and `reduce` (the slab sum's instantiation).  Raises OcrHipError with
+    the status ocr_conv2d_wgrad_f16 would give where no kernel family takes the shape."""
+    buf = ctypes.create_string_buffer(128)
+    L.call_int("ocr_conv2d_wgrad_variant", byref(d), buf, c_size_t(128))
+    kernel, *fields = buf.value.decode().split(" ")
+    v = dict(f.split("=", 1) for f in fields)
+    return {"kernel": kernel, "slabs": int(v["slabs"]), "grid": int(v["grid"]), "xcd": int(v["xcd"]), "reduce": v["reduce"]}
+
+
 def conv2d_wgrad(d, x, dy, dw, ws, alloc=None):
     """alloc (callable: nbytes -> uint8 tensor; layers pass Graph.empty while OCR_GUEST_BN is on): the slabs get a
     buffer of their own and the call is issued as its two halves — slab kernel ["side", FLOP], slab sum ["reduce"] —

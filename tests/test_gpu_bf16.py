@@ -51,6 +51,27 @@ def test_bf16_conv_epilogue_matrix(device):
     assert m and int(m.group(1)) == len(CASES) and "failed" not in r.stdout, tail
 
 
+def test_bf16_wgrad_matrix(device):
+    """tests/test_gpu_wgrad_matrix.py (every weight-gradient family and plan edge against float64) on the bf16 library:
+    every case passes at the same bar (bf16 operands and their products are exact in f32 as well)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    try:
+        import test_gpu_wgrad_matrix as W
+    finally:
+        sys.path.pop(0)
+    cases = 2 * len(W.ROWS) + len(W.UNSUPPORTED_SHAPES) + len(W.SLAB_SUM) + 1
+    env = dict(os.environ, OCR_STORAGE="bf16")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-s", "-m", "gpu", "-p", "no:cacheprovider",
+                        os.path.join(ROOT, "tests", "test_gpu_wgrad_matrix.py")],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    tail = (r.stdout + r.stderr)[-3000:]
+    import re
+    print("\n".join(re.findall(r"(?:wgrad|slab sum) .*", r.stdout)))
+    assert r.returncode == 0, tail
+    m = re.search(r"(\d+) passed", r.stdout)
+    assert m and int(m.group(1)) == cases and "failed" not in r.stdout, tail
+
+
 def test_bf16_resnet50_east_640_batch64_parity(device):
     """BASELINE configs[3] as quoted (bf16, batch 64, 640^2): n = 64 replicated == n = 2 in the bf16 library."""
     env = dict(os.environ, OCR_STORAGE="bf16")

@@ -45,6 +45,50 @@ def test_library_exports_every_declared_symbol():
     assert bf.ocr_storage_dtype() == b"bf16"
 
 
+def test_wgrad_variant_names_the_selection_and_refuses_malformed_descriptors():
+    """ocr_conv2d_wgrad_variant / ocr_conv2d_wgrad_workspace are host routines: one shape per weight-gradient family
+    (tests/test_gpu_wgrad_matrix.py runs them), an unsupported shape, and descriptors with a zero extent — which the
+    split-K plans would divide by — in both libraries."""
+    from tensorflow_ocr_amd import _lib, ops
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__ as ge
+        ge.build()
+    want = {
+        (2, 9, 37, 256, 128, 1, 1, 1): "wgrad_pw_kernel<256,128,4> slabs=20 grid=20 xcd=0 reduce=slab_reduce_kernel<16>",
+        (2, 12, 20, 128, 256, 3, 6, 1): "wgrad_pw_kernel<128,256,2> slabs=12 grid=108 xcd=0 reduce=slab_reduce_kernel<4>",
+        (1, 16, 64, 256, 256, 3, 1, 1): "wgrad3_kernel<9,128> slabs=8 grid=64 xcd=1 reduce=slab_reduce_kernel<4>",
+        (2, 13, 40, 128, 192, 3, 1, 1): "wgrad3_kernel<9,64> slabs=16 grid=96 xcd=1 reduce=slab_reduce_kernel<16>",
+        (1, 17, 19, 96, 160, 3, 1, 1): "wgrad2_kernel<64,9> slabs=10 grid=30 xcd=0 reduce=slab_reduce_kernel<4>",
+        (1, 8, 16, 96, 128, 1, 1, 1): "wgrad2_kernel<128,1> slabs=2 grid=4 xcd=0 reduce=slab_reduce_kernel<1>",
+    }
+    for path in (_lib.LIB_PATH, os.path.join(os.path.dirname(_lib.LIB_PATH), "libocr_hip_bf16.so")):
+        lib = ctypes.CDLL(path)
+        lib.ocr_conv2d_wgrad_workspace.restype = ctypes.c_size_t
+        buf = ctypes.create_string_buffer(128)
+
+        def ask(d):
+            return lib.ocr_conv2d_wgrad_variant(ctypes.byref(d), buf, ctypes.c_size_t(128)), lib.ocr_conv2d_wgrad_workspace(ctypes.byref(d))
+        for (n, h, w, cin, cout, k, dil, stride), text in want.items():
+            d = ops.conv_desc((n, h, w, cin), cout, k, k, stride, dil)
+            rc, nbytes = ask(d)
+            assert rc == 0 and buf.value.decode() == text
+            assert nbytes == int(text.split("slabs=")[1].split()[0]) * k * k * cin * cout * 4
+        assert ask(ops.conv_desc((2, 18, 36, 64), 128, 3, 3, 2, 1)) == (-2, 0)        # 3x3 stride 2: no family
+        assert ask(ops.conv_desc((2, 9, 11, 48), 64, 3, 3)) == (-2, 0)
+        for field in ("n", "h", "w", "cin", "oh", "ow", "cout", "kh", "kw", "stride", "dilation"):
+            d = ops.conv_desc((2, 9, 11, 64), 64, 3, 3)
+            setattr(d, field, 0)
+            assert ask(d) == (-1, 0), field
+        assert lib.ocr_conv2d_wgrad_variant(None, buf, ctypes.c_size_t(128)) == -1
+        assert lib.ocr_conv2d_wgrad_workspace(None) == 0
+        lib.ocr_conv2d_wgrad_guest_room.restype = ctypes.c_int
+        assert lib.ocr_conv2d_wgrad_guest_room(None) == 0
+        # (no GPU is touched: every argument is checked before anything is launched)
+        assert lib.ocr_conv2d_wgrad_f16(None, buf, buf, buf, buf, ctypes.c_size_t(1 << 20), None) == -1
+        assert lib.ocr_conv2d_wgrad_slabs_f16(None, buf, buf, buf, ctypes.c_size_t(1 << 20), None) == -1
+        assert lib.ocr_conv2d_wgrad_reduce_f32(None, buf, buf, None) == -1
+
+
 def test_loader_refuses_a_library_of_another_abi_version(monkeypatch):
     """entry points changed their argument lists; a stale libocr_hip.so must be refused at load time, not
     called with its pointers shifted by a slot."""
