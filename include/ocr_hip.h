@@ -32,7 +32,8 @@ extern "C" {
  * loss scale (ocr_loss_scale_init, ocr_grad_check_f32, the *_dyn optimiser steps and loss seeds) joined at 7 too, and so
  * did global-norm clipping (ocr_grad_clip_*, ocr_grad_check_clip_f32, the *_clip optimiser steps), the batched training
  * augmentation (ocr_augment_u8_batch, ocr_augment_desc) and gradient accumulation (ocr_grad_accum_init, ocr_grad_accum_f32,
- * ocr_grad_accum_advance, ocr_grad_accum_state) and ocr_conv2d_wgrad_variant (the name of the weight-gradient launch). */
+ * ocr_grad_accum_advance, ocr_grad_accum_state), ocr_conv2d_wgrad_variant (the name of the weight-gradient launch) and the
+ * training summaries (ocr_tensor_stats_*, ocr_summary_image_u8). */
 #define OCR_ABI_VERSION 7
 
 enum {
@@ -1121,6 +1122,67 @@ int ocr_grad_accum_init(void* state, int k, void* stream);
 int ocr_grad_accum_f32(void* grad, void* acc, int64_t n, const void* state, void* stream);
 /* micro = (micro + 1) % k; windows_total += 1 on the wrap.  One thread. */
 int ocr_grad_accum_advance(void* state, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Training summaries (summary.TensorStats, summary.FileWriter): what the reference logs per variable with
+ * tf.summary.histogram / scalar (train_pixellink.py:179-194) and per batch with tf.summary.image
+ * (multigpu_train.py:49-65), computed ON THE DEVICE from the flat buffers of the step just taken.  These calls are
+ * never part of a recorded step plan: the host enqueues them behind the step's last entry on summary steps only.
+ *
+ * A SEGMENT is one variable's [offset, offset + size) inside a flat f32 buffer; the store's pad words between
+ * variables belong to no segment and are never read.  The value examined is
+ *     v = x[i] * (mul_host * *mul_dev)          mul_dev == NULL means 1; both products in f32
+ * which is the product the optimiser kernels form: for variables pass (1, NULL); for gradients the optimiser's factor
+ * of that step — host part in mul_host, device part &ocr_grad_clip_state.g_mul or &ocr_loss_scale_state.inv_scale_used
+ * in mul_dev — so the histogram shows the gradient actually applied, with no host read.
+ *
+ * Buckets are TensorFlow's default histogram (core/lib/histogram/histogram.cc): positive limits in f64 from
+ * `v = 1e-12; while (v < 1e20) { push(v); v *= 1.1; }` then DBL_MAX (774 + 1), mirrored negative with 0 between:
+ * OCR_TENSOR_STATS_BUCKETS = 1551 limits, and a finite element counts in bucket upper_bound(limits, (double)v).
+ * The positive half is built by that recurrence on the host (ocr_tensor_stats_table) and travels inside the table.
+ * inf and NaN are COUNTED in `nonfinite` and not bucketed (TensorFlow's op raises on them instead).
+ * ------------------------------------------------------------------------- */
+#define OCR_TENSOR_STATS_POS_LIMITS 775
+#define OCR_TENSOR_STATS_BUCKETS 1551
+#define OCR_TENSOR_STATS_CHUNK 16384        /* elements one workgroup examines at a time */
+typedef struct {
+  double   sum, sum_squares;     /* over the finite elements, each term and the sums in f64, in a fixed order */
+  float    min, max;             /* over the finite elements; 0 when there is none */
+  uint32_t num;                  /* finite elements */
+  uint32_t nonfinite;            /* inf / NaN elements */
+  uint32_t bucket[OCR_TENSOR_STATS_BUCKETS];
+  uint32_t reserved;
+} ocr_tensor_stats_record;       /* 6240 bytes; 8-byte aligned device memory */
+int ocr_tensor_stats_num_buckets(void);          /* OCR_TENSOR_STATS_BUCKETS */
+int ocr_tensor_stats_chunk(void);                /* OCR_TENSOR_STATS_CHUNK */
+size_t ocr_tensor_stats_record_bytes(void);      /* sizeof(ocr_tensor_stats_record) */
+/* all OCR_TENSOR_STATS_BUCKETS limits in rising order (n must equal that count): host memory, no device involved */
+int ocr_tensor_stats_limits(double* limits_out, int n);
+/* The segment table, as ocr_pack_weights_batch_table serves ocr_pack_weights_batch_f16: fills a HOST table of
+ * ocr_tensor_stats_table_bytes(n_segments) bytes (header, the 775 positive limits, one entry per segment with its
+ * first chunk) from (offset, size) pairs in elements; the caller uploads it once (8-byte aligned) and passes the device
+ * copy to every ocr_tensor_stats_f32.  size must be in 1 .. 2^32 - 1 (32-bit counts), offset >= 0, any alignment.
+ * *n_chunks_out: the sum of ceil(size / OCR_TENSOR_STATS_CHUNK), what ocr_tensor_stats_workspace wants. */
+size_t ocr_tensor_stats_table_bytes(int n_segments);
+int ocr_tensor_stats_table(int n_segments, const int64_t* offsets, const int64_t* sizes, void* table_host,
+                           int64_t* n_chunks_out);
+size_t ocr_tensor_stats_workspace(int64_t n_chunks);   /* bytes of the per-chunk partials */
+/* records[n_segments] (ocr_tensor_stats_record each) of the segments of `x`.  One memset of the records and two launches
+ * on `stream`: persistent 256-thread workgroups take chunks in turn — an LDS histogram and the limits in LDS, a binary
+ * search of |v|, 16-byte loads between a scalar head and tail, non-zero bins flushed with global u32 atomics (integer
+ * counts: order-independent), sum / sum_squares / min / max / counts as one partial per chunk in `workspace`
+ * (8-byte aligned, caller-owned) — and one workgroup per segment then joins its partials in a fixed order: the records
+ * are bitwise reproducible.  The host cannot read the device table, so the kernels check it: when it is not a table for
+ * n_segments segments, or names more chunks than ws_bytes holds, nothing is read or written through it and every record
+ * comes back with nonfinite = 0xffffffff, num = 0 and NaN sums.  ws_bytes below n_segments partials: OCR_ERR_WORKSPACE. */
+int ocr_tensor_stats_f32(const void* x, const void* segments_dev, int n_segments, float mul_host, const void* mul_dev,
+                         void* records, void* workspace, size_t ws_bytes, void* stream);
+/* One image [h, w, c] f32 (c in 1, 3, 4) to u8 by tf.summary.image's rule for floats: min and max over the finite
+ * elements; min >= 0: scale = 255 / max, offset = 0; else scale = 127 / max(|min|, |max|), offset = 128; scale = 0 when
+ * that maximum is below 1e-6; out = (u8)(x * scale + offset), the multiply and the add rounded separately; a non-finite
+ * element gives 0.  Two launches; workspace: ocr_summary_image_workspace() bytes, 4-byte aligned. */
+size_t ocr_summary_image_workspace(void);
+int ocr_summary_image_u8(const void* x_f32, int h, int w, int c, void* out_u8, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Data-parallel exchange.  Replaces `average_gradients`

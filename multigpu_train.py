@@ -11,7 +11,9 @@ PixelLink heads + OHNM loss, the one the reference script imports; `model_vgg` /
 `pixellink` the others).  Data: `--training_data_path` (the reference's icdar.py flag) feeds ICDAR
 images + gt_*.txt through datasets/icdar.get_batch — host decode in `--num_readers` processes,
 upload + resize + label maps on the feeder's HIP stream, overlapped with the step; without it (or
-with an empty directory) batches are synthetic (`tensorflow_ocr_amd.synthetic`).  `--augment east`
+with an empty directory) batches are synthetic (`tensorflow_ocr_amd.synthetic`).  Every
+`--save_summary_steps` optimiser steps rank 0 adds scalars and images (and, with
+`--summary_variables`, per-variable histograms) to a TensorBoard event file in `--checkpoint_path`.  `--augment east`
 (or `pixellink`, or key=value,...) turns on the augmentation the reference keeps disabled
 (datasets/icdar.py:576-615), warped on the device in one launch per batch.  The stdout line
 format is the reference's (:183-184)."""
@@ -52,6 +54,10 @@ def parse(argv=None):
     # the augmentation the reference keeps disabled (datasets/icdar.py:576-615), on the device: none | east | pixellink |
     # key=value,... (datasets/augment.py: Augment.parse).  Only with --training_data_path; synthetic batches have none.
     ap.add_argument('--augment', type=_augment_arg, default=None, metavar='SPEC')
+    # not a reference flag: with the scalars and images that --save_summary_steps writes (0: no event file), the four
+    # per-variable summaries of train_pixellink.py:179-194 (histograms of every variable and gradient, their means) from
+    # one device pass over the flat buffers (summary.TensorStats)
+    ap.add_argument('--summary_variables', action='store_true')
     return ap.parse_args(argv)
 
 
@@ -203,11 +209,43 @@ def _train_loop(FLAGS, g, step, feeder, rng, rank, world, device, start):
     # `global_step` (which the optimiser continues from), so a resumed run takes max_steps MORE steps
     K = FLAGS.accumulate_steps
     first = [batch]
+    last = [batch]
 
     def next_batch():
-        return first.pop() if first else _next_batch(FLAGS, feeder, rng, device)
+        last[0] = first.pop() if first else _next_batch(FLAGS, feeder, rng, device)
+        return last[0]
+    summaries = None
+    if rank == 0 and FLAGS.save_summary_steps > 0:
+        # summary_writer = tf.summary.FileWriter(FLAGS.checkpoint_path, ...) (multigpu_train.py:145)
+        from tensorflow_ocr_amd.summary import TrainingSummaries
+        summaries = TrainingSummaries(FLAGS.checkpoint_path, step, variables=FLAGS.summary_variables)
+    try:
+        _steps(FLAGS, g, step, opt, K, next_batch, last, summaries, rank, world, start)
+    finally:
+        if summaries is not None:
+            summaries.close()
+
+
+def _write_summaries(summaries, g, opt, loss, batch):
+    """multigpu_train.py:49-65,105-106,135-136 on the step just taken (the reference runs a second train step for it,
+    :189-194): behind the window's closing call, so store.flat_grad holds that optimiser step's gradients."""
+    ml = loss.item()
+    scalars = {'model_loss': ml, 'total_loss': ml + opt.regularization_loss().item(), 'learning_rate': opt.learning_rate()}
+    if g.loss_scaler is not None:
+        scalars['loss_scale'] = g.loss_scaler.scale()
+    if opt.clip is not None:
+        scalars['grad_norm'] = opt.grad_norm()
+    images, score_maps, geo_maps = batch[0], batch[1], batch[2]
+    summaries.write(opt.global_step, scalars, [('input', images[0]), ('score_map', score_maps[0]),
+                                               ('geo_map_0', geo_maps[0][..., 0:1])])
+
+
+def _steps(FLAGS, g, step, opt, K, next_batch, last, summaries, rank, world, start):
+    from tensorflow_ocr_amd import checkpoint, dist
     for it in range(FLAGS.max_steps):
         loss = _window(step, K, next_batch)
+        if summaries is not None and it % FLAGS.save_summary_steps == 0:
+            _write_summaries(summaries, g, opt, loss, last[0])
         if it % 10 == 0:
             ml = loss.item()
             # the stop decision is collective: a rank leaving alone would strand the others in the

@@ -38,6 +38,16 @@ class SoftmaxLossDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("n", "hw", "pixel_rule", "label_rule", "link_gate", "focal")] + \
                [(n, ctypes.c_float) for n in ("neg_ratio", "alpha", "gamma")]
 
+TENSOR_STATS_BUCKETS = 1551
+
+
+class TensorStatsRecord(ctypes.Structure):
+    """ocr_tensor_stats_record (include/ocr_hip.h)."""
+    _fields_ = [("sum", ctypes.c_double), ("sum_squares", ctypes.c_double), ("min", ctypes.c_float),
+                ("max", ctypes.c_float), ("num", ctypes.c_uint32), ("nonfinite", ctypes.c_uint32),
+                ("bucket", ctypes.c_uint32 * TENSOR_STATS_BUCKETS), ("reserved", ctypes.c_uint32)]
+
+
 _lib = None
 # the value of OCR_ABI_VERSION (include/ocr_hip.h) this host layer was written against: a library built from
 # other sources would take its pointers shifted by a slot and write wildly instead of returning an OCR_ERR

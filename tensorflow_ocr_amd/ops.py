@@ -1239,6 +1239,65 @@ def grad_accum_advance(state):
     L.call("ocr_grad_accum_advance", ptr(state), _st())
 
 
+# training summaries (summary.TensorStats): `table` is the device copy of ocr_tensor_stats_table's host table (uint8),
+# `records` a uint8 tensor of n_segments * tensor_stats_record_bytes() bytes, `ws` a float64 tensor of
+# tensor_stats_workspace(n_chunks) bytes; all three belong to the caller
+def tensor_stats_num_buckets():
+    return L.call_int("ocr_tensor_stats_num_buckets")
+
+
+def tensor_stats_chunk():
+    return L.call_int("ocr_tensor_stats_chunk")
+
+
+def tensor_stats_record_bytes():
+    return L.call_size("ocr_tensor_stats_record_bytes")
+
+
+def tensor_stats_limits():
+    """The 1551 bucket limits as the library builds them (numpy float64; host only)."""
+    import numpy as np
+    out = np.empty(tensor_stats_num_buckets(), np.float64)
+    L.call("ocr_tensor_stats_limits", out.ctypes.data_as(ctypes.c_void_p), c_int(out.size))
+    return out
+
+
+def tensor_stats_table(offsets, sizes):
+    """(host table as a numpy uint8 array, n_chunks) for segments [offset, offset + size) in elements."""
+    import numpy as np
+    offs = np.ascontiguousarray(offsets, dtype=np.int64)
+    szs = np.ascontiguousarray(sizes, dtype=np.int64)
+    assert offs.ndim == 1 and offs.shape == szs.shape and offs.size > 0
+    table = np.zeros((L.call_size("ocr_tensor_stats_table_bytes", c_int(offs.size)) + 7) // 8, np.int64)
+    n_chunks = c_int64(0)
+    L.call("ocr_tensor_stats_table", c_int(offs.size), offs.ctypes.data_as(ctypes.c_void_p),
+           szs.ctypes.data_as(ctypes.c_void_p), table.ctypes.data_as(ctypes.c_void_p), byref(n_chunks))
+    return table.view(np.uint8), int(n_chunks.value)
+
+
+def tensor_stats_workspace(n_chunks):
+    return L.call_size("ocr_tensor_stats_workspace", c_int64(n_chunks))
+
+
+def tensor_stats(x, table, n_segments, mul_host, mul_dev, records, ws):
+    """Per-segment records of the f32 buffer `x` times mul_host * mul_dev[0] (mul_dev: a 1-element f32 device view or None)."""
+    assert records.numel() * records.element_size() >= n_segments * tensor_stats_record_bytes()
+    L.call("ocr_tensor_stats_f32", ptr(x), ptr(table), c_int(n_segments), c_float(mul_host), ptr(mul_dev), ptr(records),
+           ptr(ws), c_size_t(ws.numel() * ws.element_size()), _st())
+
+
+def summary_image_workspace():
+    return L.call_size("ocr_summary_image_workspace")
+
+
+def summary_image_u8(x, out, ws):
+    """One image [h, w, c] f32 -> u8 [h, w, c] by tf.summary.image's float rule."""
+    h, w, c = x.shape
+    assert x.is_contiguous() and out.is_contiguous() and out.numel() == x.numel() and out.element_size() == 1
+    assert ws.numel() * ws.element_size() >= summary_image_workspace()
+    L.call("ocr_summary_image_u8", ptr(x), c_int(h), c_int(w), c_int(c), ptr(out), ptr(ws), _st())
+
+
 def scale_(x, s):
     L.call("ocr_scale_f32", ptr(x), c_int64(x.numel()), c_float(s), _st())
 

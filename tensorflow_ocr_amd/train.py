@@ -669,6 +669,19 @@ class TrainStep:
         gs = self.reducer.grad_scale
         return gs if self.accumulate_steps == 1 else gs / self.accumulate_steps
 
+    def summary_factor(self):
+        """(mul_host, mul_dev) for `summary.TensorStats.run(store.flat_grad, ...)` behind a call that stepped the
+        optimiser: the factor that step's optimiser kernel multiplied the gradients with, its device part left on the
+        device (a 1-element f32 view of the clip state's g_mul or of the loss-scale state's inv_scale_used; None: 1).
+        No device read."""
+        gs = self._grad_scale()
+        if self.opt.clip is not None:
+            return 1.0, self.opt.clip.state[ops.GC_G_MUL:ops.GC_G_MUL + 1].view(torch.float32)
+        sc = self.g.loss_scaler
+        if sc is not None:
+            return gs, sc.state[ops.LS_INV_SCALE_USED:ops.LS_INV_SCALE_USED + 1].view(torch.float32)
+        return gs / self.g.loss_scale, None
+
     # -- eager / recording path --------------------------------------------------------------
     def _eager(self, batch, record):
         from . import _lib

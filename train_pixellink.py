@@ -56,6 +56,12 @@ def parse(argv=None):
     # of K micro-batches of --batch_size, so one card reaches the effective batch of K.  The step counters
     # below (--max_number_of_steps, --log_every_n_steps, the checkpoint interval, the staircase) count OPTIMISER steps.  1 = off.
     ap.add_argument('--accumulate_steps', type=_accumulate_steps_arg, default=1)
+    # not a reference flag (the reference's slim.learning.train writes its summaries on a timer): every N optimiser steps
+    # rank 0 adds the loss, the learning rate and the input image to a TensorBoard event file in --train_dir and, with
+    # --summary_variables, the four per-variable summaries of `sum_gradients` (:190-193) from one device pass over the
+    # flat buffers (summary.TensorStats).  0 = off: no event file.
+    ap.add_argument('--save_summary_steps', type=int, default=0)
+    ap.add_argument('--summary_variables', action='store_true')
     return ap.parse_args(argv)
 
 
@@ -187,14 +193,30 @@ def main():
     rng = np.random.default_rng(1000 + rank)
     if FLAGS.train_dir and rank == 0:
         os.makedirs(FLAGS.train_dir, exist_ok=True)
+    if FLAGS.save_summary_steps > 0 and not FLAGS.train_dir:
+        raise SystemExit('--save_summary_steps needs --train_dir (where the event file goes)')
     start = time.time()
+    last = [None]
     def next_batch():
         if feeder is not None:
-            return next(feeder)
-        im, px, lk, _ = synthetic.make_batch(rng, batch_size_per_gpu, FLAGS.train_image_height)
-        return [torch.from_numpy(a).to(device, non_blocking=True) for a in (im, px[..., 0], lk)]
+            last[0] = next(feeder)
+        else:
+            im, px, lk, _ = synthetic.make_batch(rng, batch_size_per_gpu, FLAGS.train_image_height)
+            last[0] = [torch.from_numpy(a).to(device, non_blocking=True) for a in (im, px[..., 0], lk)]
+        return last[0]
+    summaries = None
     for it in range(FLAGS.max_number_of_steps):
         loss = _window(step, FLAGS.accumulate_steps, next_batch)
+        if rank == 0 and FLAGS.save_summary_steps > 0 and it % FLAGS.save_summary_steps == 0:
+            if summaries is None:            # (the flat buffers exist once the first step has run)
+                from tensorflow_ocr_amd.summary import TrainingSummaries
+                summaries = TrainingSummaries(FLAGS.train_dir, step, variables=FLAGS.summary_variables)
+            scalars = {'total_loss': loss.item(), 'learning_rate': step.opt.learning_rate()}
+            if g.loss_scaler is not None:
+                scalars['loss_scale'] = g.loss_scaler.scale()
+            if step.opt.clip is not None:
+                scalars['grad_norm'] = step.opt.grad_norm()
+            summaries.write(step.opt.global_step, scalars, [('input', last[0][0][0])])
         if it % FLAGS.log_every_n_steps == 0:
             v = loss.item()
             dt = (time.time() - start) / FLAGS.log_every_n_steps
@@ -210,6 +232,8 @@ def main():
                 break
         if FLAGS.train_dir and rank == 0 and it > 0 and it % 1000 == 0:
             checkpoint.save_training_state(FLAGS.train_dir, g, step.opt)
+    if summaries is not None:
+        summaries.close()
     if feeder is not None:
         feeder.close()
 
