@@ -235,7 +235,11 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(FirstP p, const h
       const float yf = (float)y8[e];
       const bool pass = !bn.relu || __builtin_fmaf(yf, cA[e], cS[e]) > OCR_RELU_TIE;   // the stored activation is positive
       const float dz = pass ? (float)g8[e] : 0.f;
-      o[e] = (half_t)__builtin_fmaf(cA[e], dz, __builtin_fmaf(cB[e], yf, cC[e]));
+      // dy is the f32 value rounded to 16 bits, for EVERY element: left to itself hipcc fuses the outer fma and the
+      // conversion of SOME elements into v_fma_mix{lo,hi}_f16 (one rounding), a 16-bit ulp away on an f32 value that is a tie
+      float dyf = __builtin_fmaf(cA[e], dz, __builtin_fmaf(cB[e], yf, cC[e]));
+      asm volatile("" : "+v"(dyf));
+      o[e] = (half_t)dyf;
     }
     return __builtin_bit_cast(u32x4, o);
   };
@@ -536,7 +540,7 @@ __global__ void pack_first_kernel(const float* __restrict__ w, half_t* __restric
 int wgrad_blocks(int m_tiles) { return m_tiles < 512 ? m_tiles : 512; }
 
 int fill(FirstP* p, int n, int h, int w, int cout, int flags) {
-  OCR_CHECK_ARG(n > 0 && h > 0 && w > 0);
+  OCR_CHECK_ARG(n > 0 && h > 0 && w > 0 && cout > 0);   // (cout = 0 passes the shape rule and would launch an empty grid)
   OCR_CHECK_SHAPE(cout % 64 == 0);
   p->n = n; p->h = h; p->w = w; p->cout = cout; p->flags = flags;
   p->tiles_x = ocr_cdiv(w, TILE_W);
@@ -664,6 +668,7 @@ extern "C" int ocr_conv2d_first_moments_keep_f16(int n, int h, int w, int cout, 
   int rc = fill(&p, n, h, w, cout, 0);
   if (rc != OCR_OK) return rc;
   OCR_CHECK_ARG(x4 && w_first && stats_row && workspace);
+  OCR_CHECK_ARG(((uintptr_t)moments_f64 & 7) == 0);      // (every argument is judged before the first launch)
   if (ws_bytes < ocr_conv2d_first_moments_workspace() || ((uintptr_t)workspace & 7)) return OCR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int blocks = p.m_tiles < FM_WGS ? p.m_tiles : FM_WGS;
@@ -671,7 +676,6 @@ extern "C" int ocr_conv2d_first_moments_keep_f16(int n, int h, int w, int cout, 
   double* stage = reinterpret_cast<double*>(static_cast<char*>(workspace) + (size_t)FM_WGS * 1024 * sizeof(float));
   hipLaunchKernelGGL(first_moments_kernel, dim3(blocks), dim3(256), 0, st, p, static_cast<const half_t*>(x4), slab);
   hipLaunchKernelGGL(first_moments_stage_kernel, dim3(32), dim3(256), 0, st, slab, blocks, stage);
-  OCR_CHECK_ARG(((uintptr_t)moments_f64 & 7) == 0);
   hipLaunchKernelGGL(first_moments_finish_kernel, dim3(1), dim3(256), 0, st, stage, static_cast<const half_t*>(w_first),
                      cout, static_cast<float*>(stats_row), static_cast<double*>(moments_f64));
   return ocr_launch_status();

@@ -197,7 +197,10 @@ __global__ __launch_bounds__(256, 2) void conv_stem_wgrad_kernel(StemP p, const 
               const float yf = (float)y8[e];
               const bool pass = !bn.relu || __builtin_fmaf(yf, cA[e], cS[e]) > OCR_RELU_TIE;
               const float dz = pass ? (float)g8[e] : 0.f;
-              o[e] = (half_t)__builtin_fmaf(cA[e], dz, __builtin_fmaf(cB[e], yf, cC[e]));
+              // (rounded to f32, then to 16 bits, for EVERY element: see conv_first_wgrad_kernel's staged())
+              float dyf = __builtin_fmaf(cA[e], dz, __builtin_fmaf(cB[e], yf, cC[e]));
+              asm volatile("" : "+v"(dyf));
+              o[e] = (half_t)dyf;
             }
             v = __builtin_bit_cast(u32x4, o);
           }
@@ -255,7 +258,7 @@ __global__ void pack_stem_kernel(const float* __restrict__ w, half_t* __restrict
 int stem_blocks(int m_tiles) { return m_tiles < 512 ? m_tiles : 512; }
 
 int fill(StemP* p, int n, int h, int w, int cout, int flags) {
-  OCR_CHECK_ARG(n > 0 && h > 0 && w > 0);
+  OCR_CHECK_ARG(n > 0 && h > 0 && w > 0 && cout > 0);   // (cout = 0 passes the shape rule and would launch an empty grid)
   OCR_CHECK_SHAPE(cout % 64 == 0);
   p->n = n; p->h = h; p->w = w; p->cout = cout; p->flags = flags;
   p->oh = (h - 1) / 2 + 1;          // pad (3,3), kernel 7, stride 2, VALID
