@@ -352,7 +352,15 @@ int ocr_prep_images_norm_f16(const void* images_f32, int64_t npix, float m0, flo
  * ------------------------------------------------------------------------- */
 /* partial [T][2][C] f32 (sum, sum of squares per row block; from OCR_CONV_STATS or ocr_sc_stats)
  * -> scale/shift (a = y*scale + shift), saved mean / 1/std, moving-average update with the
- * unbiased variance.  gamma/beta/moving_* may be NULL.  workspace >= ocr_bn_reduce_workspace. */
+ * unbiased variance.  gamma/beta/moving_* may be NULL.  workspace >= ocr_bn_reduce_workspace.
+ * The partial rows are summed in f64 in one launch: up to 1024 rows by one workgroup per 64 channels, beyond that by
+ * R = ceil(T / rows) row blocks (rows = T / 16 rounded up to 32, at least 256, at most 2048) whose last arriver adds
+ * the R stage rows in row order (bitwise reproducible; ticket counters in 16 rotating, self-resetting slots).  R > 32
+ * (a second ticket level, T > 65536 = 32 blocks of 2048 rows) is reached only by calling ocr_bn_finalize /
+ * ocr_bn_bwd_sums / ocr_bn_bwd_coefficients directly: every producer of partial rows in this library stops at 2048.
+ * Status (all entries of this section): OCR_ERR_INVALID_ARG for a null required pointer or a non-positive extent,
+ * OCR_ERR_UNSUPPORTED for a channel count the entry does not take, OCR_ERR_WORKSPACE for ws_bytes below
+ * ocr_bn_reduce_workspace; nothing is launched in any of them (tests/test_gpu_bn_pool_matrix.py). */
 size_t ocr_bn_reduce_workspace(int T, int C);
 int ocr_bn_finalize(const void* partial, int T, int C, double count, const void* gamma,
                     const void* beta, float eps, float decay, void* moving_mean, void* moving_var,

@@ -25,8 +25,8 @@ __global__ void prep_images_kernel(const float* __restrict__ img, half_t* __rest
 }
 
 // ------------------------------------------------- per-channel partial reduce
-// partial [T][2][C] f32 -> stage [R][2][C] f64 (R = ceil(T/256)) -> final per-channel sums, in ONE
-// launch: every block reduces its 256 rows, publishes them and takes a ticket; the block that draws
+// partial [T][2][C] f32 -> stage [R][2][C] f64 (R = ceil(T / rows), rows = red_rows(T) below) -> final per-channel sums,
+// in ONE launch: every block reduces its `rows` rows, publishes them and takes a ticket; the block that draws
 // the last ticket of its 64-channel group sums the R stage rows IN ROW ORDER (so the result does not
 // depend on which block happens to be last: bitwise reproducible) and runs the finalisation.  No
 // block ever waits for another one (no spinning), the ticket counter resets itself.
@@ -1260,7 +1260,7 @@ extern "C" int ocr_bn_relu_bwd_f16(const void* y, const void* scale, const void*
                                    int c, int relu, int pool, void* dgamma, void* dbeta, void* dy,
                                    void* partial, void* workspace, size_t ws_bytes, void* stream) {
   OCR_CHECK_ARG(y && scale && shift && save_mean && save_invstd && dgamma && dbeta && dy);
-  OCR_CHECK_ARG(partial && workspace);
+  OCR_CHECK_ARG(partial && workspace && n > 0 && h > 0 && w > 0);
   OCR_CHECK_ARG(pool == 0 || pool == 2);
   OCR_CHECK_ARG(pool ? da_pool != nullptr : da_full != nullptr);
   OCR_CHECK_SHAPE(c % 8 == 0 && pow2(c / 8) && c / 8 <= 256);
@@ -1312,7 +1312,7 @@ extern "C" int ocr_bn_relu_bwd_reduce_f16(const void* y, const void* scale, cons
                                           int w, int c, int relu, void* dgamma, void* dbeta, void* coef_a, void* coef_b,
                                           void* coef_c, void* partial, void* workspace, size_t ws_bytes, void* stream) {
   OCR_CHECK_ARG(y && scale && shift && save_mean && save_invstd && da_full && dgamma && dbeta);
-  OCR_CHECK_ARG(coef_a && coef_b && coef_c && partial && workspace);
+  OCR_CHECK_ARG(coef_a && coef_b && coef_c && partial && workspace && n > 0 && h > 0 && w > 0);
   OCR_CHECK_SHAPE(c % 8 == 0 && pow2(c / 8) && c / 8 <= 256);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int pool = da_pool ? 2 : 0;          // da_pool: the gradient of the layer's 2x2/2 max-pool, routed to each window's first maximum
@@ -1369,7 +1369,7 @@ extern "C" int ocr_bn_relu_bwd_reduce_pooled_f16(const void* y, const void* scal
 extern "C" int ocr_maxpool_f16(const void* x, int n, int h, int w, int c, int k, int stride,
                                int pad_top, int pad_left, int oh, int ow, void* y, void* argmax,
                                void* stream) {
-  OCR_CHECK_ARG(x && y && n > 0 && k > 0 && stride > 0 && oh > 0 && ow > 0 && k * k <= 255);
+  OCR_CHECK_ARG(x && y && n > 0 && h > 0 && w > 0 && k > 0 && stride > 0 && oh > 0 && ow > 0 && k * k <= 255);
   OCR_CHECK_SHAPE(c % 8 == 0);
   PoolP p{n, h, w, c, oh, ow, k, stride, pad_top, pad_left};
   const size_t total = (size_t)n * oh * ow * (c / 8);
@@ -1383,7 +1383,7 @@ extern "C" int ocr_maxpool_f16(const void* x, int n, int h, int w, int c, int k,
 extern "C" int ocr_bn_relu_maxpool_f16(const void* bn_y, const void* scale, const void* shift, int relu, int n, int h,
                                        int w, int c, int k, int stride, int pad_top, int pad_left, int oh, int ow,
                                        void* y, void* argmax, void* stream) {
-  OCR_CHECK_ARG(bn_y && scale && shift && y && n > 0 && k > 0 && stride > 0 && oh > 0 && ow > 0 && k * k <= 255);
+  OCR_CHECK_ARG(bn_y && scale && shift && y && n > 0 && h > 0 && w > 0 && k > 0 && stride > 0 && oh > 0 && ow > 0 && k * k <= 255);
   OCR_CHECK_SHAPE(c % 8 == 0);
   PoolP p{n, h, w, c, oh, ow, k, stride, pad_top, pad_left};
   const size_t total = (size_t)n * oh * ow * (c / 8);
@@ -1398,7 +1398,7 @@ extern "C" int ocr_bn_relu_maxpool_f16(const void* bn_y, const void* scale, cons
 extern "C" int ocr_maxpool_bwd_f16(const void* x, const void* argmax, const void* dy, int n, int h, int w,
                                    int c, int k, int stride, int pad_top, int pad_left, int oh, int ow,
                                    void* dx, int accumulate, void* stream) {
-  OCR_CHECK_ARG((x || argmax) && dy && dx && n > 0 && k > 0 && stride > 0 && oh > 0 && ow > 0);
+  OCR_CHECK_ARG((x || argmax) && dy && dx && n > 0 && h > 0 && w > 0 && k > 0 && stride > 0 && oh > 0 && ow > 0);
   OCR_CHECK_SHAPE(c % 8 == 0);
   PoolP p{n, h, w, c, oh, ow, k, stride, pad_top, pad_left};
   const size_t total = (size_t)n * h * w * (c / 8);
@@ -1558,7 +1558,7 @@ extern "C" int ocr_bn_relu_bwd_apply_f16(const void* y, const void* scale, const
                                          const void* partial, int T, void* dgamma, void* dbeta,
                                          void* dy, void* workspace, size_t ws_bytes, void* stream) {
   OCR_CHECK_ARG(y && scale && shift && save_mean && save_invstd && da_full && partial && dgamma && dbeta && dy);
-  OCR_CHECK_ARG(workspace && T > 0);
+  OCR_CHECK_ARG(workspace && T > 0 && n > 0 && h > 0 && w > 0);
   OCR_CHECK_SHAPE(c % 8 == 0 && pow2(c / 8) && c / 8 <= 256);
   if (ws_bytes < ocr_bn_reduce_workspace(T, c)) return OCR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -92,6 +92,26 @@ def test_bf16_image_conv_matrix(device):
     assert m and int(m.group(1)) == I.N_TESTS and "failed" not in r.stdout, tail
 
 
+def test_bf16_bn_pool_matrix(device):
+    """tests/test_gpu_bn_pool_matrix.py (every batch-norm, pool and unpool entry against float64) on the bf16 library:
+    every case passes; the bars scale through the storage half-ulp only."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    try:
+        import test_gpu_bn_pool_matrix as B
+    finally:
+        sys.path.pop(0)
+    env = dict(os.environ, OCR_STORAGE="bf16")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-s", "-m", "gpu", "-p", "no:cacheprovider",
+                        os.path.join(ROOT, "tests", "test_gpu_bn_pool_matrix.py")],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    tail = (r.stdout + r.stderr)[-3000:]
+    import re
+    print("\n".join(re.findall(r"bn_pool .*", r.stdout)))
+    assert r.returncode == 0, tail
+    m = re.search(r"(\d+) passed", r.stdout)
+    assert m and int(m.group(1)) == B.N_TESTS and "failed" not in r.stdout, tail
+
+
 def test_bf16_resnet50_east_640_batch64_parity(device):
     """BASELINE configs[3] as quoted (bf16, batch 64, 640^2): n = 64 replicated == n = 2 in the bf16 library."""
     env = dict(os.environ, OCR_STORAGE="bf16")
