@@ -1140,7 +1140,7 @@ int sc_blocks(int P, int C) {
 extern "C" int ocr_conv1x1_small_f16(const void* x, const void* w_kc32, const void* bias, int P,
                                      int cin, int cout, void* out_f32, void* stream) {
   OCR_CHECK_ARG(x && w_kc32 && out_f32 && P > 0);
-  OCR_CHECK_SHAPE(cin % 16 == 0 && cout >= 1 && cout <= 32);
+  OCR_CHECK_SHAPE(cin > 0 && cin % 16 == 0 && cout >= 1 && cout <= 32);
   hipLaunchKernelGGL(conv1x1_small_kernel, dim3(ocr_cdiv(P, 128)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const half_t*>(x),
                      static_cast<const half_t*>(w_kc32), static_cast<const float*>(bias), P, cin,
@@ -1152,7 +1152,7 @@ extern "C" int ocr_conv1x1_small_dgrad_f16(const void* dz_f32, const void* w_ck3
                                            int cout, float grad_scale, void* dx_f16, int accumulate,
                                            void* stream) {
   OCR_CHECK_ARG(dz_f32 && w_ck32 && dx_f16 && P > 0);
-  OCR_CHECK_SHAPE(cin % 32 == 0 && cout >= 1 && cout <= 32);
+  OCR_CHECK_SHAPE(cin > 0 && cin % 32 == 0 && cout >= 1 && cout <= 32);
   hipLaunchKernelGGL(conv1x1_small_dgrad_kernel, dim3(ocr_cdiv(P, 128)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const float*>(dz_f32),
                      static_cast<const half_t*>(w_ck32), P, cin, cout,
@@ -1216,7 +1216,7 @@ extern "C" int ocr_conv1x1_small_wgrad_f16(const void* x, const void* dz_f32, in
                                            int cout, void* dw_f32, void* workspace, size_t ws_bytes,
                                            void* stream) {
   OCR_CHECK_ARG(x && dz_f32 && dw_f32 && workspace && P > 0);
-  OCR_CHECK_SHAPE(cout >= 1 && cout <= 32);
+  OCR_CHECK_SHAPE(cin >= 1 && cout >= 1 && cout <= 32);     // (any cin: the strip kernel walks channels one by one)
   if (ws_bytes < ocr_conv1x1_small_wgrad_workspace(P, cin, cout)) return OCR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (small_wgrad_mfma(P, cin)) {
@@ -1342,6 +1342,8 @@ extern "C" int ocr_sc_pointwise_fwd(const void* x, int ldx, int xo, int cin, con
                                     const void* bias, int P, void* out, int ldo, int oo, int cout,
                                     void* stream) {
   OCR_CHECK_ARG(x && w && out && P > 0 && cin > 0 && cout > 0);
+  OCR_CHECK_ARG(xo >= 0 && oo >= 0 && ldx >= xo + cin && ldo >= oo + cout);
+  OCR_CHECK_SHAPE(cin <= 32 && cout <= 32);
   if (cin == cout && (cin == 16 || cin == 2)) {
     const dim3 grid(sgrid((size_t)P));
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1365,6 +1367,8 @@ extern "C" int ocr_sc_pointwise_fwd(const void* x, int ldx, int xo, int cin, con
 extern "C" int ocr_sc_pointwise_dgrad(const void* dout, int ldo, int oo, int cout, const void* w,
                                       int P, void* dx, int ldx, int xo, int cin, void* stream) {
   OCR_CHECK_ARG(dout && w && dx && P > 0 && cin > 0 && cout > 0);
+  OCR_CHECK_ARG(xo >= 0 && oo >= 0 && ldx >= xo + cin && ldo >= oo + cout);
+  OCR_CHECK_SHAPE(cin <= 32 && cout <= 32);
   if (cin == cout && (cin == 16 || cin == 2)) {
     const dim3 grid(sgrid((size_t)P));
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1393,12 +1397,13 @@ extern "C" int ocr_sc_pointwise_wgrad(const void* x, int ldx, int xo, int cin, c
                                       int ldo, int oo, int cout, int P, void* dw, void* db,
                                       void* workspace, size_t ws_bytes, void* stream) {
   OCR_CHECK_ARG(x && dout && dw && workspace && P > 0 && cin > 0 && cout > 0);
+  OCR_CHECK_ARG(xo >= 0 && oo >= 0 && ldx >= xo + cin && ldo >= oo + cout);
+  const int pairs = cin * cout + cout;
+  OCR_CHECK_SHAPE(cin <= 32 && cout <= 32 && pairs <= 512);
   if (ws_bytes < ocr_sc_pointwise_wgrad_workspace(cin, cout)) return OCR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int B = 256;
-  const int pairs = cin * cout + cout;
   float* ws = static_cast<float*>(workspace);
-  OCR_CHECK_SHAPE(cin <= 32 && cout <= 32 && pairs <= 512);
   if (cin == 16 && cout == 16)
     hipLaunchKernelGGL(sc_pointwise_wgrad16_kernel, dim3(B), dim3(256), 0, st, static_cast<const float*>(x), ldx,
                        xo, static_cast<const float*>(dout), ldo, oo, P, ocr_cdiv(P, B), ws);
@@ -1526,7 +1531,7 @@ extern "C" int ocr_conv1x1_small_batch_f16(const ocr_head_conv_item* items, int 
   for (int i = 0; i < count; ++i) {
     const ocr_head_conv_item& a = items[i];
     OCR_CHECK_ARG(a.x && a.w_kc32 && a.out && a.P > 0);
-    OCR_CHECK_SHAPE(a.cin % 16 == 0 && a.cout >= 1 && a.cout <= 32);
+    OCR_CHECK_SHAPE(a.cin > 0 && a.cin % 16 == 0 && a.cout >= 1 && a.cout <= 32);
     const int iters = ocr_cdiv(a.P, 128 * 1024);
     tab.it[i] = HeadConvItem{static_cast<const half_t*>(a.x), static_cast<const half_t*>(a.w_kc32),
                              static_cast<const float*>(a.bias), static_cast<float*>(a.out),
@@ -1547,7 +1552,7 @@ extern "C" int ocr_conv1x1_small_dgrad_batch_f16(const ocr_head_dgrad_item* item
   for (int i = 0; i < count; ++i) {
     const ocr_head_dgrad_item& a = items[i];
     OCR_CHECK_ARG(a.dz && a.w_ck32 && a.dx && a.P > 0);
-    OCR_CHECK_SHAPE(a.cin % 32 == 0 && a.cout >= 1 && a.cout <= 32);
+    OCR_CHECK_SHAPE(a.cin > 0 && a.cin % 32 == 0 && a.cout >= 1 && a.cout <= 32);
     tab.it[i] = HeadDgradItem{static_cast<const float*>(a.dz), static_cast<const half_t*>(a.w_ck32),
                               static_cast<half_t*>(a.dx), a.P, a.cin, a.cout, a.accumulate, blocks};
     blocks += ocr_cdiv(a.P, 128);
@@ -1583,7 +1588,7 @@ extern "C" int ocr_conv1x1_small_wgrad_batch_f16(const ocr_head_wgrad_item* item
   for (int i = 0; i < count; ++i) {
     const ocr_head_wgrad_item& a = items[i];
     OCR_CHECK_ARG(a.x && a.dz && a.dw && a.slab && a.P > 0);
-    OCR_CHECK_SHAPE(a.cin % kHwCIB == 0 && a.cout >= 1 && a.cout <= 32);
+    OCR_CHECK_SHAPE(a.cin > 0 && a.cin % kHwCIB == 0 && a.cout >= 1 && a.cout <= 32);
     OCR_CHECK_SHAPE((size_t)a.P * a.cin * 2 < (1ull << 31) && (size_t)a.P * a.cout * 4 < (1ull << 31));   // 32-bit buffer offsets
     int m, t, sp;
     head_wgrad_plan(a.P, a.cin, &m, &t, &sp);
