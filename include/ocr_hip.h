@@ -846,6 +846,58 @@ int ocr_lanms(const void* boxes, const void* counts, int n_images, int max_k, fl
               size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * EAST RBOX geometry (csrc/rbox.hip): head activation, loss, per-pixel quad decode into ocr_lanms.
+ * All operands f32, P = pixels.  Status (all entries of this section): OCR_ERR_INVALID_ARG for a null required
+ * pointer or a non-positive extent, OCR_ERR_UNSUPPORTED for n * h * w beyond 2^31 - 1 or n > 65535 (decode),
+ * OCR_ERR_WORKSPACE for ws_bytes below the _workspace answer; nothing is written on error.
+ *
+ * Head (reference nets/model.py:76-80): z [P][6] -> score [P] = sigmoid(z0), geo [P][5] with
+ * geo[k] = sigmoid(z[1+k]) * text_scale (k < 4: top, right, bottom, left distances) and
+ * geo[4] = (sigmoid(z5) - 0.5) * pi/2, an angle in (-pi/4, pi/4), evaluated as tanh(z5 / 2) * pi/4 (the same
+ * function, no cancellation near 0).  The backward pass recovers sigma from the STORED outputs (geo / text_scale;
+ * geo4 / (pi/2) + 0.5) and writes dz [P][6]; a NULL dscore / dgeo counts as zeros (exact zeros in dz).
+ * ------------------------------------------------------------------------- */
+int ocr_rbox_head_fwd(const void* z, int P, float text_scale, void* score, void* geo, void* stream);
+int ocr_rbox_head_bwd(const void* score, const void* dscore, const void* geo, const void* dgeo, int P,
+                      float text_scale, void* dz, void* stream);
+/* RBOX loss.  ABSENT from the reference tree (like the focal loss): BUILD-DEFINED from the EAST paper
+ * (Zhou et al. CVPR 2017, eqs. 7-10); PARITY IS UNPINNED.  With d = (top, right, bottom, left), g = truth,
+ * p = prediction, y = y_true_cls [P], m = mask [P], geo maps [P][5]:
+ *   L_cls  = 0.01 * (1 - 2 sum(y p m) / (sum(y m) + sum(p m) + 1e-5))
+ *   A_g = (d0g + d2g)(d1g + d3g), A_p likewise; w = min(d1g, d1p) + min(d3g, d3p), h = min(d0g, d0p) + min(d2g, d2p)
+ *   A_i = w h, A_u = A_g + A_p - A_i, L_aabb = -log((A_i + 1) / (A_u + 1)), L_theta = 1 - cos(theta_p - theta_g)
+ *   loss   = (1/P) sum_pixels (L_aabb + 20 L_theta) y m + L_cls          (a mean over ALL P pixels)
+ * sums [5] = (sum y p m, sum y m, sum p m, sum L_aabb y m, sum L_theta y m); out [4] = (loss, L_cls, sums[3] / P,
+ * sums[4] / P), so loss = out[1] + out[2] + 20 out[3].  One streaming pass leaves one partial row per workgroup in the
+ * workspace, one workgroup adds the rows in f64 in a fixed order: no atomics, reproducible.  The backward pass is one
+ * elementwise pass that reads `sums`: d_cls [P] = d loss / d y_pred_cls, d_geo [P][5] = d loss / d y_pred_geo, both times
+ * grad_scale; d_geo is exactly 0 where y m = 0.  Gradient of min: the prediction receives gradient only where it is
+ * STRICTLY the smaller operand; at a tie the truth counts as the minimum (d_geo has no intersection share there). */
+size_t ocr_rbox_loss_workspace(int P);
+int ocr_rbox_loss_fwd(const void* y_true_cls, const void* y_pred_cls, const void* y_true_geo, const void* y_pred_geo,
+                      const void* mask, int P, void* sums, void* out, void* workspace, size_t ws_bytes, void* stream);
+int ocr_rbox_loss_bwd(const void* y_true_cls, const void* y_true_geo, const void* y_pred_geo, const void* mask, int P,
+                      const void* sums, float grad_scale, void* d_cls, void* d_geo, void* stream);
+/* seed = grad_scale * *loss_scale, read on the device (see ocr_dice_loss_bwd_dyn) */
+int ocr_rbox_loss_bwd_dyn(const void* y_true_cls, const void* y_true_geo, const void* y_pred_geo, const void* mask, int P,
+                          const void* sums, float grad_scale, const float* loss_scale, void* d_cls, void* d_geo,
+                          void* stream);
+/* Decode (the inverse of the geometry; reference datasets/icdar.py:410-483 restore_rectangle_rbox): per image the pixels
+ * with score > score_thresh (the f32 comparison), in RASTER order, one row x1,y1,..,x4,y4,score each into boxes
+ * [n][max_k][9]; total [n] i32 = the true number selected, counts [n] i32 = min(total, max_k); nothing is written at or
+ * beyond boxes[i][counts[i]].  score [n][h][w], geo [n][h][w][5].  With origin = (x * scale, y * scale), H = d0 + d2,
+ * W = d1 + d3 and R(q) = (qx cos + qy sin, -qx sin + qy cos) of theta = geo[4]:
+ *   theta >= 0: local corners (0,-H) (W,-H) (W,0) (0,0),   anchor a = (d3, -d2)
+ *   theta <  0: local corners (-W,-H) (0,-H) (0,0) (-W,0), anchor a = (-d1, -d2)
+ *   corner_i = origin + R(local_i) - R(a)
+ * DEVIATION from the reference's NumPy routine, which returns all theta >= 0 rows before all theta < 0 rows: raster
+ * order is kept, as ocr_lanms requires and Algorithm 1 of the paper assumes.  Ordered compaction (workgroup counts by
+ * ballot, one scan per image, write pass): no atomic counter, the order does not depend on scheduling. */
+size_t ocr_rbox_decode_workspace(int n, int h, int w);
+int ocr_rbox_decode(const void* score, const void* geo, int n, int h, int w, float score_thresh, float scale, int max_k,
+                    void* boxes, void* counts, void* total, void* workspace, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * One oriented box per component: the device side of
  *   rectangle = cv2.minAreaRect(show_xy); box = np.int0(cv2.boxPoints(rectangle))
  * (test_pixellink_fast.py:193-202, test_pixellink.py:207-216; cv2 = OpenCV 3.x convexHull +

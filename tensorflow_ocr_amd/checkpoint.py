@@ -45,6 +45,8 @@ def _guess_widths(total, k):
         return (2, 16)
     if k == 2 and total == 9:              # EAST's F_score (1) + geo_map (8) heads on the merge branch's output
         return (1, 8)
+    if k == 3 and total == 6:              # EAST's RBOX heads: F_score (1) + four distances (4) + angle (1)
+        return (1, 4, 1)
     if total % k:
         raise ValueError("cannot split %d channels over %d scopes" % (total, k))
     return (total // k,) * k

@@ -1242,6 +1242,8 @@ extern "C" int ocr_conv1x1_small_wgrad_f16(const void* x, const void* dz_f32, in
     switch (cout) {
       case 1: hipLaunchKernelGGL(conv1x1_small_wgrad_narrow_kernel<1>, dim3(S), dim3(256), 0, st, xp, dp, P, cin, strip, ws); break;
       case 2: hipLaunchKernelGGL(conv1x1_small_wgrad_narrow_kernel<2>, dim3(S), dim3(256), 0, st, xp, dp, P, cin, strip, ws); break;
+      case 4: hipLaunchKernelGGL(conv1x1_small_wgrad_narrow_kernel<4>, dim3(S), dim3(256), 0, st, xp, dp, P, cin, strip, ws); break;
+      case 6: hipLaunchKernelGGL(conv1x1_small_wgrad_narrow_kernel<6>, dim3(S), dim3(256), 0, st, xp, dp, P, cin, strip, ws); break;
       case 8: hipLaunchKernelGGL(conv1x1_small_wgrad_narrow_kernel<8>, dim3(S), dim3(256), 0, st, xp, dp, P, cin, strip, ws); break;
       case 9: hipLaunchKernelGGL(conv1x1_small_wgrad_narrow_kernel<9>, dim3(S), dim3(256), 0, st, xp, dp, P, cin, strip, ws); break;
       case 16: hipLaunchKernelGGL(conv1x1_small_wgrad_narrow_kernel<16>, dim3(S), dim3(256), 0, st, xp, dp, P, cin, strip, ws); break;

@@ -1,6 +1,7 @@
 """Mirror of reference nets/model_vgg_16.py: `model_vgg` (VGG-16 trunk + BN'd PixelLink fuse
 heads, :138-177), `dice_coefficient` (:179-193), `loss` (:196-225) with the same call
-signatures and output names (pixel_cls [N,H/4,W/4,2], link_cls [N,H/4,W/4,16]).
+signatures and output names (pixel_cls [N,H/4,W/4,2], link_cls [N,H/4,W/4,16]); plus `model_rbox` / `loss_rbox`:
+EAST's RBOX geometry (reference nets/model.py:76-80) on the merge branch of `model`, and the paper's loss for it.
 """
 import numpy as np
 import torch
@@ -31,13 +32,12 @@ def _to_device(g, arr, dtype=F32):
     return torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).to(g.device)
 
 
-def model(images, weight_decay=1e-5, is_training=True, graph=None, blocks=None):
-    """nets/model_vgg_16.py:85-136: ResNet-v1-50 + the EAST feature-merging branch
-    h_i = conv3x3(conv1x1(concat(unpool(h_{i-1}), f_i))), widths 128/64/32, one more 3x3, then
-    F_score = sigmoid(conv1x1 -> 1), geo_map = sigmoid(conv1x1 -> 8)."""
+def _merge_branch(images, weight_decay, is_training, g, blocks):
+    """The part `model` and `model_rbox` share (nets/model_vgg_16.py:85-128): ResNet-v1-50 trunk and the feature-merging
+    branch down to its last 3x3 convolution.  Returns the branch's output and the iterator over the slim auto-names
+    of `feature_fusion` that are left for the heads (Conv_7, Conv_8, Conv_9)."""
     from .. import resnet_layers as R
     from . import resnet_v1
-    g = graph or get_default_graph()
     g.weight_decay = weight_decay
     x4 = mean_image_subtraction(images, graph=g)
     if blocks is None:
@@ -47,7 +47,7 @@ def model(images, weight_decay=1e-5, is_training=True, graph=None, blocks=None):
     g.end_points = end_points
     f = [end_points['pool5'], end_points['pool4'], end_points['pool3'], end_points['pool2']]
     num_outputs = [None, 128, 64, 32]
-    names = iter(['Conv'] + ['Conv_%d' % i for i in range(1, 9)])
+    names = iter(['Conv'] + ['Conv_%d' % i for i in range(1, 10)])
     with g.variable_scope('feature_fusion'):
         h = f[0]
         for i in range(1, 4):
@@ -55,8 +55,35 @@ def model(images, weight_decay=1e-5, is_training=True, graph=None, blocks=None):
             c1_1 = R.unpool_concat_conv_bn_relu(g, h, f[i], num_outputs[i], next(names), is_training)
             h = R.conv_bn_act(g, c1_1, num_outputs[i], 3, next(names), is_training=is_training)
         gi = R.conv_bn_act(g, h, num_outputs[3], 3, next(names), is_training=is_training)
+    end_points['feature_fusion'] = gi            # the 32-channel map the heads read, beside the trunk's end points
+    return gi, names
+
+
+def model(images, weight_decay=1e-5, is_training=True, graph=None, blocks=None):
+    """nets/model_vgg_16.py:85-136: ResNet-v1-50 + the EAST feature-merging branch
+    h_i = conv3x3(conv1x1(concat(unpool(h_{i-1}), f_i))), widths 128/64/32, one more 3x3, then
+    F_score = sigmoid(conv1x1 -> 1), geo_map = sigmoid(conv1x1 -> 8)."""
+    from .. import resnet_layers as R
+    g = graph or get_default_graph()
+    gi, names = _merge_branch(images, weight_decay, is_training, g, blocks)
+    with g.variable_scope('feature_fusion'):
         F_score, geo_map = R.sigmoid_heads(g, gi, (1, 8), (next(names), next(names)))
     return F_score, geo_map
+
+
+def model_rbox(images, weight_decay=1e-5, is_training=True, text_scale=512, graph=None, blocks=None):
+    """The same trunk and merge branch as `model` with EAST's RBOX geometry on top (reference nets/model.py:76-80):
+    F_score = sigmoid(conv1x1 -> 1), four distances = sigmoid(conv1x1 -> 4) * text_scale, angle =
+    (sigmoid(conv1x1 -> 1) - 0.5) * pi/2.  Variable scopes feature_fusion/Conv_7 (score), Conv_8 (distances), Conv_9
+    (angle): slim's auto-naming order, so an RBOX checkpoint maps by name.  `text_scale` defaults to the reference flag
+    (nets/model.py:6).  Returns (F_score [N,H/4,W/4,1], F_geometry [N,H/4,W/4,5]); `graph.end_points['feature_fusion']` is the
+    merge branch's output the heads read."""
+    from .. import resnet_layers as R
+    g = graph or get_default_graph()
+    gi, names = _merge_branch(images, weight_decay, is_training, g, blocks)
+    with g.variable_scope('feature_fusion'):
+        F_score, F_geometry = R.rbox_heads(g, gi, (next(names), next(names), next(names)), text_scale)
+    return F_score, F_geometry
 
 
 def model_vgg(images, weight_decay=1e-5, is_training=True, graph=None):
@@ -124,6 +151,31 @@ def loss(y_true_pixel, y_pred_pixel, y_true_link, y_pred_link, training_mask, gr
                                   y_pred_link.grad)
         else:
             ops.dice_loss_bwd(ytp, ytl, m, sums, g.seed_scale(), y_pred_pixel.grad, y_pred_link.grad)
+    g.record(backward)
+    res = Scalar(out)
+    g.collections["losses"].append(res)
+    return res
+
+
+def loss_rbox(y_true_cls, y_pred_cls, y_true_geo, y_pred_geo, training_mask, graph=None):
+    """EAST's RBOX loss (Zhou et al. 2017, eqs. 7-10; the reference tree has none, so it is build-defined and its parity
+    unpinned — include/ocr_hip.h states the formulas): 0.01 * dice(score) + mean over all pixels of
+    (-log IoU of the distance boxes + 20 * (1 - cos(angle difference))) * y_true_cls * training_mask.
+    y_true_cls / training_mask [N,h,w,1], y_true_geo [N,h,w,5]; y_pred_* the handles of `model_rbox`.
+    Returns a Scalar (loss, L_cls, mean aabb term, mean angle term) and records the backward seed."""
+    g = graph or get_default_graph()
+    ytc, ytg, m = _to_device(g, y_true_cls), _to_device(g, y_true_geo), _to_device(g, training_mask)
+    sums, out = g.empty((5,), F32), g.empty((4,), F32)        # fully written by the finalize kernel
+    ops.rbox_loss_fwd(ytc, y_pred_cls.data, ytg, y_pred_geo.data, m, sums, out, g.workspace())
+
+    def backward():
+        y_pred_cls.grad = g.empty(y_pred_cls.data.shape, F32)
+        y_pred_geo.grad = g.empty(y_pred_geo.data.shape, F32)
+        if g.loss_scaler is not None:       # dynamic loss scaling: the kernel reads the scale from the device state
+            ops.rbox_loss_bwd_dyn(ytc, ytg, y_pred_geo.data, m, sums, 1.0 / g.loss_div, g.loss_scaler.scale_ptr,
+                                  y_pred_cls.grad, y_pred_geo.grad)
+        else:
+            ops.rbox_loss_bwd(ytc, ytg, y_pred_geo.data, m, sums, g.seed_scale(), y_pred_cls.grad, y_pred_geo.grad)
     g.record(backward)
     res = Scalar(out)
     g.collections["losses"].append(res)

@@ -1046,6 +1046,65 @@ def lanms(boxes, counts, iou_thresh, merged, n_merged, keep_idx, n_keep, ws):
            ptr(merged), ptr(n_merged), ptr(keep_idx), ptr(n_keep), ptr(buf), c_size_t(nbytes), _st())
 
 
+# ------------------------------------------------------------------------------- EAST RBOX geometry (csrc/rbox.hip)
+def rbox_head_fwd(z, text_scale, score, geo):
+    """z [..., 6] f32 -> score [..., 1], geo [..., 5] (four distances * text_scale, angle in (-pi/4, pi/4))."""
+    P = score.numel()
+    if z.numel() != 6 * P or geo.numel() != 5 * P:
+        raise ValueError("rbox_head_fwd: z, score, geo must hold 6, 1, 5 values per pixel")
+    L.call("ocr_rbox_head_fwd", ptr(z), c_int(P), c_float(text_scale), ptr(score), ptr(geo), _st())
+
+
+def rbox_head_bwd(score, dscore, geo, dgeo, text_scale, dz):
+    """dz [..., 6] from the stored outputs; dscore / dgeo may be None (zeros)."""
+    P = score.numel()
+    if dz.numel() != 6 * P or geo.numel() != 5 * P or (dscore is not None and dscore.numel() != P) or \
+            (dgeo is not None and dgeo.numel() != 5 * P):
+        raise ValueError("rbox_head_bwd: dz, score, geo must hold 6, 1, 5 values per pixel, the gradients as their outputs")
+    L.call("ocr_rbox_head_bwd", ptr(score), ptr(dscore), ptr(geo), ptr(dgeo), c_int(P), c_float(text_scale), ptr(dz), _st())
+
+
+def _rbox_loss_pixels(mask, per_pixel):
+    P = mask.numel()
+    for t, c in per_pixel:
+        if t.numel() != c * P:
+            raise ValueError("rbox loss: every map must cover the mask's %d pixels" % P)
+    return P
+
+
+def rbox_loss_fwd(yt_cls, yp_cls, yt_geo, yp_geo, mask, sums5, out4, ws):
+    P = _rbox_loss_pixels(mask, ((yt_cls, 1), (yp_cls, 1), (yt_geo, 5), (yp_geo, 5)))
+    nbytes = L.call_size("ocr_rbox_loss_workspace", c_int(P))
+    buf = ws.get(nbytes)
+    L.call("ocr_rbox_loss_fwd", ptr(yt_cls), ptr(yp_cls), ptr(yt_geo), ptr(yp_geo), ptr(mask), c_int(P), ptr(sums5),
+           ptr(out4), ptr(buf), c_size_t(nbytes), _st())
+
+
+def rbox_loss_bwd(yt_cls, yt_geo, yp_geo, mask, sums5, grad_scale, d_cls, d_geo):
+    P = _rbox_loss_pixels(mask, ((yt_cls, 1), (yt_geo, 5), (yp_geo, 5), (d_cls, 1), (d_geo, 5)))
+    L.call("ocr_rbox_loss_bwd", ptr(yt_cls), ptr(yt_geo), ptr(yp_geo), ptr(mask), c_int(P), ptr(sums5),
+           c_float(grad_scale), ptr(d_cls), ptr(d_geo), _st())
+
+
+def rbox_loss_bwd_dyn(yt_cls, yt_geo, yp_geo, mask, sums5, grad_scale, loss_scale, d_cls, d_geo):
+    """rbox_loss_bwd with the seed grad_scale * loss_scale[0], `loss_scale` a DEVICE f32 (LossScaleState.scale_ptr)."""
+    P = _rbox_loss_pixels(mask, ((yt_cls, 1), (yt_geo, 5), (yp_geo, 5), (d_cls, 1), (d_geo, 5)))
+    L.call("ocr_rbox_loss_bwd_dyn", ptr(yt_cls), ptr(yt_geo), ptr(yp_geo), ptr(mask), c_int(P), ptr(sums5),
+           c_float(grad_scale), ptr(loss_scale), ptr(d_cls), ptr(d_geo), _st())
+
+
+def rbox_decode(score, geo, n, h, w, score_thresh, scale, boxes, counts, total, ws):
+    """score [n,h,w], geo [n,h,w,5] -> boxes [n,max_k,9] in raster order, counts / total int32 [n]."""
+    max_k = boxes.shape[1]
+    if score.numel() != n * h * w or geo.numel() != 5 * n * h * w or boxes.numel() != n * max_k * 9 or \
+            counts.numel() != n or total.numel() != n:
+        raise ValueError("rbox_decode: tensors do not match n, h, w, max_k")
+    nbytes = L.call_size("ocr_rbox_decode_workspace", c_int(n), c_int(h), c_int(w))
+    buf = ws.get(nbytes)
+    L.call("ocr_rbox_decode", ptr(score), ptr(geo), c_int(n), c_int(h), c_int(w), c_float(score_thresh), c_float(scale),
+           c_int(max_k), ptr(boxes), ptr(counts), ptr(total), ptr(buf), c_size_t(nbytes), _st())
+
+
 def min_area_rects(labels, ncomp, max_comps, scale_x, scale_y, hull_n, hull_head, calipers, ws):
     n, h, w = labels.shape
     nbytes = L.call_size("ocr_min_area_rects_workspace", c_int(n), c_int(h), c_int(w), c_int(max_comps))

@@ -647,6 +647,45 @@ def sigmoid_heads(g, feat, couts, scopes):
     return o0, o1
 
 
+def rbox_heads(g, feat, scopes, text_scale):
+    """EAST's RBOX heads on the merge branch's output (reference nets/model.py:76-80): F_score = sigmoid(conv1x1 -> 1),
+    four distances = sigmoid(conv1x1 -> 4) * text_scale, angle = (sigmoid(conv1x1 -> 1) - 0.5) * pi/2, as ONE merged 1x1
+    convolution (layers.head_conv_bias: variable `<s0>+<s1>+<s2>/weights` [cin, 1+4+1], split back into the reference's
+    three by checkpoint.internal_to_tf) and one f32 activation kernel (ops.rbox_head_fwd).  Returns the handles
+    (F_score [n,h,w,1], F_geometry [n,h,w,5]).  With the f32 inference precision or OCR_RESNET_MERGE_HEADS=0: one
+    convolution per head, the same activation kernel on their concatenation."""
+    import torch
+    from .layers import SmallAct, head_conv_bias
+    couts = (1, 4, 1)
+    if g.precision == "f32" or not MERGE_HEADS:
+        if g.keepalive is not None:
+            # the columns are gathered / scattered by torch copies, which a recorded step plan does not replay
+            raise NotImplementedError("rbox_heads with OCR_RESNET_MERGE_HEADS=0 cannot run inside a recorded step")
+        zs = [head_conv_bias(g, feat, (s,), (c,))[0] for s, c in zip(scopes, couts)]
+        z = SmallAct(torch.cat([t.data for t in zs], dim=-1))
+    else:
+        zs = None
+        z, _, _ = head_conv_bias(g, feat, tuple(scopes), couts)
+    n, h, w, _ = z.data.shape
+    o0 = SmallAct(g.empty((n, h, w, 1), F32))
+    o1 = SmallAct(g.empty((n, h, w, 5), F32))
+    ops.rbox_head_fwd(z.data, float(text_scale), o0.data, o1.data)
+
+    def backward():
+        if o0.grad is None and o1.grad is None:
+            return
+        z.grad = g.empty(z.data.shape, F32)
+        ops.rbox_head_bwd(o0.data, o0.grad, o1.data, o1.grad, float(text_scale), z.grad)
+        if zs is not None:
+            o = 0
+            for t, c in zip(zs, couts):
+                t.grad = z.grad[..., o:o + c].contiguous()
+                o += c
+        o0.grad = o1.grad = None
+    g.record(backward)
+    return o0, o1
+
+
 MERGE_REORDER = __import__("os").environ.get("OCR_RESNET_MERGE_REORDER", "1") == "1"   # 1x1 merge conv before the upsample
 
 

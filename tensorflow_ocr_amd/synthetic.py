@@ -26,3 +26,30 @@ def make_batch(rng, n, size, rects=8):
         link[..., d] = ((ids > 0) & ((nb == ids) | (nb == -1))).astype(np.float32)
     mask = np.ones((n, q4, q4, 1), np.float32)
     return images, pixel, link, mask
+
+
+def rbox_labels(n, size, rng, rects=3):
+    """EAST RBOX label maps at 1/4 resolution for tests and smoke training (NOT the reference's generate_rbox: labels
+    from ICDAR polygons are a follow-up): per image `rects` random rotated rectangles, later ones on top.  Returns
+    (score [n,q,q,1], geo [n,q,q,5], mask [n,q,q,1]) float32 with q = size // 4: inside a rectangle score = 1 and geo =
+    (distance to its top, right, bottom, left edge in IMAGE pixels, its angle in (-pi/4, pi/4)), zeros outside; mask = 1.
+    Map cell (x, y) stands for image point (4x, 4y); the rectangle's right-pointing axis is (cos a, -sin a) with y down,
+    the convention tool/rbox.decode inverts."""
+    q4 = size // 4
+    score = np.zeros((n, q4, q4, 1), np.float32)
+    geo = np.zeros((n, q4, q4, 5), np.float32)
+    ys, xs = np.mgrid[0:q4, 0:q4]
+    px, py = 4.0 * xs, 4.0 * ys
+    for b in range(n):
+        for _ in range(rects):
+            a = float(rng.uniform(-0.7, 0.7))                                    # inside (-pi/4, pi/4)
+            half_w, half_h = float(rng.uniform(size / 10.0, size / 3.2)), float(rng.uniform(size / 20.0, size / 8.0))
+            cx, cy = float(rng.uniform(0.25 * size, 0.75 * size)), float(rng.uniform(0.25 * size, 0.75 * size))
+            c, s = np.cos(a), np.sin(a)
+            lx = (px - cx) * c - (py - cy) * s                                   # along the right-pointing axis
+            ly = (px - cx) * s + (py - cy) * c                                   # along the down-pointing axis
+            inside = (np.abs(lx) <= half_w) & (np.abs(ly) <= half_h)
+            d = np.stack([ly + half_h, half_w - lx, half_h - ly, lx + half_w, np.full_like(lx, a)], axis=-1)
+            score[b, inside, 0] = 1.0
+            geo[b, inside] = d[inside].astype(np.float32)
+    return score, geo, np.ones((n, q4, q4, 1), np.float32)

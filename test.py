@@ -4,6 +4,10 @@ config 0's script — on the MI355X path: `model.model(is_training=False)` (ResN
 heads), softmax scores, the script's own `pixel_detect`, one `cv2.minAreaRect` box per
 `cv2.findContours` contour, `order_points`, `res_<name>.txt`.
 
+`--geometry RBOX` runs the geometry the default checkpoint path is named for instead: `model_vgg_16.model_rbox`
+(score, four distances x `--text_scale`, angle), per-pixel quads in raster order, locality-aware NMS, all on the device
+(`main_rbox`); the default `--geometry link` is the path described above, unchanged.
+
     python test.py --test_data_path ./exhibition --checkpoint_path /tmp/east_icdar2015_resnet_v1_50_rbox/ --output_dir /tmp/res/
 
 Same flag names / defaults.  Everything per-pixel runs on the GPU (network, cv2.resize, softmaxes,
@@ -19,7 +23,7 @@ import numpy as np
 import torch
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--input_size', type=int, default=512)
     ap.add_argument('--gpu_list', type=str, default='1')
@@ -33,7 +37,12 @@ def parse():
     ap.add_argument('--fold-bn', dest='fold_bn', action=argparse.BooleanOptionalAction, default=None,
                     help="f32 / f16x2 only (ignored with f16): run each convolution, its frozen batch norm, the residual add and the "
                     "ReLU as one kernel (Graph(fold_bn=True)).  Default per precision: FOLD_BN_DEFAULT")
-    return ap.parse_args()
+    ap.add_argument('--geometry', choices=['link', 'RBOX'], default='link', help="link: the PixelLink heads and the contour "
+                    "decode of this script; RBOX: EAST's score + four distances + angle heads (model_vgg_16.model_rbox), decoded "
+                    "per pixel into quads and merged by locality-aware NMS on the device (tool/rbox.detect)")
+    ap.add_argument('--text_scale', type=int, default=512, help="RBOX only: the distance scale of the geometry head "
+                    "(the reference's nets/model.py flag)")
+    return ap.parse_args(argv)
 
 
 # --fold-bn when the flag is not given: on where the folded graph measured faster than the unfolded one at this script's
@@ -132,9 +141,62 @@ def boxes_from_mask(score_map_res, ratio_h, ratio_w, graph=None):
     return out
 
 
+def _restore(FLAGS, g):
+    """variable_averages.variables_to_restore(): the EMA shadows (test.py:149-158)."""
+    from tensorflow_ocr_amd import checkpoint
+    if not (os.path.exists(os.path.join(FLAGS.checkpoint_path, 'checkpoint')) or os.path.exists(FLAGS.checkpoint_path + '.index')):
+        # the reference dies here too (`ckpt_state.model_checkpoint_path` on None, test.py:155-157):
+        # never write boxes produced by randomly initialised weights
+        raise FileNotFoundError('no checkpoint under --checkpoint_path %r' % FLAGS.checkpoint_path)
+    sd, _ = checkpoint.load_tf_checkpoint(FLAGS.checkpoint_path, use_moving_averages=True)
+    g.store.load_state_dict(checkpoint.tf_to_internal(g.store.order, sd), strict=False)
+    print('Restore from {}'.format(FLAGS.checkpoint_path))
+
+
+def main_rbox(FLAGS):
+    """--geometry RBOX: model_rbox -> per-pixel quads -> locality-aware NMS, all on the device; the kept quads, divided
+    by the resize ratios and truncated to integers, in the res_<name>.txt format of the link path.  Not here: the
+    mean-score filter over each quad's raster that EAST's eval script applies after the NMS."""
+    from tensorflow_ocr_amd.datasets import icdar
+    from tensorflow_ocr_amd.graph import Graph
+    from tensorflow_ocr_amd.infer import GraphedForward
+    from tensorflow_ocr_amd.nets import model_vgg_16
+    from tensorflow_ocr_amd.tool import rbox
+    os.makedirs(FLAGS.output_dir, exist_ok=True)
+    g = Graph('cuda:0', **graph_kwargs(FLAGS.precision, FLAGS.fold_bn))
+    restored = False
+
+    def network(gr, im):
+        return model_vgg_16.model_rbox(im, is_training=False, text_scale=FLAGS.text_scale, graph=gr)
+    forward = GraphedForward(g, network)
+    for im_fn in get_images(FLAGS.test_data_path):
+        im = icdar.read_image_rgb(im_fn)
+        start_time = time.time()
+        im_resized, (ratio_h, ratio_w) = resize_image(im, graph=g)
+        x = im_resized[None]
+        f_score, f_geometry = forward(x)
+        if not restored:
+            _restore(FLAGS, g)
+            f_score, f_geometry = forward(x)
+            restored = True
+        torch.cuda.synchronize()
+        print('net time:' + str((time.time() - start_time) * 1000) + 'ms')
+        quads = rbox.detect(f_score, f_geometry, graph=g)[0]
+        res_file = os.path.join(FLAGS.output_dir, 'res_{}.txt'.format(os.path.basename(im_fn).split('.')[0]))
+        with open(res_file, 'w') as f:
+            for q in quads:
+                box = q[:8].reshape(4, 2).astype(np.float64)
+                box[:, 0] /= ratio_w
+                box[:, 1] /= ratio_h
+                box = box.astype(np.int32)
+                f.write('{},{},{},{},{},{},{},{}\r\n'.format(box[0, 0], box[0, 1], box[1, 0], box[1, 1],
+                                                            box[2, 0], box[2, 1], box[3, 0], box[3, 1]))
+
+
 def main():
     FLAGS = parse()
-    from tensorflow_ocr_amd import checkpoint
+    if FLAGS.geometry == 'RBOX':
+        return main_rbox(FLAGS)
     from tensorflow_ocr_amd.datasets import icdar
     from tensorflow_ocr_amd.graph import Graph
     from tensorflow_ocr_amd.infer import GraphedForward
@@ -157,14 +219,7 @@ def main():
         x = im_resized[None]
         scores, pixel_score = forward(x)
         if not restored:
-            # variable_averages.variables_to_restore(): the EMA shadows (test.py:149-158)
-            if not (os.path.exists(os.path.join(FLAGS.checkpoint_path, 'checkpoint')) or os.path.exists(FLAGS.checkpoint_path + '.index')):
-                # the reference dies here too (`ckpt_state.model_checkpoint_path` on None, test.py:155-157):
-                # never write boxes produced by randomly initialised weights
-                raise FileNotFoundError('no checkpoint under --checkpoint_path %r' % FLAGS.checkpoint_path)
-            sd, _ = checkpoint.load_tf_checkpoint(FLAGS.checkpoint_path, use_moving_averages=True)
-            g.store.load_state_dict(checkpoint.tf_to_internal(g.store.order, sd), strict=False)
-            print('Restore from {}'.format(FLAGS.checkpoint_path))
+            _restore(FLAGS, g)
             scores, pixel_score = forward(x)
             restored = True
         cls_score = scores[:, :, :, 1:2].contiguous()           # softmax(f_score)[..., 1:2]; pixel_score: softmax over the pairs
