@@ -584,7 +584,9 @@ int ocr_dice_loss_bwd_dyn(const void* y_true_pixel, int pc, const void* y_true_l
  * Softmax cross-entropy losses with online hard negative mining / focal links.
  *   pixel_rule 0: nets/model.py:204-261 `loss` (OHNM: per image the k = min(neg_ratio*n_pos,
  *                 n_neg) negatives with the smallest P(neg), tie-inclusive; pixel term
- *                 sum(CE*selected)/n_pos_batch, 0 without positives)
+ *                 sum(CE*selected)/n_pos_batch, 0 without positives).  The mining count is
+ *                 k = (int)min((double)n_pos * (double)neg_ratio, (double)n_neg), the same definition as
+ *                 ocr_ohnm_select: the product is exact in double, so a non-integer ratio mines the same pixels in both.
  *   pixel_rule 1: nets/model_vgg_16.py:243-282 `ohem_loss` (positives only)
  *   pixel_rule 2: nets/pixellink.py:88-263 `PixelLinkNet.build_loss` (mean over all pixels)
  *   label_rule 0: pos = (label == 1), neg = (label == 0);  1: pos = (label > 0), neg = !pos

@@ -280,6 +280,11 @@ __global__ void dice_bwd22_kernel(DiceP d, const float* __restrict__ ytp, const 
   }
 }
 
+// The vector kernels read and write whole 8- / 16-byte words: they are chosen only when every pointer they vectorise is
+// aligned to its word (a pixel's vectors then are too: 8 / 32 / 64 bytes per pixel); any other pointer takes the generic
+// kernel, whose scalar accesses form the same sums in the same order.
+inline bool dice_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
 int dice_blocks(int P) {
   int b = ocr_cdiv(P, 256 * 4);
   if (b > 1024) b = 1024;
@@ -301,7 +306,9 @@ extern "C" int ocr_dice_loss_fwd(const void* y_true_pixel, const void* y_pred_pi
   hipStream_t st = static_cast<hipStream_t>(stream);
   DiceP d{P, pc, G};
   const int T = dice_blocks(P);
-  hipLaunchKernelGGL(pc == 2 && G == 2 ? dice_reduce22_kernel : pc == 1 && G == 1 ? dice_reduce11_kernel : dice_reduce_kernel,
+  const bool vec = dice_aligned(y_true_link, 16) && dice_aligned(y_pred_link, 16);
+  const bool v22 = pc == 2 && G == 2 && vec && dice_aligned(y_pred_pixel, 8), v11 = pc == 1 && G == 1 && vec;
+  hipLaunchKernelGGL(v22 ? dice_reduce22_kernel : v11 ? dice_reduce11_kernel : dice_reduce_kernel,
                      dim3(T), dim3(256), 0, st, d,
                      static_cast<const float*>(y_true_pixel), static_cast<const float*>(y_pred_pixel),
                      static_cast<const float*>(y_true_link), static_cast<const float*>(y_pred_link),
@@ -319,7 +326,9 @@ int dice_bwd_launch(const void* y_true_pixel, int pc, const void* y_true_link, i
   OCR_CHECK_ARG(y_true_pixel && y_true_link && training_mask && sums27 && d_pred_pixel && d_pred_link);
   OCR_CHECK_ARG(P > 0 && pc >= 1 && G >= 1);
   DiceP d{P, pc, G};
-  hipLaunchKernelGGL(pc == 2 && G == 2 ? dice_bwd22_kernel<Seed> : pc == 1 && G == 1 ? dice_bwd11_kernel<Seed> : dice_bwd_kernel<Seed>,
+  const bool vec = dice_aligned(y_true_link, 16) && dice_aligned(d_pred_link, 16);
+  const bool v22 = pc == 2 && G == 2 && vec && dice_aligned(d_pred_pixel, 8), v11 = pc == 1 && G == 1 && vec;
+  hipLaunchKernelGGL(v22 ? dice_bwd22_kernel<Seed> : v11 ? dice_bwd11_kernel<Seed> : dice_bwd_kernel<Seed>,
                      dim3(dice_blocks(P) * 2), dim3(256), 0,
                      static_cast<hipStream_t>(stream), d, static_cast<const float*>(y_true_pixel),
                      static_cast<const float*>(y_true_link), static_cast<const float*>(training_mask),

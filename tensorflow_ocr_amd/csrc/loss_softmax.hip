@@ -101,7 +101,9 @@ __global__ __launch_bounds__(1024) void ohnm_threshold_kernel(SlP p, const float
   atomicAdd(&s_cnt[1], nn);
   __syncthreads();
   const int n_pos = s_cnt[0], n_neg = s_cnt[1];
-  int k = (int)fminf((float)n_pos * p.neg_ratio, (float)n_neg);
+  // the mining count of ohnm_select_kernel: the product is exact in double (an f32 product can round UP to the next
+  // integer: 10 * 0.7f = 7.0f, while 10 * (double)0.7f = 6.9999998)
+  const int k = (int)fmin((double)n_pos * (double)p.neg_ratio, (double)n_neg);
   if (n_pos == 0 || k <= 0) {
     if (threadIdx.x == 0) thr[img] = -1.f;   // nothing is selected (scores are >= 0)
     return;
@@ -449,6 +451,10 @@ int sl_blocks(size_t total) {
 int fill(const ocr_softmax_loss_desc* d, SlP* p) {
   OCR_CHECK_ARG(d != nullptr && d->n > 0 && d->hw > 0);
   OCR_CHECK_ARG(d->pixel_rule >= 0 && d->pixel_rule <= 2);
+  OCR_CHECK_ARG((d->label_rule == 0 || d->label_rule == 1) && (d->link_gate == 0 || d->link_gate == 1) &&
+                (d->focal == 0 || d->focal == 1));
+  OCR_CHECK_ARG(d->neg_ratio >= 0.f);                                 // (a NaN ratio fails the comparison too)
+  OCR_CHECK_SHAPE((int64_t)d->n * d->hw <= (int64_t)INT32_MAX);       // pixels are counted in int by the mining kernels
   p->n = d->n; p->hw = d->hw; p->pixel_rule = d->pixel_rule; p->label_rule = d->label_rule;
   p->link_gate = d->link_gate; p->focal = d->focal;
   p->neg_ratio = d->neg_ratio; p->alpha = d->alpha; p->gamma = d->gamma;
@@ -458,7 +464,7 @@ int fill(const ocr_softmax_loss_desc* d, SlP* p) {
 }  // namespace
 
 extern "C" size_t ocr_softmax_loss_workspace(const ocr_softmax_loss_desc* d) {
-  if (!d) return 0;
+  if (!d || d->n <= 0 || d->hw <= 0) return 0;
   return (size_t)sl_blocks((size_t)d->n * d->hw) * NS * sizeof(float);
 }
 

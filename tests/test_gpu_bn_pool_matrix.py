@@ -3,7 +3,7 @@ the general max-pool, the legacy bilinear unpool, bias+ReLU backward and the tic
 float64 restatement in NumPy on the same 16-bit-exact operands (no autograd, no oracle routine, no device route compared
 with another).  Every entry is called through ctypes on the library tensorflow_ocr_amd.ops binds: the status of each call
 is part of what is asserted, and several wrappers hide an argument (max_workgroups, ws_bytes, T).  Not covered here:
-ocr_bn_finalize_batch, ocr_bn_bwd_sums_batch (bn_finalize_batch_kernel) and ocr_prep_images_f16 / _norm_f16.
+ocr_prep_images_f16 / _norm_f16.
 
 Kernels and the rows that reach them (ROWS, FIN_SHAPES, WINDOWS below):
   reduce_finalize_kernel<BnFin|BnBwdFin|BnBwdFinC>  FIN_SHAPES: (1,8) one partial row; (1024,64) | (1025,64) the R = 1 /
@@ -14,6 +14,13 @@ Kernels and the rows that reach them (ROWS, FIN_SHAPES, WINDOWS below):
                             groups and the second-level counter).
                             Behind the row entries: tickets_c64 (T = 1049, rows 256, R = 5, last block 25 rows),
                             c2048_cap (32 channel groups).
+  bn_finalize_batch_kernel                  test_finalize_batch (ocr_bn_finalize_batch, ocr_bn_bwd_sums_batch): C 1 | 3 | 18 |
+                            32 (row lanes RL = 1024 / 2C = 512 | 170 | 28 | 16; at C = 3 and 18 the last 4 | 16 threads
+                            own no lane) x T 1 | RL - 1 | RL | RL + 1 | 8 RL - 1 | 8 RL + 1 | 2048 (those <= 2048: the
+                            launcher refuses more), all T of a C in one launch; test_finalize_batch_mixed: count 1..8,
+                            C and T differing between the items, gamma / beta, moving statistics, save buffers given
+                            or NULL per item; out0 against kind 0 and out1 against kind 1 separately (a swap of the
+                            BnBwdFin{out1, out0} wiring fails both); test_batch_status_codes
   bn_inference_params_kernel                test_forward, every row
   bn_relu_kernel<relu, 0 | 2>               test_forward: pool 0 | 2 x relu 0 | 1 x with / without a_full; the index form
                             with / without a_full and y_pool; stream_cap: the capped grid's second pass (pool 0)
@@ -95,6 +102,8 @@ still shows the final rounding, up to 0.999 of u |ref|; 0.000 = the stored value
   bias_relu_bwd (bias gradient)      0.047 / 0.040      maxpool_bwd                        0.999 / 0.996
   unpool                             0.998 / 0.996      unpool_bwd                         0.996 / 0.996
   unpool_add_stats                   0.999 / 0.996
+  bn_finalize_batch                  0.971 / same       bn_bwd_sums_batch out0, out1       0.977, 0.994 / same
+  (the batched entries read f32 partials only: one figure for both libraries, like bn_finalize / bn_bwd_sums)
   per-channel sums (`_sums` lines):  bn_relu_bwd 0.099 / 0.163, bn_relu_bwd_reduce 0.083 / 0.163,
                                      bn_relu_pool_bwd_idx 0.099 / 0.079, bn_relu_bwd_reduce_pooled 0.043 / 0.045
   The (T, C) sums sit at 0.98 because their bar is one f32 rounding of the result (the f64 stage adds nothing
@@ -142,7 +151,8 @@ FIN_R = {(1, 8): 1, (1024, 64): 1, (1025, 64): 5, (6400, 256): 16, (70000, 8): 3
 WINDOWS = {"k2s2": (2, 2), "k3s2": (3, 2), "k3s1": (3, 1), "k1s2": (1, 2), "k5s3": (5, 3)}
 POOL_MAPS = {"odd": (2, 7, 9, 64), "even": (2, 8, 6, 64), "c24": (2, 5, 7, 24)}
 POOL_CASES = [(win, m) for m in ("odd", "even") for win in WINDOWS] + [("k3s2", "c24")]
-N_TESTS = (2 * len(FIN_SHAPES) + 3 + 2 * len(SMALL) + 1 + 2 * len(ROWS) + 2 * 3 + 2 * len(BWD_ROWS)
+BATCH_C = [1, 3, 18, 32]
+N_TESTS = (2 * len(BATCH_C) + 8 + 1 + 2 * len(FIN_SHAPES) + 3 + 2 * len(SMALL) + 1 + 2 * len(ROWS) + 2 * 3 + 2 * len(BWD_ROWS)
            + 2 * 3 * len(GUEST_ROWS) + 2 * len(POOL_CASES) + 1)
 
 BAND = 512
@@ -615,6 +625,158 @@ def test_finalize_family(device, T, C, kind):
     _check_outs("bn_finalize_null", row, o2, {k: fb[k] for k in ("scale", "shift")})
     assert ws.ok() and ws2.ok() and ws3.ok()
     assert np.array_equal(pd.cpu().numpy(), p)
+
+
+# ---- the batched finalisation (bn_finalize_batch_kernel): up to eight small reductions per launch ----
+class BnSumsItem(ctypes.Structure):
+    """ocr_bn_sums_item (include/ocr_hip.h)"""
+    _fields_ = [("partial", ctypes.c_void_p), ("T", ctypes.c_int32), ("C", ctypes.c_int32), ("out0", ctypes.c_void_p), ("out1", ctypes.c_void_p)]
+
+
+def _batch_T(C):
+    RL = 1024 // (2 * C)
+    return [T for T in (1, RL - 1, RL, RL + 1, 8 * RL - 1, 8 * RL + 1, 2048) if T <= 2048]
+
+
+def _dp(v):
+    return None if v is None else (v.t if isinstance(v, Guard) else v).data_ptr()
+
+
+def _run_batch(device, spec, kind, tag):
+    """spec: [(T, C, opts)], opts bit 0: gamma / beta given, bit 1: moving statistics, bit 2: save buffers.  One launch
+    of ocr_bn_bwd_sums_batch and one of ocr_bn_finalize_batch over all items, against the float64 references of the
+    single forms."""
+    from tensorflow_ocr_amd import _lib as L
+    from tensorflow_ocr_amd import ops
+    n = len(spec)
+    exact = kind == "exact"
+    its = []
+    for i, (T, C, opts) in enumerate(spec):
+        it = NS(T=T, C=C, opts=opts, row="%s_i%d_T%d_C%d_o%d" % (tag, i, T, C, opts))
+        it.p = _fin_partials(T, C, kind, seed=i)
+        it.pd = Guard((T, 2, C), torch.float32, device, it.p)
+        it.o = {k: Guard((C,), torch.float32, device) for k in ("out0", "out1")}
+        its.append(it)
+    arr = (BnSumsItem * n)(*[BnSumsItem(_dp(it.pd), it.T, it.C, _dp(it.o["out0"]), _dp(it.o["out1"])) for it in its])
+    assert _rc(L, "ocr_bn_bwd_sums_batch", arr, n) == OK
+    torch.cuda.synchronize()
+    for it in its:
+        p, T = it.p, it.T
+        it.s, it.q = p[:, 0].sum(0, dtype=f64), p[:, 1].sum(0, dtype=f64)
+        it.ds, it.dq = T * 2.0 ** -53 * np.abs(p[:, 0]).sum(0, dtype=f64), T * 2.0 ** -53 * np.abs(p[:, 1]).sum(0, dtype=f64)
+        if exact:
+            _bits_equal(it.o["out0"].np(), it.s.astype(f32), "batch sums kind 0 " + it.row)
+            _bits_equal(it.o["out1"].np(), it.q.astype(f32), "batch sums kind 1 " + it.row)
+        else:
+            _check_outs("bn_bwd_sums_batch_out0", it.row, it.o, {"out0": (it.s, it.ds + U32 * np.abs(it.s))})
+            _check_outs("bn_bwd_sums_batch_out1", it.row, it.o, {"out1": (it.q, it.dq + U32 * np.abs(it.q))})
+        assert np.array_equal(it.pd.np(), p)
+    eps, dec = (f32(0.0), f32(0.5)) if exact else (f32(1e-5), f32(0.997))
+    rows = []
+    for i, it in enumerate(its):
+        T, C, opts = it.T, it.C, it.opts
+        rng = np.random.default_rng(T * 131 + C + i)
+        if exact:
+            it.p2, it.mean, it.var, it.count = _fin_partials_stats(T, C)
+            g, b, mm, mv = rng.choice([0.5, 1.0, 2.0], C), rng.integers(-4, 5, C) / 4.0, rng.integers(-4, 5, C) / 4.0, rng.choice([0.5, 1.0, 2.0], C)
+        else:
+            it.p2, it.count = it.p, 16.0 * T
+            g, b, mm, mv = rng.uniform(0.5, 1.5, C), rng.standard_normal(C), rng.standard_normal(C), rng.uniform(0.5, 2.0, C)
+        it.g, it.b, it.mm, it.mv = (np.asarray(v, f32) for v in (g, b, mm, mv))
+        it.pd2 = _d32(it.p2, device)
+        it.f = {k: Guard((C,), torch.float32, device) for k in ("scale", "shift")}
+        if opts & 2:
+            it.f["moving_mean"], it.f["moving_var"] = Guard((C,), torch.float32, device, it.mm), Guard((C,), torch.float32, device, it.mv)
+        if opts & 4:
+            it.f["save_mean"], it.f["save_invstd"] = Guard((C,), torch.float32, device), Guard((C,), torch.float32, device)
+        gd, bd = (_d32(it.g, device), _d32(it.b, device)) if opts & 1 else (None, None)
+        it.keep = (gd, bd)
+        rows.append((_dp(it.pd2), T, C, float(it.count), _dp(gd), _dp(bd), _dp(it.f.get("moving_mean")), _dp(it.f.get("moving_var")),
+                     _dp(it.f["scale"]), _dp(it.f["shift"]), _dp(it.f.get("save_mean")), _dp(it.f.get("save_invstd"))))
+    arr = (ops.BnFinalizeItem * n)(*[ops.BnFinalizeItem(*r) for r in rows])
+    assert _rc(L, "ocr_bn_finalize_batch", arr, n, FL(eps), FL(dec)) == OK
+    torch.cuda.synchronize()
+    for it in its:
+        C = it.C
+        g64, b64 = (it.g.astype(f64), it.b.astype(f64)) if it.opts & 1 else (np.ones(C), np.zeros(C))
+        if exact:
+            inv = 1.0 / np.sqrt(it.var)
+            want = {"scale": g64 * inv, "shift": b64 - it.mean * g64 * inv, "save_mean": it.mean, "save_invstd": inv,
+                    "moving_mean": 0.5 * it.mm.astype(f64) + 0.5 * it.mean}
+            for k, ref in want.items():
+                if k in it.f:
+                    _bits_equal(it.f[k].np(), _exact32(ref), "finalize_batch %s %s" % (k, it.row))
+            fb = _fin_bounds(it.count * it.mean, it.count * (it.var + it.mean ** 2), 0.0, 0.0, it.count, g64, b64, 0.0, dec,
+                             it.mm.astype(f64), it.mv.astype(f64))
+            if "moving_var" in it.f:
+                assert _ratio(np.abs(it.f["moving_var"].np() - fb["moving_var"][0]), fb["moving_var"][1]) <= 1
+        else:
+            fb = _fin_bounds(it.s, it.q, it.ds, it.dq, it.count, g64, b64, f64(eps), dec, it.mm.astype(f64), it.mv.astype(f64))
+            _check_outs("bn_finalize_batch", it.row, it.f, {k: fb[k] for k in it.f})
+
+
+@pytest.mark.parametrize("C", BATCH_C)
+@pytest.mark.parametrize("kind", KINDS)
+def test_finalize_batch(device, C, kind):
+    """every T of one C in ONE launch (up to seven items): the row-lane edges RL - 1 | RL | RL + 1, the eight-in-flight
+    loop's 8 RL - 1 | 8 RL + 1 and the largest T the launcher takes"""
+    Ts = _batch_T(C)
+    assert (1024 // (2 * C), len(Ts)) == {1: (512, 5), 3: (170, 7), 18: (28, 7), 32: (16, 7)}[C]
+    _run_batch(device, [(T, C, (1, 7, 0, 3, 5, 6, 2)[i]) for i, T in enumerate(Ts)], kind, "C%d" % C)
+
+
+@pytest.mark.parametrize("count", range(1, 9))
+def test_finalize_batch_mixed(device, count):
+    """count items whose C and T all differ; optional operands given or NULL per item"""
+    pool = [(29, 18, 7), (2048, 1, 0), (171, 3, 5), (16, 32, 2), (225, 18, 1), (1, 32, 6), (1361, 3, 3), (513, 1, 4)]
+    spec = (pool[count - 1:] + pool[:count - 1])[:count]
+    _run_batch(device, spec, "random" if count % 2 else "exact", "n%d" % count)
+
+
+def test_batch_status_codes(device):
+    """count 0 | 9, T 0 | 2049, C 0 | 33, a NULL partial / scale / shift / out0 / out1, count <= 0.0, in the first item
+    and in the second of two: nothing is written (the items are validated before the launch)"""
+    from tensorflow_ocr_amd import _lib as L
+    from tensorflow_ocr_amd import ops
+    T, C = 20, 18
+    part = torch.zeros((T, 2, C), dtype=torch.float32, device=device)
+    G = {k: Guard((C,), torch.float32, device) for k in ("a0", "a1", "b0", "b1")}
+    pp = part.data_ptr()
+
+    def fin(**over):
+        v = dict(partial=pp, T=T, C=C, count=64.0, gamma=None, beta=None, moving_mean=None, moving_var=None,
+                 scale=_dp(G["a0"]), shift=_dp(G["a1"]), save_mean=None, save_invstd=None)
+        v.update(over)
+        return ops.BnFinalizeItem(**v)
+
+    def sums(**over):
+        v = dict(partial=pp, T=T, C=C, out0=_dp(G["b0"]), out1=_dp(G["b1"]))
+        v.update(over)
+        return BnSumsItem(**v)
+
+    def rc_fin(items, n=None):
+        return _rc(L, "ocr_bn_finalize_batch", (ops.BnFinalizeItem * max(len(items), 1))(*items), len(items) if n is None else n, FL(1e-5), FL(0.9))
+
+    def rc_sums(items, n=None):
+        return _rc(L, "ocr_bn_bwd_sums_batch", (BnSumsItem * max(len(items), 1))(*items), len(items) if n is None else n)
+
+    for mk, rc, nulls in ((fin, rc_fin, ("partial", "scale", "shift")), (sums, rc_sums, ("partial", "out0", "out1"))):
+        assert rc([mk()], 0) == INVALID_ARG and rc([mk()] * 9) == INVALID_ARG and rc([mk()], -1) == INVALID_ARG
+        for lead in ([], [mk()]):
+            for k in nulls:
+                assert rc(lead + [mk(**{k: None})]) == INVALID_ARG, k
+            for k, v in (("T", 0), ("T", 2049), ("C", 0), ("C", 33)):
+                assert rc(lead + [mk(**{k: v})]) == UNSUPPORTED, (k, v)
+    assert _rc(L, "ocr_bn_finalize_batch", None, 1, FL(1e-5), FL(0.9)) == INVALID_ARG
+    assert _rc(L, "ocr_bn_bwd_sums_batch", None, 1) == INVALID_ARG
+    for cnt in (0.0, -1.0):
+        assert rc_fin([fin(count=cnt)]) == INVALID_ARG and rc_fin([fin(), fin(count=cnt)]) == INVALID_ARG
+    torch.cuda.synchronize()
+    for k, g in G.items():
+        assert g.untouched(), k
+    assert rc_fin([fin()]) == OK and rc_sums([sums()]) == OK
+    torch.cuda.synchronize()
+    assert all(g.ok() for g in G.values()) and not G["b0"].np().any() and not G["b1"].np().any()
 
 
 @pytest.mark.parametrize("T,C,R", [(1025, 64, 5), (70000, 8, 35)], ids=["R5", "R35"])

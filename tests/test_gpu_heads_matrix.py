@@ -6,7 +6,8 @@ kernels read as 16-bit are drawn on the storage grid; where a kernel rounds on l
 gradient, dz in the MFMA and batched weight gradients) the reference rounds the float64 operand the same way first.
 Weights go through ocr_pack_weights_small_f16, whose [32][cin] / [cin][32] layouts are asserted.  Every output sits in a
 NaN-filled buffer between guard bands, every strided output inside sentinel columns; both must be bit-identical after
-the call.  Not covered here: loss_dice.hip, loss_softmax.hip, ocr_bn_finalize_batch, ocr_bn_bwd_sums_batch.
+the call.  loss_dice.hip and loss_softmax.hip have their own matrix (test_gpu_loss_matrix.py); ocr_bn_finalize_batch and
+ocr_bn_bwd_sums_batch are rows of test_gpu_bn_pool_matrix.py.
 
 Kernels and the rows that reach them
   conv1x1_small_kernel                 test_conv: CONV_ROWS (P 1 | 31 | 33 | 129 | 257 x cin 16 | 48 | 80 | 128 | 1024 x
