@@ -33,7 +33,8 @@ extern "C" {
  * did global-norm clipping (ocr_grad_clip_*, ocr_grad_check_clip_f32, the *_clip optimiser steps), the batched training
  * augmentation (ocr_augment_u8_batch, ocr_augment_desc) and gradient accumulation (ocr_grad_accum_init, ocr_grad_accum_f32,
  * ocr_grad_accum_advance, ocr_grad_accum_state), ocr_conv2d_wgrad_variant (the name of the weight-gradient launch) and the
- * training summaries (ocr_tensor_stats_*, ocr_summary_image_u8). */
+ * training summaries (ocr_tensor_stats_*, ocr_summary_image_u8), and the RBOX training labels with the post-NMS score
+ * filter (ocr_icdar_rbox_labels, ocr_quad_mean_score). */
 #define OCR_ABI_VERSION 7
 
 enum {
@@ -971,6 +972,19 @@ int ocr_icdar_labels(const void* cover_u32, int n, int h, int w, int step, void*
  * [n][new_h][new_w][8]. */
 int ocr_pixellink_labels(const void* cover_u32, int n, int h, int w, int new_h, int new_w, void* score_f32,
                          void* link_f32, void* stream);
+/* EAST RBOX labels at every `step`-th pixel.  BUILD-DEFINED: the reference tree keeps only the helpers of EAST's RBOX
+ * label generator (datasets/icdar.py:202-407), restated on the host in datasets/rbox_labels.py; PARITY with an upstream
+ * run IS UNPINNED.  Two cover maps of ocr_poly_cover over the same polygon list: cover_score from the SHRUNK polygons
+ * (ignore flags 0), cover_full from the full polygons with the ignore flags.  rects f32 [n][max_polys][5][3]: per
+ * polygon the normalised lines (a, b, c), a^2 + b^2 = 1, of its rectangle's edges r0r1 (top), r1r2 (right), r2r3
+ * (bottom), r3r0 (left) and (angle, 0, 0).  Output cell (Y, X) stands for the image point (x, y) = (X step, Y step); its
+ * owner is bits 8-15 of cover_score (the largest covering index: later polygons on top).  With an owner: score = 1,
+ * geo[k] = |a_k x + b_k y + c_k| (k < 4, image pixels; separate f32 multiplies and adds), geo[4] = angle; without:
+ * all six are 0.  mask = 0 where bit 16 of cover_full is set, else 1.  score / mask f32 [n][oh][ow][1], geo f32
+ * [n][oh][ow][5], oh = ceil(h / step); h != w is fine.  OCR_ERR_UNSUPPORTED without a launch unless n, h, w, step >= 1,
+ * 1 <= max_polys <= 254, n <= 65535 and h, w <= 16384 (the bounds of ocr_poly_cover). */
+int ocr_icdar_rbox_labels(const void* cover_score_u32, const void* cover_full_u32, const void* rects_f32, int n, int max_polys,
+                    int h, int w, int step, void* score_f32, void* geo_f32, void* mask_f32, void* stream);
 
 /* Evaluation (tool/bboxes.py:246-283 np_bboxes_jaccard, called from bboxes_matching :171-240): pixel
  * counts of the filled rasters (cv2.drawContours thickness=-1 = the fillPoly raster) of every
@@ -978,6 +992,14 @@ int ocr_pixellink_labels(const void* cover_u32, int n, int h, int w, int new_h, 
  * int32 [nd][ng].  dets int32 [nd][verts][2], gts int32 [ng][verts][2]; 3 <= verts <= 8. */
 int ocr_quad_iou(const void* dets_i32, int nd, const void* gts_i32, int ng, int verts, int mask_h, int mask_w,
                  void* inter_i32, void* union_i32, void* stream);
+/* The post-NMS filter of EAST's eval script (csrc/rbox.hip): quads f32 [k][8] in image pixels, score f32 [h][w].  Per quad
+ * the vertices floor(trunc(coord) * inv_scale) — `box.astype(np.int32) // 4` for inv_scale = 0.25, exactly, below 2^22
+ * in magnitude (larger coordinates are clamped there) — and mean [k] f32 = the sum of the score over the cv2.fillPoly raster
+ * of those vertices clipped to the map, divided by its pixel count; 0 for an empty raster or a non-finite coordinate.
+ * f64 sums added in a fixed order: the result does not depend on scheduling.  k = 0 is OCR_OK without a launch;
+ * OCR_ERR_UNSUPPORTED for k < 0, h or w outside [1, 32768], inv_scale outside (0, 1]. */
+int ocr_quad_mean_score(const void* quads_f32, int k, const void* score_f32, int h, int w, float inv_scale,
+                        void* mean_f32, void* stream);
 
 /* Strided 3x3 convolutions of ResNet-v1 (nets/resnet_utils.py:85-122 conv2d_same with stride 2) as one
  * stride-1 2x2 convolution over a space-to-depth copy: xs[n][Y][X][(a*2+b)*c + ch] = x[n][2Y+a][2X+b][ch]

@@ -14,6 +14,9 @@ upload + resize + label maps on the feeder's HIP stream, overlapped with the ste
 with an empty directory) batches are synthetic (`tensorflow_ocr_amd.synthetic`).  Every
 `--save_summary_steps` optimiser steps rank 0 adds scalars and images (and, with
 `--summary_variables`, per-variable histograms) to a TensorBoard event file in `--checkpoint_path`.  `--augment east`
+`--net east --geometry RBOX` trains EAST's RBOX heads (`model_vgg_16.model_rbox` / `loss_rbox`, distances x `--text_scale`)
+on RBOX label maps made on the device from the same ICDAR polygons (or `synthetic.rbox_labels` without data) — the head
+`test.py --geometry RBOX` runs.  `--augment east`
 (or `pixellink`, or key=value,...) turns on the augmentation the reference keeps disabled
 (datasets/icdar.py:576-615), warped on the device in one launch per batch.  The stdout line
 format is the reference's (:183-184)."""
@@ -58,7 +61,15 @@ def parse(argv=None):
     # per-variable summaries of train_pixellink.py:179-194 (histograms of every variable and gradient, their means) from
     # one device pass over the flat buffers (summary.TensorStats)
     ap.add_argument('--summary_variables', action='store_true')
-    return ap.parse_args(argv)
+    # not a flag of this reference script (EAST's own has the head built in): link = the PixelLink-style 8 link maps the
+    # reference trains; RBOX = EAST's score + four distances + angle (--net east only), labels from the same polygons
+    ap.add_argument('--geometry', choices=['link', 'RBOX'], default='link')
+    ap.add_argument('--text_scale', type=int, default=512, help="RBOX only: the distance scale of the geometry head "
+                    "(the reference's nets/model.py flag)")
+    FLAGS = ap.parse_args(argv)
+    if FLAGS.geometry == 'RBOX' and FLAGS.net != 'east':
+        ap.error('--geometry RBOX needs --net east (the RBOX heads sit on the EAST merge branch)')
+    return FLAGS
 
 
 def _augment_arg(text):
@@ -93,9 +104,16 @@ def _loss_scale_arg(text):
         raise argparse.ArgumentTypeError(str(e))
 
 
-def build_forward_loss(net):
+def build_forward_loss(net, geometry='link', text_scale=512):
     from tensorflow_ocr_amd.nets import model, model_vgg_16, pixellink
-    if net == 'model':
+    if geometry == 'RBOX':
+        if net != 'east':
+            raise ValueError("geometry 'RBOX' needs net 'east'")
+
+        def f(g, im, sm, gm, tm):
+            a, b = model_vgg_16.model_rbox(im, is_training=True, text_scale=text_scale, graph=g)
+            return model_vgg_16.loss_rbox(sm, a, gm, b, tm, graph=g)
+    elif net == 'model':
         def f(g, im, sm, gm, tm):
             a, b = model.model(im, is_training=True, graph=g)
             return model.loss(sm, a, gm, b, tm, graph=g)
@@ -138,7 +156,7 @@ def main():
         os.makedirs(FLAGS.checkpoint_path, exist_ok=True)
 
     g = Graph(device, loss_scale=FLAGS.loss_scale, seed=1)
-    step = TrainStep(g, build_forward_loss(FLAGS.net),
+    step = TrainStep(g, build_forward_loss(FLAGS.net, FLAGS.geometry, FLAGS.text_scale),
                      lambda gr: AdamOptimizer(gr, learning_rate=FLAGS.learning_rate,
                                               moving_average_decay=FLAGS.moving_average_decay,
                                               clip_norm=FLAGS.clip_norm),
@@ -151,7 +169,7 @@ def main():
             # multigpu_train.py:164-167: icdar.get_batch(num_workers, input_size, batch_size)
             feeder = icdar.get_batch(num_workers=FLAGS.num_readers, training_data_path=FLAGS.training_data_path,
                                      input_size=FLAGS.input_size, batch_size=FLAGS.batch_size_per_gpu,
-                                     graph=g, seed=1000 + rank, augment=FLAGS.augment)
+                                     graph=g, seed=1000 + rank, augment=FLAGS.augment, geometry=FLAGS.geometry)
     start = time.time()
     try:
         _train_loop(FLAGS, g, step, feeder, rng, rank, world, device, start)
@@ -166,6 +184,8 @@ def _next_batch(FLAGS, feeder, rng, device):
         images, _, score_maps, geo_maps, training_masks = next(feeder)
         return [images, score_maps, geo_maps, training_masks]
     data = synthetic.make_batch(rng, FLAGS.batch_size_per_gpu, FLAGS.input_size)
+    if FLAGS.geometry == 'RBOX':
+        data = [data[0]] + list(synthetic.rbox_labels(FLAGS.batch_size_per_gpu, FLAGS.input_size, rng))
     return [torch.from_numpy(a).to(device, non_blocking=True) for a in data]
 
 

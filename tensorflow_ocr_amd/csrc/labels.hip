@@ -7,6 +7,9 @@
 //                         cv2.fillPoly raster contains it, and whether an ignored polygon covers it
 //   ocr_icdar_labels      icdar.generate_rbox + the generator's subsample, from the cover map
 //   ocr_pixellink_labels  pixellink_fn.generate_rbox, from the cover map
+//   ocr_icdar_rbox_labels       EAST's RBOX maps (score / four edge distances + angle / training mask) from two cover maps
+//                         and a per-polygon table of rectangle edge lines (BUILD-DEFINED: the reference tree keeps only
+//                         the helpers of that generator, datasets/icdar.py:202-407; host side datasets/rbox_labels.py)
 //
 // The reference draws the polygons one after another and evaluates `valid_link` between draws; all
 // of it is a function of (first, last) covering index per pixel:
@@ -175,6 +178,50 @@ __global__ void pixellink_labels_kernel(const unsigned* __restrict__ cover, int 
   }
 }
 
+constexpr int kRectFloats = 15;      // four lines (a, b, c) and (angle, 0, 0)
+constexpr int kMaxPolys = 254;
+
+// grid (cells / 256, n), one thread per output cell.  The image's table sits in LDS; the five geometry values of the
+// workgroup's 256 cells are staged there too and leave as one contiguous run (the [cell][5] layout would otherwise
+// store with a stride of five floats).
+__global__ __launch_bounds__(256) void rbox_labels_kernel(const unsigned* __restrict__ cover_score,
+                                                          const unsigned* __restrict__ cover_full,
+                                                          const float* __restrict__ rects, int P, int h, int w, int step,
+                                                          int oh, int ow, float* __restrict__ score,
+                                                          float* __restrict__ geo, float* __restrict__ mask) {
+#pragma clang fp contract(off)
+  __shared__ float s_tab[kMaxPolys * kRectFloats];
+  __shared__ float s_geo[256 * 5];
+  const int img = blockIdx.y;
+  const float* tab = rects + (size_t)img * P * kRectFloats;
+  for (int i = threadIdx.x; i < P * kRectFloats; i += 256) s_tab[i] = tab[i];
+  __syncthreads();
+  const int cells = oh * ow, cell0 = blockIdx.x * 256, cell = cell0 + threadIdx.x;
+  float g[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  if (cell < cells) {
+    const int x = (cell % ow) * step, y = (cell / ow) * step;
+    const size_t at = ((size_t)img * h + y) * w + x;
+    unsigned owner = (cover_score[at] >> 8) & 255u;
+    if (owner > (unsigned)P) owner = 0;                 // a cover map made with another polygon count
+    if (owner) {
+      const float* r = s_tab + (owner - 1) * kRectFloats;
+      const float fx = (float)x, fy = (float)y;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) g[k] = fabsf(r[3 * k] * fx + r[3 * k + 1] * fy + r[3 * k + 2]);
+      g[4] = r[12];
+    }
+    const size_t o = (size_t)img * cells + cell;
+    score[o] = owner ? 1.f : 0.f;
+    mask[o] = (cover_full[at] >> 16) & 1u ? 0.f : 1.f;
+  }
+#pragma unroll
+  for (int k = 0; k < 5; ++k) s_geo[threadIdx.x * 5 + k] = g[k];
+  __syncthreads();
+  const int run = min(256, cells - cell0) * 5;
+  float* out = geo + ((size_t)img * cells + cell0) * 5;
+  for (int i = threadIdx.x; i < run; i += 256) out[i] = s_geo[i];
+}
+
 unsigned lgrid(size_t items) {
   size_t b = (items + 255) / 256;
   if (b > 16384) b = 16384;
@@ -217,5 +264,19 @@ extern "C" int ocr_pixellink_labels(const void* cover_u32, int n, int h, int w, 
   hipLaunchKernelGGL(pixellink_labels_kernel, dim3(lgrid((size_t)n * new_h * new_w * 8)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const unsigned*>(cover_u32), n, h, w, new_h,
                      new_w, ifx, ify, static_cast<float*>(score_f32), static_cast<float*>(link_f32));
+  return ocr_launch_status();
+}
+
+extern "C" int ocr_icdar_rbox_labels(const void* cover_score_u32, const void* cover_full_u32, const void* rects_f32, int n,
+                               int max_polys, int h, int w, int step, void* score_f32, void* geo_f32, void* mask_f32,
+                               void* stream) {
+  OCR_CHECK_ARG(cover_score_u32 && cover_full_u32 && rects_f32 && score_f32 && geo_f32 && mask_f32);
+  OCR_CHECK_SHAPE(n >= 1 && h >= 1 && w >= 1 && step >= 1 && max_polys >= 1 && max_polys <= kMaxPolys);
+  OCR_CHECK_SHAPE(n <= 65535 && h <= 16384 && w <= 16384);     // the bounds of ocr_poly_cover, which makes the covers
+  const int oh = ocr_cdiv(h, step), ow = ocr_cdiv(w, step);
+  hipLaunchKernelGGL(rbox_labels_kernel, dim3(ocr_cdiv(oh * ow, 256), n), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned*>(cover_score_u32), static_cast<const unsigned*>(cover_full_u32),
+                     static_cast<const float*>(rects_f32), max_polys, h, w, step, oh, ow, static_cast<float*>(score_f32),
+                     static_cast<float*>(geo_f32), static_cast<float*>(mask_f32));
   return ocr_launch_status();
 }

@@ -12,8 +12,12 @@
 //           restore_rectangle_rbox returns the theta >= 0 rows before the theta < 0 rows): per-workgroup counts by
 //           ballot + popcount, one scan per image, a write pass with the wave prefix.  No atomic counter.
 //
+//   mean    the post-NMS filter of EAST's eval script: per kept quad the mean of the score map over the cv2.fillPoly
+//           raster of its vertices `box.astype(np.int32) // 4` (raster.h, the bit-exact closed form the label and IoU
+//           kernels use).  One workgroup per quad; f64 sums added in a fixed order.
+//
 // Coordinate geometry: compiled without FMA contraction (Makefile NOFMA), like lanms and boxes.
-#include "common.h"
+#include "raster.h"
 
 namespace {
 
@@ -315,6 +319,87 @@ __global__ __launch_bounds__(256) void rbox_write_kernel(DecodeP d, const float*
   o[8] = sc;
 }
 
+// ------------------------------------------------------------------------------------------------ mean score
+constexpr float kCoordLimit = 4194304.f;      // 2^22: vertices beyond it are clamped (keeps the raster's 16.16 arithmetic in range)
+
+// grid (k), one workgroup per quad.  A quad with a non-finite coordinate has an empty raster.
+__global__ __launch_bounds__(256) void quad_mean_score_kernel(const float* __restrict__ quads,
+                                                              const float* __restrict__ score, int h, int w,
+                                                              float inv_scale, float* __restrict__ mean) {
+  __shared__ raster::Seg s_seg[4];
+  __shared__ raster::FillEdge s_edge[4];
+  __shared__ int s_v[8];
+  __shared__ int s_box[4];
+  __shared__ int s_fill, s_ok;
+  __shared__ double s_sum[4];
+  __shared__ int s_cnt[4];
+  const float* q = quads + (size_t)blockIdx.x * 8;
+  if (threadIdx.x == 0) {
+    int ok = 1;
+    for (int j = 0; j < 8; ++j) {
+      const float c = q[j];
+      ok &= isfinite(c) ? 1 : 0;
+      // int32(trunc(c)) // 4 for inv_scale = 0.25: the product and its floor are exact in f32 below 2^24
+      const float t = fminf(fmaxf(truncf(ok ? c : 0.f), -kCoordLimit), kCoordLimit);
+      s_v[j] = (int)fminf(fmaxf(floorf(t * inv_scale), -kCoordLimit), kCoordLimit);
+    }
+    s_ok = ok;
+  }
+  __syncthreads();
+  if (!s_ok) {
+    if (threadIdx.x == 0) mean[blockIdx.x] = 0.f;
+    return;
+  }
+  if (threadIdx.x < 4) {
+    const int e = threadIdx.x, e0 = e == 0 ? 3 : e - 1;
+    raster::Seg sg;
+    raster::FillEdge fe;
+    raster::setup_edge(s_v[2 * e0], s_v[2 * e0 + 1], s_v[2 * e], s_v[2 * e + 1], w, h, sg, fe);
+    s_seg[e] = sg;
+    s_edge[e] = fe;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    s_fill = raster::fill_enabled(s_edge, 4, w, h) ? 1 : 0;
+    int x0 = INT_MAX, y0 = INT_MAX, x1 = INT_MIN, y1 = INT_MIN;
+    for (int j = 0; j < 4; ++j) {
+      x0 = min(x0, s_v[2 * j]); x1 = max(x1, s_v[2 * j]);
+      y0 = min(y0, s_v[2 * j + 1]); y1 = max(y1, s_v[2 * j + 1]);
+    }
+    s_box[0] = max(x0 - 1, 0);
+    s_box[1] = max(y0 - 1, 0);
+    s_box[2] = min(x1 + 1, w - 1);
+    s_box[3] = min(y1 + 1, h - 1);
+  }
+  __syncthreads();
+  const int bx0 = s_box[0], by0 = s_box[1], bw = s_box[2] - bx0 + 1, bh = s_box[3] - by0 + 1;
+  double sum = 0.0;
+  int cnt = 0;
+  if (bw > 0 && bh > 0) {
+    const long long total = (long long)bw * bh;
+    for (long long i = threadIdx.x; i < total; i += 256) {
+      const int y = by0 + (int)(i / bw), x = bx0 + (int)(i % bw);
+      if (raster::covers(s_seg, s_edge, 4, s_fill != 0, x, y)) {
+        sum += (double)score[(size_t)y * w + x];
+        ++cnt;
+      }
+    }
+  }
+  sum = wave_sum_d(sum);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if ((threadIdx.x & 63) == 0) {
+    s_sum[threadIdx.x >> 6] = sum;
+    s_cnt[threadIdx.x >> 6] = cnt;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int c = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    const double s = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+    mean[blockIdx.x] = c > 0 ? (float)(s / (double)c) : 0.f;
+  }
+}
+
 }  // namespace
 
 extern "C" int ocr_rbox_head_fwd(const void* z, int P, float text_scale, void* score, void* geo, void* stream) {
@@ -387,5 +472,16 @@ extern "C" int ocr_rbox_decode(const void* score, const void* geo, int n, int h,
                      static_cast<int*>(total));
   hipLaunchKernelGGL(rbox_write_kernel, dim3(d.blocks, n), dim3(256), 0, st, d, static_cast<const float*>(score),
                      static_cast<const float*>(geo), static_cast<const int*>(bc), static_cast<float*>(boxes));
+  return ocr_launch_status();
+}
+
+extern "C" int ocr_quad_mean_score(const void* quads_f32, int k, const void* score_f32, int h, int w, float inv_scale,
+                                   void* mean_f32, void* stream) {
+  OCR_CHECK_SHAPE(k >= 0 && h >= 1 && w >= 1 && h <= 32768 && w <= 32768 && inv_scale > 0.f && inv_scale <= 1.f);
+  if (k == 0) return OCR_OK;
+  OCR_CHECK_ARG(quads_f32 && score_f32 && mean_f32);
+  hipLaunchKernelGGL(quad_mean_score_kernel, dim3(k), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const float*>(quads_f32), static_cast<const float*>(score_f32), h, w, inv_scale,
+                     static_cast<float*>(mean_f32));
   return ocr_launch_status();
 }

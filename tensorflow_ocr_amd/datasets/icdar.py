@@ -8,7 +8,11 @@ Same function names and argument order as the reference where it has them:
   generate_rbox             icdar.py:486-539 (one image, full resolution, NumPy results)
   generator / get_batch     icdar.py:542-668 (resize to input_size, BGR->RGB float, labels at 1/4)
 plus the batched device entry points the feeder uses:
-  generate_rbox_batch       all images of a batch in two launches; device tensors at 1/4 resolution
+  generate_rbox_batch       all images of a batch in two launches; device tensors at 1/4 resolution.  geometry='RBOX':
+                            EAST's score / four distances + angle / training mask instead of the link maps (one rectangle
+                            per polygon on the host, datasets/rbox_labels.py; every pixel on the device: ocr_poly_cover
+                            twice + ocr_icdar_rbox_labels).  BUILD-DEFINED from the helpers the reference keeps (:202-407) and
+                            the EAST paper; parity with an upstream run is unpinned
   augment_images            the augmentation the reference keeps disabled (icdar.py:576-615: random scale, crop_area,
                             pad, resize) plus rotations and colour distortion: the policy draws a plan per sample on the
                             host (datasets/augment.py), ONE launch warps the batch (ocr_augment_u8_batch)
@@ -73,13 +77,70 @@ def pack_polys(polys_list, tags_list, min_text_size=MIN_TEXT_SIZE):
     return polys, counts, ignore
 
 
-def generate_rbox_batch(im_size, polys_list, tags_list, step=4, min_text_size=MIN_TEXT_SIZE, graph=None):
+_NOWHERE = -16              # vertices of a polygon that must cover no pixel: outside every image, no edge with a height
+
+
+def pack_rbox(polys_list, tags_list, min_text_size=MIN_TEXT_SIZE, shrink=0.3):
+    """Host packing for the RBOX labels: (shrunk int32 [n,P,4,2], full int32 [n,P,4,2], counts [n], ignore uint8 [n,P],
+    rects float32 [n,P,5,3]).  Per polygon one rectangle (rbox_labels.fit_rectangle) whose four edge lines and angle go
+    into `rects`, computed in float64 and cast; a polygon without one (degenerate) is ignored — training mask 0 over its
+    full raster — and its slot in the shrunk list covers nothing, so the table index stays that of the full list.
+    shrink = 0: the score is drawn from the full polygons."""
+    from . import rbox_labels as RL
+    full, counts, ignore = pack_polys(polys_list, tags_list, min_text_size)
+    shrunk = full.copy()
+    rects = np.zeros(full.shape[:2] + (5, 3), np.float32)
+    for b, pl in enumerate(polys_list):
+        pl = np.asarray(pl, np.float32).reshape(-1, 4, 2)
+        for i, poly in enumerate(pl):
+            fit = RL.fit_rectangle(poly)
+            if fit is None:
+                ignore[b, i] = 1
+                shrunk[b, i] = _NOWHERE
+                continue
+            rect, angle = fit
+            rects[b, i, :4] = RL.rect_lines(rect)
+            rects[b, i, 4, 0] = angle
+            if shrink:
+                shrunk[b, i] = RL.shrink_poly(poly, RL.shrink_radii(poly), shrink).astype(np.int32)
+    return shrunk, full, counts, ignore, rects
+
+
+def _generate_rbox_geometry(g, im_size, polys_list, tags_list, step, min_text_size, shrink):
+    h, w = im_size
+    shrunk, full, counts, ignore, rects = pack_rbox(polys_list, tags_list, min_text_size, shrink)
+    n = len(counts)
+    dev = g.device
+    d_counts = torch.from_numpy(counts).to(dev)
+    cover_s = torch.empty((n, h, w), dtype=torch.int32, device=dev)
+    cover_f = torch.empty((n, h, w), dtype=torch.int32, device=dev)
+    ops.poly_cover(torch.from_numpy(shrunk).to(dev), d_counts, torch.zeros(ignore.shape, dtype=torch.uint8, device=dev), h, w,
+                   cover_s)
+    ops.poly_cover(torch.from_numpy(full).to(dev), d_counts, torch.from_numpy(ignore).to(dev), h, w, cover_f)
+    oh, ow = -(-h // step), -(-w // step)
+    score = torch.empty((n, oh, ow, 1), dtype=F32, device=dev)
+    geo = torch.empty((n, oh, ow, 5), dtype=F32, device=dev)
+    mask = torch.empty((n, oh, ow, 1), dtype=F32, device=dev)
+    ops.rbox_labels(cover_s, cover_f, torch.from_numpy(rects).to(dev), step, score, geo, mask)
+    return score, geo, mask
+
+
+def generate_rbox_batch(im_size, polys_list, tags_list, step=4, min_text_size=MIN_TEXT_SIZE, graph=None, geometry='link',
+                        shrink=0.3):
     """generate_rbox for every image of a batch + the generator's `[::step, ::step]` subsample and
     float casts (icdar.py:632-634).  Returns device tensors score [n,h/s,w/s,1], geo [n,h/s,w/s,8],
     training mask [n,h/s,w/s,1] (float32) — the feeds `input_score_maps`, `input_geo_maps`,
-    `input_training_masks` of multigpu_train.py:98-101."""
+    `input_training_masks` of multigpu_train.py:98-101.
+    geometry='RBOX': geo [n,h/s,w/s,5] = the distances of the image point (x step, y step) to the top, right, bottom and
+    left edge of its polygon's rectangle (image pixels) and the rectangle's angle — what `model_vgg_16.loss_rbox` takes and
+    `tool/rbox.decode` inverts; score = the polygons shrunk by `shrink` (EAST's 0.3; 0 = not shrunk), later polygons on top;
+    mask = 0 over tagged, small and degenerate polygons.  The image need not be square (`shrink` is RBOX only)."""
     g = graph or get_default_graph()
     h, w = im_size
+    if geometry == 'RBOX':
+        return _generate_rbox_geometry(g, (h, w), polys_list, tags_list, step, min_text_size, shrink)
+    if geometry != 'link':
+        raise ValueError("geometry must be 'link' or 'RBOX', got %r" % (geometry,))
     if h != w:
         raise ValueError("generate_rbox needs a square image: the reference's valid_link border rule "
                          "(icdar.py:84) indexes out of range otherwise")
@@ -160,7 +221,7 @@ def augment_images(images_u8, plans, input_size, graph=None):
 
 
 def generator(training_data_path, input_size=512, batch_size=32, graph=None, shuffle=True, seed=None,
-              num_workers=0, worker_kind=None, augment=None):
+              num_workers=0, worker_kind=None, augment=None, geometry='link'):
     """icdar.py:542-649 with the branches the reference has live (no random scale / crop: `if (0)`):
     read image + gt, validate polygons, resize to input_size x input_size, scale the polygons,
     labels at 1/4 resolution.  Yields (images [B,S,S,3] float32 RGB, image_fns, score_maps, geo_maps,
@@ -172,7 +233,10 @@ def generator(training_data_path, input_size=512, batch_size=32, graph=None, shu
     and more: the decode jobs leave the polygons in source pixels, the plan of each sample (inverse map, colour matrix,
     moved polygons) is drawn HERE, from the generator's own RandomState in sample order, so a batch does not depend on
     num_workers or worker_kind; one launch warps the whole batch (augment_images) and the labels come from the planned
-    polygons.  A sample whose plan is None (the reference's `continue`) is skipped."""
+    polygons.  A sample whose plan is None (the reference's `continue`) is skipped.
+    geometry: 'link' (the reference's maps) or 'RBOX' (generate_rbox_batch: geo_maps [B,S/4,S/4,5])."""
+    if geometry not in ('link', 'RBOX'):
+        raise ValueError("geometry must be 'link' or 'RBOX', got %r" % (geometry,))
     image_list = np.array(sorted(get_images(training_data_path)))
     print('{} training images in {}'.format(image_list.shape[0], training_data_path))
     if len(image_list) == 0:
@@ -253,7 +317,8 @@ def generator(training_data_path, input_size=512, batch_size=32, graph=None, shu
                     for sl in slots:
                         if dpool is not None:
                             dpool.release(sl)
-                    score, geo, mask = generate_rbox_batch((input_size, input_size), polys_l, tags_l, graph=graph)
+                    score, geo, mask = generate_rbox_batch((input_size, input_size), polys_l, tags_l, graph=graph,
+                                                           geometry=geometry)
                     produced = True
                     yield images, fns, score, geo, mask
                     ims, fns, polys_l, tags_l, slots = [], [], [], [], []
@@ -273,7 +338,8 @@ def generator(training_data_path, input_size=512, batch_size=32, graph=None, shu
 def get_batch(num_workers=0, device_prefetch=2, **kwargs):
     """icdar.py:652-668: background producer + queue.  Host decode/parsing runs in `num_workers`
     threads; upload, resize and label kernels run on the feeder's own HIP stream
-    (feeder.DeviceFeeder), `device_prefetch` batches ahead of the training step."""
+    (feeder.DeviceFeeder), `device_prefetch` batches ahead of the training step.  The generator's keywords pass
+    through (`geometry='RBOX'` among them)."""
     from ..feeder import DeviceFeeder
     graph = kwargs.get("graph") or get_default_graph()
     return DeviceFeeder(lambda: generator(num_workers=num_workers, **kwargs), graph.device, depth=device_prefetch)

@@ -1105,6 +1105,16 @@ def rbox_decode(score, geo, n, h, w, score_thresh, scale, boxes, counts, total, 
            c_int(max_k), ptr(boxes), ptr(counts), ptr(total), ptr(buf), c_size_t(nbytes), _st())
 
 
+def quad_mean_score(quads, score, inv_scale, mean):
+    """quads f32 [k,8] (image px), score f32 [h,w] -> mean f32 [k]: the score's mean over the fillPoly raster of each quad's
+    vertices floor(trunc(coord) * inv_scale); 0 for an empty raster."""
+    k = quads.shape[0]
+    h, w = score.shape
+    if quads.numel() != 8 * k or mean.numel() != k or not (quads.is_contiguous() and score.is_contiguous()):
+        raise ValueError("quad_mean_score: quads [k,8], score [h,w], mean [k], contiguous")
+    L.call("ocr_quad_mean_score", ptr(quads), c_int(k), ptr(score), c_int(h), c_int(w), c_float(inv_scale), ptr(mean), _st())
+
+
 def min_area_rects(labels, ncomp, max_comps, scale_x, scale_y, hull_n, hull_head, calipers, ws):
     n, h, w = labels.shape
     nbytes = L.call_size("ocr_min_area_rects_workspace", c_int(n), c_int(h), c_int(w), c_int(max_comps))
@@ -1157,6 +1167,18 @@ def icdar_labels(cover, step, score, geo, mask):
     n, h, w = cover.shape
     L.call("ocr_icdar_labels", ptr(cover), c_int(n), c_int(h), c_int(w), c_int(step), ptr(score), ptr(geo),
            ptr(mask), _st())
+
+
+def rbox_labels(cover_score, cover_full, rects, step, score, geo, mask):
+    """Two cover maps [n,h,w] (shrunk / full polygons) + rects f32 [n,P,5,3] -> score, geo [..,5], mask at every step-th pixel."""
+    n, h, w = cover_score.shape
+    P = rects.shape[1]
+    oh, ow = -(-h // max(step, 1)), -(-w // max(step, 1))
+    if tuple(cover_full.shape) != (n, h, w) or tuple(rects.shape) != (n, P, 5, 3) or score.numel() != n * oh * ow or \
+            geo.numel() != 5 * n * oh * ow or mask.numel() != n * oh * ow:
+        raise ValueError("rbox_labels: tensors do not match n, h, w, step, max_polys")
+    L.call("ocr_icdar_rbox_labels", ptr(cover_score), ptr(cover_full), ptr(rects), c_int(n), c_int(P), c_int(h), c_int(w),
+           c_int(step), ptr(score), ptr(geo), ptr(mask), _st())
 
 
 def pixellink_labels(cover, new_h, new_w, score, link):

@@ -29,8 +29,8 @@ def make_batch(rng, n, size, rects=8):
 
 
 def rbox_labels(n, size, rng, rects=3):
-    """EAST RBOX label maps at 1/4 resolution for tests and smoke training (NOT the reference's generate_rbox: labels
-    from ICDAR polygons are a follow-up): per image `rects` random rotated rectangles, later ones on top.  Returns
+    """EAST RBOX label maps at 1/4 resolution for tests and smoke training (NOT labels from ICDAR polygons: those
+    are datasets/icdar.generate_rbox_batch(geometry='RBOX'), in the same convention): per image `rects` random rotated rectangles, later ones on top.  Returns
     (score [n,q,q,1], geo [n,q,q,5], mask [n,q,q,1]) float32 with q = size // 4: inside a rectangle score = 1 and geo =
     (distance to its top, right, bottom, left edge in IMAGE pixels, its angle in (-pi/4, pi/4)), zeros outside; mask = 1.
     Map cell (x, y) stands for image point (4x, 4y); the rectangle's right-pointing axis is (cos a, -sin a) with y down,

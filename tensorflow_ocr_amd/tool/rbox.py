@@ -3,8 +3,9 @@ datasets/icdar.py:410-483 `restore_rectangle_rbox`) chained into locality-aware 
 
 Two deliberate deviations from the reference's NumPy routine: the quads stay in RASTER order (the reference returns the
 theta >= 0 rows before the theta < 0 rows; LANMS needs raster order) and the whole chain runs on the device with one
-host synchronisation at its end.  Not here (follow-ups): the post-NMS mean-score filter over each quad's raster, and RBOX
-ground-truth maps from ICDAR polygons."""
+host synchronisation at its end.  `detect(box_thresh=...)` adds the filter EAST's eval script applies after the NMS: a
+kept quad stays when the mean of the score map over its raster is above the threshold (ocr_quad_mean_score).  The RBOX
+ground-truth maps are datasets/icdar.generate_rbox_batch(geometry='RBOX')."""
 import numpy as np
 import torch
 
@@ -50,19 +51,46 @@ def decode(score_map, geo_map, score_map_thresh=0.8, scale=4.0, max_k=None, grap
     return boxes, counts, total
 
 
-def detect(score_map, geo_map, score_map_thresh=0.8, nms_thres=0.2, max_k=None, graph=None):
+def quad_mean_scores(quads, valid, score, graph=None):
+    """quads f32 [n,k,8] (image px), valid bool [n,k], score f32 [n,h,w], all on the device -> f32 [n,k]: per valid quad the
+    mean of its image's score map over the fillPoly raster of `quad.astype(np.int32) // 4`; 0 for the others (their rows
+    are handed to the kernel as NaN, which it answers without rasterising).  One launch per image, no host sync."""
+    g = graph or get_default_graph()
+    n, k, _ = quads.shape
+    q = torch.where(valid[..., None], quads, torch.full((), float("nan"), dtype=F32, device=g.device)).contiguous()
+    means = torch.empty((n, k), dtype=F32, device=g.device)
+    for i in range(n):
+        ops.quad_mean_score(q[i], score[i], 0.25, means[i])
+    return means
+
+
+def detect(score_map, geo_map, score_map_thresh=0.8, nms_thres=0.2, max_k=None, graph=None, box_thresh=None):
     """decode + lanms.lanms_batch on the device, one synchronisation at the end.  Returns one [m, 9] array of kept quads
     (merged coordinates, summed scores) per image.  Raises ValueError when an image selects more than max_k pixels:
-    candidates are never dropped silently."""
+    candidates are never dropped silently.  box_thresh: None = no filter; a number = only the kept quads whose mean
+    score over their raster (quad_mean_scores) is STRICTLY above it, EAST's `box_thresh` (0.1 there); the means are
+    computed on the device in front of the same single synchronisation."""
     g = graph or get_default_graph()
     boxes, counts, total = decode(score_map, geo_map, score_map_thresh, 4.0, max_k, graph=g)
     if boxes.shape[1] > LANMS_MAX_K:
         raise ValueError("max_k %d is beyond the %d quads per image LANMS accepts" % (boxes.shape[1], LANMS_MAX_K))
     merged, _, keep, n_keep = lanms.lanms_batch(boxes, counts, nms_thres, graph=g)
+    passed = None
+    if box_thresh is not None:
+        score, _, n, h, w = _maps(g, score_map, geo_map)
+        k = boxes.shape[1]
+        valid = torch.arange(k, device=g.device)[None, :] < n_keep[:, None]
+        idx = torch.where(valid, keep, torch.zeros_like(keep)).long().clamp_(0, k - 1)
+        kept = torch.gather(merged[..., :8], 1, idx[..., None].expand(-1, -1, 8))
+        passed = valid & (quad_mean_scores(kept, valid, score.reshape(n, h, w), graph=g) > float(box_thresh))
     total_h = total.cpu().numpy()                               # the single sync: everything below is already computed
     if (total_h > boxes.shape[1]).any():
         raise ValueError("%s pixels above the threshold, max_k = %d: raise max_k or the threshold"
                          % (total_h.tolist(), boxes.shape[1]))
     n_keep_h = n_keep.cpu().numpy()
     merged_h, keep_h = merged.cpu().numpy(), keep.cpu().numpy()
-    return [merged_h[i][keep_h[i, :n_keep_h[i]]] for i in range(len(total_h))]
+    out = [merged_h[i][keep_h[i, :n_keep_h[i]]] for i in range(len(total_h))]
+    if passed is not None:
+        passed_h = passed.cpu().numpy()
+        out = [q[passed_h[i, :n_keep_h[i]]] for i, q in enumerate(out)]
+    return out

@@ -42,6 +42,8 @@ def parse(argv=None):
                     "per pixel into quads and merged by locality-aware NMS on the device (tool/rbox.detect)")
     ap.add_argument('--text_scale', type=int, default=512, help="RBOX only: the distance scale of the geometry head "
                     "(the reference's nets/model.py flag)")
+    ap.add_argument('--box_thresh', type=float, default=None, help="RBOX only: after the NMS keep only the quads whose mean "
+                    "score over their raster is above this (EAST's eval.py uses 0.1).  Default: no filter")
     return ap.parse_args(argv)
 
 
@@ -155,7 +157,7 @@ def _restore(FLAGS, g):
 
 def main_rbox(FLAGS):
     """--geometry RBOX: model_rbox -> per-pixel quads -> locality-aware NMS, all on the device; the kept quads, divided
-    by the resize ratios and truncated to integers, in the res_<name>.txt format of the link path.  Not here: the
+    by the resize ratios and truncated to integers, in the res_<name>.txt format of the link path.  --box_thresh adds the
     mean-score filter over each quad's raster that EAST's eval script applies after the NMS."""
     from tensorflow_ocr_amd.datasets import icdar
     from tensorflow_ocr_amd.graph import Graph
@@ -181,7 +183,7 @@ def main_rbox(FLAGS):
             restored = True
         torch.cuda.synchronize()
         print('net time:' + str((time.time() - start_time) * 1000) + 'ms')
-        quads = rbox.detect(f_score, f_geometry, graph=g)[0]
+        quads = rbox.detect(f_score, f_geometry, graph=g, box_thresh=FLAGS.box_thresh)[0]
         res_file = os.path.join(FLAGS.output_dir, 'res_{}.txt'.format(os.path.basename(im_fn).split('.')[0]))
         with open(res_file, 'w') as f:
             for q in quads:
