@@ -114,22 +114,21 @@ still shows the final rounding, up to 0.999 of u |ref|; 0.000 = the stored value
 """
 import ctypes
 import zlib
+from functools import partial
 from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
 import torch
 
+import matrix_support
+from matrix_support import (DB, F16, FL, I64, INVALID_ARG, OK, SZ, TINY, U16, U32, UNSUPPORTED, WORKSPACE, Guard, _bits_equal,
+                            _d32, _dev, _exact32, _h, _ratio, _rc, _rng, f32, f64)
 from oracle import ocr_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-OK, INVALID_ARG, UNSUPPORTED, WORKSPACE = 0, -1, -2, -4
-F16 = O.STORAGE == torch.float16
-U16 = 2.0 ** -11 if F16 else 2.0 ** -8
-TINY = 2.0 ** -24 if F16 else 2.0 ** -133
-U32 = 2.0 ** -24
-f32, f64 = np.float32, np.float64
+_note = partial(matrix_support._note, "bn_pool")
 
 # name: ([shapes (n, h, w, c)], storage-grid scale/shift)
 ROWS = {
@@ -155,21 +154,10 @@ BATCH_C = [1, 3, 18, 32]
 N_TESTS = (2 * len(BATCH_C) + 8 + 1 + 2 * len(FIN_SHAPES) + 3 + 2 * len(SMALL) + 1 + 2 * len(ROWS) + 2 * 3 + 2 * len(BWD_ROWS)
            + 2 * 3 * len(GUEST_ROWS) + 2 * len(POOL_CASES) + 1)
 
-BAND = 512
 _CACHE = {}
 
 
 # ------------------------------------------------------------------------------------------------ host helpers
-def _h(a):
-    """round to the library's 16-bit storage type"""
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=f32)).to(O.STORAGE).float().numpy()
-
-
-def _z(a):
-    """bit pattern with a zero's sign dropped"""
-    return (np.asarray(a, f32) + f32(0)).view(np.int32)
-
-
 def red_rows(T):
     if T <= 1024:
         return (T + 63) // 64 * 64
@@ -179,24 +167,6 @@ def red_rows(T):
 def bwd_blocks(units, c):
     lanes = 256 // (c // 8)
     return min((units + lanes - 1) // lanes, 2048)
-
-
-def _note(entry, row, ratio):
-    print("bn_pool %s %s ratio=%.3f" % (entry, row, ratio))
-    assert ratio <= 1.0, (entry, row, ratio)
-
-
-def _ratio(err, bound, skip=None):
-    with np.errstate(divide="ignore", invalid="ignore"):
-        r = np.where(bound > 0, err / bound, np.where(err == 0, 0.0, np.inf))
-    if skip is not None:
-        r = np.where(skip, 0.0, r)
-    assert np.isfinite(err[~skip] if skip is not None else err).all()
-    if r.size and r.max() > 1:
-        j = np.unravel_index(int(r.argmax()), r.shape)
-        print("over the bound at %s: |err| %.6g, bound %.6g (%d elements over)" % (j, float(np.broadcast_to(err, r.shape)[j]),
-                                                                                  float(np.broadcast_to(bound, r.shape)[j]), int((r > 1).sum())))
-    return float(r.max()) if r.size else 0.0
 
 
 def _r16(got, ref, M, skip=None):
@@ -220,71 +190,7 @@ def _eq16(got, ref, what, skip=None):
     _bits_equal(got, _h(np.asarray(ref, f32)), what, skip)
 
 
-def _bits_equal(got, ref, what, skip=None):
-    bad = _z(got) != _z(ref)
-    if skip is not None:
-        bad &= ~skip
-    assert not bad.any(), "%s: %d elements differ, first %s" % (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-
-
 # ------------------------------------------------------------------------------------------------ device helpers
-class Guard:
-    """An output or scratch buffer carved out of a larger allocation: 0xFF-filled (NaN in every float type, 255 in
-    bytes) between two sentinel bands."""
-
-    def __init__(self, shape, dtype, device, init=None):
-        shape = tuple(int(s) for s in np.atleast_1d(shape))
-        item = torch.empty((), dtype=dtype).element_size()
-        self.nbytes = int(np.prod(shape)) * item
-        self.flat = torch.empty(2 * BAND + (self.nbytes + 15) // 16 * 16, dtype=torch.uint8, device=device)
-        self.flat.fill_(0x5E)
-        self.flat[BAND:BAND + self.nbytes].fill_(0xFF)
-        self.t = self.flat[BAND:BAND + self.nbytes].view(dtype).view(shape)
-        assert self.t.data_ptr() % 16 == 0
-        if init is not None:
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(init)).to(dtype))
-
-    def ok(self):
-        return bool((self.flat[:BAND] == 0x5E).all()) and bool((self.flat[BAND + self.nbytes:] == 0x5E).all())
-
-    def untouched(self):
-        return self.ok() and bool((self.flat[BAND:BAND + self.nbytes] == 0xFF).all())
-
-    def np(self):
-        assert self.ok(), "written outside the buffer"
-        t = self.t
-        a = (t.float() if t.dtype in (torch.float16, torch.bfloat16) else t).cpu().numpy()
-        if a.dtype.kind == "f":
-            assert np.isfinite(a).all(), "elements the kernel did not write"
-        return a
-
-
-def _dev(a, device, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=f32)).to(dtype or O.STORAGE).to(device)
-
-
-def _d32(a, device):
-    return _dev(a, device, torch.float32)
-
-
-def _a(L, v):
-    if isinstance(v, Guard):
-        return L.ptr(v.t)
-    if v is None or isinstance(v, torch.Tensor):
-        return L.ptr(v)
-    if isinstance(v, (int, np.integer)):
-        return ctypes.c_int(int(v))
-    return v
-
-
-def _rc(L, name, *args):
-    """the status of a C-ABI call, not raised; the stream is appended"""
-    return int(L._fn(name, ctypes.c_int)(*[_a(L, v) for v in args], L.stream_ptr()))
-
-
-I64, SZ, FL, DB = ctypes.c_int64, ctypes.c_size_t, ctypes.c_float, ctypes.c_double
-
-
 def _ws(L, T, c, device):
     nbytes = L.call_size("ocr_bn_reduce_workspace", ctypes.c_int(T), ctypes.c_int(c))
     rows = red_rows(T)
@@ -374,7 +280,7 @@ def _prep(row, i, kind):
     grid = True if row == "stream_cap" else ROWS[row][1]
     n, h, w, c = shape
     oh, ow = (h + 1) // 2, (w + 1) // 2
-    rng = np.random.default_rng(zlib.crc32(repr((row, i, kind)).encode()))
+    rng = _rng(row, i, kind)
     P = NS(shape=shape, n=n, h=h, w=w, c=c, oh=oh, ow=ow, kind=kind, row="%s%s" % (row, "" if i == 0 else "_b"))
     if kind == "exact":
         y = rng.integers(-32, 33, shape) / 8.0
@@ -505,7 +411,7 @@ def _coef_bounds(s, q, ds, dq, count, sc, mu, inv):
 
 
 def _fin_partials(T, C, kind, seed=0):
-    rng = np.random.default_rng(zlib.crc32(repr((T, C, kind, seed)).encode()))
+    rng = _rng(T, C, kind, seed)
     if kind == "exact":
         return (rng.integers(-32, 33, (T, 2, C)) / 8.0).astype(f32)
     mean, var = rng.standard_normal(C) * 0.5, rng.uniform(0.5, 2.0, C)
@@ -519,7 +425,7 @@ def _fin_partials_stats(T, C):
     """dyadic partials whose column sums are count * mean and count * (var + mean^2) exactly, count = 1024, mean k / 2,
     var in {0.25, 1, 4}: every closed form of bn_fin_apply<BnFin> is then exact (eps = 0, decay = 0.5) but the
     unbiased variance var * count / (count - 1)"""
-    rng = np.random.default_rng(zlib.crc32(repr((T, C, "stats")).encode()))
+    rng = _rng(T, C, "stats")
     p = rng.integers(-32, 33, (T, 2, C)) / 8.0
     mean, var, count = rng.integers(-2, 3, C) / 2.0, rng.choice([0.25, 1.0, 4.0], C), 1024.0
     p[0, 0] += count * mean - p[:, 0].sum(0)
@@ -528,12 +434,6 @@ def _fin_partials_stats(T, C):
     assert np.array_equal(p32.astype(f64), p)
     assert np.array_equal(p32[:, 0].sum(0, dtype=f64), count * mean) and np.array_equal(p32[:, 1].sum(0, dtype=f64), count * (var + mean ** 2))
     return p32, mean, var, count
-
-
-def _exact32(v):
-    v32 = np.asarray(v, f64).astype(f32)
-    assert np.array_equal(v32.astype(f64), v), "the reference itself must be exact in f32"
-    return v32
 
 
 def _check_outs(entry, row, outs, refs):
@@ -1072,7 +972,7 @@ def test_unpool(device, shape, kind):
     n, lh, lw, c = shape
     H, W = 2 * lh, 2 * lw
     exact = kind == "exact"
-    rng = np.random.default_rng(zlib.crc32(repr((shape, kind)).encode()))
+    rng = _rng(shape, kind)
     draw = (lambda s: (rng.integers(-32, 33, s) / 8.0).astype(f32)) if exact else (lambda s: _h(rng.standard_normal(s)))
     x, dy, old, yold = draw(shape), draw((n, H, W, c)), draw(shape), draw((n, H, W, c))
     worst = {}
@@ -1365,7 +1265,7 @@ def test_maxpool(device, win, parity, kind):
     n, h, w, c = shape
     exact = kind == "exact"
     name = "%s_%s" % (win, parity)
-    rng = np.random.default_rng(zlib.crc32(repr((win, parity, kind)).encode()))
+    rng = _rng(win, parity, kind)
     P = NS(shape=shape, n=n, h=h, w=w, c=c)
     if exact:
         P.y = (rng.integers(-8, 9, shape) / 2.0).astype(f32)              # few values: ties in most windows

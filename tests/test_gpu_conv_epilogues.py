@@ -27,12 +27,11 @@ Every output and partial buffer is carved out of a larger allocation with sentin
 elements on each side (what ragged tiles write outside the tensor would show there), and is pre-filled with NaN where
 the launch does not read it: the product hands these kernels uninitialised buffers, so every element and every
 partial row must be written."""
-import zlib
-
 import numpy as np
 import pytest
 import torch
 
+from matrix_support import _h, _rng, bands_untouched, carve
 from oracle import ocr_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -81,18 +80,8 @@ CASES = [(f, m) for f in FAMILIES for m in MODES if not (FAMILIES[f][1][7] != 1 
 
 Y_BAND = 16 * 32 * 256          # elements: the largest tile (16 rows x 32 columns x 256 couts)
 P_BAND = 2 * 512 * 4            # floats: four partial rows of the widest layer
-SENT16, SENT32 = 0x5EED, 0x5EEDF00D
 
 _REF = {}                       # (family, form) -> (x, w_kc, float64 convolution), computed once per shape
-
-
-def _h(x):
-    """round to the library's 16-bit storage type"""
-    return torch.from_numpy(np.asarray(x, np.float32)).to(O.STORAGE).float().numpy()
-
-
-def _seed(*key):
-    return zlib.crc32(repr(key).encode())
 
 
 def _desc(ops, shape, form, flags):
@@ -118,7 +107,7 @@ def _reference(ops, family, form):
         shape = FAMILIES[family][1]
         n, h, w, cin, cout, k, dil, stride = shape
         d = _desc(ops, shape, form, 0)
-        rng = np.random.default_rng(_seed(shape, form))
+        rng = _rng(shape, form)
         x = _h(rng.standard_normal((n, h, w, cin)))
         wk = _h(rng.standard_normal((k * k, cout, cin)) * np.sqrt(2.0 / (k * k * cin)))
         wt = torch.from_numpy(wk).double().reshape(k, k, cout, cin)
@@ -132,28 +121,6 @@ def _reference(ops, family, form):
         assert ref.shape == (n, d.oh, d.ow, cout)
         _REF[key] = (x, wk, ref)
     return _REF[key]
-
-
-def _carve(shape, dtype, band, device, fill):
-    """A tensor inside a larger flat allocation, `band` sentinel elements on each side."""
-    numel = int(np.prod(shape))
-    flat = torch.empty(2 * band + numel, dtype=dtype, device=device)
-    if dtype == torch.float32:
-        flat.view(torch.int32).fill_(SENT32)
-    else:
-        flat.view(torch.int16).fill_(SENT16)
-    t = flat[band:band + numel].view(shape)
-    assert t.data_ptr() % 16 == 0
-    if isinstance(fill, float):
-        t.fill_(fill)
-    else:
-        t.copy_(fill)
-    return flat, t
-
-
-def _bands_untouched(flat, band):
-    iv, s = (flat.view(torch.int32), SENT32) if flat.dtype == torch.float32 else (flat.view(torch.int16), SENT16)
-    return bool((iv[:band] == s).all()) and bool((iv[-band:] == s).all())
 
 
 def _bn_inputs(rng, shape_out, cout, bias_net):
@@ -180,7 +147,7 @@ def _bn_inputs(rng, shape_out, cout, bias_net):
 def bn_unsure_share(family, mode):
     """CPU only: the share of elements excluded from the exact mask comparison for the case's seed."""
     n, h, w, cin, cout, k, dil, stride = FAMILIES[family][1]
-    rng = np.random.default_rng(_seed(FAMILIES[family][1], mode))
+    rng = _rng(FAMILIES[family][1], mode)
     rng.standard_normal((n, h, w, cout))                                  # (`old` is drawn first in every case)
     unsure = _bn_inputs(rng, (n, h, w, cout), cout, mode == "H" and family == BIAS_NET_FAMILY)[6]
     return float(unsure.mean())
@@ -201,15 +168,15 @@ def test_conv_epilogue_vs_float64(device, family, mode):
     accum = bool(flags & ACCUM)
     tol = 8e-3 if bf16 else (1.5e-3 if accum else 1e-3)
 
-    rng = np.random.default_rng(_seed(shape, mode))
+    rng = _rng(shape, mode)
     old = _h(rng.standard_normal(oshape) * 0.5)
     dev16 = lambda a: torch.from_numpy(a).to(O.STORAGE).to(device)
     f32 = lambda a: torch.from_numpy(a).to(device)
     xd, wd = dev16(x), dev16(wk)
-    yflat, y = _carve(oshape, O.STORAGE, Y_BAND, device, dev16(old) if accum else float("nan"))
+    yg, y = carve(oshape, O.STORAGE, Y_BAND, device, dev16(old) if accum else float("nan"))
     want_partial = entry == "bnred" or bool(flags & STATS)
     T = ops.conv2d_num_mtiles(d)
-    pflat, part = _carve((T, 2, cout), torch.float32, P_BAND, device, float("nan"))
+    pg, part = carve((T, 2, cout), torch.float32, P_BAND, device, float("nan"))
 
     pre = conv                                                            # float64 value in front of the ReLU
     bias = None
@@ -238,7 +205,7 @@ def test_conv_epilogue_vs_float64(device, family, mode):
             with pytest.raises(OcrHipError, match=r"\(-2\)"):
                 ops.conv2d_bnred(d, xd, wd, y, part, ctx, store_masked=bool(store_masked))
             torch.cuda.synchronize()
-            assert torch.equal(y, dev16(old)) and _bands_untouched(yflat, Y_BAND) and _bands_untouched(pflat, P_BAND)
+            assert torch.equal(y, dev16(old)) and bands_untouched(yg) and bands_untouched(pg)
             print("%s %s variant %s: refused (OCR_ERR_UNSUPPORTED)" % (family, mode, variant))
             return
         ops.conv2d_bnred(d, xd, wd, y, part, ctx, store_masked=bool(store_masked))
@@ -291,8 +258,8 @@ def test_conv_epilogue_vs_float64(device, family, mode):
     else:
         assert bool(torch.isnan(part).all())                              # ... and not touched without STATS
     # 7. nothing written outside the tensors
-    assert _bands_untouched(yflat, Y_BAND), "stores outside y"
-    assert _bands_untouched(pflat, P_BAND), "stores outside the partial rows"
+    assert bands_untouched(yg), "stores outside y"
+    assert bands_untouched(pg), "stores outside the partial rows"
     # 1. the stored tensor
     assert e_y < tol, (e_y, tol)
     assert masked_exact, "masked store: non-zero values where the ReLU mask is false"

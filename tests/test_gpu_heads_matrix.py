@@ -103,52 +103,25 @@ still shows its final rounding, up to 0.999 of u |ref|: the two dgrad lines)
   chunked float64 product on the host.
 """
 import ctypes
-import zlib
+from functools import partial
 from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
 import torch
 
+import matrix_support
+from matrix_support import (FL, I64, INVALID_ARG, OK, SZ, TINY, U16, UNSUPPORTED, WORKSPACE, Guard, Strided, _bits_equal,
+                            _cdiv, _d32, _dev, _exact32, _g, _h, _items, _lib, _ratio, _rc, _rng, f32, f64)
 from oracle import ocr_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-OK, INVALID_ARG, UNSUPPORTED, WORKSPACE = 0, -1, -2, -4
-F16 = O.STORAGE == torch.float16
-U16 = 2.0 ** -11 if F16 else 2.0 ** -8
-TINY = 2.0 ** -24 if F16 else 2.0 ** -133
-U32 = 2.0 ** -24
-f32, f64 = np.float32, np.float64
 KINDS = ("exact", "random")
-BAND = 512
-SENT = f32(-12345.5)
-SZ, FL, I64 = ctypes.c_size_t, ctypes.c_float, ctypes.c_int64
+_note = partial(matrix_support._note, "heads")
 
 
 # ------------------------------------------------------------------------------------------------ host helpers
-def _h(a):
-    """round to the library's 16-bit storage type"""
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=f32)).to(O.STORAGE).float().numpy()
-
-
-def _z(a):
-    return (np.asarray(a, f32) + f32(0)).view(np.int32)
-
-
-def _g(m):
-    m = np.asarray(m, f64)
-    return m * U32 / (1.0 - m * U32)
-
-
-def _cdiv(a, b):
-    return -(-a // b)
-
-
-def _rng(*key):
-    return np.random.default_rng(zlib.crc32(repr(key).encode()))
-
-
 def _draw(rng, shape, kind, sd=1.0, grid=False):
     if kind == "exact":
         return (rng.integers(-32, 33, shape) / 8.0).astype(f32)
@@ -160,37 +133,6 @@ def _pow2(rng, shape, kind, lo=0.5, hi=1.5):
     if kind == "exact":
         return rng.choice([0.5, 1.0, 2.0], shape).astype(f32)
     return rng.uniform(lo, hi, shape).astype(f32)
-
-
-def _exact32(v):
-    v32 = np.asarray(v, f64).astype(f32)
-    assert np.array_equal(v32.astype(f64), np.asarray(v, f64)), "the reference itself must be exact in f32"
-    return v32
-
-
-def _bits_equal(got, ref, what, skip=None):
-    bad = _z(got) != _z(ref)
-    if skip is not None:
-        bad &= ~skip
-    assert not bad.any(), "%s: %d elements differ, first %s" % (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-
-
-def _ratio(err, bound, skip=None):
-    err, bound = np.broadcast_arrays(np.asarray(err, f64), np.asarray(bound, f64))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        r = np.where(bound > 0, err / bound, np.where(err == 0, 0.0, np.inf))
-    if skip is not None:
-        r = np.where(skip, 0.0, r)
-    assert not np.isnan(r).any()
-    if r.size and r.max() > 1:
-        j = np.unravel_index(int(r.argmax()), r.shape)
-        print("over the bound at %s: |err| %.6g, bound %.6g (%d elements over)" % (j, float(err[j]), float(bound[j]), int((r > 1).sum())))
-    return float(r.max()) if r.size else 0.0
-
-
-def _note(entry, row, ratio):
-    print("heads %s %s ratio=%.3f" % (entry, row, ratio))
-    assert ratio <= 1.0, (entry, row, ratio)
 
 
 def _c32(entry, row, got, ref, m, S, kind, skip=None):
@@ -211,105 +153,6 @@ def _c16(entry, row, got, ref, m, S, kind):
         return _note(entry, row + "_exact", 0.0)
     assert np.isfinite(got).all()
     _note(entry, row, _ratio(np.abs(got.astype(f64) - ref), U16 * np.abs(ref) + _g(m) * np.asarray(S, f64) + TINY))
-
-
-# ------------------------------------------------------------------------------------------------ device helpers
-class Guard:
-    """An output or scratch buffer carved out of a larger allocation: 0xFF-filled (NaN in every float type) between two
-    sentinel bands."""
-
-    def __init__(self, shape, dtype, device, init=None):
-        shape = tuple(int(s) for s in np.atleast_1d(shape))
-        item = torch.empty((), dtype=dtype).element_size()
-        self.nbytes = int(np.prod(shape)) * item
-        self.flat = torch.empty(2 * BAND + (self.nbytes + 15) // 16 * 16, dtype=torch.uint8, device=device)
-        self.flat.fill_(0x5E)
-        self.flat[BAND:BAND + self.nbytes].fill_(0xFF)
-        self.t = self.flat[BAND:BAND + self.nbytes].view(dtype).view(shape)
-        assert self.t.data_ptr() % 16 == 0
-        if init is not None:
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(init)).to(dtype))
-
-    def ok(self):
-        return bool((self.flat[:BAND] == 0x5E).all()) and bool((self.flat[BAND + self.nbytes:] == 0x5E).all())
-
-    def untouched(self):
-        return self.ok() and bool((self.flat[BAND:BAND + self.nbytes] == 0xFF).all())
-
-    def raw(self):
-        assert self.ok(), "written outside the buffer"
-        t = self.t
-        return (t.float() if t.dtype in (torch.float16, torch.bfloat16) else t).cpu().numpy()
-
-    def np(self):
-        a = self.raw()
-        if a.dtype.kind == "f":
-            assert not np.isnan(a).any(), "elements the kernel did not write"
-        return a
-
-
-class Strided:
-    """[P][ld] f32 with the live columns [off, off + width) NaN (an output) or data (an input) and every other column a
-    sentinel that must come back bit for bit."""
-
-    def __init__(self, P, ld, off, width, device, data=None):
-        self.P, self.ld, self.off, self.width = P, ld, off, width
-        host = np.full((P, ld), SENT, f32)
-        host[:, off:off + width] = np.nan if data is None else data
-        self.host = host
-        self.g = Guard((P, ld), torch.float32, device, host)
-
-    def np(self):
-        a = self.g.raw()
-        live = np.zeros(self.ld, bool)
-        live[self.off:self.off + self.width] = True
-        assert np.array_equal(a[:, ~live].view(np.int32), self.host[:, ~live].view(np.int32)), "sentinel columns written"
-        out = a[:, live]
-        assert not np.isnan(out).any(), "elements the kernel did not write"
-        return out
-
-
-def _dev(a, device, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=f32)).to(dtype or O.STORAGE).to(device)
-
-
-def _d32(a, device):
-    return _dev(a, device, torch.float32)
-
-
-def _a(L, v):
-    if isinstance(v, Strided):
-        v = v.g
-    if isinstance(v, Guard):
-        return L.ptr(v.t)
-    if v is None or isinstance(v, torch.Tensor):
-        return L.ptr(v)
-    if isinstance(v, (int, np.integer)):
-        return ctypes.c_int(int(v))
-    return v
-
-
-def _rc(L, name, *args):
-    """the status of a C-ABI call, not raised; the stream is appended"""
-    return int(L._fn(name, ctypes.c_int)(*[_a(L, v) for v in args], L.stream_ptr()))
-
-
-def _p(v):
-    if isinstance(v, Strided):
-        v = v.g
-    if isinstance(v, Guard):
-        v = v.t
-    return None if v is None else v.data_ptr()
-
-
-def _items(cls, rows):
-    return (cls * max(len(rows), 1))(*[cls(*[_p(v) if not isinstance(v, (int, np.integer)) else int(v) for v in r]) for r in rows])
-
-
-def _lib():
-    from tensorflow_ocr_amd import _lib as L
-    from tensorflow_ocr_amd import ops
-    return L, ops
 
 
 # ------------------------------------------------------------------------------------------------ packed weights

@@ -80,20 +80,19 @@ Out of scope: ocr_conv2d_bnred_first_f16, ocr_conv2d_bnred_first_wgrad_f16 and o
 the 64-channel persistent igemm kernel, not in these two files (their tests: test_gpu_layers.py); ocr_conv2d_stem_f16
 requires y — it has no statistics-only form (asserted: INVALID_ARG)."""
 import ctypes
-import zlib
 
 import numpy as np
 import pytest
 import torch
 
+from matrix_support import (BF16, INVALID_ARG, OK, UNSUPPORTED, WORKSPACE, _h, _rng, _seed, bands_untouched, carve, untouched,
+                            written)
 from oracle import ocr_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-OK, INVALID_ARG, UNSUPPORTED, WORKSPACE = 0, -1, -2, -4
 BIAS, RELU, STATS = 1, 2, 4
 FLAG_MODES = (0, BIAS, BIAS | RELU, STATS, BIAS | RELU | STATS)
-BF16 = O.STORAGE == torch.bfloat16
 RELU_TIE = 2.0 ** -134 if BF16 else 2.0 ** -25          # OCR_RELU_TIE (csrc/common.h)
 GEOM = {"first": (3, 1, 1), "stem": (7, 2, 3)}          # kernel extent, stride, padding
 # kind -> row -> ((n, h, w, cout), tiles)
@@ -111,8 +110,6 @@ SEED_SEARCHED = 20000           # elements: the fused rows whose seed is searche
 N_TESTS = 3 * len(CASES) + len(ROWS["first"]) + len(MOMENT_ROWS) + 2 * len(IMPULSE) + 4 + 2
 
 WG_CAP, MOMENT_CAP = 512, 1024  # wgrad_blocks / stem_blocks, FM_WGS
-SENT16, SENT32 = 0x5EED, 0x5EEDF00D
-NAN16, NAN32 = 0x7FBE, 0x7FC0BEEF      # quiet NaNs with a payload in f16, bf16, f32 and (twice NAN32) f64
 WGRAD_BAR = 5e-6
 # the cap rows' dy: chosen on the CPU per storage type (see _operands); sequential f32 sum / bar with these seeds:
 # first 0.91 (f16) 0.62 (bf16), stem 0.99 (f16) 0.84 (bf16)
@@ -121,15 +118,6 @@ Y_TOL = 8e-3 if BF16 else 1e-3
 A_TOL = 8e-3 if BF16 else 1.5e-3
 
 _REF = {}
-
-
-def _h(a):
-    """round to the library's 16-bit storage type"""
-    return torch.from_numpy(np.array(a, np.float32)).to(O.STORAGE).float().numpy()
-
-
-def _seed(*key):
-    return zlib.crc32(repr(key).encode())
 
 
 def _out(kind, h, w):
@@ -174,7 +162,7 @@ def _operands(kind, row):
     if key not in _REF:
         (n, h, w, cout), _ = ROWS[kind][row]
         k = GEOM[kind][0]
-        rng = np.random.default_rng(_seed(kind, row))
+        rng = _rng(kind, row)
         x = _h(rng.integers(0, 256, (n, h, w, 3)) - np.array([123.68, 116.78, 103.94]))
         wt = _h(rng.standard_normal((k, k, 3, cout)) * np.sqrt(2.0 / (k * k * 3)) / 64.0)
         conv = _conv_float64(kind, x, wt)
@@ -184,7 +172,7 @@ def _operands(kind, row):
             # max|ref| over seeds, whatever the distribution; the kernels, which sum by tiles, are at 1e-7): dy has
             # zero mean per channel and a seed chosen on the CPU so that it does (asserted in
             # test_plain_wgrad_vs_float64)
-            dy = np.random.default_rng(_seed(kind, "cap", "dy", CAP_DY_SEED[kind])).standard_normal(conv.shape) * 0.25
+            dy = _rng(kind, "cap", "dy", CAP_DY_SEED[kind]).standard_normal(conv.shape) * 0.25
             dy -= dy.mean((0, 1, 2))
         dy = _h(dy)
         _REF[key] = dict(x=x, w=wt, conv=conv, dy=dy, dw=_dw_float64(kind, x, dy))
@@ -194,44 +182,6 @@ def _operands(kind, row):
 
 
 # ---------------------------------------------------------------------------------------------------- device side
-def _fill(t, f16, f32):
-    if t.dtype in (torch.float32, torch.float64):
-        t.view(torch.int32).fill_(f32)
-    else:
-        t.view(torch.int16).fill_(f16)
-
-
-def _carve(shape, dtype, device, band):
-    """A NaN-filled tensor inside a larger flat allocation, `band` sentinel elements on each side."""
-    numel = int(np.prod(shape))
-    flat = torch.empty(2 * band + numel, dtype=dtype, device=device)
-    _fill(flat, SENT16, SENT32)
-    t = flat[band:band + numel]
-    assert t.data_ptr() % 16 == 0
-    _fill(t, NAN16, NAN32)
-    return (flat, band), t.view(shape)
-
-
-def _bands_untouched(guard):
-    flat, band = guard
-    if flat.dtype in (torch.float32, torch.float64):
-        iv, s = flat.view(torch.int32), SENT32
-        band *= flat.element_size() // 4
-    else:
-        iv, s = flat.view(torch.int16), SENT16
-    return bool((iv[:band] == s).all()) and bool((iv[-band:] == s).all())
-
-
-def _untouched(t):
-    if t.dtype in (torch.float32, torch.float64):
-        return bool((t.reshape(-1).view(torch.int32) == NAN32).all())
-    return bool((t.reshape(-1).view(torch.int16) == NAN16).all())
-
-
-def _written(t):
-    return not bool(torch.isnan(t.reshape(-1).float()).any())
-
-
 def _dev16(a, device):
     return torch.from_numpy(np.array(a, np.float32)).to(O.STORAGE).to(device)
 
@@ -286,7 +236,7 @@ def _pack(kind, wt, device):
     from tensorflow_ocr_amd import _lib as L
     cout = wt.shape[-1]
     shape = (3, cout, 16) if kind == "first" else (7, 2, cout, 16)
-    guard, wp = _carve(shape, O.STORAGE, device, 1024)
+    guard, wp = carve(shape, O.STORAGE, 1024, device)
     wd = torch.from_numpy(np.array(wt, np.float32)).to(device)
     rc = L._fn("ocr_pack_weights_%s_f16" % kind, ctypes.c_int)(L.ptr(wd), ctypes.c_int(cout), L.ptr(wp), L.stream_ptr())
     assert rc == OK
@@ -334,11 +284,11 @@ def _packed_numpy(kind, wt):
 @pytest.mark.parametrize("kind,cout", [("first", 64), ("first", 128), ("stem", 64), ("stem", 128)])
 def test_packers_exact_layout(device, kind, cout):
     k = GEOM[kind][0]
-    wt = np.random.default_rng(_seed("pack", kind, cout)).standard_normal((k, k, 3, cout)).astype(np.float32)
+    wt = _rng("pack", kind, cout).standard_normal((k, k, 3, cout)).astype(np.float32)
     guard, wp = _pack(kind, wt, device)
     torch.cuda.synchronize()
     want = torch.from_numpy(_packed_numpy(kind, wt)).to(O.STORAGE)
-    assert _written(wp) and _bands_untouched(guard)
+    assert written(wp) and bands_untouched(guard)
     assert torch.equal(wp.cpu().view(torch.int16), want.view(torch.int16))          # +0 in every zero slot as well
 
 
@@ -347,18 +297,18 @@ def _check_forward(kind, v, x, wt, conv, oshape, tiles, device, tag):
     """Every flag mode of the forward entry on one shape; returns the largest error of y."""
     n, oh, ow, cout = oshape
     name = "ocr_conv2d_%s_f16" % kind
-    rng = np.random.default_rng(_seed("bias", tag))
+    rng = _rng("bias", tag)
     bias = rng.standard_normal(cout).astype(np.float32)
     bd = torch.from_numpy(bias).to(device)
     worst = 0.0
     for flags in FLAG_MODES:
-        yg, y = _carve(oshape, O.STORAGE, device, 8 * 32 * cout)
-        pg, part = _carve((tiles, 2, cout), torch.float32, device, 2 * cout)
+        yg, y = carve(oshape, O.STORAGE, 8 * 32 * cout, device)
+        pg, part = carve((tiles, 2, cout), torch.float32, 2 * cout, device)
         assert _call(name, v, flags=flags, bias=bd if flags & BIAS else None, y=y,
                      stats=part if flags & STATS else None) == OK
         torch.cuda.synchronize()
-        assert _written(y), "%s flags %d: elements of y not written" % (tag, flags)
-        assert _bands_untouched(yg) and _bands_untouched(pg), "%s flags %d: stores outside a buffer" % (tag, flags)
+        assert written(y), "%s flags %d: elements of y not written" % (tag, flags)
+        assert bands_untouched(yg) and bands_untouched(pg), "%s flags %d: stores outside a buffer" % (tag, flags)
         pre = conv + bias.astype(np.float64) if flags & BIAS else conv
         ref = np.maximum(pre, 0.0) if flags & RELU else pre
         got = y.float().cpu().numpy().astype(np.float64)
@@ -369,17 +319,17 @@ def _check_forward(kind, v, x, wt, conv, oshape, tiles, device, tag):
         if flags & RELU:
             assert (got >= 0).all() and (got[pre < -Y_TOL * m] == 0).all() and (got[pre > Y_TOL * m] > 0).all()
         if not flags & STATS:
-            assert _untouched(part)
+            assert untouched(part)
             continue
-        assert _written(part), "%s flags %d: partial rows not written" % (tag, flags)
+        assert written(part), "%s flags %d: partial rows not written" % (tag, flags)
         sums = part.double().sum(0).cpu().numpy()
         assert np.allclose(sums[0], got.sum((0, 1, 2)), rtol=1e-4, atol=1e-2), (tag, flags)
         assert np.allclose(sums[1], (got * got).sum((0, 1, 2)), rtol=1e-4), (tag, flags)
         if kind == "first":                               # y = NULL: the same partial rows, bit for bit, nothing stored
-            p2g, part2 = _carve((tiles, 2, cout), torch.float32, device, 2 * cout)
+            p2g, part2 = carve((tiles, 2, cout), torch.float32, 2 * cout, device)
             assert _call(name, v, flags=flags, bias=bd if flags & BIAS else None, y=None, stats=part2) == OK
             torch.cuda.synchronize()
-            assert torch.equal(part2.view(torch.int32), part.view(torch.int32)) and _bands_untouched(p2g)
+            assert torch.equal(part2.view(torch.int32), part.view(torch.int32)) and bands_untouched(p2g)
     return worst
 
 
@@ -394,13 +344,13 @@ def test_first_forward_on_prepared_images(device):
     """ocr_prep_images_f16's own output ([n,h,w,4], channel 3 zero) through the same forward check."""
     from tensorflow_ocr_amd import _lib as L
     n, h, w, cout = 2, 20, 45, 64
-    rng = np.random.default_rng(_seed("prep"))
+    rng = _rng("prep")
     img = torch.from_numpy(rng.uniform(0, 255, (n, h, w, 3)).astype(np.float32)).to(device)
-    xg, x4 = _carve((n, h, w, 4), O.STORAGE, device, 1024)
+    xg, x4 = carve((n, h, w, 4), O.STORAGE, 1024, device)
     L.call("ocr_prep_images_f16", L.ptr(img), ctypes.c_int64(n * h * w), ctypes.c_float(123.68), ctypes.c_float(116.78),
            ctypes.c_float(103.94), L.ptr(x4), L.stream_ptr())
     torch.cuda.synchronize()
-    assert _written(x4) and _bands_untouched(xg)
+    assert written(x4) and bands_untouched(xg)
     xh = x4.float().cpu().numpy()
     assert (xh[..., 3] == 0).all()
     want = img.cpu().numpy().astype(np.float64) - np.array([123.68, 116.78, 103.94], np.float32).astype(np.float64)
@@ -419,21 +369,21 @@ def test_first_bn_relu_vs_float64_and_the_elementwise_pass(device, row):
     from tensorflow_ocr_amd import ops
     v, ref, oshape, tiles = _row_setup("first", row, device)
     cout = oshape[-1]
-    rng = np.random.default_rng(_seed("bnrelu", row))
+    rng = _rng("bnrelu", row)
     scale = (rng.uniform(0.5, 1.5, cout) * rng.choice([-1.0, 1.0], cout, p=[0.1, 0.9])).astype(np.float32)
     shift = rng.normal(0, 0.3, cout).astype(np.float32)
     assert (scale < 0).any()
     sd, hd = torch.from_numpy(scale).to(device), torch.from_numpy(shift).to(device)
-    yg, y = _carve(oshape, O.STORAGE, device, 8 * 32 * cout)
+    yg, y = carve(oshape, O.STORAGE, 8 * 32 * cout, device)
     assert _call("ocr_conv2d_first_f16", v, y=y, bias=None, stats=None) == OK
     y16 = _h(ref["conv"]).astype(np.float64)               # the value the first pass stores, from the reference
     for relu in (1, 0):
-        ag, a = _carve(oshape, O.STORAGE, device, 8 * 32 * cout)
+        ag, a = carve(oshape, O.STORAGE, 8 * 32 * cout, device)
         assert _call("ocr_conv2d_first_bn_relu_f16", v, scale=sd, shift=hd, relu=relu, y=a) == OK
-        eg, a_el = _carve(oshape, O.STORAGE, device, 8 * 32 * cout)
+        eg, a_el = carve(oshape, O.STORAGE, 8 * 32 * cout, device)
         ops.bn_relu(y, sd, hd, bool(relu), 0, a_full=a_el)
         torch.cuda.synchronize()
-        assert _written(a) and _bands_untouched(ag) and _bands_untouched(yg) and _bands_untouched(eg)
+        assert written(a) and bands_untouched(ag) and bands_untouched(yg) and bands_untouched(eg)
         want = y16 * scale.astype(np.float64) + shift.astype(np.float64)
         if relu:
             want = np.maximum(want, 0.0)
@@ -454,8 +404,8 @@ def _wgrad_buffers(kind, v, device):
     # (_run_wgrad) holds only if the workspace is exactly the rows the kernel stores; a change of the partial layout
     # has to change this line with it
     assert nbytes == blocks * 2 * elems * 4
-    wg, ws = _carve((nbytes // 4,), torch.float32, device, elems)
-    dg, dw = _carve((k, k, 3, v["cout"]), torch.float32, device, elems)
+    wg, ws = carve((nbytes // 4,), torch.float32, elems, device)
+    dg, dw = carve((k, k, 3, v["cout"]), torch.float32, elems, device)
     return wg, ws, dg, dw, nbytes
 
 
@@ -463,9 +413,9 @@ def _run_wgrad(name, kind, v, device, **operands):
     wg, ws, dg, dw, nbytes = _wgrad_buffers(kind, v, device)
     assert _call(name, v, dw=dw, ws=ws, ws_bytes=nbytes, **operands) == OK
     torch.cuda.synchronize()
-    assert _written(ws), "%s: workspace elements the kernel did not write" % name
+    assert written(ws), "%s: workspace elements the kernel did not write" % name
     assert bool(torch.isfinite(ws).all()) and bool(torch.isfinite(dw).all())
-    assert _bands_untouched(wg) and _bands_untouched(dg), "%s: written outside a buffer" % name
+    assert bands_untouched(wg) and bands_untouched(dg), "%s: written outside a buffer" % name
     return dw.cpu().numpy()
 
 
@@ -545,7 +495,7 @@ def _bn_case(kind, row, relu, y16):
 def test_fused_wgrad_vs_float64(device, kind, row):
     v, ref, oshape, tiles = _row_setup(kind, row, device)
     cout = oshape[-1]
-    yg, y = _carve(oshape, O.STORAGE, device, 8 * 32 * cout)
+    yg, y = carve(oshape, O.STORAGE, 8 * 32 * cout, device)
     assert _call("ocr_conv2d_%s_f16" % kind, v, y=y, bias=None, stats=None) == OK     # the y of the forward launch
     torch.cuda.synchronize()
     y16 = y.float().cpu().numpy()
@@ -564,7 +514,7 @@ def test_fused_wgrad_vs_float64(device, kind, row):
         if kind == "first":
             re = _run_wgrad(name, kind, v, device, bn_y=None, wp_re=v["wp"], **args)
             assert np.array_equal(re.view(np.int32), got.view(np.int32)), "the recomputing form is not bit-identical"
-    assert _bands_untouched(yg)
+    assert bands_untouched(yg)
 
 
 # ---------------------------------------------------------------------------------------------------- moments
@@ -587,21 +537,21 @@ def test_first_moments_vs_float64(device, row):
     assert trips == (2 if row == "cap" else 1)
     bound = (64 * trips + 3) * 2.0 ** -24 * absM
     for keep in (True, False):
-        wg, ws = _carve((nbytes // 4,), torch.float32, device, 1024)
-        rg, srow = _carve((2, cout), torch.float32, device, 2 * cout)
-        mg, mom = _carve((32, 32), torch.float64, device, 1024)
+        wg, ws = carve((nbytes // 4,), torch.float32, 1024, device)
+        rg, srow = carve((2, cout), torch.float32, 2 * cout, device)
+        mg, mom = carve((32, 32), torch.float64, 1024, device)
         name = "ocr_conv2d_first_moments_keep_f16" if keep else "ocr_conv2d_first_moments_f16"
         assert _call(name, v, row=srow, mom=mom, ws=ws, ws_bytes=nbytes) == OK
         torch.cuda.synchronize()
-        assert _written(srow) and _bands_untouched(wg) and _bands_untouched(rg) and _bands_untouched(mg)
+        assert written(srow) and bands_untouched(wg) and bands_untouched(rg) and bands_untouched(mg)
         got = srow.double().cpu().numpy()
         gmean, gvar = got[0] / N, got[1] / N - (got[0] / N) ** 2
         e_m, e_v = float(np.abs(gmean - mean).max() / np.sqrt(var).max()), float(np.abs(gvar / var - 1).max())
         assert e_m <= 1e-5 and e_v <= 1e-5, (e_m, e_v)
         if not keep:
-            assert _untouched(mom)
+            assert untouched(mom)
             continue
-        assert _written(mom)
+        assert written(mom)
         gm = mom.cpu().numpy()
         err = np.abs(gm - M)
         print("image conv first %-8s moments: mean %.2e sd, variance %.2e, M %.3f of its bound" % (
@@ -646,11 +596,11 @@ def test_impulse_forward_exact(device, kind, shape):
     assert np.array_equal(ref.astype(np.float32).astype(np.float64), ref)       # exact in f32, hence in any order
     oshape = ref.shape
     _, wp = _pack(kind, wt, device)
-    yg, y = _carve(oshape, O.STORAGE, device, 8 * 32 * cout)
+    yg, y = carve(oshape, O.STORAGE, 8 * 32 * cout, device)
     v = dict(n=n, h=h, w=w, cout=cout, x4=_x4(x, device), wp=wp, flags=0, bias=None, stats=None, y=y)
     assert _call("ocr_conv2d_%s_f16" % kind, v) == OK
     torch.cuda.synchronize()
-    assert _written(y) and _bands_untouched(yg)
+    assert written(y) and bands_untouched(yg)
     bad = np.argwhere(y.float().cpu().numpy() != _h(ref))
     assert bad.size == 0, "%d elements differ, first (n, oy, ox, co) = %s" % (len(bad), bad[:4].tolist())
 
@@ -680,8 +630,8 @@ def test_status_codes_and_nothing_launched(device):
     from tensorflow_ocr_amd import _lib as L
     outputs, guards = [], []
 
-    def carve(shape, dtype, band=256):
-        g, t = _carve(shape, dtype, device, band)
+    def filled(shape, dtype, band=256):
+        g, t = carve(shape, dtype, band, device)
         outputs.append(t)
         guards.append(g)
         return t
@@ -695,16 +645,16 @@ def test_status_codes_and_nothing_launched(device):
         nbytes = L.call_size("ocr_conv2d_%s_wgrad_workspace" % kind, *(ctypes.c_int(a) for a in (n, h, w, cout)))
         base = dict(n=n, h=h, w=w, cout=cout, x4=z16((n, h, w, 4)), wp=z16((3, cout, 16) if kind == "first" else (7, 2, cout, 16)),
                     bias=z32(cout), flags=BIAS | STATS, relu=1, scale=z32(cout), shift=z32(cout), A=z32(cout), B=z32(cout),
-                    C=z32(cout), dy=z16(oshape), bn_y=z16(oshape), y=carve(oshape, O.STORAGE),
-                    stats=carve((tiles, 2, cout), torch.float32), dw=carve((k, k, 3, cout), torch.float32))
+                    C=z32(cout), dy=z16(oshape), bn_y=z16(oshape), y=filled(oshape, O.STORAGE),
+                    stats=filled((tiles, 2, cout), torch.float32), dw=filled((k, k, 3, cout), torch.float32))
         base["wp_re"] = None
-        wgrad = dict(base, ws=carve((nbytes // 4,), torch.float32), ws_bytes=nbytes)
+        wgrad = dict(base, ws=filled((nbytes // 4,), torch.float32), ws_bytes=nbytes)
         entries = [("ocr_conv2d_%s_f16" % kind, base, ("x4", "wp", "bias", "stats")),
                    ("ocr_conv2d_%s_wgrad_f16" % kind, wgrad, ("x4", "dy", "dw", "ws")),
                    ("ocr_conv2d_%s_wgrad_bn_f16" % kind, wgrad, ("x4", "dy", "bn_y", "shift", "A", "B", "C", "dw", "ws"))]
         if kind == "first":
-            moments = dict(base, row=carve((2, cout), torch.float32), mom=carve((32, 32), torch.float64),
-                           ws=carve((mbytes // 4,), torch.float32), ws_bytes=mbytes)
+            moments = dict(base, row=filled((2, cout), torch.float32), mom=filled((32, 32), torch.float64),
+                           ws=filled((mbytes // 4,), torch.float32), ws_bytes=mbytes)
             entries += [("ocr_conv2d_first_bn_relu_f16", base, ("x4", "wp", "scale", "shift", "y")),
                         ("ocr_conv2d_first_moments_keep_f16", moments, ("x4", "wp", "row", "ws")),
                         ("ocr_conv2d_first_moments_f16", moments, ("x4", "wp", "row", "ws"))]
@@ -729,5 +679,5 @@ def test_status_codes_and_nothing_launched(device):
             for name in ("ocr_conv2d_first_moments_keep_f16", "ocr_conv2d_first_moments_f16"):
                 assert _call(name, moments, ws=odd, ws_bytes=mbytes) == WORKSPACE
     torch.cuda.synchronize()
-    assert all(_untouched(t) for t in outputs), "an error return launched something"
-    assert all(_bands_untouched(g) for g in guards)
+    assert all(untouched(t) for t in outputs), "an error return launched something"
+    assert all(bands_untouched(g) for g in guards)

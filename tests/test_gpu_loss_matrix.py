@@ -104,34 +104,24 @@ MEASURED (largest |err| / bound over the rows, f16 library; 0.000 = bit-exact in
   references over 1 M pixels on the host), every other test under 0.6 s.
 """
 import ctypes
-import zlib
+from functools import partial
 from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
 import torch
 
+import matrix_support
+from matrix_support import (FL, I64, INVALID_ARG, OK, SZ, U32, UNSUPPORTED, WORKSPACE, Guard, Strided, _bits_equal, _cdiv, _d32,
+                            _g, _lib, _ratio, _rc, _rng, f32, f64)
 from oracle import ocr_oracle as O
-from test_gpu_heads_matrix import (FL, I64, SZ, Guard, Strided, _bits_equal, _cdiv, _d32, _g, _lib, _ratio, _rc, _z)
 
 pytestmark = pytest.mark.gpu
 
-OK, INVALID_ARG, UNSUPPORTED, WORKSPACE = 0, -1, -2, -4
-U32 = 2.0 ** -24
-f32, f64 = np.float32, np.float64
+_note = partial(matrix_support._note, "loss")
 ELOG = 3.064        # ulps: logf measured 2.064 ulp on [1, 2] (the result goes to 0 at 1), plus one (MEASURED)
 EPOW = 2.322        # ulps: powf measured 1.322 ulp over the rows' range, plus one (MEASURED)
 M_GRAD = 13
-
-
-
-def _rng(*key):
-    return np.random.default_rng(zlib.crc32(repr(key).encode()))
-
-
-def _note(entry, row, ratio):
-    print("loss %s %s ratio=%.3f" % (entry, row, ratio))
-    assert ratio <= 1.0, (entry, row, ratio)
 
 
 def _blocks(total):

@@ -34,6 +34,7 @@ import pytest
 import torch
 
 import test_rbox_host as H
+from matrix_support import _cdiv, _g as _gm, _h as _h16
 from oracle import lanms as OL
 from oracle import ocr_oracle as O
 
@@ -291,18 +292,6 @@ def test_loss_dynamic_seed_equals_the_static_product(device, loss_case):
 
 
 # ------------------------------------------------------------------------------------------------ graph
-def _h16(a):
-    return torch.from_numpy(np.asarray(a, f32)).to(O.STORAGE).float().numpy()
-
-
-def _gm(m):
-    return m * 2.0 ** -24 / (1.0 - m * 2.0 ** -24)
-
-
-def _cdiv(a, b):
-    return -(-a // b)
-
-
 HEAD = "feature_fusion/Conv_7+Conv_8+Conv_9/"
 MERGED = [(HEAD, 0, 6)]
 PER_HEAD = [("feature_fusion/Conv_7/", 0, 1), ("feature_fusion/Conv_8/", 1, 4), ("feature_fusion/Conv_9/", 5, 1)]

@@ -60,11 +60,10 @@ import numpy as np
 import pytest
 import torch
 
+from matrix_support import INVALID_ARG, OK, UNSUPPORTED, WORKSPACE, _h, _raw, bands_untouched, carve, untouched
 from oracle import ocr_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-OK, INVALID_ARG, UNSUPPORTED, WORKSPACE = 0, -1, -2, -4
 
 # name: (expected slab kernel, (n, h, w, cin, cout, k | (kh, kw), dilation, stride)); SAME padding from ops.conv_desc
 ROWS = {
@@ -134,16 +133,9 @@ SLAB_SUM = {
     "eight_on_1": (8, "slab_reduce_kernel<1>", (1, 16, 8, 2048, 1024, 1, 1, 1)),
 }
 
-SENT32 = 0x5EEDF00D
-NAN32 = 0x7FC0BEEF              # a quiet NaN with a payload: "still what the test wrote"
 BAR = 5e-6
 
 _REF = {}                       # (row, kind) -> (x, dy, float64 dw), computed once
-
-
-def _h(a):
-    """round to the library's 16-bit storage type"""
-    return torch.from_numpy(np.asarray(a, np.float32)).to(O.STORAGE).float().numpy()
 
 
 def _desc(ops, shape):
@@ -217,27 +209,8 @@ def _operands(ops, row, kind):
     return _REF[key]
 
 
-def _carve(numel, band, device):
-    """`numel` f32 elements filled with NaN inside a larger flat allocation, `band` sentinel elements on each side."""
-    flat = torch.empty(2 * band + numel, dtype=torch.float32, device=device)
-    flat.view(torch.int32).fill_(SENT32)
-    t = flat[band:band + numel]
-    assert t.data_ptr() % 16 == 0
-    t.view(torch.int32).fill_(NAN32)
-    return flat, t
-
-
-def _bands_untouched(flat, band):
-    iv = flat.view(torch.int32)
-    return bool((iv[:band] == SENT32).all()) and bool((iv[-band:] == SENT32).all())
-
-
-def _untouched(t):
-    return bool((t.view(torch.int32) == NAN32).all())
-
-
 def _buffers(L, d, device, slabs=None):
-    """(workspace flat, workspace, dw flat, dw, band): the workspace is exactly ocr_conv2d_wgrad_workspace bytes (or
+    """(workspace guard, workspace, dw guard, dw): the workspace is exactly ocr_conv2d_wgrad_workspace bytes (or
     `slabs` slabs where that is 0), the bands one slab's worth."""
     elems = d.kh * d.kw * d.cin * d.cout
     band = (elems + 3) // 4 * 4
@@ -245,14 +218,9 @@ def _buffers(L, d, device, slabs=None):
     if slabs is None:
         assert nbytes > 0 and nbytes % (4 * elems) == 0
         slabs = nbytes // (4 * elems)
-    wflat, ws = _carve(slabs * elems, band, device)
-    dflat, dw = _carve(elems, band, device)
-    return wflat, ws, dflat, dw, band
-
-
-def _raw(L, name, *args):
-    """the status of a C-ABI call, not raised"""
-    return int(L._fn(name, ctypes.c_int)(*args))
+    wg, ws = carve((slabs * elems,), torch.float32, band, device)
+    dg, dw = carve((elems,), torch.float32, band, device)
+    return wg, ws, dg, dw
 
 
 def _launch(L, form, d, xd, dyd, ws, dw):
@@ -277,14 +245,14 @@ def _run(ops, L, device, row, kind, form):
     x, dy, ref = _operands(ops, row, kind)
     xd = torch.from_numpy(x).to(O.STORAGE).to(device)       # (copies: the shared operands stay as they were drawn)
     dyd = torch.from_numpy(dy).to(O.STORAGE).to(device)
-    wflat, ws, dflat, dw, band = _buffers(L, d, device)
+    wg, ws, dg, dw = _buffers(L, d, device)
     assert ws.numel() == v["slabs"] * dw.numel(), (v, ws.numel(), dw.numel())
     assert _launch(L, form, d, xd, dyd, ws, dw) == OK
     torch.cuda.synchronize()
     assert not bool(torch.isnan(ws).any()), "%s: slab elements the kernel did not write" % row
     assert bool(torch.isfinite(ws).all()) and bool(torch.isfinite(dw).all())
-    assert _bands_untouched(wflat, band), "%s: written outside the workspace" % row
-    assert _bands_untouched(dflat, band), "%s: written outside dw" % row
+    assert bands_untouched(wg), "%s: written outside the workspace" % row
+    assert bands_untouched(dg), "%s: written outside dw" % row
     return dw.cpu().numpy().reshape(ref.shape), ref, v
 
 
@@ -326,12 +294,12 @@ def test_unsupported_shapes_write_nothing(device, name):
     assert _raw(L, "ocr_conv2d_wgrad_variant", ctypes.byref(d), buf, ctypes.c_size_t(128)) == UNSUPPORTED
     xd = torch.zeros((d.n, d.h, d.w, d.cin), dtype=O.STORAGE, device=device)
     dyd = torch.zeros((d.n, d.oh, d.ow, d.cout), dtype=O.STORAGE, device=device)
-    wflat, ws, dflat, dw, band = _buffers(L, d, device, slabs=2)
+    wg, ws, dg, dw = _buffers(L, d, device, slabs=2)
     for form in ("one", "two"):
         assert _launch(L, form, d, xd, dyd, ws, dw) == UNSUPPORTED
     assert _raw(L, "ocr_conv2d_wgrad_reduce_f32", ctypes.byref(d), L.ptr(ws), L.ptr(dw), L.stream_ptr()) == UNSUPPORTED
     torch.cuda.synchronize()
-    assert _untouched(ws) and _untouched(dw) and _bands_untouched(wflat, band) and _bands_untouched(dflat, band)
+    assert untouched(ws) and untouched(dw) and bands_untouched(wg) and bands_untouched(dg)
 
 
 @pytest.mark.parametrize("name", list(SLAB_SUM))
@@ -347,7 +315,7 @@ def test_slab_sum_alone(device, name):
     elems = d.kh * d.kw * d.cin * d.cout
     rng = np.random.default_rng(zlib.crc32(name.encode()))
     host = rng.standard_normal((slabs, elems), dtype=np.float32)
-    wflat, ws, dflat, dw, band = _buffers(L, d, device)
+    wg, ws, dg, dw = _buffers(L, d, device)
     assert ws.numel() == slabs * elems
     ws.copy_(torch.from_numpy(host).reshape(-1))
     assert _raw(L, "ocr_conv2d_wgrad_reduce_f32", ctypes.byref(d), L.ptr(ws), L.ptr(dw), L.stream_ptr()) == OK
@@ -358,7 +326,7 @@ def test_slab_sum_alone(device, name):
     excess = np.abs(got - ref) - bound
     print("slab sum %-10s %3d slabs %s: max |err| / bound %.3f" % (name, slabs, reduce, float((np.abs(got - ref) / bound).max())))
     assert np.isfinite(got).all() and excess.max() <= 0
-    assert _bands_untouched(dflat, band) and _bands_untouched(wflat, band)
+    assert bands_untouched(dg) and bands_untouched(wg)
     assert np.array_equal(ws.cpu().numpy().reshape(slabs, elems), host)           # the slabs are only read
 
 
@@ -368,7 +336,7 @@ def test_return_codes_and_nothing_written(device):
     d = _desc(ops, shape)
     xd = torch.zeros((d.n, d.h, d.w, d.cin), dtype=O.STORAGE, device=device)
     dyd = torch.zeros((d.n, d.oh, d.ow, d.cout), dtype=O.STORAGE, device=device)
-    wflat, ws, dflat, dw, band = _buffers(L, d, device)
+    wg, ws, dg, dw = _buffers(L, d, device)
     st = L.stream_ptr()
     nbytes = ws.numel() * 4
     ref, px, pdy, pws, pdw = ctypes.byref(d), L.ptr(xd), L.ptr(dyd), L.ptr(ws), L.ptr(dw)
@@ -396,7 +364,7 @@ def test_return_codes_and_nothing_written(device):
         assert _raw(L, "ocr_conv2d_wgrad_variant", b, name, ctypes.c_size_t(128)) == INVALID_ARG, field
         assert L.call_size("ocr_conv2d_wgrad_workspace", b) == 0, field
     torch.cuda.synchronize()
-    assert _untouched(ws) and _untouched(dw) and _bands_untouched(wflat, band) and _bands_untouched(dflat, band)
+    assert untouched(ws) and untouched(dw) and bands_untouched(wg) and bands_untouched(dg)
     # and the same buffers take the well-formed call
     assert _raw(L, "ocr_conv2d_wgrad_f16", ref, px, pdy, pdw, pws, ctypes.c_size_t(nbytes), st) == OK
     torch.cuda.synchronize()
