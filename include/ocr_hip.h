@@ -632,7 +632,10 @@ int ocr_softmax_loss_bwd_dyn(const ocr_softmax_loss_desc* d, const void* pixel_l
  * ON THE PRODUCT LIBRARY (16-bit storage costs ~1e-2 of the logit range after 16 layers).  Forward only.
  * Tensors NHWC f32; conv weights in the TF HWIO master layout [kh][kw][cin][cout] (no packing).
  * ------------------------------------------------------------------------- */
-/* flags: OCR_CONV_BIAS, OCR_CONV_RELU, OCR_CONV_ACCUM_F16 (here: y += conv, f32); any kernel size, stride, dilation */
+/* flags: OCR_CONV_BIAS, OCR_CONV_RELU, OCR_CONV_ACCUM_F16 (here: y += conv, f32); any kernel size, stride, dilation.
+ * Forward only.  A request the entry does not serve is refused, never dropped: OCR_ERR_INVALID_ARG for flip_taps != 0 and for
+ * any flag bit outside the three above (OCR_CONV_STATS, the `_ep` flags, unknown bits); nothing is written.  The same holds
+ * for ocr_conv2d_f32_split, and for the two `_ep` entries with the six flags they list. */
 int ocr_conv2d_f32_mfma(const ocr_conv_desc* d, const void* x, const void* w_hwio, const void* bias, void* y,
                         void* stream);
 /* The same convolution with the whole f32 epilogue, so that a convolution, its inference-mode batch norm (moving statistics:
@@ -645,7 +648,8 @@ int ocr_conv2d_f32_mfma(const ocr_conv_desc* d, const void* x, const void* w_hwi
  *   5. OCR_CONV_RELU        v < 0 -> 0                      (a NaN stays NaN)
  *   6. OCR_CONV_ACCUM_F16   v += y_old                      (after the ReLU: the meaning it has above)
  * All operands f32: bias, scale, shift [cout]; residual [n,oh,ow,cout].  OCR_ERR_INVALID_ARG when a flag is set and its
- * pointer is NULL, or when OCR_CONV_ACCUM_IN and OCR_CONV_ACCUM_F16 are both set.  Store contract as above: every element of
+ * pointer is NULL, when OCR_CONV_ACCUM_IN and OCR_CONV_ACCUM_F16 are both set, for flip_taps != 0 and for a flag bit outside
+ * these six (OCR_CONV_STATS included).  Store contract as above: every element of
  * y is stored, nothing outside it is written; a cout that is no multiple of 4 (or of the cout tile) and an unaligned y take
  * scalar stores with the same arithmetic.  ocr_conv2d_f32_mfma / ocr_conv2d_f32_split are thin callers of the same kernels
  * with steps 3, 5, 6 only (tests/test_gpu_fold_bn.py). */
@@ -660,6 +664,9 @@ int ocr_channel_stats_f32_num_partials(int64_t npix, int c);
 int ocr_channel_stats_f32(const void* x, int64_t npix, int c, void* partial, void* stream);
 int ocr_bn_relu_f32(const void* y, const void* scale, const void* shift, int n, int h, int w, int c, int relu,
                     int pool, void* a_full, void* a_pool, void* stream);
+/* NaN rule of the element-wise f32 kernels: a NaN that comes in goes out.  The ReLU is `v < 0 -> 0` (as step 5 above), and the
+ * maxima of ocr_maxpool_f32 and of ocr_bn_relu_f32's pool = 2 give NaN for a window that holds one; otherwise the first
+ * maximum of the window is kept and -inf passes through.  Every extent (h and w of ocr_maxpool_f32 included) must be > 0. */
 int ocr_maxpool_f32(const void* x, int n, int h, int w, int c, int k, int stride, int pad_top, int pad_left,
                     int oh, int ow, void* y, void* stream);
 int ocr_prep_images_f32(const void* images, int64_t npix, float mean_r, float mean_g, float mean_b, void* out,
@@ -674,7 +681,9 @@ int ocr_unpool_f32(const void* x, int n, int lh, int lw, int c, void* y, void* s
  * apart, joined in the epilogue).  IEEE half in BOTH libraries (f32 in, f32 out: independent of the 16-bit storage type).
  * Same contract and flags as ocr_conv2d_f32_mfma, plus `workspace` (16-byte aligned, at least
  * ocr_conv2d_f32_split_workspace(d) bytes): EVERY call splits and packs the weights into it on `stream`, then convolves.
- * Range: |x|, |w| >= 65504 saturate to the largest finite half (wrong but finite result); NaN operands stay NaN. */
+ * Range: |x|, |w| >= 65504 saturate to the largest finite half (wrong but finite result); NaN operands stay NaN.
+ * Status: OCR_ERR_INVALID_ARG for a workspace that is NULL or not 16-byte aligned, OCR_ERR_WORKSPACE for workspace_bytes below
+ * ocr_conv2d_f32_split_workspace(d) (0 for an invalid descriptor); nothing is written. */
 size_t ocr_conv2d_f32_split_workspace(const ocr_conv_desc* d);
 int ocr_conv2d_f32_split(const ocr_conv_desc* d, const void* x, const void* w_hwio, const void* bias, void* y,
                          void* workspace, size_t workspace_bytes, void* stream);

@@ -219,7 +219,9 @@ size_t split_plane_elems(const ocr_conv_desc* d) {
 int launch_split(const ocr_conv_desc* d, int flags, const void* x, const void* w_hwio, const F32Ep& ep, void* y,
                  void* workspace, size_t workspace_bytes, void* stream) {
   OCR_CHECK_ARG(split_desc_ok(d) && x && w_hwio && y && workspace);
-  OCR_CHECK_ARG(((uintptr_t)workspace & 15) == 0 && workspace_bytes >= ocr_conv2d_f32_split_workspace(d));
+  OCR_CHECK_ARG(d->flip_taps == 0);                        // forward only, as ocr_conv2d_f32_mfma
+  OCR_CHECK_ARG(((uintptr_t)workspace & 15) == 0);
+  if (workspace_bytes < ocr_conv2d_f32_split_workspace(d)) return OCR_ERR_WORKSPACE;   // as every other workspace of the ABI
   OCR_CHECK_SHAPE((size_t)d->n * d->oh * d->ow < (1ull << 31));
   const int tc = split_tc(d->cout);
   SplitP p{d->n, d->h, d->w, d->cin, d->oh, d->ow, d->cout, d->kh, d->kw, d->stride, d->dilation, d->pad_top, d->pad_left,
@@ -255,8 +257,9 @@ extern "C" size_t ocr_conv2d_f32_split_workspace(const ocr_conv_desc* d) {
 extern "C" int ocr_conv2d_f32_split(const ocr_conv_desc* d, const void* x, const void* w_hwio, const void* bias, void* y,
                                     void* workspace, size_t workspace_bytes, void* stream) {
   OCR_CHECK_ARG(d);
+  OCR_CHECK_ARG(!(d->flags & ~kF32PlainFlags));            // a request this entry does not serve is refused, not dropped
   OCR_CHECK_ARG(!(d->flags & OCR_CONV_BIAS) || bias);
-  return launch_split(d, d->flags & kF32PlainFlags, x, w_hwio, F32Ep{static_cast<const float*>(bias), nullptr, nullptr, nullptr},
+  return launch_split(d, d->flags, x, w_hwio, F32Ep{static_cast<const float*>(bias), nullptr, nullptr, nullptr},
                       y, workspace, workspace_bytes, stream);
 }
 
@@ -267,6 +270,7 @@ extern "C" int ocr_conv2d_f32_split_ep(const ocr_conv_desc* d, const void* x, co
                                        size_t workspace_bytes, void* stream) {
   OCR_CHECK_ARG(d);
   F32Ep ep;
+  OCR_CHECK_ARG(!(d->flags & ~kF32EpFlags));
   OCR_CHECK_ARG(f32_ep_args(d->flags, epilogue, &ep));
-  return launch_split(d, d->flags & kF32EpFlags, x, w_hwio, ep, y, workspace, workspace_bytes, stream);
+  return launch_split(d, d->flags, x, w_hwio, ep, y, workspace, workspace_bytes, stream);
 }

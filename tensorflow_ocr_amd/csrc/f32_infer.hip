@@ -138,7 +138,8 @@ __global__ void channel_stats_f32_kernel(const float* __restrict__ x, size_t npi
   }
 }
 
-// a = [relu](y*scale + shift); pool = 2: also the 2x2/2 SAME max-pool of a
+// a = [relu](y*scale + shift); pool = 2: also the 2x2/2 SAME max-pool of a.  NaN rule of the f32 path:
+// the ReLU is `v < 0 -> 0` and the maximum takes a NaN, so a NaN that comes in goes out.
 __global__ void bn_relu_f32_kernel(const float* __restrict__ y, const float* __restrict__ scale,
                                    const float* __restrict__ shift, int n, int h, int w, int c, int relu,
                                    float* __restrict__ a_full, float* __restrict__ a_pool, int pool) {
@@ -170,7 +171,7 @@ __global__ void bn_relu_f32_kernel(const float* __restrict__ y, const float* __r
         float v = y[j] * scale[ch] + shift[ch];
         if (relu && v < 0.f) v = 0.f;
         if (a_full) a_full[j] = v;
-        m = v > m ? v : m;
+        m = (v > m || v != v) ? v : m;                     // first maximum; a NaN in the window gives NaN
       }
     a_pool[i] = m;
   }
@@ -192,7 +193,7 @@ __global__ void maxpool_f32_kernel(const float* __restrict__ x, int n, int h, in
         const int iy = oy * stride + ky - pt, ix = ox * stride + kx - pl;
         if (iy < 0 || iy >= h || ix < 0 || ix >= w) continue;
         const float v = x[(((size_t)img * h + iy) * w + ix) * c + ch];
-        m = v > m ? v : m;
+        m = (v > m || v != v) ? v : m;                     // first maximum; a NaN in the window gives NaN
       }
     y[i] = m;
   }
@@ -235,8 +236,9 @@ __global__ void bn_add_relu_f32_kernel(const float* __restrict__ y, const float*
                                        size_t total, int c, float* __restrict__ out) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int ch = (int)(i % c);
-    const float v = y[i] * scale[ch] + shift[ch] + sc[i];
-    out[i] = v > 0.f ? v : 0.f;
+    float v = y[i] * scale[ch] + shift[ch] + sc[i];
+    if (v < 0.f) v = 0.f;                                  // the ReLU of f32_conv_ep.h: a NaN stays NaN
+    out[i] = v;
   }
 }
 
@@ -278,6 +280,7 @@ namespace {
 int launch_f32_mfma(const ocr_conv_desc* d, int flags, const void* x, const void* w_hwio, const F32Ep& ep, void* y,
                     void* stream) {
   OCR_CHECK_ARG(d && x && w_hwio && y);
+  OCR_CHECK_ARG(d->flip_taps == 0);                        // forward only; ocr_conv2d_f32 (verify_f32.hip) refuses it too
   OCR_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->oh > 0 && d->ow > 0 && d->cin > 0 && d->cout > 0);
   OCR_CHECK_ARG(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->dilation > 0);
   OCR_CHECK_SHAPE((size_t)d->n * d->oh * d->ow < (1ull << 31));
@@ -296,8 +299,9 @@ int launch_f32_mfma(const ocr_conv_desc* d, int flags, const void* x, const void
 extern "C" int ocr_conv2d_f32_mfma(const ocr_conv_desc* d, const void* x, const void* w_hwio, const void* bias, void* y,
                                    void* stream) {
   OCR_CHECK_ARG(d);
+  OCR_CHECK_ARG(!(d->flags & ~kF32PlainFlags));            // a request this entry does not serve is refused, not dropped
   OCR_CHECK_ARG(!(d->flags & OCR_CONV_BIAS) || bias);
-  return launch_f32_mfma(d, d->flags & kF32PlainFlags, x, w_hwio,
+  return launch_f32_mfma(d, d->flags, x, w_hwio,
                          F32Ep{static_cast<const float*>(bias), nullptr, nullptr, nullptr}, y, stream);
 }
 
@@ -306,8 +310,9 @@ extern "C" int ocr_conv2d_f32_mfma_ep(const ocr_conv_desc* d, const void* x, con
                                       const ocr_conv_f32_epilogue* epilogue, void* y, void* stream) {
   OCR_CHECK_ARG(d);
   F32Ep ep;
+  OCR_CHECK_ARG(!(d->flags & ~kF32EpFlags));
   OCR_CHECK_ARG(f32_ep_args(d->flags, epilogue, &ep));
-  return launch_f32_mfma(d, d->flags & kF32EpFlags, x, w_hwio, ep, y, stream);
+  return launch_f32_mfma(d, d->flags, x, w_hwio, ep, y, stream);
 }
 
 extern "C" int ocr_channel_stats_f32_num_partials(int64_t npix, int c) {
@@ -341,7 +346,7 @@ extern "C" int ocr_bn_relu_f32(const void* y, const void* scale, const void* shi
 
 extern "C" int ocr_maxpool_f32(const void* x, int n, int h, int w, int c, int k, int stride, int pad_top,
                                int pad_left, int oh, int ow, void* y, void* stream) {
-  OCR_CHECK_ARG(x && y && n > 0 && k > 0 && stride > 0 && oh > 0 && ow > 0 && c > 0);
+  OCR_CHECK_ARG(x && y && n > 0 && h > 0 && w > 0 && k > 0 && stride > 0 && oh > 0 && ow > 0 && c > 0);
   hipLaunchKernelGGL(maxpool_f32_kernel, dim3(vgrid((size_t)n * oh * ow * c)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const float*>(x), n, h, w, c, k, stride,
                      pad_top, pad_left, oh, ow, static_cast<float*>(y));

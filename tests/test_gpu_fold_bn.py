@@ -149,7 +149,7 @@ def test_epilogue_unaligned_y_and_residual(device, route):
 @pytest.mark.parametrize("route", ROUTES)
 def test_plain_entry_points_are_thin_callers(device, route):
     """ocr_conv2d_f32_mfma / ocr_conv2d_f32_split (the host layer no longer calls them) give the bits of the `_ep` entry points
-    under the flags they always took, and ignore the new ones."""
+    under the flags they always took, and refuse the new ones (OCR_ERR_INVALID_ARG, y as it was) instead of dropping them."""
     from tensorflow_ocr_amd import _lib as L, ops
     shape = SHAPES[1]
     n, h, w, cin, cout, k, stride, rate = shape
@@ -161,14 +161,21 @@ def test_plain_entry_points_are_thin_callers(device, route):
         want = torch.from_numpy(c["y_old"]).to(device)
         ops.conv2d_f32(d, x, wt, want, bias if flags & BIAS else None, route=route)
         got = torch.from_numpy(c["y_old"]).to(device)
-        d.flags = flags | AFFINE | RESIDUAL | ACCUM_IN                     # meaningless here: ignored
-        if route == "split":
-            nbytes = ops.conv2d_f32_split_workspace(d)
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            L.call("ocr_conv2d_f32_split", ctypes.byref(d), L.ptr(x), L.ptr(wt), L.ptr(bias), L.ptr(got), L.ptr(buf),
-                   ctypes.c_size_t(nbytes), L.stream_ptr())
-        else:
-            L.call("ocr_conv2d_f32_mfma", ctypes.byref(d), L.ptr(x), L.ptr(wt), L.ptr(bias), L.ptr(got), L.stream_ptr())
+        nbytes = ops.conv2d_f32_split_workspace(d)
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+        def plain():
+            if route == "split":
+                return L._fn("ocr_conv2d_f32_split", ctypes.c_int)(ctypes.byref(d), L.ptr(x), L.ptr(wt), L.ptr(bias), L.ptr(got),
+                                                                   L.ptr(buf), ctypes.c_size_t(nbytes), L.stream_ptr())
+            return L._fn("ocr_conv2d_f32_mfma", ctypes.c_int)(ctypes.byref(d), L.ptr(x), L.ptr(wt), L.ptr(bias), L.ptr(got), L.stream_ptr())
+        for new_flag in (AFFINE, RESIDUAL, ACCUM_IN, AFFINE | RESIDUAL | ACCUM_IN):
+            d.flags = flags | new_flag                                     # not served by the plain entries: refused
+            assert plain() == -1, (flags, new_flag)
+        torch.cuda.synchronize()
+        assert torch.equal(got, torch.from_numpy(c["y_old"]).to(device)), flags
+        d.flags = flags
+        assert plain() == 0
         torch.cuda.synchronize()
         assert torch.equal(got, want), flags
 
