@@ -104,7 +104,10 @@ int ocr_conv2d_num_mtiles(const ocr_conv_desc* d);
 
 /* Name of the kernel instantiation ocr_conv2d_f16 launches for `d`:
  * "conv_igemm_kernel<BN,CK,WCO,M16,TH>" (cout tile, channel chunk, cout waves, 16x16x32 MFMA, tile rows),
- * as it appears (mangled) in rocprofv3 kernel traces.  Measurement only. */
+ * as it appears (mangled) in rocprofv3 kernel traces.  Measurement only.
+ * The name is the family's NOMINAL tile, in two cases not the launched one: a pointwise cin = 64 launch whose
+ * epilogue loads nothing runs conv_pw_kernel<128,2> under the name <256,4>, and the bottleneck tail
+ * (ocr_conv2d_bnred_tail_f16, which no descriptor expresses) runs conv_igemm_kernel where the name is a 4-wave kernel. */
 int ocr_conv2d_variant(const ocr_conv_desc* d, char* out, size_t cap);
 
 /* conv3x3 + bias + ReLU + 2x2/2 max-pool (SAME: windows over an odd edge ignore the missing pixels) in one kernel for

@@ -2116,110 +2116,7 @@ __global__ __launch_bounds__(512) void conv_c64_persist_kernel(
   }
 }
 
-static bool pw_xcd_swizzle() { return true; }
-
-template <int BN, int WCO>
-int launch_pw(const ConvP& p, const void* x, const void* w, const void* bias, void* y, void* stats,
-              hipStream_t st) {
-  // one K stage (cin = 64): nothing to double-buffer
-  const size_t main_bytes = (p.cin == 64 ? 1 : 2) * ((size_t)BN * 128 + 256 * 128);
-  const bool epi_loads = (p.flags & OCR_CONV_ACCUM_F16) != 0 || p.br.y != nullptr;
-  // the store-only epilogue takes a 256-cout tile in two halves, the one with global operands in one piece
-  const size_t epi_bytes = conv_epilogue_lds(epi_loads ? BN : (BN > 128 ? 128 : BN), 512);
-  const size_t lds = main_bytes > epi_bytes ? main_bytes : epi_bytes;
-  // two instantiations: the epilogue with global operands (ACCUM / BN-backward / tail) batches its loads
-  // ahead of its stores (conv_epilogue.h) and needs ~40 more registers than the store-only one
-  auto kern = epi_loads ? conv_pw_kernel<BN, WCO, true> : conv_pw_kernel<BN, WCO, false>;
-  static bool configured[2] = {false, false};
-  if (!configured[epi_loads]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(160 * 1024)) != hipSuccess)
-      return OCR_ERR_HIP;
-    configured[epi_loads] = true;
-  }
-  const unsigned m_tiles = (unsigned)((p.npix + 255) / 256);
-  ConvP q = p;
-  q.xcd_swizzle = pw_xcd_swizzle() && p.n_tiles > 1 && (m_tiles * p.n_tiles) % 8 == 0;
-  hipLaunchKernelGGL(kern, dim3(m_tiles * p.n_tiles), dim3(512), lds, st, q, static_cast<const half_t*>(x),
-                     static_cast<const half_t*>(w), static_cast<const float*>(bias), static_cast<half_t*>(y),
-                     static_cast<float*>(stats));
-  return ocr_launch_status();
-}
-
 struct TileCfg { int bn, ck, th; };
-
-template <int BN, int WCO, int MODE, bool PROJ>
-int launch_pwx(const ConvP& p, const PwX& t, const void* w, void* y, void* stats, hipStream_t st) {
-  const size_t main_bytes = 2 * ((size_t)BN * 128 + 256 * 128) + (size_t)p.cin * 16;     // two stages + coefficients
-  if (main_bytes > 160 * 1024) return OCR_ERR_UNSUPPORTED;
-  constexpr bool epi_loads = MODE == 2;          // the backward form carries the fused BN-backward reduction
-  const size_t epi_bytes = conv_epilogue_lds(epi_loads ? BN : (BN > 128 ? 128 : BN), 512);
-  const size_t lds = main_bytes > epi_bytes ? main_bytes : epi_bytes;
-  auto kern = conv_pwx_kernel<BN, WCO, epi_loads, MODE, PROJ>;
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(160 * 1024)) != hipSuccess)
-      return OCR_ERR_HIP;
-    configured = true;
-  }
-  const unsigned m_tiles = (unsigned)((p.npix + 255) / 256);
-  ConvP q = p;
-  q.xcd_swizzle = pw_xcd_swizzle() && p.n_tiles > 1 && (m_tiles * p.n_tiles) % 8 == 0;
-  hipLaunchKernelGGL(kern, dim3(m_tiles * p.n_tiles), dim3(512), lds, st, q, t, static_cast<const half_t*>(w),
-                     static_cast<half_t*>(y), static_cast<float*>(stats));
-  return ocr_launch_status();
-}
-
-template <int MODE>
-int dispatch_pwx(ConvP& p, const TileCfg& c, const PwX& t, const void* w, void* y, void* stats, hipStream_t st) {
-  if (!p.pw || p.cin < 128) return OCR_ERR_UNSUPPORTED;      // (cin = 64: one stage, nothing to overlap the loads with)
-  if ((MODE == 1 && t.f1 != nullptr) ||          // the shortcut is a projection: its batch norm is applied too
-      (MODE == 2 && t.f3 != nullptr)) {          // the batch norm above is followed by a ReLU: its mask is applied too
-    if (c.bn == 256) return launch_pwx<256, 4, MODE, true>(p, t, w, y, stats, st);
-    if (c.bn == 128) return launch_pwx<128, 2, MODE, true>(p, t, w, y, stats, st);
-    return launch_pwx<64, 1, MODE, true>(p, t, w, y, stats, st);
-  }
-  if (c.bn == 256) return launch_pwx<256, 4, MODE, false>(p, t, w, y, stats, st);
-  if (c.bn == 128) return launch_pwx<128, 2, MODE, false>(p, t, w, y, stats, st);
-  return launch_pwx<64, 1, MODE, false>(p, t, w, y, stats, st);
-}
-
-template <int BN, int CK, int WCO, bool M16, int TH, int NW = 2>
-int launch_t(const ConvP& p, const void* x, const void* w, const void* bias, void* y,
-             void* stats, hipStream_t st) {
-  if constexpr (NW == 2 && BN == 256 && M16 && TH == 8) {
-    // a three-slot weight ring for the 256-cout tiles, the slice requested two taps ahead (a four-slot ring was measured
-    // too, on fc6 — 144 tap steps of 32 MFMAs per tile — and the strided ResNet convolutions: headline 19.85 -> 19.96 ms,
-    // ResNet 39.31 -> 39.22: the tap step's cost is not the slice's fetch)
-    const int taps = p.kh * p.kw;
-    if (taps >= 3 && (size_t)p.halo_bytes + 3 * BN * conv_wrs(CK) <= 160 * 1024)
-      return launch_t<BN, CK, WCO, M16, TH, 3>(p, x, w, bias, y, stats, st);
-  }
-  size_t main_bytes = (size_t)p.halo_bytes + NW * BN * conv_wrs(CK);
-  size_t epi_bytes = conv_epilogue_lds(BN > 128 ? 128 : BN, 512);
-  size_t lds = main_bytes > epi_bytes ? main_bytes : epi_bytes;
-  if (lds > 160 * 1024) return OCR_ERR_UNSUPPORTED;
-  auto kern = conv_igemm_kernel<BN, CK, WCO, M16, TH, NW>;
-  static_assert(NW == 2 || (BN * (CK / 8)) % 512 == 0, "counted waits: every thread issues the same number of requests");
-  static size_t configured = 0;
-  if (lds > configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(160 * 1024)) != hipSuccess)
-      return OCR_ERR_HIP;
-    configured = 160 * 1024;
-  }
-  const int m_tiles = p.n * p.tiles_x * p.tiles_y;
-  dim3 grid((unsigned)(m_tiles * p.n_tiles));
-  ConvP q = p;
-  q.xcd_swizzle = grid.x % 8 == 0;      // XCD-aware order: A/B -0.04 ms on the headline step (profiles/r06_ab_xcd_swizzle.txt)
-  hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, q,
-                     static_cast<const half_t*>(x), static_cast<const half_t*>(w),
-                     static_cast<const float*>(bias), static_cast<half_t*>(y),
-                     static_cast<float*>(stats));
-  return ocr_launch_status();
-}
 
 // persistent weight-stationary variant: cin == 64, 64-cout tiles, 16x16x32 MFMA, 8-row tiles
 static bool conv_c64_ok(const ConvP& p) {
@@ -2230,7 +2127,7 @@ static bool conv_c64_ok(const ConvP& p) {
 }
 
 // workgroups per cout tile of the persistent 64-channel kernel: one workgroup per CU in all
-static int c64_per(const ConvP& p) {
+static int c64_per(int m_tiles, int n_tiles) {
   static int cus = 0;
   if (!cus) {
     int dev = 0;
@@ -2238,8 +2135,7 @@ static int c64_per(const ConvP& p) {
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
     cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
-  const int m_tiles = p.n * p.tiles_x * p.tiles_y;
-  int per = cus / p.n_tiles;
+  int per = cus / n_tiles;
   if (per < 1) per = 1;
   if (per > m_tiles) per = m_tiles;
   return per;
@@ -2250,71 +2146,18 @@ static int c64_per(const ConvP& p) {
 static int epi_mode(const ConvP& p) {
   const bool br = p.br.y != nullptr;
   const int fl = p.flags;
-  if (p.br.first_x4 != nullptr) return p.br.first_s1 != nullptr ? 7 : 6;      // (conv_c64_persist_kernel only: the entry point checks the variant)
+  if (p.br.first_x4 != nullptr) return p.br.first_s1 != nullptr ? 7 : 6;      // (conv_c64_persist_kernel only: the entry point checks the family)
   if (fl == OCR_CONV_STATS && !br) return 1;
   if (fl == OCR_CONV_STATS && br && p.br.mask == nullptr && p.br.mask_bits == nullptr) return p.br.store_dz ? 4 : 2;
   if (fl == (OCR_CONV_BIAS | OCR_CONV_RELU) && !br) return 3;
   if (fl == 0 && !br) return 5;
   return 0;
 }
-typedef void (*ConvKernT)(ConvP, const half_t*, const half_t*, const float*, half_t*, float*);
-
-template <bool POOL = false>
-static int launch_c64(const ConvP& p0, const void* x, const void* w, const void* bias, void* y, void* stats,
-                      hipStream_t st) {
-  // (the pooled variant exists for bias + ReLU layers only: its other modes are the generic instantiation)
-  constexpr bool P = POOL;
-  const int epi = P && epi_mode(p0) != 3 ? 0 : epi_mode(p0);
-  static const ConvKernT kerns[8] = {conv_c64_persist_kernel<64, P, 0>, conv_c64_persist_kernel<64, P, P ? 0 : 1>,
-                                     conv_c64_persist_kernel<64, P, P ? 0 : 2>, conv_c64_persist_kernel<64, P, 3>,
-                                     conv_c64_persist_kernel<64, P, P ? 0 : 4>, conv_c64_persist_kernel<64, P, P ? 0 : 5>,
-                                     conv_c64_persist_kernel<64, P, P ? 0 : 6>, conv_c64_persist_kernel<64, P, P ? 0 : 7>};
-  const ConvKernT kern = kerns[epi];
-  static bool configured[8] = {false, false, false, false, false, false, false, false};
-  if (!configured[epi]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(160 * 1024)) != hipSuccess)
-      return OCR_ERR_HIP;
-    configured[epi] = true;
-  }
-  ConvP p = p0;
-  p.tiles_y = ocr_cdiv(p.oh, 8);                 // (the tile configuration may have chosen 16-row tiles)
-  const int per = c64_per(p);
-  if (per <= 0) return OCR_ERR_HIP;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(per * p.n_tiles)), dim3(512), (size_t)C64_LDS, st, p,
-                     static_cast<const half_t*>(x), static_cast<const half_t*>(w), static_cast<const float*>(bias),
-                     static_cast<half_t*>(y), static_cast<float*>(stats));
-  return ocr_launch_status();
-}
 
 // 4-wave kernel: 3x3 / stride 1 / dilation 1, 64-channel chunks, 256-cout tiles, 16x16x32 MFMA
 static bool conv_w4_ok(const ConvP& p) {
   static const int on = [] { const char* e = getenv("OCR_CONV_W4"); return e ? atoi(e) : 1; }();
   return on && p.m16 && p.kh == 3 && p.kw == 3 && p.dil == 1 && p.stride == 1 && p.cin % 64 == 0 && p.cout % 256 == 0;
-}
-
-static int launch_w4(const ConvP& p, const void* x, const void* w, const void* bias, void* y, void* stats,
-                     hipStream_t st) {
-  const int epi = epi_mode(p);
-  typedef ConvKernT KernT;
-  static const KernT kerns[6] = {conv3x3_w4_kernel<0>, conv3x3_w4_kernel<1>, conv3x3_w4_kernel<2>,
-                                 conv3x3_w4_kernel<3>, conv3x3_w4_kernel<4>, conv3x3_w4_kernel<5>};
-  const KernT kern = kerns[epi];
-  static bool configured[6] = {false, false, false, false, false, false};
-  if (!configured[epi]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(160 * 1024)) != hipSuccess)
-      return OCR_ERR_HIP;
-    configured[epi] = true;
-  }
-  const int m_tiles = p.n * p.tiles_x * p.tiles_y;
-  dim3 grid((unsigned)(m_tiles * p.n_tiles));
-  ConvP q = p;
-  q.xcd_swizzle = grid.x % 8 == 0;      // XCD-aware order: A/B -0.04 ms on the headline step (profiles/r06_ab_xcd_swizzle.txt)
-  hipLaunchKernelGGL(kern, grid, dim3(256), (size_t)W4_LDS, st, q, static_cast<const half_t*>(x),
-                     static_cast<const half_t*>(w), static_cast<const float*>(bias), static_cast<half_t*>(y),
-                     static_cast<float*>(stats));
-  return ocr_launch_status();
 }
 
 // small-tile variant: two workgroups per CU; couts in 64- or 128-wide tiles (the 256-multiples go to conv3x3_w4)
@@ -2329,43 +2172,210 @@ static int conv_w4s_bn(const ConvP& p) {
   return p.cout % 128 == 0 ? 128 : p.cout % 64 == 0 ? 64 : 0;
 }
 
+// Which kernel runs one call, on what grid, leaving how many partial rows — the ONE place this is decided: the launch
+// (dispatch / dispatch_pwx), the row count the caller allocates (ocr_conv2d_num_mtiles), the name ocr_conv2d_variant
+// reports and the entry points that exist for one family only all read it.
+struct ConvPlan {
+  enum Family { PW, PWX, W4S, W4, C64, IGEMM } family = IGEMM;
+  int status = OCR_OK;            // OCR_ERR_UNSUPPORTED: no kernel takes this call
+  int bn = 0, ck = 0, th = 0;     // the tile the launch uses (PW with cin = 64: not always the TileCfg's)
+  int epi = 0;                    // W4S / W4 / C64: epi_mode; PW / PWX: the epilogue has global operands
+  int ring = 2;                   // IGEMM: slots of the weight ring
+  unsigned grid = 0, block = 512;
+  size_t lds = 0;
+  int xcd_swizzle = 0, tiles_y = 0, n_tiles = 0;      // ConvP's fields as the launch passes them
+  int rows = 0;                   // partial rows [rows][2][cout] the launch writes
+};
 
-// the persistent 64-channel kernel runs this shape (its partial rows are per wave of the grid, not per tile)
-static bool uses_c64(const ConvP& p, const TileCfg& c) {
-  return !p.pw && conv_w4s_bn(p) == 0 && c.bn == 64 && c.ck == 64 && c.th == 8 && conv_c64_ok(p);
+// p: filled, with the flags and p.br of the call; pool: the pooled epilogue (ocr_conv2d_relu_pool_f16); pwx: the
+// operand-transforming pointwise kernel's MODE (0: the plain entry points)
+static ConvPlan conv_plan(const ConvP& p, const TileCfg& c, bool pool = false, int pwx = 0) {
+  ConvPlan s;
+  s.bn = c.bn; s.ck = c.ck; s.th = c.th;
+  s.tiles_y = p.tiles_y;
+  s.n_tiles = p.n_tiles;
+  if (p.pw || pwx) {
+    s.family = pwx ? ConvPlan::PWX : ConvPlan::PW;
+    if (pool || (pwx && (!p.pw || p.cin < 128))) {       // (cin = 64: one stage, nothing to overlap the loads with)
+      s.status = OCR_ERR_UNSUPPORTED;
+      return s;
+    }
+    // two instantiations: the epilogue with global operands (ACCUM / BN-backward / tail) batches its loads
+    // ahead of its stores (conv_epilogue.h) and needs ~40 more registers than the store-only one; the backward
+    // form of the operand-transforming kernel always carries the fused BN-backward reduction
+    s.epi = pwx ? pwx == 2 : (p.flags & OCR_CONV_ACCUM_F16) != 0 || p.br.y != nullptr;
+    // cin = 64 (one K stage, nothing to prefetch under) without global operands in the epilogue: 128-cout tiles
+    // need 70 KB of LDS and 118 registers — two workgroups per CU, whose phases overlap (ResNet's 64 -> 256
+    // forward convolutions: one 256-cout workgroup per CU exposes its fetch latency on every tile)
+    // (the same split for the epilogue WITH global operands — ResNet stage-1 tails, 64 -> 256 input gradients with four
+    // operand streams — and 128-cout tiles on ONE stage buffer for store-only launches were measured too: not faster)
+    if (!pwx && c.bn == 256 && p.cin == 64 && !s.epi) {
+      s.bn = 128;
+      s.n_tiles = p.cout / 128;
+    }
+    const size_t stage = (size_t)s.bn * 128 + 256 * 128;
+    // one K stage (cin = 64): nothing to double-buffer; the transforming kernel: two stages + coefficients
+    const size_t main_bytes = pwx ? 2 * stage + (size_t)p.cin * 16 : (p.cin == 64 ? 1 : 2) * stage;
+    if (main_bytes > 160 * 1024) s.status = OCR_ERR_UNSUPPORTED;
+    // the store-only epilogue takes a 256-cout tile in two halves, the one with global operands in one piece
+    const size_t epi_bytes = conv_epilogue_lds(s.epi ? s.bn : (s.bn > 128 ? 128 : s.bn), 512);
+    s.lds = main_bytes > epi_bytes ? main_bytes : epi_bytes;
+    s.rows = (int)((p.npix + 255) / 256);                // flat 256-pixel tiles
+    s.grid = (unsigned)s.rows * s.n_tiles;
+    s.xcd_swizzle = s.n_tiles > 1 && s.grid % 8 == 0;
+    return s;
+  }
+  s.rows = p.n * p.tiles_x * ocr_cdiv(p.oh, TILE_H);     // one row per 8-row pixel tile (the persistent kernel: below)
+  const bool tail = p.br.mask != nullptr || p.br.mask_bits != nullptr;   // only the kernels ending in conv_epilogue_store implement it
+  const bool tile64 = c.ck == 64 && c.th == 8;
+  if (const int bn = tail || pool ? 0 : conv_w4s_bn(p)) {
+    s.family = ConvPlan::W4S;
+    s.bn = bn; s.ck = 64; s.th = 8;
+    s.epi = epi_mode(p);
+    s.tiles_y = ocr_cdiv(p.oh, 8);                 // (the tile configuration may have chosen 16-row tiles)
+    s.n_tiles = p.cout / bn;
+    s.block = 256;
+    s.lds = (size_t)w4s_lds(bn);
+  } else if (c.bn == 256 && tile64 && !tail && !pool && conv_w4_ok(p)) {
+    s.family = ConvPlan::W4;
+    s.epi = epi_mode(p);
+    s.block = 256;
+    s.lds = (size_t)W4_LDS;
+  } else if (c.bn == 64 && tile64 && conv_c64_ok(p)) {
+    s.family = ConvPlan::C64;
+    // (the pooled variant exists for bias + ReLU layers only: its other modes are the generic instantiation)
+    s.epi = pool && epi_mode(p) != 3 ? 0 : epi_mode(p);
+    s.lds = (size_t)C64_LDS;
+    const int per = c64_per(p.n * p.tiles_x * p.tiles_y, p.n_tiles);
+    s.grid = (unsigned)(per * p.n_tiles);
+    s.rows = 8 * per;                              // one row per wave of the persistent grid, not per tile ...
+    if (per <= 0) s.status = OCR_ERR_HIP;
+    if (tail) s.status = OCR_ERR_UNSUPPORTED;      // ... which the tail's kernels would not fill
+    return s;
+  } else {
+    s.family = ConvPlan::IGEMM;
+    // a three-slot weight ring for the 256-cout tiles, the slice requested two taps ahead (a four-slot ring was measured
+    // too, on fc6 — 144 tap steps of 32 MFMAs per tile — and the strided ResNet convolutions: headline 19.85 -> 19.96 ms,
+    // ResNet 39.31 -> 39.22: the tap step's cost is not the slice's fetch)
+    if (c.bn == 256 && p.m16 && c.th == 8 && p.kh * p.kw >= 3 &&
+        (size_t)p.halo_bytes + 3 * c.bn * conv_wrs(c.ck) <= 160 * 1024)
+      s.ring = 3;
+    const size_t main_bytes = (size_t)p.halo_bytes + s.ring * c.bn * conv_wrs(c.ck);
+    const size_t epi_bytes = conv_epilogue_lds(c.bn > 128 ? 128 : c.bn, 512);
+    s.lds = main_bytes > epi_bytes ? main_bytes : epi_bytes;
+    if (s.lds > 160 * 1024 || pool) s.status = OCR_ERR_UNSUPPORTED;
+  }
+  s.grid = (unsigned)(p.n * p.tiles_x * s.tiles_y * s.n_tiles);
+  s.xcd_swizzle = s.grid % 8 == 0;      // XCD-aware order: A/B -0.04 ms on the headline step (profiles/r06_ab_xcd_swizzle.txt)
+  return s;
 }
 
-template <int BN>
-static int launch_w4s(const ConvP& p0, const void* x, const void* w, const void* bias, void* y, void* stats,
-                      hipStream_t st) {
-  const int epi = epi_mode(p0);
-  static const ConvKernT kerns[6] = {conv3x3_w4s_kernel<BN, 0>, conv3x3_w4s_kernel<BN, 1>, conv3x3_w4s_kernel<BN, 2>,
-                                     conv3x3_w4s_kernel<BN, 3>, conv3x3_w4s_kernel<BN, 4>, conv3x3_w4s_kernel<BN, 5>};
-  const ConvKernT kern = kerns[epi];
-  static bool configured[6] = {false, false, false, false, false, false};
-  if (!configured[epi]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+// A kernel and whether its dynamic-LDS limit has been raised (once per process; not atomic).
+template <typename... KA>
+struct Kern {
+  void (*fn)(KA...);
+  bool configured;
+};
+typedef Kern<ConvP, const half_t*, const half_t*, const float*, half_t*, float*> ConvKern;
+typedef Kern<ConvP, PwX, const half_t*, half_t*, float*> PwxKern;
+
+template <typename... KA>
+static int launch_planned(Kern<KA...>& k, const ConvPlan& s, hipStream_t st, KA... args) {
+  void (*const fn)(KA...) = k.fn;
+  if (!k.configured) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(160 * 1024)) != hipSuccess)
       return OCR_ERR_HIP;
-    configured[epi] = true;
+    k.configured = true;
   }
-  ConvP p = p0;
-  p.tiles_y = ocr_cdiv(p.oh, 8);                 // (the tile configuration may have chosen 16-row tiles)
-  p.n_tiles = p.cout / BN;
-  const int m_tiles = p.n * p.tiles_x * p.tiles_y;
-  dim3 grid((unsigned)(m_tiles * p.n_tiles));
-  p.xcd_swizzle = grid.x % 8 == 0;
-  hipLaunchKernelGGL(kern, grid, dim3(256), (size_t)w4s_lds(BN), st, p, static_cast<const half_t*>(x),
-                     static_cast<const half_t*>(w), static_cast<const float*>(bias), static_cast<half_t*>(y),
-                     static_cast<float*>(stats));
+  hipLaunchKernelGGL(fn, dim3(s.grid), dim3(s.block), s.lds, st, args...);
   return ocr_launch_status();
 }
 
+// p as the planned launch passes it
+static ConvP planned_params(const ConvP& p, const ConvPlan& s) {
+  ConvP q = p;
+  q.tiles_y = s.tiles_y;
+  q.n_tiles = s.n_tiles;
+  q.xcd_swizzle = s.xcd_swizzle;
+  return q;
+}
+
+template <int BN, int WCO>
+static ConvKern* pw_kern(const ConvPlan& s) {
+  static ConvKern k[2] = {{conv_pw_kernel<BN, WCO, false>}, {conv_pw_kernel<BN, WCO, true>}};
+  return &k[s.epi];
+}
+
 template <int BN, int CK, int WCO, int TH = 8>
-int launch(const ConvP& p, const void* x, const void* w, const void* bias, void* y, void* stats,
-           hipStream_t st) {
-  return p.m16 ? launch_t<BN, CK, WCO, true, TH>(p, x, w, bias, y, stats, st)
-               : launch_t<BN, CK, WCO, false, TH>(p, x, w, bias, y, stats, st);
+static ConvKern* igemm_kern(const ConvPlan& s, bool m16) {
+  static ConvKern k[2] = {{conv_igemm_kernel<BN, CK, WCO, false, TH>}, {conv_igemm_kernel<BN, CK, WCO, true, TH>}};
+  if constexpr (BN == 256 && TH == 8) {
+    static_assert((BN * (CK / 8)) % 512 == 0, "counted waits: every thread issues the same number of requests");
+    static ConvKern k3 = {conv_igemm_kernel<BN, CK, WCO, true, TH, 3>};
+    if (s.ring == 3) return &k3;
+  }
+  return &k[m16];
+}
+
+template <int BN>
+static ConvKern* w4s_kern(const ConvPlan& s) {
+  static ConvKern k[6] = {{conv3x3_w4s_kernel<BN, 0>}, {conv3x3_w4s_kernel<BN, 1>}, {conv3x3_w4s_kernel<BN, 2>},
+                          {conv3x3_w4s_kernel<BN, 3>}, {conv3x3_w4s_kernel<BN, 4>}, {conv3x3_w4s_kernel<BN, 5>}};
+  return &k[s.epi];
+}
+
+template <bool P>
+static ConvKern* c64_kern(const ConvPlan& s) {
+  static ConvKern k[8] = {{conv_c64_persist_kernel<64, P, 0>}, {conv_c64_persist_kernel<64, P, P ? 0 : 1>},
+                          {conv_c64_persist_kernel<64, P, P ? 0 : 2>}, {conv_c64_persist_kernel<64, P, 3>},
+                          {conv_c64_persist_kernel<64, P, P ? 0 : 4>}, {conv_c64_persist_kernel<64, P, P ? 0 : 5>},
+                          {conv_c64_persist_kernel<64, P, P ? 0 : 6>}, {conv_c64_persist_kernel<64, P, P ? 0 : 7>}};
+  return &k[s.epi];
+}
+
+static ConvKern* conv_kern(const ConvPlan& s, const ConvP& p) {
+  static ConvKern w4[6] = {{conv3x3_w4_kernel<0>}, {conv3x3_w4_kernel<1>}, {conv3x3_w4_kernel<2>},
+                           {conv3x3_w4_kernel<3>}, {conv3x3_w4_kernel<4>}, {conv3x3_w4_kernel<5>}};
+  const bool k64 = s.ck == 64;
+  switch (s.family) {
+    case ConvPlan::PW: return s.bn == 256 ? pw_kern<256, 4>(s) : s.bn == 128 ? pw_kern<128, 2>(s) : pw_kern<64, 1>(s);
+    case ConvPlan::W4S: return s.bn == 128 ? w4s_kern<128>(s) : w4s_kern<64>(s);
+    case ConvPlan::W4: return &w4[s.epi];
+    case ConvPlan::C64: return p.pool_out ? c64_kern<true>(s) : c64_kern<false>(s);
+    case ConvPlan::IGEMM:
+      if (s.bn == 256) return k64 ? igemm_kern<256, 64, 4>(s, p.m16) : igemm_kern<256, 32, 4>(s, p.m16);
+      if (s.bn == 128 && s.th == 16) return k64 ? igemm_kern<128, 64, 2, 16>(s, p.m16) : igemm_kern<128, 32, 2, 16>(s, p.m16);
+      if (s.bn == 128) return k64 ? igemm_kern<128, 64, 2>(s, p.m16) : igemm_kern<128, 32, 2>(s, p.m16);
+      if (s.bn == 64) return k64 ? igemm_kern<64, 64, 2>(s, p.m16) : igemm_kern<64, 32, 2>(s, p.m16);
+      return k64 ? igemm_kern<32, 64, 1>(s, p.m16) : igemm_kern<32, 32, 1>(s, p.m16);
+    case ConvPlan::PWX: break;
+  }
+  return nullptr;
+}
+
+static int dispatch(const ConvP& p, const ConvPlan& s, const void* x, const void* w_kc, const void* bias, void* y,
+                    void* stats, hipStream_t st) {
+  if (s.status != OCR_OK) return s.status;
+  ConvKern* k = conv_kern(s, p);
+  if (!k) return OCR_ERR_UNSUPPORTED;
+  return launch_planned(*k, s, st, planned_params(p, s), static_cast<const half_t*>(x), static_cast<const half_t*>(w_kc),
+                        static_cast<const float*>(bias), static_cast<half_t*>(y), static_cast<float*>(stats));
+}
+
+template <int MODE>
+static int dispatch_pwx(const ConvP& p, const ConvPlan& s, const PwX& t, const void* w, void* y, void* stats,
+                        hipStream_t st) {
+  if (s.status != OCR_OK) return s.status;
+  constexpr bool EL = MODE == 2;
+  static PwxKern kerns[3][2] = {
+      {{conv_pwx_kernel<64, 1, EL, MODE, false>}, {conv_pwx_kernel<64, 1, EL, MODE, true>}},
+      {{conv_pwx_kernel<128, 2, EL, MODE, false>}, {conv_pwx_kernel<128, 2, EL, MODE, true>}},
+      {{conv_pwx_kernel<256, 4, EL, MODE, false>}, {conv_pwx_kernel<256, 4, EL, MODE, true>}}};
+  const bool proj = (MODE == 1 && t.f1 != nullptr) ||    // the shortcut is a projection: its batch norm is applied too
+                    (MODE == 2 && t.f3 != nullptr);      // the batch norm above is followed by a ReLU: its mask is applied too
+  return launch_planned(kerns[s.bn == 256 ? 2 : s.bn == 128][proj], s, st, planned_params(p, s), t,
+                        static_cast<const half_t*>(w), static_cast<half_t*>(y), static_cast<float*>(stats));
 }
 
 // Tile selection.  Workgroup tile = BN couts x (TH rows x 32 columns) pixels, CK input channels per
@@ -2443,117 +2453,75 @@ int fill_params(const ocr_conv_desc* d, ConvP* p, TileCfg* cfg) {
 
 OCR_DIAG_READER(ocr_diag_read_conv, ocr_diag_conv)
 
+// every entry point opens with it: the filled parameters p and tile cfg of d, or fill_params' code
+#define OCR_CONV_FILL(d, p, cfg)                        \
+  ConvP p;                                              \
+  TileCfg cfg;                                          \
+  do {                                                  \
+    const int rc_ = fill_params(d, &p, &cfg);           \
+    if (rc_ != OCR_OK) return rc_;                      \
+  } while (0)
+
+static BnRed bn_red(const void* bn_y, const void* bn_scale, const void* bn_shift, const void* bn_mean,
+                    const void* bn_invstd, int bn_relu) {
+  return BnRed{static_cast<const half_t*>(bn_y), static_cast<const float*>(bn_scale), static_cast<const float*>(bn_shift),
+               static_cast<const float*>(bn_mean), static_cast<const float*>(bn_invstd), bn_relu};
+}
+
 extern "C" int ocr_conv2d_num_mtiles(const ocr_conv_desc* d) {
   if (!d) return OCR_ERR_INVALID_ARG;
-  if (conv_is_pw(d)) return (int)(((long long)d->n * d->oh * d->ow + 255) / 256);   // flat 256-pixel tiles
   ConvP p;
   TileCfg c;
-  if (fill_params(d, &p, &c) == OCR_OK && uses_c64(p, c)) {
-    const int per = c64_per(p);                      // one row per wave of the persistent grid
-    return per > 0 ? 8 * per : OCR_ERR_HIP;
-  }
-  return d->n * ocr_cdiv(d->ow, TILE_W) * ocr_cdiv(d->oh, TILE_H);
+  if (fill_params(d, &p, &c) != OCR_OK)            // (no kernel takes d: the row count of its pixel tiles, as ever)
+    return conv_is_pw(d) ? (int)(((long long)d->n * d->oh * d->ow + 255) / 256)
+                         : d->n * ocr_cdiv(d->ow, TILE_W) * ocr_cdiv(d->oh, TILE_H);
+  const ConvPlan s = conv_plan(p, c);
+  return s.status == OCR_OK ? s.rows : s.status;
 }
 
+// The name is the NOMINAL tile of the family, which is not always the launched one: pointwise cin = 64 launches
+// without global operands in the epilogue run conv_pw_kernel<128,2> under the name <256,4>, and a bottleneck tail
+// (which a descriptor cannot express) moves the 4-wave families' shapes to conv_igemm_kernel.
 extern "C" int ocr_conv2d_variant(const ocr_conv_desc* d, char* out, size_t cap) {
-  ConvP p;
-  TileCfg c;
-  int rc = fill_params(d, &p, &c);
-  if (rc != OCR_OK) return rc;
+  OCR_CONV_FILL(d, p, c);
   OCR_CHECK_ARG(out && cap > 0);
-  if (p.pw) {
-    snprintf(out, cap, "conv_pw_kernel<%d,%d>", c.bn, c.bn == 256 ? 4 : c.bn == 128 ? 2 : 1);
-    return OCR_OK;
+  const ConvPlan s = conv_plan(p, c);
+  switch (s.family) {
+    case ConvPlan::PW:
+    case ConvPlan::PWX: snprintf(out, cap, "conv_pw_kernel<%d,%d>", c.bn, c.bn == 256 ? 4 : c.bn == 128 ? 2 : 1); break;
+    case ConvPlan::W4S: snprintf(out, cap, "conv3x3_w4s_kernel<%d>", s.bn); break;
+    case ConvPlan::W4: snprintf(out, cap, "conv3x3_w4_kernel"); break;
+    case ConvPlan::C64: snprintf(out, cap, "conv_c64_persist_kernel<64>"); break;
+    case ConvPlan::IGEMM:
+      snprintf(out, cap, "conv_igemm_kernel<%d,%d,%d,%d,%d>", c.bn, c.ck, c.bn == 256 ? 4 : c.bn == 32 ? 1 : 2, p.m16, c.th);
   }
-  const int wco = c.bn == 256 ? 4 : c.bn == 32 ? 1 : 2;
-  if (const int bn = conv_w4s_bn(p)) {
-    snprintf(out, cap, "conv3x3_w4s_kernel<%d>", bn);
-    return OCR_OK;
-  }
-  if (c.bn == 256 && c.ck == 64 && c.th == 8 && conv_w4_ok(p)) {
-    snprintf(out, cap, "conv3x3_w4_kernel");
-    return OCR_OK;
-  }
-  if (c.bn == 64 && c.ck == 64 && c.th == 8 && conv_c64_ok(p)) {
-    snprintf(out, cap, "conv_c64_persist_kernel<64>");
-    return OCR_OK;
-  }
-  snprintf(out, cap, "conv_igemm_kernel<%d,%d,%d,%d,%d>", c.bn, c.ck, wco, p.m16, c.th);
   return OCR_OK;
-}
-
-static int dispatch(ConvP& p, TileCfg c, const void* x, const void* w_kc, const void* bias, void* y,
-                    void* stats, hipStream_t st) {
-  if (p.pw) {
-    // cin = 64 (one K stage, nothing to prefetch under) without global operands in the epilogue: 128-cout tiles
-    // need 70 KB of LDS and 118 registers — two workgroups per CU, whose phases overlap (ResNet's 64 -> 256
-    // forward convolutions: one 256-cout workgroup per CU exposes its fetch latency on every tile)
-    const bool epi_loads = (p.flags & OCR_CONV_ACCUM_F16) != 0 || p.br.y != nullptr;
-    if (c.bn == 256 && p.cin == 64 && !epi_loads) {
-      p.n_tiles = p.cout / 128;
-      return launch_pw<128, 2>(p, x, w_kc, bias, y, stats, st);
-    }
-    // (the same split for the epilogue WITH global operands — ResNet stage-1 tails, 64 -> 256 input gradients with four
-    // operand streams — and 128-cout tiles on ONE stage buffer for store-only launches were measured too: not faster)
-    if (c.bn == 256) return launch_pw<256, 4>(p, x, w_kc, bias, y, stats, st);
-    if (c.bn == 128) return launch_pw<128, 2>(p, x, w_kc, bias, y, stats, st);
-    return launch_pw<64, 1>(p, x, w_kc, bias, y, stats, st);
-  }
-  const bool tail = p.br.mask != nullptr || p.br.mask_bits != nullptr;   // only the kernels ending in conv_epilogue_store implement it
-  if (const int bn = tail ? 0 : conv_w4s_bn(p))
-    return bn == 128 ? launch_w4s<128>(p, x, w_kc, bias, y, stats, st) : launch_w4s<64>(p, x, w_kc, bias, y, stats, st);
-  const int key = c.bn * 10000 + c.ck * 100 + c.th;
-  switch (key) {
-    case 2566408:
-      if (!tail && conv_w4_ok(p)) return launch_w4(p, x, w_kc, bias, y, stats, st);
-      return launch<256, 64, 4>(p, x, w_kc, bias, y, stats, st);
-    case 2563208: return launch<256, 32, 4>(p, x, w_kc, bias, y, stats, st);
-    case 1286416: return launch<128, 64, 2, 16>(p, x, w_kc, bias, y, stats, st);
-    case 1283216: return launch<128, 32, 2, 16>(p, x, w_kc, bias, y, stats, st);
-    case 1286408: return launch<128, 64, 2>(p, x, w_kc, bias, y, stats, st);
-    case 1283208: return launch<128, 32, 2>(p, x, w_kc, bias, y, stats, st);
-    case 646408:
-      if (conv_c64_ok(p)) {
-        if (tail) return OCR_ERR_UNSUPPORTED;      // (ocr_conv2d_num_mtiles sized the partials for launch_c64)
-        return launch_c64<false>(p, x, w_kc, bias, y, stats, st);
-      }
-      return launch<64, 64, 2>(p, x, w_kc, bias, y, stats, st);
-    case 643208: return launch<64, 32, 2>(p, x, w_kc, bias, y, stats, st);
-    case 326408: return launch<32, 64, 1>(p, x, w_kc, bias, y, stats, st);
-    case 323208: return launch<32, 32, 1>(p, x, w_kc, bias, y, stats, st);
-  }
-  return OCR_ERR_UNSUPPORTED;
 }
 
 extern "C" int ocr_conv2d_f16(const ocr_conv_desc* d, const void* x, const void* w_kc,
                               const void* bias, void* y, void* stats, void* stream) {
-  ConvP p;
-  TileCfg cfg;
-  int rc = fill_params(d, &p, &cfg);
-  if (rc != OCR_OK) return rc;
+  OCR_CONV_FILL(d, p, cfg);
   OCR_CHECK_ARG(x && w_kc && y);
   OCR_CHECK_ARG(!(d->flags & OCR_CONV_BIAS) || bias);
   OCR_CHECK_ARG(!(d->flags & OCR_CONV_STATS) || stats);
-  return dispatch(p, cfg, x, w_kc, bias, y, stats, static_cast<hipStream_t>(stream));
+  return dispatch(p, conv_plan(p, cfg), x, w_kc, bias, y, stats, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ocr_conv2d_bnred_f16(const ocr_conv_desc* d, const void* x, const void* w_kc, void* y,
                                     void* partial, const void* bn_y, const void* bn_scale,
                                     const void* bn_shift, const void* bn_mean, const void* bn_invstd,
                                     int bn_relu, int store_masked, void* stream) {
-  ConvP p;
-  TileCfg cfg;
-  int rc = fill_params(d, &p, &cfg);
-  if (rc != OCR_OK) return rc;
+  OCR_CONV_FILL(d, p, cfg);
   OCR_CHECK_ARG(x && w_kc && y && partial && bn_y && bn_scale && bn_shift && bn_mean && bn_invstd);
   OCR_CHECK_ARG(!(d->flags & (OCR_CONV_BIAS | OCR_CONV_RELU)));
   p.flags |= OCR_CONV_STATS;
-  p.br = BnRed{static_cast<const half_t*>(bn_y), static_cast<const float*>(bn_scale),
-               static_cast<const float*>(bn_shift), static_cast<const float*>(bn_mean),
-               static_cast<const float*>(bn_invstd), bn_relu};
+  p.br = bn_red(bn_y, bn_scale, bn_shift, bn_mean, bn_invstd, bn_relu);
   p.br.store_dz = store_masked;
-  return dispatch(p, cfg, x, w_kc, nullptr, y, partial, static_cast<hipStream_t>(stream));
+  return dispatch(p, conv_plan(p, cfg), x, w_kc, nullptr, y, partial, static_cast<hipStream_t>(stream));
 }
+
+// the two entry points below exist for the persistent kernel's 64 -> 64 launches only
+static bool first_ok(const ConvP& p, const ConvPlan& s) { return s.family == ConvPlan::C64 && p.cout == 64; }
 
 // ocr_conv2d_bnred_f16 for the convolution that consumes conv1_1's activation (conv1_2 of nets/vgg.py:17): the fused
 // BN-backward sums need conv1_1's y, and instead of reading 128 B per pixel the epilogue evaluates it again from the
@@ -2562,19 +2530,16 @@ extern "C" int ocr_conv2d_bnred_first_f16(const ocr_conv_desc* d, const void* x,
                                           void* partial, const void* x4, const void* w_first,
                                           const void* bn_scale, const void* bn_shift, const void* bn_mean,
                                           const void* bn_invstd, int bn_relu, void* stream) {
-  ConvP p;
-  TileCfg cfg;
-  int rc = fill_params(d, &p, &cfg);
-  if (rc != OCR_OK) return rc;
+  OCR_CONV_FILL(d, p, cfg);
   OCR_CHECK_ARG(x && w_kc && y && partial && x4 && w_first && bn_scale && bn_shift && bn_mean && bn_invstd);
   OCR_CHECK_ARG(!(d->flags & (OCR_CONV_BIAS | OCR_CONV_RELU | OCR_CONV_ACCUM_F16)));
-  if (!uses_c64(p, cfg) || p.cout != 64) return OCR_ERR_UNSUPPORTED;
   p.flags |= OCR_CONV_STATS;
-  p.br = BnRed{nullptr, static_cast<const float*>(bn_scale), static_cast<const float*>(bn_shift),
-               static_cast<const float*>(bn_mean), static_cast<const float*>(bn_invstd), bn_relu};
+  p.br = bn_red(nullptr, bn_scale, bn_shift, bn_mean, bn_invstd, bn_relu);
   p.br.first_x4 = static_cast<const half_t*>(x4);
   p.br.first_wf = static_cast<const half_t*>(w_first);
-  return launch_c64<false>(p, x, w_kc, nullptr, y, partial, static_cast<hipStream_t>(stream));
+  const ConvPlan s = conv_plan(p, cfg);
+  if (!first_ok(p, s)) return OCR_ERR_UNSUPPORTED;
+  return dispatch(p, s, x, w_kc, nullptr, y, partial, static_cast<hipStream_t>(stream));
 }
 
 // ocr_conv2d_bnred_first_f16 that does not store the gradient but the sums conv1_1's weight gradient is made of
@@ -2583,29 +2548,25 @@ extern "C" int ocr_conv2d_bnred_first_wgrad_blocks(const ocr_conv_desc* d) {
   ConvP p;
   TileCfg cfg;
   if (fill_params(d, &p, &cfg) != OCR_OK) return -1;
-  if (!uses_c64(p, cfg) || p.cout != 64) return -1;
-  p.tiles_y = ocr_cdiv(p.oh, 8);
-  return c64_per(p) * p.n_tiles;
+  const ConvPlan s = conv_plan(p, cfg);
+  return first_ok(p, s) && s.status == OCR_OK ? (int)s.grid : -1;
 }
 
 extern "C" int ocr_conv2d_bnred_first_wgrad_f16(const ocr_conv_desc* d, const void* x, const void* w_kc, void* partial,
                                                 const void* x4, const void* w_first, const void* bn_scale,
                                                 const void* bn_shift, const void* bn_mean, const void* bn_invstd,
                                                 int bn_relu, void* s1_blocks, void* stream) {
-  ConvP p;
-  TileCfg cfg;
-  int rc = fill_params(d, &p, &cfg);
-  if (rc != OCR_OK) return rc;
+  OCR_CONV_FILL(d, p, cfg);
   OCR_CHECK_ARG(x && w_kc && partial && x4 && w_first && bn_scale && bn_shift && bn_mean && bn_invstd && s1_blocks);
   OCR_CHECK_ARG(!(d->flags & (OCR_CONV_BIAS | OCR_CONV_RELU | OCR_CONV_ACCUM_F16)));
-  if (!uses_c64(p, cfg) || p.cout != 64) return OCR_ERR_UNSUPPORTED;
   p.flags |= OCR_CONV_STATS;
-  p.br = BnRed{nullptr, static_cast<const float*>(bn_scale), static_cast<const float*>(bn_shift),
-               static_cast<const float*>(bn_mean), static_cast<const float*>(bn_invstd), bn_relu};
+  p.br = bn_red(nullptr, bn_scale, bn_shift, bn_mean, bn_invstd, bn_relu);
   p.br.first_x4 = static_cast<const half_t*>(x4);
   p.br.first_wf = static_cast<const half_t*>(w_first);
   p.br.first_s1 = static_cast<float*>(s1_blocks);
-  return launch_c64<false>(p, x, w_kc, nullptr, nullptr, partial, static_cast<hipStream_t>(stream));
+  const ConvPlan s = conv_plan(p, cfg);
+  if (!first_ok(p, s)) return OCR_ERR_UNSUPPORTED;
+  return dispatch(p, s, x, w_kc, nullptr, nullptr, partial, static_cast<hipStream_t>(stream));
 }
 
 // 1x1 convolution whose input is the previous bottleneck's output relu(bn(conv3) + shortcut), computed while the
@@ -2615,10 +2576,7 @@ extern "C" int ocr_conv2d_pw_bnaddrelu_f16(const ocr_conv_desc* d, const void* p
                                            const void* prev_shift, const void* shortcut, const void* sc_scale,
                                            const void* sc_shift, void* x_out, void* mask_bits, const void* w_kc,
                                            void* y, void* stats, void* stream) {
-  ConvP p;
-  TileCfg cfg;
-  int rc = fill_params(d, &p, &cfg);
-  if (rc != OCR_OK) return rc;
+  OCR_CONV_FILL(d, p, cfg);
   OCR_CHECK_ARG(prev_y && prev_scale && prev_shift && shortcut && x_out && w_kc && y);
   OCR_CHECK_ARG((sc_scale == nullptr) == (sc_shift == nullptr));
   OCR_CHECK_ARG(!(d->flags & (OCR_CONV_BIAS | OCR_CONV_RELU | OCR_CONV_ACCUM_F16)));
@@ -2626,7 +2584,7 @@ extern "C" int ocr_conv2d_pw_bnaddrelu_f16(const ocr_conv_desc* d, const void* p
   PwX t{static_cast<const half_t*>(prev_y), static_cast<const half_t*>(shortcut), static_cast<const float*>(prev_scale),
         static_cast<const float*>(sc_scale), static_cast<const float*>(prev_shift), static_cast<const float*>(sc_shift),
         static_cast<half_t*>(x_out), static_cast<unsigned char*>(mask_bits)};
-  return dispatch_pwx<1>(p, cfg, t, w_kc, y, stats, static_cast<hipStream_t>(stream));
+  return dispatch_pwx<1>(p, conv_plan(p, cfg, false, 1), t, w_kc, y, stats, static_cast<hipStream_t>(stream));
 }
 
 // 1x1 convolution whose input x = relu(prev_y * prev_scale + prev_shift) — the batch norm + ReLU of the layer before it —
@@ -2635,16 +2593,13 @@ extern "C" int ocr_conv2d_pw_bnaddrelu_f16(const ocr_conv_desc* d, const void* p
 extern "C" int ocr_conv2d_pw_bnrelu_f16(const ocr_conv_desc* d, const void* prev_y, const void* prev_scale,
                                         const void* prev_shift, void* x_out, const void* w_kc, void* y, void* stats,
                                         void* stream) {
-  ConvP p;
-  TileCfg cfg;
-  int rc = fill_params(d, &p, &cfg);
-  if (rc != OCR_OK) return rc;
+  OCR_CONV_FILL(d, p, cfg);
   OCR_CHECK_ARG(prev_y && prev_scale && prev_shift && x_out && w_kc && y);
   OCR_CHECK_ARG(!(d->flags & (OCR_CONV_BIAS | OCR_CONV_RELU | OCR_CONV_ACCUM_F16)));
   OCR_CHECK_ARG(!(d->flags & OCR_CONV_STATS) || stats);
   PwX t{static_cast<const half_t*>(prev_y), nullptr, static_cast<const float*>(prev_scale), nullptr,
         static_cast<const float*>(prev_shift), nullptr, static_cast<half_t*>(x_out), nullptr};
-  return dispatch_pwx<3>(p, cfg, t, w_kc, y, stats, static_cast<hipStream_t>(stream));
+  return dispatch_pwx<3>(p, conv_plan(p, cfg, false, 3), t, w_kc, y, stats, static_cast<hipStream_t>(stream));
 }
 
 // Input-gradient 1x1 convolution whose operand is the batch-norm backward apply dy = A*dz + B*bn_y_in + C of the
@@ -2656,38 +2611,31 @@ extern "C" int ocr_conv2d_pw_bnbwd_bnred_f16(const ocr_conv_desc* d, const void*
                                              const void* w_kc, void* dx, void* partial, const void* bn_y,
                                              const void* bn_scale, const void* bn_shift, const void* bn_mean,
                                              const void* bn_invstd, int bn_relu, void* stream) {
-  ConvP p;
-  TileCfg cfg;
-  int rc = fill_params(d, &p, &cfg);
-  if (rc != OCR_OK) return rc;
+  OCR_CONV_FILL(d, p, cfg);
   OCR_CHECK_ARG(dz && y_above && coef_a && coef_b && coef_c && dy_out && w_kc && dx);
   OCR_CHECK_ARG(partial && bn_y && bn_scale && bn_shift && bn_mean && bn_invstd);
   OCR_CHECK_ARG(!(d->flags & (OCR_CONV_BIAS | OCR_CONV_RELU | OCR_CONV_ACCUM_F16)));
   p.flags |= OCR_CONV_STATS;
-  p.br = BnRed{static_cast<const half_t*>(bn_y), static_cast<const float*>(bn_scale),
-               static_cast<const float*>(bn_shift), static_cast<const float*>(bn_mean),
-               static_cast<const float*>(bn_invstd), bn_relu};
+  p.br = bn_red(bn_y, bn_scale, bn_shift, bn_mean, bn_invstd, bn_relu);
   PwX t{static_cast<const half_t*>(dz), static_cast<const half_t*>(y_above), static_cast<const float*>(coef_a),
         static_cast<const float*>(coef_b), static_cast<const float*>(coef_c), nullptr, static_cast<half_t*>(dy_out),
         nullptr};
-  return dispatch_pwx<2>(p, cfg, t, w_kc, dx, partial, static_cast<hipStream_t>(stream));
+  return dispatch_pwx<2>(p, conv_plan(p, cfg, false, 2), t, w_kc, dx, partial, static_cast<hipStream_t>(stream));
 }
 
 // conv + bias + ReLU + 2x2/2 max-pool in one kernel for 64 -> 64 channel 3x3 layers (PixelLink's conv1_2 and the same
 // layer at 1024^2 inference): only the pooled activation and its first-max positions are written.
 extern "C" int ocr_conv2d_relu_pool_f16(const ocr_conv_desc* d, const void* x, const void* w_kc, const void* bias,
                                         void* pooled, void* argmax_u8, void* stream) {
-  ConvP p;
-  TileCfg cfg;
-  int rc = fill_params(d, &p, &cfg);
-  if (rc != OCR_OK) return rc;
+  OCR_CONV_FILL(d, p, cfg);
   OCR_CHECK_ARG(x && w_kc && pooled);
   OCR_CHECK_ARG(!(d->flags & OCR_CONV_BIAS) || bias);
   OCR_CHECK_ARG(!(d->flags & (OCR_CONV_STATS | OCR_CONV_ACCUM_F16)));
-  if (p.pw || cfg.bn != 64 || cfg.ck != 64 || !conv_c64_ok(p)) return OCR_ERR_UNSUPPORTED;
   p.pool_out = static_cast<half_t*>(pooled);
   p.pool_idx = static_cast<unsigned char*>(argmax_u8);
-  return launch_c64<true>(p, x, w_kc, bias, nullptr, nullptr, static_cast<hipStream_t>(stream));
+  const ConvPlan s = conv_plan(p, cfg, true);
+  if (s.family != ConvPlan::C64) return OCR_ERR_UNSUPPORTED;
+  return dispatch(p, s, x, w_kc, bias, nullptr, nullptr, static_cast<hipStream_t>(stream));
 }
 
 // q = (P * m) >> (31 + l) == P / d for every P < 2^31 (round-up method: m = ceil(2^(31+l) / d), l = ceil(log2 d))
@@ -2698,19 +2646,12 @@ static void magic31(unsigned d, unsigned long long* m, int* l) {
   *m = ((1ull << (31 + k)) + d - 1) / d;
 }
 
-extern "C" int ocr_conv2d_bnred_tail_f16(const ocr_conv_desc* d, const void* x, const void* w_kc, void* y,
-                                         void* partial, const void* bn_y, const void* bn_mean,
-                                         const void* bn_invstd, const void* tail_out, const void* tail_mask_bits,
-                                         const void* sub_grad, void* stream) {
-  ConvP p;
-  TileCfg cfg;
-  int rc = fill_params(d, &p, &cfg);
-  if (rc != OCR_OK) return rc;
-  OCR_CHECK_ARG(x && w_kc && y && partial && bn_y && bn_mean && bn_invstd && (tail_out || tail_mask_bits));
-  OCR_CHECK_ARG(!(d->flags & (OCR_CONV_BIAS | OCR_CONV_RELU)));
+// the bottleneck tail of ocr_conv2d_bnred_tail_f16 in p (its arguments checked by the caller)
+static int set_tail(ConvP& p, const ocr_conv_desc* d, const void* bn_y, const void* bn_mean, const void* bn_invstd,
+                    const void* tail_out, const void* tail_mask_bits, const void* sub_grad) {
   p.flags |= OCR_CONV_STATS;
-  p.br = BnRed{static_cast<const half_t*>(bn_y), nullptr, nullptr, static_cast<const float*>(bn_mean),
-               static_cast<const float*>(bn_invstd), 0, static_cast<const half_t*>(tail_mask_bits ? nullptr : tail_out)};
+  p.br = bn_red(bn_y, nullptr, nullptr, bn_mean, bn_invstd, 0);
+  p.br.mask = static_cast<const half_t*>(tail_mask_bits ? nullptr : tail_out);
   p.br.mask_bits = static_cast<const unsigned char*>(tail_mask_bits);
   if (sub_grad != nullptr) {
     OCR_CHECK_SHAPE((long long)d->n * d->oh * d->ow < (1ll << 31));
@@ -2720,7 +2661,18 @@ extern "C" int ocr_conv2d_bnred_tail_f16(const ocr_conv_desc* d, const void* x, 
     magic31((unsigned)(d->oh * d->ow), &p.br.sub_m_hw, &p.br.sub_l_hw);
     magic31((unsigned)d->ow, &p.br.sub_m_w, &p.br.sub_l_w);
   }
-  return dispatch(p, cfg, x, w_kc, nullptr, y, partial, static_cast<hipStream_t>(stream));
+  return OCR_OK;
+}
+
+extern "C" int ocr_conv2d_bnred_tail_f16(const ocr_conv_desc* d, const void* x, const void* w_kc, void* y,
+                                         void* partial, const void* bn_y, const void* bn_mean,
+                                         const void* bn_invstd, const void* tail_out, const void* tail_mask_bits,
+                                         const void* sub_grad, void* stream) {
+  OCR_CONV_FILL(d, p, cfg);
+  OCR_CHECK_ARG(x && w_kc && y && partial && bn_y && bn_mean && bn_invstd && (tail_out || tail_mask_bits));
+  OCR_CHECK_ARG(!(d->flags & (OCR_CONV_BIAS | OCR_CONV_RELU)));
+  if (const int rc = set_tail(p, d, bn_y, bn_mean, bn_invstd, tail_out, tail_mask_bits, sub_grad)) return rc;
+  return dispatch(p, conv_plan(p, cfg), x, w_kc, nullptr, y, partial, static_cast<hipStream_t>(stream));
 }
 
 // ocr_conv2d_pw_bnbwd_bnred_f16's loader (the BN-backward apply of the layer ABOVE computed on the operand rows, optionally
@@ -2732,32 +2684,19 @@ extern "C" int ocr_conv2d_pw_bnbwd_tail_f16(const ocr_conv_desc* d, const void* 
                                             const void* w_kc, void* dx, void* partial, const void* bn_y,
                                             const void* bn_mean, const void* bn_invstd, const void* tail_out,
                                             const void* tail_mask_bits, const void* sub_grad, void* stream) {
-  ConvP p;
-  TileCfg cfg;
-  int rc = fill_params(d, &p, &cfg);
-  if (rc != OCR_OK) return rc;
+  OCR_CONV_FILL(d, p, cfg);
   OCR_CHECK_ARG(dz && y_above && coef_a && coef_b && coef_c && dy_out && w_kc && dx);
   OCR_CHECK_ARG(!(d->flags & (OCR_CONV_BIAS | OCR_CONV_RELU | OCR_CONV_STATS)));
   const bool tail = bn_y != nullptr;
   if (tail) {
     OCR_CHECK_ARG(partial && bn_mean && bn_invstd && (tail_out || tail_mask_bits));
-    p.flags |= OCR_CONV_STATS;
-    p.br = BnRed{static_cast<const half_t*>(bn_y), nullptr, nullptr, static_cast<const float*>(bn_mean),
-                 static_cast<const float*>(bn_invstd), 0, static_cast<const half_t*>(tail_mask_bits ? nullptr : tail_out)};
-    p.br.mask_bits = static_cast<const unsigned char*>(tail_mask_bits);
-    if (sub_grad != nullptr) {
-      OCR_CHECK_SHAPE((long long)d->n * d->oh * d->ow < (1ll << 31));
-      p.br.sub = static_cast<const half_t*>(sub_grad);
-      p.br.sub_h = d->oh;
-      p.br.sub_w = d->ow;
-      magic31((unsigned)(d->oh * d->ow), &p.br.sub_m_hw, &p.br.sub_l_hw);
-      magic31((unsigned)d->ow, &p.br.sub_m_w, &p.br.sub_l_w);
-    }
+    if (const int rc = set_tail(p, d, bn_y, bn_mean, bn_invstd, tail_out, tail_mask_bits, sub_grad)) return rc;
   } else {
     OCR_CHECK_ARG(!bn_mean && !bn_invstd && !tail_out && !tail_mask_bits && !sub_grad);
   }
   PwX t{static_cast<const half_t*>(dz), static_cast<const half_t*>(y_above), static_cast<const float*>(coef_a),
         static_cast<const float*>(coef_b), static_cast<const float*>(coef_c), static_cast<const float*>(relu_shift),
         static_cast<half_t*>(dy_out), nullptr};
-  return dispatch_pwx<2>(p, cfg, t, w_kc, dx, tail ? partial : nullptr, static_cast<hipStream_t>(stream));
+  return dispatch_pwx<2>(p, conv_plan(p, cfg, false, 2), t, w_kc, dx, tail ? partial : nullptr,
+                         static_cast<hipStream_t>(stream));
 }

@@ -88,37 +88,37 @@ def conv2d_variant(d):
     return v
 
 
-def conv2d(d, x, w_kc, y, bias=None, stats=None):
-    flops = 2.0 * d.n * d.oh * d.ow * d.cout * d.cin * d.kh * d.kw
-    # tag: (kernel instantiation, FLOP, phase) -- phase "fwd" launches run with nothing beside them,
-    # "dgrad" launches share the GPU with the side-stream weight gradients
-    tag = (conv2d_variant(d), flops, "dgrad" if d.flip_taps else "fwd")
-    if KERNEL_TIMING is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L.call("ocr_conv2d_f16", byref(d), ptr(x), ptr(w_kc), ptr(bias), ptr(y), ptr(stats), _st())
-        e1.record()
-        KERNEL_TIMING.append(tag + (e0, e1))
-    else:
-        L.call("ocr_conv2d_f16", byref(d), ptr(x), ptr(w_kc), ptr(bias), ptr(y), ptr(stats), _st())
+def _conv_call(fn, d, *args, phase, pwx=False, timed=False):
+    """One conv entry point `fn(d, *args, stream)` with its tag (kernel instantiation, FLOP, phase) for the recorder:
+    phase "fwd" launches run with nothing beside them, "dgrad" launches share the GPU with the side-stream weight
+    gradients.  pwx: the operand-transforming 1x1 entries run conv_pwx_kernel where ocr_conv2d_variant names
+    conv_pw_kernel.  timed: bracketed by HIP events when KERNEL_TIMING is a list."""
+    tag = None
+    if timed or L.RECORDER is not None:
+        v = conv2d_variant(d)
+        if pwx:
+            v = v.replace("conv_pw_kernel", "conv_pwx_kernel")
+        tag = (v, 2.0 * d.n * d.oh * d.ow * d.cout * d.cin * d.kh * d.kw, phase)
+    events = None
+    if timed and KERNEL_TIMING is not None:
+        events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        events[0].record()
+    L.call(fn, byref(d), *args, _st())
+    if events is not None:
+        events[1].record()
+        KERNEL_TIMING.append(tag + events)
     if L.RECORDER is not None:
         L.RECORDER.tag_last(tag)
+
+
+def conv2d(d, x, w_kc, y, bias=None, stats=None):
+    _conv_call("ocr_conv2d_f16", d, ptr(x), ptr(w_kc), ptr(bias), ptr(y), ptr(stats),
+               phase="dgrad" if d.flip_taps else "fwd", timed=True)
 
 
 def conv2d_relu_pool(d, x, w_kc, bias, pooled, argmax=None):
     """conv3x3 + bias + ReLU + 2x2/2 max-pool in one kernel (64 -> 64 channels): pooled output (+ first-max positions) only."""
-    flops = 2.0 * d.n * d.oh * d.ow * d.cout * d.cin * d.kh * d.kw
-    tag = (conv2d_variant(d), flops, "fwd")
-    if KERNEL_TIMING is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L.call("ocr_conv2d_relu_pool_f16", byref(d), ptr(x), ptr(w_kc), ptr(bias), ptr(pooled), ptr(argmax), _st())
-        e1.record()
-        KERNEL_TIMING.append(tag + (e0, e1))
-    else:
-        L.call("ocr_conv2d_relu_pool_f16", byref(d), ptr(x), ptr(w_kc), ptr(bias), ptr(pooled), ptr(argmax), _st())
-    if L.RECORDER is not None:
-        L.RECORDER.tag_last(tag)
+    _conv_call("ocr_conv2d_relu_pool_f16", d, ptr(x), ptr(w_kc), ptr(bias), ptr(pooled), ptr(argmax), phase="fwd", timed=True)
 
 
 def conv2d_bnred(d, x, w_kc, y, partial, bn_ctx, store_masked=False):
@@ -127,11 +127,8 @@ def conv2d_bnred(d, x, w_kc, y, partial, bn_ctx, store_masked=False):
     by, sc, sh, mu, istd, relu = bn_ctx
     if isinstance(by, LazyFirstY):
         by = by.tensor()                 # a consumer that cannot recompute conv1_1's y: evaluate and store it now
-    L.call("ocr_conv2d_bnred_f16", byref(d), ptr(x), ptr(w_kc), ptr(y), ptr(partial), ptr(by), ptr(sc),
-           ptr(sh), ptr(mu), ptr(istd), c_int(int(relu)), c_int(int(store_masked)), _st())
-    if L.RECORDER is not None:
-        flops = 2.0 * d.n * d.oh * d.ow * d.cout * d.cin * d.kh * d.kw
-        L.RECORDER.tag_last((conv2d_variant(d), flops, "dgrad"))
+    _conv_call("ocr_conv2d_bnred_f16", d, ptr(x), ptr(w_kc), ptr(y), ptr(partial), ptr(by), ptr(sc), ptr(sh), ptr(mu),
+               ptr(istd), c_int(int(relu)), c_int(int(store_masked)), phase="dgrad")
 
 
 class LazyFirstY:
@@ -155,11 +152,8 @@ def conv2d_bnred_first(d, x, w_kc, y, partial, first_ctx):
     """conv2d_bnred for the consumer of conv1_1's activation with conv1_1's y recomputed from the image instead of read:
     first_ctx = (x4, w_first, scale, shift, mean, invstd, relu)."""
     x4, wf, sc, sh, mu, istd, relu = first_ctx
-    L.call("ocr_conv2d_bnred_first_f16", byref(d), ptr(x), ptr(w_kc), ptr(y), ptr(partial), ptr(x4), ptr(wf), ptr(sc),
-           ptr(sh), ptr(mu), ptr(istd), c_int(int(relu)), _st())
-    if L.RECORDER is not None:
-        flops = 2.0 * d.n * d.oh * d.ow * d.cout * d.cin * d.kh * d.kw
-        L.RECORDER.tag_last((conv2d_variant(d), flops, "dgrad"))
+    _conv_call("ocr_conv2d_bnred_first_f16", d, ptr(x), ptr(w_kc), ptr(y), ptr(partial), ptr(x4), ptr(wf), ptr(sc), ptr(sh),
+               ptr(mu), ptr(istd), c_int(int(relu)), phase="dgrad")
 
 
 def conv2d_bnred_first_wgrad_blocks(d):
@@ -171,11 +165,8 @@ def conv2d_bnred_first_wgrad(d, x, w_kc, partial, first_ctx, s1):
     """conv2d_bnred_first that does not store the gradient: `s1` [blocks][32][64] f32 receives the sums conv1_1's weight
     gradient is finished from (conv2d_first_wgrad_sums)."""
     x4, wf, sc, sh, mu, istd, relu = first_ctx
-    L.call("ocr_conv2d_bnred_first_wgrad_f16", byref(d), ptr(x), ptr(w_kc), ptr(partial), ptr(x4), ptr(wf), ptr(sc),
-           ptr(sh), ptr(mu), ptr(istd), c_int(int(relu)), ptr(s1), _st())
-    if L.RECORDER is not None:
-        flops = 2.0 * d.n * d.oh * d.ow * d.cout * d.cin * d.kh * d.kw
-        L.RECORDER.tag_last((conv2d_variant(d), flops, "dgrad"))
+    _conv_call("ocr_conv2d_bnred_first_wgrad_f16", d, ptr(x), ptr(w_kc), ptr(partial), ptr(x4), ptr(wf), ptr(sc), ptr(sh),
+               ptr(mu), ptr(istd), c_int(int(relu)), ptr(s1), phase="dgrad")
 
 
 def conv2d_first_wgrad_sums(s1, moments, w_first, coef, dw):
@@ -192,29 +183,20 @@ def conv2d_bnred_tail(d, x, w_kc, y, partial, tail_ctx, sub_grad=None):
     with `bits` (the output's ReLU mask, one byte per 8 channels) the kernel reads them instead of `out`."""
     by, mu, istd, out = tail_ctx[:4]
     bits = tail_ctx[4] if len(tail_ctx) > 4 else None
-    L.call("ocr_conv2d_bnred_tail_f16", byref(d), ptr(x), ptr(w_kc), ptr(y), ptr(partial), ptr(by), ptr(mu),
-           ptr(istd), ptr(out), ptr(bits), ptr(sub_grad), _st())
-    if L.RECORDER is not None:
-        flops = 2.0 * d.n * d.oh * d.ow * d.cout * d.cin * d.kh * d.kw
-        L.RECORDER.tag_last((conv2d_variant(d), flops, "dgrad"))
+    _conv_call("ocr_conv2d_bnred_tail_f16", d, ptr(x), ptr(w_kc), ptr(y), ptr(partial), ptr(by), ptr(mu), ptr(istd),
+               ptr(out), ptr(bits), ptr(sub_grad), phase="dgrad")
 
 
 def conv2d_pw_bnaddrelu(d, prev_y, prev_scale, prev_shift, shortcut, sc_scale, sc_shift, x_out, bits, w_kc, y, stats):
     """1x1 conv whose input x = relu(bn(prev_y) + shortcut) is computed while it is loaded and written to x_out (+ bits)."""
-    L.call("ocr_conv2d_pw_bnaddrelu_f16", byref(d), ptr(prev_y), ptr(prev_scale), ptr(prev_shift), ptr(shortcut),
-           ptr(sc_scale), ptr(sc_shift), ptr(x_out), ptr(bits), ptr(w_kc), ptr(y), ptr(stats), _st())
-    if L.RECORDER is not None:
-        flops = 2.0 * d.n * d.oh * d.ow * d.cout * d.cin
-        L.RECORDER.tag_last((conv2d_variant(d).replace("conv_pw_kernel", "conv_pwx_kernel"), flops, "fwd"))
+    _conv_call("ocr_conv2d_pw_bnaddrelu_f16", d, ptr(prev_y), ptr(prev_scale), ptr(prev_shift), ptr(shortcut),
+               ptr(sc_scale), ptr(sc_shift), ptr(x_out), ptr(bits), ptr(w_kc), ptr(y), ptr(stats), phase="fwd", pwx=True)
 
 
 def conv2d_pw_bnrelu(d, prev_y, prev_scale, prev_shift, x_out, w_kc, y, stats):
     """1x1 conv whose input x = relu(bn(prev_y)) is computed while it is loaded and written to x_out."""
-    L.call("ocr_conv2d_pw_bnrelu_f16", byref(d), ptr(prev_y), ptr(prev_scale), ptr(prev_shift), ptr(x_out), ptr(w_kc), ptr(y),
-           ptr(stats), _st())
-    if L.RECORDER is not None:
-        flops = 2.0 * d.n * d.oh * d.ow * d.cout * d.cin
-        L.RECORDER.tag_last((conv2d_variant(d).replace("conv_pw_kernel", "conv_pwx_kernel"), flops, "fwd"))
+    _conv_call("ocr_conv2d_pw_bnrelu_f16", d, ptr(prev_y), ptr(prev_scale), ptr(prev_shift), ptr(x_out), ptr(w_kc), ptr(y),
+               ptr(stats), phase="fwd", pwx=True)
 
 
 def conv2d_pw_bnbwd_bnred(d, dz, y_above, coef, dy_out, w_kc, dx, partial, bn_ctx):
@@ -224,11 +206,8 @@ def conv2d_pw_bnbwd_bnred(d, dz, y_above, coef, dy_out, w_kc, dx, partial, bn_ct
     if isinstance(by, LazyFirstY):
         by = by.tensor()
     a, b, c = coef
-    L.call("ocr_conv2d_pw_bnbwd_bnred_f16", byref(d), ptr(dz), ptr(y_above), ptr(a), ptr(b), ptr(c), ptr(dy_out),
-           ptr(w_kc), ptr(dx), ptr(partial), ptr(by), ptr(sc), ptr(sh), ptr(mu), ptr(istd), c_int(int(relu)), _st())
-    if L.RECORDER is not None:
-        flops = 2.0 * d.n * d.oh * d.ow * d.cout * d.cin
-        L.RECORDER.tag_last((conv2d_variant(d).replace("conv_pw_kernel", "conv_pwx_kernel"), flops, "dgrad"))
+    _conv_call("ocr_conv2d_pw_bnbwd_bnred_f16", d, ptr(dz), ptr(y_above), ptr(a), ptr(b), ptr(c), ptr(dy_out), ptr(w_kc),
+               ptr(dx), ptr(partial), ptr(by), ptr(sc), ptr(sh), ptr(mu), ptr(istd), c_int(int(relu)), phase="dgrad", pwx=True)
 
 
 def conv2d_pw_bnbwd_tail(d, dz, y_above, coef, relu_shift, dy_out, w_kc, dx, partial=None, tail_ctx=None, sub_grad=None):
@@ -239,12 +218,9 @@ def conv2d_pw_bnbwd_tail(d, dz, y_above, coef, relu_shift, dy_out, w_kc, dx, par
     if tail_ctx is not None:
         by, mu, istd, out = tail_ctx[:4]
         bits = tail_ctx[4] if len(tail_ctx) > 4 else None
-    L.call("ocr_conv2d_pw_bnbwd_tail_f16", byref(d), ptr(dz), ptr(y_above), ptr(a), ptr(b), ptr(c), ptr(relu_shift),
-           ptr(dy_out), ptr(w_kc), ptr(dx), ptr(partial), ptr(by), ptr(mu), ptr(istd), ptr(out), ptr(bits), ptr(sub_grad),
-           _st())
-    if L.RECORDER is not None:
-        flops = 2.0 * d.n * d.oh * d.ow * d.cout * d.cin
-        L.RECORDER.tag_last((conv2d_variant(d).replace("conv_pw_kernel", "conv_pwx_kernel"), flops, "dgrad"))
+    _conv_call("ocr_conv2d_pw_bnbwd_tail_f16", d, ptr(dz), ptr(y_above), ptr(a), ptr(b), ptr(c), ptr(relu_shift), ptr(dy_out),
+               ptr(w_kc), ptr(dx), ptr(partial), ptr(by), ptr(mu), ptr(istd), ptr(out), ptr(bits), ptr(sub_grad),
+               phase="dgrad", pwx=True)
 
 
 def bn_bwd_sums(partial, T, c, out0, out1, ws):
