@@ -114,7 +114,10 @@ int ocr_conv2d_variant(const ocr_conv_desc* d, char* out, size_t cap);
  * 64 -> 64 channel layers on maps of >= 128 tiles (the persistent 64-channel kernel; OCR_ERR_UNSUPPORTED otherwise):
  * pooled [n][ceil(oh/2)][ceil(ow/2)][cout] f16 and argmax_u8 (may be NULL; ocr_maxpool_f16's format, position dy*2+dx of
  * the first maximum) are the ONLY outputs — for bias nets whose full-resolution activation nobody reads
- * (nets/vgg.py:17-18 under nets/pixellink.py:41-48: conv1_2 -> pool1).  d->flags: OCR_CONV_BIAS | OCR_CONV_RELU. */
+ * (nets/vgg.py:17-18 under nets/pixellink.py:41-48: conv1_2 -> pool1).  d->flags: OCR_CONV_BIAS | OCR_CONV_RELU is what
+ * the product issues (the kernel's compiled-in epilogue); OCR_CONV_BIAS alone and 0 are served too, by the generic
+ * instantiation of the same kernel (the maximum is then taken of conv [+ bias] without the ReLU;
+ * tests/test_gpu_conv_fused_matrix.py: POOL_SUPPORTED); OCR_CONV_STATS / OCR_CONV_ACCUM_F16: OCR_ERR_INVALID_ARG. */
 int ocr_conv2d_relu_pool_f16(const ocr_conv_desc* d, const void* x, const void* w_kc, const void* bias, void* pooled,
                              void* argmax_u8, void* stream);
 
@@ -211,7 +214,9 @@ int ocr_conv2d_pw_bnbwd_bnred_f16(const ocr_conv_desc* d, const void* dz, const 
  * plain store, accumulate into dx (OCR_CONV_ACCUM_F16 in d->flags), or — bn_y ... sub_grad given as for
  * ocr_conv2d_bnred_tail_f16 — the bottleneck tail (the gradient past the previous unit's output ReLU + that unit's
  * BN-backward sums in `partial`); all of them null: no tail, `partial` unused.  Replaces the apply pass
- * ocr_bn_relu_bwd_apply_f16 in front of ocr_conv2d_bnred_tail_f16 / ocr_conv2d_f16.  cout of the convolution >= 128. */
+ * ocr_bn_relu_bwd_apply_f16 in front of ocr_conv2d_bnred_tail_f16 / ocr_conv2d_f16.  Every cout tile of the pointwise
+ * kernel is served, cout = 64 included, with each of these epilogues (the product issues cout >= 128 only;
+ * tests/test_gpu_conv_fused_matrix.py: COUT64_SUPPORTED). */
 int ocr_conv2d_pw_bnbwd_tail_f16(const ocr_conv_desc* d, const void* dz, const void* y_above, const void* coef_a,
                                  const void* coef_b, const void* coef_c, const void* relu_shift, void* dy_out,
                                  const void* w_kc, void* dx, void* partial, const void* bn_y, const void* bn_mean,

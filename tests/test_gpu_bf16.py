@@ -51,6 +51,25 @@ def test_bf16_conv_epilogue_matrix(device):
     assert m and int(m.group(1)) == len(CASES) and "failed" not in r.stdout, tail
 
 
+def test_bf16_conv_fused_matrix(device):
+    """tests/test_gpu_conv_fused_matrix.py (the fused loader, tail and pooled conv entries against float64) on the bf16
+    library: every case passes, at the bf16 bounds derived in that file."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    try:
+        from test_gpu_conv_fused_matrix import N_TESTS
+    finally:
+        sys.path.pop(0)
+    env = dict(os.environ, OCR_STORAGE="bf16")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider",
+                        os.path.join(ROOT, "tests", "test_gpu_conv_fused_matrix.py")],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    tail = (r.stdout + r.stderr)[-3000:]
+    assert r.returncode == 0, tail
+    import re
+    m = re.search(r"(\d+) passed", r.stdout)
+    assert m and int(m.group(1)) == N_TESTS and "failed" not in r.stdout, tail
+
+
 def test_bf16_wgrad_matrix(device):
     """tests/test_gpu_wgrad_matrix.py (every weight-gradient family and plan edge against float64) on the bf16 library:
     every case passes at the same bar (bf16 operands and their products are exact in f32 as well)."""
