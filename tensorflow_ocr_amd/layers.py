@@ -5,6 +5,8 @@ graph's tape.  Variable names follow tf.contrib.slim so checkpoints/state-dicts 
 the reference: `<scope>/weights`, `<scope>/biases`,
 `<scope>/BatchNorm/{gamma,beta,moving_mean,moving_variance}`.
 """
+import os
+
 import torch
 
 from . import ops
@@ -13,7 +15,35 @@ from ._lib import CONV_ACCUM_F16, CONV_BIAS, CONV_RELU, CONV_STATS
 
 BN_DECAY = 0.997
 BN_EPS = 1e-5
-FUSE_BN_REDUCE = __import__("os").environ.get("OCR_FUSE_BN", "1") == "1"   # BN-backward reduction inside the consumer's input-gradient kernel
+
+
+def _switch(name, default=True):
+    """A host-side switch: `name` in the environment ("1" / "0"), read once at import."""
+    return os.environ.get(name, "1" if default else "0") == "1"
+
+
+def _switch_int(name, default):
+    return int(os.environ.get(name, str(default)))
+
+
+FUSE_BN_REDUCE = _switch("OCR_FUSE_BN")   # BN-backward reduction inside the consumer's input-gradient kernel
+FUSE_BIAS_POOL = _switch("OCR_FUSE_BIAS_POOL")   # bias nets: conv1_2's bias + ReLU + pool in the conv epilogue
+FUSE_BIAS_RELU = _switch("OCR_FUSE_BIAS_RELU")   # bias nets: ReLU mask + bias gradient in the consumer's dgrad epilogue
+FUSE_BN_W4_MAXHW = _switch_int("OCR_FUSE_BN_W4_MAXHW", 1000000)
+FUSE_BN_POOL_REDUCE = _switch("OCR_FUSE_BN_POOL_REDUCE")    # measurement switch
+FIRST_RECOMPUTE = _switch("OCR_FIRST_RECOMPUTE")            # measurement switch (forward: 439 -> 318 us)
+FIRST_DROP_Y = _switch("OCR_FIRST_DROP_Y")                  # conv1_1's y is never stored (ops.LazyFirstY)
+FIRST_MOMENTS = _switch("OCR_FIRST_MOMENTS")                # ... and its statistics come from the image's moments
+# conv1_1's weight gradient recomputing y even when y IS stored: bit-identical, but no faster by itself (413 vs 402 us at
+# 32 x 512^2: with one stream instead of two the kernel is bound by its per-tile LDS work, not by HBM).  With
+# FIRST_DROP_Y (y never stored) the recomputing form is what runs regardless of this switch.
+FIRST_WGRAD_RECOMPUTE = _switch("OCR_FIRST_WGRAD_RECOMPUTE", False)
+GUEST_REDUCE = _switch("OCR_GUEST_REDUCE")            # end-point layers' BN-backward reduction as a guest pass
+FUSE_FIRST_WGRAD = _switch("OCR_FUSE_FIRST_WGRAD")    # measurement switch
+# conv1_1's weight gradient from SUMS (csrc/conv_first.hip: first_wgrad_sums_kernel): conv1_2's input-gradient launch
+# leaves S1 = V^T dz instead of the 1 GiB gradient, dW = A .* S1 + B .* (M W) + C .* m
+FIRST_WGRAD_SUMS = _switch("OCR_FIRST_WGRAD_SUMS")
+BATCH_HEADS = _switch("OCR_BATCH_HEADS")    # one launch per kernel kind over the head sources
 
 
 def _bn_vars(g, C):
@@ -23,6 +53,41 @@ def _bn_vars(g, C):
         mm = g.get_variable("moving_mean", (C,), constant(0.0), trainable=False)
         mv = g.get_variable("moving_variance", (C,), constant(1.0), trainable=False)
     return gamma, beta, mm, mv
+
+
+def _bn_buffers(g, C):
+    """scale, shift, mean, invstd of one batch norm (f32 [C] each)."""
+    return g.empty((C,), F32), g.empty((C,), F32), g.empty((C,), F32), g.empty((C,), F32)
+
+
+def _bn_params(g, C, bn_vars, stats):
+    """scale, shift, mean, invstd: from the batch's partial sums while training (stats = (part, T, count, stage); moves
+    the moving statistics too), from the moving statistics otherwise (stats = None)."""
+    gamma, beta, mm, mv = bn_vars
+    scale, shift, mean, invstd = _bn_buffers(g, C)
+    if stats is not None:
+        part, T, count, stage = stats
+        ops.bn_finalize(part, T, C, count, gamma.data, beta.data, BN_EPS, BN_DECAY, mm.data, mv.data,
+                        scale, shift, mean, invstd, stage)
+    else:
+        ops.bn_inference_params(gamma.data, beta.data, mm.data, mv.data, BN_EPS, scale, shift)
+    return scale, shift, mean, invstd
+
+
+def _coef(g, c):
+    """The batch-norm backward's apply coefficients (A, B, C): dy = A * dz + B * y + C per channel."""
+    return g.empty((c,), F32), g.empty((c,), F32), g.empty((c,), F32)
+
+
+def _bn_bwd_coef(g, bn, partial, T, count, pre=False):
+    """dgamma / dbeta and the apply coefficients from sums already reduced to `partial` rows; bn = (scale, mean, invstd,
+    gamma, beta); pre: tagged as the front of a guest apply pass."""
+    scale, mean, invstd, gamma, beta = bn
+    c = scale.numel()
+    coef = _coef(g, c)
+    fn = ops.bn_bwd_coefficients_pre if pre else ops.bn_bwd_coefficients
+    fn(partial, T, c, count, scale, mean, invstd, gamma.grad, beta.grad, coef, g.workspace())
+    return coef
 
 
 def _packs(g, w, first):
@@ -43,10 +108,6 @@ def _packs(g, w, first):
     return g.packed(w, "kc_ck", mk)
 
 
-FUSE_BIAS_POOL = __import__("os").environ.get("OCR_FUSE_BIAS_POOL", "1") == "1"   # bias nets: conv1_2's bias + ReLU + pool in the conv epilogue
-FUSE_BIAS_RELU = __import__("os").environ.get("OCR_FUSE_BIAS_RELU", "1") == "1"   # bias nets: ReLU mask + bias gradient in the consumer's dgrad epilogue
-
-
 def _const_vec(g, n, value):
     """A cached per-graph constant f32 vector (filled once, outside any recorded step)."""
     cache = g.__dict__.setdefault("_const_vecs", {})
@@ -54,22 +115,6 @@ def _const_vec(g, n, value):
     if t is None:
         t = cache[(n, value)] = torch.full((n,), float(value), dtype=F32, device=g.device)
     return t
-
-
-FUSE_BN_W4_MAXHW = int(__import__("os").environ.get("OCR_FUSE_BN_W4_MAXHW", "1000000"))
-FUSE_BN_POOL_REDUCE = __import__("os").environ.get("OCR_FUSE_BN_POOL_REDUCE", "1") == "1"    # measurement switch
-FIRST_RECOMPUTE = __import__("os").environ.get("OCR_FIRST_RECOMPUTE", "1") == "1"            # measurement switch (forward: 439 -> 318 us)
-FIRST_DROP_Y = __import__("os").environ.get("OCR_FIRST_DROP_Y", "1") == "1"                  # conv1_1's y is never stored (ops.LazyFirstY)
-FIRST_MOMENTS = __import__("os").environ.get("OCR_FIRST_MOMENTS", "1") == "1"                # ... and its statistics come from the image's moments
-# conv1_1's weight gradient recomputing y even when y IS stored: bit-identical, but no faster by itself (413 vs 402 us at
-# 32 x 512^2: with one stream instead of two the kernel is bound by its per-tile LDS work, not by HBM).  With
-# FIRST_DROP_Y (y never stored) the recomputing form is what runs regardless of this switch.
-FIRST_WGRAD_RECOMPUTE = __import__("os").environ.get("OCR_FIRST_WGRAD_RECOMPUTE", "0") == "1"
-GUEST_REDUCE = __import__("os").environ.get("OCR_GUEST_REDUCE", "1") == "1"            # end-point layers' BN-backward reduction as a guest pass
-FUSE_FIRST_WGRAD = __import__("os").environ.get("OCR_FUSE_FIRST_WGRAD", "1") == "1"    # measurement switch
-# conv1_1's weight gradient from SUMS (csrc/conv_first.hip: first_wgrad_sums_kernel): conv1_2's input-gradient launch
-# leaves S1 = V^T dz instead of the 1 GiB gradient, dW = A .* S1 + B .* (M W) + C .* m
-FIRST_WGRAD_SUMS = __import__("os").environ.get("OCR_FIRST_WGRAD_SUMS", "1") == "1"
 
 
 def conv2d(g, x, cout, k, scope, *, stride=1, rate=1, normalizer="bn", relu=True, pool=0,
@@ -89,6 +134,7 @@ def conv2d(g, x, cout, k, scope, *, stride=1, rate=1, normalizer="bn", relu=True
                                  relu=relu, pool=pool, keep_full=keep_full, is_training=is_training,
                                  bn_training=bn_training, first=first, weight_decay=weight_decay,
                                  initializer=initializer)
+    # what the two layers share: variables, operand packs, descriptor, partial-row count and the raw output
     n, h, w, cin_x = x.shape
     cin = 3 if first else cin_x
     bn_training = is_training if bn_training is None else bn_training
@@ -96,12 +142,11 @@ def conv2d(g, x, cout, k, scope, *, stride=1, rate=1, normalizer="bn", relu=True
         init = initializer or variance_scaling(g.rng)
         wv = g.get_variable("weights", (k, k, cin, cout), init, regularized=weight_decay)
         if normalizer == "bn":
-            gamma, beta, mm, mv = _bn_vars(g, cout)
-            bias = None
+            bn_vars = _bn_vars(g, cout)
         else:
             bias = g.get_variable("biases", (cout,), constant(0.0))
-    ws = g.workspace()
-    w_fwd, w_dg = _packs(g, wv, first)
+    g.workspace()
+    packs = _packs(g, wv, first)
     if first:
         d = None
         oh, ow = h, w
@@ -114,174 +159,182 @@ def conv2d(g, x, cout, k, scope, *, stride=1, rate=1, normalizer="bn", relu=True
     # the two readers of y in the backward pass (conv1_2's fused BN-backward sums, conv1_1's own weight gradient)
     # evaluate the 3-channel convolution again; a consumer that cannot asks the LazyFirstY for the tensor
     drop_y = (first and normalizer == "bn" and not pool and cout == 64 and FIRST_RECOMPUTE and FIRST_DROP_Y
-              and (is_training if bn_training is None else bn_training) and FUSE_FIRST_WGRAD)
-    y = ops.LazyFirstY(g.empty, x.data, w_fwd, (n, oh, ow, cout)) if drop_y else g.empty((n, oh, ow, cout))
-
+              and bn_training and FUSE_FIRST_WGRAD)
+    shape = (n, oh, ow, cout)
+    y = ops.LazyFirstY(g.empty, x.data, packs[0], shape) if drop_y else g.empty(shape)
     if normalizer == "bn":
-        train_stats = bn_training
-        flags = CONV_STATS if train_stats else 0
-        part, stage = g.ws_small.two(mt * 2 * cout * 4, ops.bn_reduce_workspace(mt, cout))
-        mt_fin = mt
-        if first and drop_y and train_stats and FIRST_MOMENTS:
-            # the statistics from the image's second moments (csrc/conv_first.hip: first_moments_kernel): no pass over the
-            # 64-channel output at all; one partial row
-            if FIRST_WGRAD_SUMS:
-                y.moments = g.empty((32 * 32,), torch.float64)      # kept for the backward (ops.conv2d_first_wgrad_sums)
-            ops.conv2d_first_moments(x.data, w_fwd, part, cout, ws, moments=y.moments)
-            mt_fin = 1
-        elif first:
-            ops.conv2d_first(x.data, w_fwd, None if drop_y else y, flags, None, part if train_stats else None, cout=cout)
-        else:
-            d.flags = flags
-            ops.conv2d(d, x.data, w_fwd, y, None, part if train_stats else None)
-        scale, shift = g.empty((cout,), F32), g.empty((cout,), F32)
-        mean, invstd = g.empty((cout,), F32), g.empty((cout,), F32)
-        if train_stats:
-            ops.bn_finalize(part, mt_fin, cout, float(n) * oh * ow, gamma.data, beta.data, BN_EPS, BN_DECAY,
-                            mm.data, mv.data, scale, shift, mean, invstd, stage)
-        else:
-            ops.bn_inference_params(gamma.data, beta.data, mm.data, mv.data, BN_EPS, scale, shift)
-        full = pooled = None
-        argmax = y_pool = argmax_full = None
-        if pool:
-            pooled = g.empty((n, (oh + 1) // 2, (ow + 1) // 2, cout))
-            if keep_full:
-                full = g.empty((n, oh, ow, cout))
-                if train_stats and relu and ops.guest_apply_ok((n, oh, ow, cout)) and oh % 2 == 0 and ow % 2 == 0:
-                    # an end point that is also pooled (conv3_3 / conv4_3): keep the first-max positions, so that the
-                    # backward's apply pass can run as a guest (ops.bn_relu_poolfull_bwd_apply_affine) without
-                    # re-deriving them
-                    argmax_full = g.empty(pooled.shape, torch.uint8)
-                    ops.bn_relu_pool_idx(y, scale, shift, relu, full, pooled, argmax_full, None)
-                else:
-                    ops.bn_relu(y, scale, shift, relu, 2, full, pooled)
-            else:
-                # the pool is the only consumer: keep the first-max position so that the backward routes
-                # the pooled gradient without re-deriving the four candidates' activations
-                argmax = g.empty(pooled.shape, torch.uint8)
-                # ... and, while training, the conv output AT that position: dz is zero everywhere else, so the conv
-                # that consumes the pooled activation can sum this layer's BN-backward terms over the pooled
-                # positions in its input-gradient epilogue (a_pool.bn_ctx below) and the reduction pass over y goes
-                y_pool = g.empty(pooled.shape) if (train_stats and FUSE_BN_POOL_REDUCE) else None
-                ops.bn_relu_pool_idx(y, scale, shift, relu, None, pooled, argmax, y_pool)
-        else:
-            full = g.empty((n, oh, ow, cout))
-            if first and FIRST_RECOMPUTE:
-                # conv1_1: evaluating the 3-channel convolution again costs 67 MB of reads, the element-wise pass 1 GiB
-                ops.conv2d_first_bn_relu(x.data, w_fwd, scale, shift, relu, full)
-            else:
-                ops.bn_relu(y.tensor() if isinstance(y, ops.LazyFirstY) else y, scale, shift, relu, 0, full, None)
-        a_full = Act(full, name=scope) if full is not None else None
-        a_pool = Act(pooled, name=scope + "/pool") if pooled is not None else None
-        if not pool and train_stats:
-            # lets the consumer conv's input-gradient kernel do this layer's BN-backward reduction
-            a_full.bn_ctx = (y, scale, shift, mean, invstd, relu)
-        if pool and argmax is not None and y_pool is not None:
-            a_pool.bn_ctx = (y_pool, scale, shift, mean, invstd, relu)
+        return _conv2d_bn(g, x, scope, wv, bn_vars, packs, d, mt, y, shape, relu, pool, keep_full, bn_training, first)
+    return _conv2d_bias(g, x, scope, wv, bias, packs, d, y, shape, relu, pool, keep_full, is_training, first)
 
-        def backward():
-            if not train_stats:
-                raise NotImplementedError("backward through inference-mode batch norm")
-            da_full = a_full.grad if a_full is not None else None
-            da_pool = a_pool.grad if a_pool is not None else None
-            if first and a_full is not None and a_full.first_s1 is not None:
-                # conv1_1 whose sole consumer left the sums instead of the gradient (_conv_dgrad): dgamma / dbeta and the
-                # apply coefficients from the partial rows, then dW = A .* S1 + B .* (M W) + C .* m — no pass over a
-                # 64-channel tensor at all
-                part_f, T_f = a_full.bn_partial
-                coef = (g.empty((cout,), F32), g.empty((cout,), F32), g.empty((cout,), F32))
-                ops.bn_bwd_coefficients(part_f, T_f, cout, float(n) * oh * ow, scale, mean, invstd, gamma.grad,
-                                        beta.grad, coef, ws)
-                ops.conv2d_first_wgrad_sums(a_full.first_s1, y.moments, w_fwd, coef, wv.grad)
-                a_full.bn_partial = None
-                a_full.first_s1 = None
-                return
-            if da_full is None and da_pool is None:
-                return
-            if pool and da_pool is None:
-                da_pool = g.empty(a_pool.data.shape)
-                ops.fill_(da_pool, 0.0)
-            if not pool and da_full is None:
-                return
-            if first and not pool and a_full.bn_partial is not None and FUSE_FIRST_WGRAD:
-                # conv1_1: no input gradient, so the weight gradient is the only reader of dy — it applies the BN
-                # backward while staging its tiles and dy is never written (ocr_conv2d_first_wgrad_bn_f16)
-                part_f, T_f = a_full.bn_partial
-                coef = (g.empty((cout,), F32), g.empty((cout,), F32), g.empty((cout,), F32))
-                ops.bn_bwd_coefficients(part_f, T_f, cout, float(n) * oh * ow, scale, mean, invstd, gamma.grad,
-                                        beta.grad, coef, ws)
-                lazy = isinstance(y, ops.LazyFirstY)
-                if lazy and y.t is not None:
-                    lazy, y_t = False, y.t                # somebody had it evaluated: read it
-                else:
-                    y_t = None if lazy else y
-                ops.conv2d_first_wgrad_bn(x.data, da_full, y_t, shift, coef, relu, wv.grad, ws,
-                                          w_first=w_fwd if (lazy or FIRST_WGRAD_RECOMPUTE) else None)
-                a_full.bn_partial = None
-                a_full.grad = None
-                return
-            if isinstance(y, ops.LazyFirstY):
-                y_b = y.tensor()                  # (the unfused routes below read y)
-            else:
-                y_b = y
-            dy = g.empty(y_b.shape)
-            if not pool and a_full.bn_partial is not None:
-                part_f, T_f = a_full.bn_partial
-                if ops.guest_apply_ok(y_b.shape):
-                    # the apply pass as a GUEST (csrc/guest_bn.hip): dgamma / dbeta / coefficients first, then one slim
-                    # launch that the recorded step runs beside the weight gradient of the layer above
-                    coef = (g.empty((cout,), F32), g.empty((cout,), F32), g.empty((cout,), F32))
-                    ops.bn_bwd_coefficients_pre(part_f, T_f, cout, float(n) * oh * ow, scale, mean, invstd, gamma.grad,
-                                                beta.grad, coef, ws)
-                    ops.bn_relu_bwd_apply_affine(y_b, da_full, scale, shift, coef[1], coef[2], relu, dy)
-                else:
-                    ops.bn_relu_bwd_apply(y_b, scale, shift, mean, invstd, da_full, relu, part_f, T_f,
-                                          gamma.grad, beta.grad, dy, ws)
-                a_full.bn_partial = None
-            elif pool and argmax is not None and da_full is None and a_pool.bn_partial is not None:
-                part_p, T_p = a_pool.bn_partial
-                if ops.guest_apply_ok(y_b.shape) and oh % 2 == 0 and ow % 2 == 0:
-                    coef = (g.empty((cout,), F32), g.empty((cout,), F32), g.empty((cout,), F32))
-                    ops.bn_bwd_coefficients_pre(part_p, T_p, cout, float(n) * oh * ow, scale, mean, invstd, gamma.grad,
-                                                beta.grad, coef, ws)
-                    ops.bn_relu_pool_bwd_idx_apply_affine(y_b, argmax, da_pool, coef, relu, dy)
-                else:
-                    ops.bn_relu_pool_bwd_idx_apply(y_b, scale, mean, invstd, argmax, da_pool, relu, part_p, T_p,
-                                                   gamma.grad, beta.grad, dy, ws)
-                a_pool.bn_partial = None
-            elif pool and argmax is not None and da_full is None:
-                ops.bn_relu_pool_bwd_idx(y_b, scale, mean, invstd, a_pool.data, argmax, da_pool, relu,
-                                         gamma.grad, beta.grad, dy, ws)
-            elif (not pool or argmax_full is not None) and da_full is not None and ops.guest_apply_ok(y_b.shape):
-                # no consumer summed this layer's terms (several contributed to its gradient: an end point of the fuse
-                # heads): the reduction pass stays, its finalize emits the coefficients, the apply pass is a guest
-                coef = (g.empty((cout,), F32), g.empty((cout,), F32), g.empty((cout,), F32))
-                if GUEST_REDUCE and (relu or not pool):
-                    # ... as a guest as well (beside weight gradients still held back), its rows folded on the main stream
-                    part_e, T_e = ops.bn_relu_bwd_reduce_rows(y_b, da_full, scale, shift, mean, invstd, relu, g.empty,
-                                                              da_pool=da_pool if pool else None,
-                                                              argmax=argmax_full if pool else None)
-                    ops.bn_bwd_coefficients_pre(part_e, T_e, cout, float(n) * oh * ow, scale, mean, invstd, gamma.grad,
-                                                beta.grad, coef, ws)
-                else:
-                    ops.bn_relu_bwd_reduce(y_b, scale, shift, mean, invstd, da_full, relu, gamma.grad, beta.grad, coef, ws,
-                                           da_pool=da_pool if pool else None)
-                if pool:
-                    ops.bn_relu_poolfull_bwd_apply_affine(y_b, da_full, da_pool, argmax_full, scale, shift, coef, relu, dy)
-                else:
-                    ops.bn_relu_bwd_apply_affine(y_b, da_full, scale, shift, coef[1], coef[2], relu, dy)
-            else:
-                ops.bn_relu_bwd(y_b, scale, shift, mean, invstd, da_full, da_pool, relu, 2 if pool else 0,
-                                gamma.grad, beta.grad, dy, ws)
-            _conv_backward(g, x, wv, w_dg, d, dy, first)
-            if a_full is not None:
-                a_full.grad = None
-            if a_pool is not None:
-                a_pool.grad = None
-        g.record(backward, (wv, gamma, beta))
-        return a_full, a_pool
 
-    # bias (+ReLU) path: PixelLinkNet's VGG (nets/pixellink.py:41-48)
+def _conv2d_bn(g, x, scope, wv, bn_vars, packs, d, mt, y, shape, relu, pool, keep_full, train_stats, first):
+    """conv2d's batch-norm layer: statistics in the convolution's epilogue, normalise + ReLU (+ pool) in one pass."""
+    gamma, beta = bn_vars[:2]
+    w_fwd, w_dg = packs
+    n, oh, ow, cout = shape
+    count = float(n) * oh * ow
+    ws = g.workspace()
+    drop_y = isinstance(y, ops.LazyFirstY)
+    flags = CONV_STATS if train_stats else 0
+    part, stage = g.ws_small.two(mt * 2 * cout * 4, ops.bn_reduce_workspace(mt, cout))
+    mt_fin = mt
+    if first and drop_y and train_stats and FIRST_MOMENTS:
+        # the statistics from the image's second moments (csrc/conv_first.hip: first_moments_kernel): no pass over the
+        # 64-channel output at all; one partial row
+        if FIRST_WGRAD_SUMS:
+            y.moments = g.empty((32 * 32,), torch.float64)      # kept for the backward (ops.conv2d_first_wgrad_sums)
+        ops.conv2d_first_moments(x.data, w_fwd, part, cout, ws, moments=y.moments)
+        mt_fin = 1
+    elif first:
+        ops.conv2d_first(x.data, w_fwd, None if drop_y else y, flags, None, part if train_stats else None, cout=cout)
+    else:
+        d.flags = flags
+        ops.conv2d(d, x.data, w_fwd, y, None, part if train_stats else None)
+    scale, shift, mean, invstd = _bn_params(g, cout, bn_vars, (part, mt_fin, count, stage) if train_stats else None)
+    bn = (scale, mean, invstd, gamma, beta)
+    even = oh % 2 == 0 and ow % 2 == 0
+    full = pooled = None
+    argmax = y_pool = argmax_full = None
+    if pool:
+        pooled = g.empty((n, (oh + 1) // 2, (ow + 1) // 2, cout))
+        if keep_full:
+            full = g.empty(shape)
+            if train_stats and relu and ops.guest_apply_ok(shape) and even:
+                # an end point that is also pooled (conv3_3 / conv4_3): keep the first-max positions, so that the
+                # backward's apply pass can run as a guest (ops.bn_relu_poolfull_bwd_apply_affine) without
+                # re-deriving them
+                argmax_full = g.empty(pooled.shape, torch.uint8)
+                ops.bn_relu_pool_idx(y, scale, shift, relu, full, pooled, argmax_full, None)
+            else:
+                ops.bn_relu(y, scale, shift, relu, 2, full, pooled)
+        else:
+            # the pool is the only consumer: keep the first-max position so that the backward routes
+            # the pooled gradient without re-deriving the four candidates' activations
+            argmax = g.empty(pooled.shape, torch.uint8)
+            # ... and, while training, the conv output AT that position: dz is zero everywhere else, so the conv
+            # that consumes the pooled activation can sum this layer's BN-backward terms over the pooled
+            # positions in its input-gradient epilogue (a_pool.bn_ctx below) and the reduction pass over y goes
+            y_pool = g.empty(pooled.shape) if (train_stats and FUSE_BN_POOL_REDUCE) else None
+            ops.bn_relu_pool_idx(y, scale, shift, relu, None, pooled, argmax, y_pool)
+    else:
+        full = g.empty(shape)
+        if first and FIRST_RECOMPUTE:
+            # conv1_1: evaluating the 3-channel convolution again costs 67 MB of reads, the element-wise pass 1 GiB
+            ops.conv2d_first_bn_relu(x.data, w_fwd, scale, shift, relu, full)
+        else:
+            ops.bn_relu(y.tensor() if drop_y else y, scale, shift, relu, 0, full, None)
+    a_full = Act(full, name=scope) if full is not None else None
+    a_pool = Act(pooled, name=scope + "/pool") if pooled is not None else None
+    if not pool and train_stats:
+        # lets the consumer conv's input-gradient kernel do this layer's BN-backward reduction
+        a_full.bn_ctx = (y, scale, shift, mean, invstd, relu)
+    if pool and argmax is not None and y_pool is not None:
+        a_pool.bn_ctx = (y_pool, scale, shift, mean, invstd, relu)
+
+    def first_from_sums():
+        # conv1_1 whose sole consumer left the sums instead of the gradient (_conv_dgrad): dgamma / dbeta and the
+        # apply coefficients from the partial rows, then dW = A .* S1 + B .* (M W) + C .* m — no pass over a
+        # 64-channel tensor at all
+        coef = _bn_bwd_coef(g, bn, *a_full.bn_partial, count)
+        ops.conv2d_first_wgrad_sums(a_full.first_s1, y.moments, w_fwd, coef, wv.grad)
+        a_full.bn_partial = None
+        a_full.first_s1 = None
+
+    def first_wgrad_applies(da_full):
+        # conv1_1: no input gradient, so the weight gradient is the only reader of dy — it applies the BN
+        # backward while staging its tiles and dy is never written (ocr_conv2d_first_wgrad_bn_f16)
+        coef = _bn_bwd_coef(g, bn, *a_full.bn_partial, count)
+        lazy = drop_y
+        if lazy and y.t is not None:
+            lazy, y_t = False, y.t                # somebody had it evaluated: read it
+        else:
+            y_t = None if lazy else y
+        ops.conv2d_first_wgrad_bn(x.data, da_full, y_t, shift, coef, relu, wv.grad, ws,
+                                  w_first=w_fwd if (lazy or FIRST_WGRAD_RECOMPUTE) else None)
+        a_full.bn_partial = None
+        a_full.grad = None
+
+    def backward():
+        if not train_stats:
+            raise NotImplementedError("backward through inference-mode batch norm")
+        da_full = a_full.grad if a_full is not None else None
+        da_pool = a_pool.grad if a_pool is not None else None
+        if first and a_full is not None and a_full.first_s1 is not None:
+            return first_from_sums()                          # conv1_1
+        if da_full is None and da_pool is None:
+            return
+        if pool and da_pool is None:
+            da_pool = g.empty(a_pool.data.shape)
+            ops.fill_(da_pool, 0.0)
+        if not pool and da_full is None:
+            return
+        if first and not pool and a_full.bn_partial is not None and FUSE_FIRST_WGRAD:
+            return first_wgrad_applies(da_full)               # conv1_1 with FIRST_WGRAD_SUMS off
+        y_b = y.tensor() if drop_y else y                     # (the unfused routes below read y)
+        dy = g.empty(y_b.shape)
+        guest_ok = ops.guest_apply_ok(y_b.shape)
+        if not pool and a_full.bn_partial is not None:
+            # the sole consumer's input-gradient kernel summed this layer's terms (conv2_1 ... conv5_2, fc6)
+            part_f, T_f = a_full.bn_partial
+            if guest_ok:
+                # the apply pass as a GUEST (csrc/guest_bn.hip): dgamma / dbeta / coefficients first, then one slim
+                # launch that the recorded step runs beside the weight gradient of the layer above
+                coef = _bn_bwd_coef(g, bn, part_f, T_f, count, pre=True)
+                ops.bn_relu_bwd_apply_affine(y_b, da_full, scale, shift, coef[1], coef[2], relu, dy)
+            else:
+                ops.bn_relu_bwd_apply(y_b, scale, shift, mean, invstd, da_full, relu, part_f, T_f,
+                                      gamma.grad, beta.grad, dy, ws)
+            a_full.bn_partial = None
+        elif pool and argmax is not None and da_full is None and a_pool.bn_partial is not None:
+            # ... summed them over the pooled positions (conv1_2, conv2_2: the pool is the only reader)
+            part_p, T_p = a_pool.bn_partial
+            if guest_ok and even:
+                coef = _bn_bwd_coef(g, bn, part_p, T_p, count, pre=True)
+                ops.bn_relu_pool_bwd_idx_apply_affine(y_b, argmax, da_pool, coef, relu, dy)
+            else:
+                ops.bn_relu_pool_bwd_idx_apply(y_b, scale, mean, invstd, argmax, da_pool, relu, part_p, T_p,
+                                               gamma.grad, beta.grad, dy, ws)
+            a_pool.bn_partial = None
+        elif pool and argmax is not None and da_full is None:
+            # the same layers with nobody having summed (FUSE_BN_REDUCE / FUSE_BN_POOL_REDUCE off): one pass, routed by index
+            ops.bn_relu_pool_bwd_idx(y_b, scale, mean, invstd, a_pool.data, argmax, da_pool, relu,
+                                     gamma.grad, beta.grad, dy, ws)
+        elif (not pool or argmax_full is not None) and da_full is not None and guest_ok:
+            # no consumer summed this layer's terms (several contributed to its gradient: an end point of the fuse
+            # heads — conv3_3, conv4_3, conv5_3, fc7): the reduction pass stays, its finalize emits the coefficients,
+            # the apply pass is a guest
+            if GUEST_REDUCE and (relu or not pool):
+                # ... as a guest as well (beside weight gradients still held back), its rows folded on the main stream
+                part_e, T_e = ops.bn_relu_bwd_reduce_rows(y_b, da_full, scale, shift, mean, invstd, relu, g.empty,
+                                                          da_pool=da_pool if pool else None,
+                                                          argmax=argmax_full if pool else None)
+                coef = _bn_bwd_coef(g, bn, part_e, T_e, count, pre=True)
+            else:
+                coef = _coef(g, cout)
+                ops.bn_relu_bwd_reduce(y_b, scale, shift, mean, invstd, da_full, relu, gamma.grad, beta.grad, coef, ws,
+                                       da_pool=da_pool if pool else None)
+            if pool:
+                ops.bn_relu_poolfull_bwd_apply_affine(y_b, da_full, da_pool, argmax_full, scale, shift, coef, relu, dy)
+            else:
+                ops.bn_relu_bwd_apply_affine(y_b, da_full, scale, shift, coef[1], coef[2], relu, dy)
+        else:
+            # everything else (shapes the guest passes do not take, a pooled end point without its index): the plain pass
+            ops.bn_relu_bwd(y_b, scale, shift, mean, invstd, da_full, da_pool, relu, 2 if pool else 0,
+                            gamma.grad, beta.grad, dy, ws)
+        _conv_backward(g, x, wv, w_dg, d, dy, first)
+        if a_full is not None:
+            a_full.grad = None
+        if a_pool is not None:
+            a_pool.grad = None
+    g.record(backward, (wv, gamma, beta))
+    return a_full, a_pool
+
+
+def _conv2d_bias(g, x, scope, wv, bias, packs, d, y, shape, relu, pool, keep_full, is_training, first):
+    """conv2d's bias (+ReLU) layer: PixelLinkNet's VGG (nets/pixellink.py:41-48)."""
+    w_fwd, w_dg = packs
+    n, oh, ow, cout = shape
+    ws = g.workspace()
     flags = CONV_BIAS | (CONV_RELU if relu else 0)
     if (pool == 2 and relu and not keep_full and not first and FUSE_BIAS_POOL
             and ops.conv2d_variant(d) == "conv_c64_persist_kernel<64>"):
@@ -307,8 +360,8 @@ def conv2d(g, x, cout, k, scope, *, stride=1, rate=1, normalizer="bn", relu=True
             # gradient is routed to is), then the routed gradient IS dz of the convolution
             dzp = g.empty(pooled.shape)
             ops.bias_relu_bwd(pooled, a_pool.grad, True, dzp, bias.grad, ws)
-            dz = g.empty((n, oh, ow, cout))
-            ops.maxpool_bwd(None, dzp, 2, 2, (0, 0), dz, False, argmax=argmax, in_shape=(n, oh, ow, cout))
+            dz = g.empty(shape)
+            ops.maxpool_bwd(None, dzp, 2, 2, (0, 0), dz, False, argmax=argmax, in_shape=shape)
             _conv_backward(g, x, wv, w_dg, d, dz, first)
             a_pool.grad = None
         g.record(backward_pool, (wv, bias))
@@ -348,14 +401,54 @@ def conv2d(g, x, cout, k, scope, *, stride=1, rate=1, normalizer="bn", relu=True
     return a_full, a_pool
 
 
+def _wgrad_desc(d):
+    """The weight gradient's descriptor of the forward convolution `d`: same geometry, no flags."""
+    return ops.ConvDesc(d.n, d.h, d.w, d.cin, d.oh, d.ow, d.cout, d.kh, d.kw, d.stride, d.dilation,
+                        d.pad_top, d.pad_left, 0, 0)
+
+
+def _dgrad_desc(d, flags):
+    """dx = conv(dy, W^T flipped) of the stride-1 convolution `d`: input = dy [n,oh,ow,cout], output = [n,h,w,cin]."""
+    pt = d.dilation * (d.kh - 1) - d.pad_top
+    pl = d.dilation * (d.kw - 1) - d.pad_left
+    return ops.ConvDesc(d.n, d.oh, d.ow, d.cout, d.h, d.w, d.cin, d.kh, d.kw, 1, d.dilation, pt, pl, 1, flags)
+
+
+def _partial_rows(g, dg):
+    """(partial, T): the [T, 2, channels] f32 rows a fused input-gradient epilogue leaves its sums in."""
+    T = ops.conv2d_num_mtiles(dg)
+    return g.empty((T, 2, dg.cout), F32), T
+
+
+def _open_input_grad(g, x):
+    """-> the input-gradient launch's flags: 0 for the first contribution (x.grad allocated here), CONV_ACCUM_F16 for
+    a later one, which also drops what an earlier consumer's fused epilogue left: its BN-backward sums no longer cover
+    the full gradient, nor does its masked store (backward_bias then masks the whole sum again: idempotent)."""
+    if x.grad is None:
+        x.grad = g.empty(x.shape)
+        return 0
+    x.bn_partial = None
+    x.bias_partial = None
+    return CONV_ACCUM_F16
+
+
+def _count_contribution(x, owner):
+    """-> whether this is the LAST gradient contribution to a bottleneck output.  Only the owning unit's two are counted
+    (any other consumer of x was built later, runs earlier in the backward pass and has added its share)."""
+    if x.pending is None or owner is None or owner is not x.pending_owner:
+        return False
+    x.pending -= 1
+    assert x.pending >= 0, "more gradient contributions than the owning unit has consumers"
+    return x.pending == 0
+
+
 def _conv_backward(g, x, wv, w_dg, d, dy, first):
     """Weight gradient (always) and input gradient (when the input needs one)."""
     ws = g.workspace()
     if first:
         ops.conv2d_first_wgrad(x.data, dy, wv.grad, ws)
         return
-    dd = ops.ConvDesc(d.n, d.h, d.w, d.cin, d.oh, d.ow, d.cout, d.kh, d.kw, d.stride, d.dilation,
-                      d.pad_top, d.pad_left, 0, 0)
+    dd = _wgrad_desc(d)
     if ops.GUEST_BN and x.requires_grad:
         # input gradient FIRST: the layer below can then start its backward while this layer's weight gradient runs —
         # its batch-norm apply pass is a guest beside it (csrc/guest_bn.hip; the recorded step pairs the two)
@@ -371,38 +464,26 @@ def _conv_backward(g, x, wv, w_dg, d, dy, first):
 def _conv_dgrad(g, x, wv, w_dg, d, dy):
     if d.stride != 1:
         raise NotImplementedError("strided dgrad")
-    # dx = conv(dy, W^T flipped): input = dy [n,oh,ow,cout], output = [n,h,w,cin]
-    pt = d.dilation * (d.kh - 1) - d.pad_top
-    pl = d.dilation * (d.kw - 1) - d.pad_left
-    flags = 0
-    by0 = x.bn_ctx[0] if x.bn_ctx is not None else None
-    if (x.grad is None and x.sole_consumer and FIRST_WGRAD_SUMS and FUSE_BN_REDUCE and isinstance(by0, ops.LazyFirstY)
-            and by0.t is None and by0.moments is not None and d.cin == 64):
+    by = x.bn_ctx[0] if x.bn_ctx is not None else None
+    lazy_first = isinstance(by, ops.LazyFirstY) and by.t is None and d.cin == 64      # conv1_1's y, stored by nobody
+    if x.grad is None and x.sole_consumer and FIRST_WGRAD_SUMS and FUSE_BN_REDUCE and lazy_first and by.moments is not None:
         # conv1_1's activation, read by this convolution only: its gradient has one more reader — conv1_1's weight
         # gradient — which needs sums of it, not the tensor; the launch leaves those (epilogue mode 7) and nothing else
-        dg = ops.ConvDesc(d.n, d.oh, d.ow, d.cout, d.h, d.w, d.cin, d.kh, d.kw, 1, d.dilation, pt, pl, 1, 0)
+        dg = _dgrad_desc(d, 0)
         blocks = ops.conv2d_bnred_first_wgrad_blocks(dg)
         if blocks > 0:
-            T = ops.conv2d_num_mtiles(dg)
-            partial = g.empty((T, 2, d.cin), F32)
+            partial, T = _partial_rows(g, dg)
             s1 = g.empty((blocks, 32, 64), F32)
-            ops.conv2d_bnred_first_wgrad(dg, dy, w_dg, partial, (by0.x4, by0.w_first) + tuple(x.bn_ctx[1:]), s1)
+            ops.conv2d_bnred_first_wgrad(dg, dy, w_dg, partial, (by.x4, by.w_first) + tuple(x.bn_ctx[1:]), s1)
             x.bn_partial = (partial, T)
             x.first_s1 = s1
             return
-    if x.grad is None:
-        x.grad = g.empty(x.shape)
-    else:
-        flags |= CONV_ACCUM_F16
-        x.bn_partial = None     # an earlier consumer's fused BN-backward sums no longer cover the full gradient
-        x.bias_partial = None   # ... nor its masked store (backward_bias then masks the whole sum again: idempotent)
-    dg = ops.ConvDesc(d.n, d.oh, d.ow, d.cout, d.h, d.w, d.cin, d.kh, d.kw, 1, d.dilation, pt, pl, 1,
-                      flags)
+    flags = _open_input_grad(g, x)
+    dg = _dgrad_desc(d, flags)
     if x.bias_ctx is not None and x.sole_consumer and not flags and FUSE_BIAS_RELU:
         # bias + ReLU producer whose only reader is this convolution: dz and the bias-gradient partial sums come out of
         # this kernel's epilogue, the producer's bias_relu_bwd pass (read a, read da, write dz) disappears
-        T = ops.conv2d_num_mtiles(dg)
-        partial = g.empty((T, 2, d.cin), F32)
+        partial, T = _partial_rows(g, dg)
         ops.conv2d_bnred(dg, dy, w_dg, x.grad, partial, x.bias_ctx, store_masked=True)
         x.bias_partial = (partial, T)
         return
@@ -410,11 +491,8 @@ def _conv_dgrad(g, x, wv, w_dg, d, dy):
     if fuse and d.h >= FUSE_BN_W4_MAXHW and ops.conv2d_variant(dg) == "conv3x3_w4_kernel":
         fuse = False        # (measurement switch: the one-wave-per-SIMD kernel cannot overlap its epilogue with anything)
     if fuse:
-        T = ops.conv2d_num_mtiles(dg)
-        partial = g.empty((T, 2, d.cin), F32)
-        by = x.bn_ctx[0]
-        if (isinstance(by, ops.LazyFirstY) and by.t is None and d.cin == 64
-                and ops.conv2d_variant(dg) == "conv_c64_persist_kernel<64>"):
+        partial, T = _partial_rows(g, dg)
+        if lazy_first and ops.conv2d_variant(dg) == "conv_c64_persist_kernel<64>":
             # the consumer of conv1_1's activation (conv1_2): conv1_1's y is recomputed in the epilogue, not read
             ops.conv2d_bnred_first(dg, dy, w_dg, x.grad, partial, (by.x4, by.w_first) + tuple(x.bn_ctx[1:]))
         else:
@@ -502,41 +580,64 @@ class SmallAct:
         self.grad = None
 
 
+def _head_vars(g, names, cin, couts, mode, initializer=None):
+    """One merged parameter per head source, its columns mapping onto the reference variables `names`
+    -> (weights [cin, sum(couts)], BN variables | None, biases | None)."""
+    C = sum(couts)
+    with g.variable_scope("+".join(names)):
+        init = _merged_init(g, cin, couts, None if mode == "bn" else (initializer or xavier_uniform))
+        wv = g.get_variable("weights", (cin, C), init, regularized=True)
+        if mode == "bn":
+            return wv, _bn_vars(g, C), None
+        return wv, None, g.get_variable("biases", (C,), constant(0.0))
+
+
+def _small_packs(g, wv, cin):
+    """f16 operand layouts of a merged head weight, padded to 32 columns: forward [32][cin] and dgrad [cin][32]."""
+    def mk(old):
+        if old is None:
+            old = (g.empty((32, cin)), g.empty((cin, 32)))
+        ops.pack_weights_small(wv.data, old[0], old[1])
+        return old
+    return g.packed(wv, "small", mk)
+
+
+def _small_stats(g, z, C):
+    """Batch statistics of an f32 head tensor [..., C]: the `stats` of _bn_params."""
+    P = z.numel() // C
+    T = ops.sc_num_partials(P, C)
+    part, stage = g.ws_small.two(T * 2 * C * 4, ops.bn_reduce_workspace(T, C))
+    ops.sc_stats(z, C, part)
+    return part, T, float(P), stage
+
+
+def _pointwise_vars(g, scope, c, mode, initializer=None):
+    """One predication convolution's (weights [1,1,c,c], BN variables | None, biases | None)."""
+    with g.variable_scope(scope):
+        init = variance_scaling(g.rng) if mode == "bn" else (initializer or xavier_uniform)(g.rng)
+        wv = g.get_variable("weights", (1, 1, c, c), init, regularized=True)
+        if mode == "bn":
+            return wv, _bn_vars(g, c), None
+        return wv, None, g.get_variable("biases", (c,), constant(0.0))
+
+
 def head_conv_bn(g, feat, names, couts, is_training=True, relu=True):
     """The BN'd 1x1 fuse convs that several heads apply to ONE feature map, evaluated in a single
     pass over the feature: slim.conv2d(feat, c, 1) for c in couts (nets/model_vgg_16.py:160-172).
     Returns (z, scale, shift, ctx): z = raw conv output [n,h,w,sum(couts)] f32."""
     n, h, w, cin = feat.shape
     C = sum(couts)
-    ws, ws_small = g.workspace(), g.ws_small
-    # one merged parameter per source; columns map onto the reference variables `names`
-    with g.variable_scope("+".join(names)):
-        wv = g.get_variable("weights", (cin, C), _merged_init(g, cin, couts), regularized=True)
-        gamma, beta, mm, mv = _bn_vars(g, C)
-
-    def mk(old):
-        if old is None:
-            old = (g.empty((32, cin)), g.empty((cin, 32)))
-        ops.pack_weights_small(wv.data, old[0], old[1])
-        return old
-    w_kc32, w_ck32 = g.packed(wv, "small", mk)
+    ws = g.workspace()
+    wv, bn_vars, _ = _head_vars(g, names, cin, couts, "bn")
+    gamma, beta = bn_vars[:2]
+    w_kc32, w_ck32 = _small_packs(g, wv, cin)
     z = g.empty((n, h, w, C), F32)
     if g.precision == "f32":
         from . import layers_f32
         layers_f32.head_conv(g, feat, wv, C, z)
     else:
         ops.conv1x1_small(feat.data, w_kc32, C, z)
-    P = n * h * w
-    scale, shift = g.empty((C,), F32), g.empty((C,), F32)
-    mean, invstd = g.empty((C,), F32), g.empty((C,), F32)
-    if is_training:
-        T = ops.sc_num_partials(P, C)
-        part, stage = ws_small.two(T * 2 * C * 4, ops.bn_reduce_workspace(T, C))
-        ops.sc_stats(z, C, part)
-        ops.bn_finalize(part, T, C, float(P), gamma.data, beta.data, BN_EPS, BN_DECAY, mm.data, mv.data,
-                        scale, shift, mean, invstd, stage)
-    else:
-        ops.bn_inference_params(gamma.data, beta.data, mm.data, mv.data, BN_EPS, scale, shift)
+    scale, shift, mean, invstd = _bn_params(g, C, bn_vars, _small_stats(g, z, C) if is_training else None)
     out = SmallAct(z)   # grad of out = gradient w.r.t. relu(bn(z))
 
     def backward():
@@ -562,17 +663,8 @@ def head_conv_bias(g, feat, names, couts, initializer=None):
     n, h, w, cin = feat.shape
     C = sum(couts)
     ws = g.workspace()
-    with g.variable_scope("+".join(names)):
-        init = _merged_init(g, cin, couts, initializer or xavier_uniform)
-        wv = g.get_variable("weights", (cin, C), init, regularized=True)
-        bias = g.get_variable("biases", (C,), constant(0.0))
-
-    def mk(old):
-        if old is None:
-            old = (g.empty((32, cin)), g.empty((cin, 32)))
-        ops.pack_weights_small(wv.data, old[0], old[1])
-        return old
-    w_kc32, w_ck32 = g.packed(wv, "small", mk)
+    wv, _, bias = _head_vars(g, names, cin, couts, "bias", initializer)
+    w_kc32, w_ck32 = _small_packs(g, wv, cin)
     z = g.empty((n, h, w, C), F32)
     if g.precision == "f32":
         from . import layers_f32
@@ -596,9 +688,6 @@ def head_conv_bias(g, feat, names, couts, initializer=None):
     return out, None, None
 
 
-BATCH_HEADS = __import__("os").environ.get("OCR_BATCH_HEADS", "1") == "1"    # one launch per kernel kind over the head sources
-
-
 def head_group(g, feats, names_list, couts, *, mode="bn", is_training=True, relu=True, initializer=None):
     """The fuse convs of ALL head sources (nets/model_vgg_16.py:160-172: fc7, conv5_3, conv4_3, conv3_3; nets/pixellink.py:
     58-67; nets/model.py:129-141) with one launch per kernel kind over the sources instead of one per source: per feature map
@@ -616,30 +705,15 @@ def head_group(g, feats, names_list, couts, *, mode="bn", is_training=True, relu
     srcs = []
     for feat, names in zip(feats, names_list):
         n, h, w, cin = feat.shape
-        with g.variable_scope("+".join(names)):
-            if mode == "bn":
-                wv = g.get_variable("weights", (cin, C), _merged_init(g, cin, couts), regularized=True)
-                gamma, beta, mm, mv = _bn_vars(g, C)
-                bias = None
-            else:
-                wv = g.get_variable("weights", (cin, C), _merged_init(g, cin, couts, initializer or xavier_uniform),
-                                    regularized=True)
-                bias = g.get_variable("biases", (C,), constant(0.0))
-                gamma = beta = mm = mv = None
-
-        def mk(old, wv=wv, cin=cin):
-            if old is None:
-                old = (g.empty((32, cin)), g.empty((cin, 32)))
-            ops.pack_weights_small(wv.data, old[0], old[1])
-            return old
-        w_kc32, w_ck32 = g.packed(wv, "small", mk)
+        wv, bn_vars, bias = _head_vars(g, names, cin, couts, mode, initializer)
+        gamma, beta, mm, mv = bn_vars or (None,) * 4
+        w_kc32, w_ck32 = _small_packs(g, wv, cin)
         srcs.append(dict(feat=feat, P=n * h * w, cin=cin, wv=wv, bias=bias, gamma=gamma, beta=beta, mm=mm, mv=mv,
                          w_kc32=w_kc32, w_ck32=w_ck32, z=g.empty((n, h, w, C), F32)))
     train_bn = mode == "bn" and is_training
     for s in srcs:
         if mode == "bn":
-            s["scale"], s["shift"] = g.empty((C,), F32), g.empty((C,), F32)
-            s["mean"], s["invstd"] = g.empty((C,), F32), g.empty((C,), F32)
+            s["scale"], s["shift"], s["mean"], s["invstd"] = _bn_buffers(g, C)
         if train_bn:
             s["T"] = ops.conv1x1_small_batch_rows(s["P"])
             s["part"] = g.empty((s["T"], 2, C), F32)
@@ -724,15 +798,8 @@ def pointwise_pair(g, x, scopes, *, mode="bn", is_training=True, relu=True, init
     ws = g.workspace()
     hd = []
     for scope, c in zip(scopes, (2, 16)):
-        with g.variable_scope(scope):
-            if mode == "bn":
-                wv = g.get_variable("weights", (1, 1, c, c), variance_scaling(g.rng), regularized=True)
-                gamma, beta, mm, mv = _bn_vars(g, c)
-                bias = None
-            else:
-                wv = g.get_variable("weights", (1, 1, c, c), (initializer or xavier_uniform)(g.rng), regularized=True)
-                bias = g.get_variable("biases", (c,), constant(0.0))
-                gamma = beta = mm = mv = None
+        wv, bn_vars, bias = _pointwise_vars(g, scope, c, mode, initializer)
+        gamma, beta, mm, mv = bn_vars or (None,) * 4
         hd.append(dict(c=c, wv=wv, bias=bias, gamma=gamma, beta=beta, mm=mm, mv=mv, z=g.empty((n, h, w, c), F32)))
     a, b = hd
     train_bn = mode == "bn" and is_training
@@ -744,8 +811,7 @@ def pointwise_pair(g, x, scopes, *, mode="bn", is_training=True, relu=True, init
                               b["bias"].data if b["bias"] is not None else None, a["z"], b["z"], a.get("part"), b.get("part"))
     if mode == "bn":
         for d in hd:
-            d["scale"], d["shift"] = g.empty((d["c"],), F32), g.empty((d["c"],), F32)
-            d["mean"], d["invstd"] = g.empty((d["c"],), F32), g.empty((d["c"],), F32)
+            d["scale"], d["shift"], d["mean"], d["invstd"] = _bn_buffers(g, d["c"])
         if train_bn:
             ops.bn_finalize_batch([(d["part"], T, d["c"], float(P), d["gamma"].data, d["beta"].data, d["mm"].data,
                                     d["mv"].data, d["scale"], d["shift"], d["mean"], d["invstd"]) for d in hd],
@@ -801,9 +867,7 @@ def pointwise_bias(g, x, xo, c, scope, initializer=None):
     slice of the fused head tensor (nets/pixellink.py:61,67).  Returns contiguous logits."""
     n, h, w, C = x.data.shape
     ws = g.workspace()
-    with g.variable_scope(scope):
-        wv = g.get_variable("weights", (1, 1, c, c), (initializer or xavier_uniform)(g.rng), regularized=True)
-        bias = g.get_variable("biases", (c,), constant(0.0))
+    wv, _, bias = _pointwise_vars(g, scope, c, "bias", initializer)
     out = SmallAct(g.empty((n, h, w, c), F32))
     ops.sc_pointwise_fwd(x.data, xo, c, wv.data, out.data, 0, c, bias.data)
 
@@ -862,23 +926,12 @@ def pointwise_bn(g, x, xo, c, scope, is_training=True, relu=True):
     out = relu(bn(conv1x1(x[..., xo:xo+c], c)))   (pixel_cls / link_cls,
     nets/model_vgg_16.py:166,173).  Returns a contiguous SmallAct [n,h,w,c]."""
     n, h, w, C = x.data.shape
-    P = n * h * w
     ws = g.workspace()
-    with g.variable_scope(scope):
-        wv = g.get_variable("weights", (1, 1, c, c), variance_scaling(g.rng), regularized=True)
-        gamma, beta, mm, mv = _bn_vars(g, c)
+    wv, bn_vars, _ = _pointwise_vars(g, scope, c, "bn")
+    gamma, beta = bn_vars[:2]
     z = g.empty((n, h, w, c), F32)
     ops.sc_pointwise_fwd(x.data, xo, c, wv.data, z, 0, c)
-    scale, shift = g.empty((c,), F32), g.empty((c,), F32)
-    mean, invstd = g.empty((c,), F32), g.empty((c,), F32)
-    if is_training:
-        T = ops.sc_num_partials(P, c)
-        part, stage = g.ws_small.two(T * 2 * c * 4, ops.bn_reduce_workspace(T, c))
-        ops.sc_stats(z, c, part)
-        ops.bn_finalize(part, T, c, float(P), gamma.data, beta.data, BN_EPS, BN_DECAY, mm.data, mv.data,
-                        scale, shift, mean, invstd, stage)
-    else:
-        ops.bn_inference_params(gamma.data, beta.data, mm.data, mv.data, BN_EPS, scale, shift)
+    scale, shift, mean, invstd = _bn_params(g, c, bn_vars, _small_stats(g, z, c) if is_training else None)
     out = SmallAct(g.empty((n, h, w, c), F32))
     ops.sc_fuse(out.data, z, scale, shift, relu=relu)
 

@@ -13,25 +13,27 @@ import torch
 
 from . import ops
 from .graph import Act, F32, constant, variance_scaling
-from .layers import BN_DECAY, BN_EPS, FUSE_BN_REDUCE, _bn_vars, _packs
+from .layers import (FUSE_BN_REDUCE, _bn_bwd_coef, _bn_params, _bn_vars, _coef, _count_contribution, _dgrad_desc,
+                     _open_input_grad, _packs, _partial_rows, _switch, _wgrad_desc)
 from ._lib import CONV_ACCUM_F16, CONV_STATS
 
-
-USE_S2D = __import__("os").environ.get("OCR_RESNET_S2D", "1") == "1"     # measurement switch (A/B against the subsample form)
-FUSE_TAIL = __import__("os").environ.get("OCR_RESNET_FUSE_TAIL", "1") == "1"   # measurement switch (bottleneck tail fusion)
-FUSE_SUB = __import__("os").environ.get("OCR_RESNET_FUSE_SUB", "1") == "1"     # ... subsampled shortcut gradient in that conv's epilogue
+USE_S2D = _switch("OCR_RESNET_S2D")     # measurement switch (A/B against the subsample form)
+FUSE_TAIL = _switch("OCR_RESNET_FUSE_TAIL")   # measurement switch (bottleneck tail fusion)
+FUSE_SUB = _switch("OCR_RESNET_FUSE_SUB")     # ... subsampled shortcut gradient in that conv's epilogue
 # round 3: the element-wise passes around the 1x1 convolutions applied while those convolutions load their operand
-FUSE_FWD = __import__("os").environ.get("OCR_RESNET_FUSE_FWD", "1") == "1"     # relu(bn(conv3) + shortcut) inside the NEXT 1x1 conv
-FUSE_BWD = __import__("os").environ.get("OCR_RESNET_FUSE_BWD", "1") == "1"     # conv3's BN-backward apply inside its input-gradient conv
+FUSE_FWD = _switch("OCR_RESNET_FUSE_FWD")     # relu(bn(conv3) + shortcut) inside the NEXT 1x1 conv
+FUSE_BWD = _switch("OCR_RESNET_FUSE_BWD")     # conv3's BN-backward apply inside its input-gradient conv
 # round 4: the same on-load apply for the BN (+ReLU) above conv1 and above a projection shortcut, in front of the tail epilogue
 # relu(bn(conv2)) inside conv3 (ocr_conv2d_pw_bnrelu_f16): measured NEUTRAL at 64 x 640^2 (stage 2 -7 us per unit, stages 3 / 4
 # +6 / +12: the register-staged loader gives back in the 256 -> 1024 GEMM what the removed pass saved), off; path kept under test
-FUSE_FWD_ACT = __import__("os").environ.get("OCR_RESNET_FUSE_FWD_ACT", "0") == "1"
-FUSE_BWD_WIDE = __import__("os").environ.get("OCR_RESNET_FUSE_BWD_WIDE", "1") == "1"
-FUSE_ROOT_POOL = __import__("os").environ.get("OCR_RESNET_FUSE_ROOT_POOL", "1") == "1"   # root conv: BN + ReLU inside the max-pool that follows
-FUSE_ROOT_WGRAD = __import__("os").environ.get("OCR_RESNET_FUSE_ROOT_WGRAD", "1") == "1"   # root conv: BN-backward apply inside its weight gradient
-FUSE_ROOT_GATHER = __import__("os").environ.get("OCR_RESNET_FUSE_ROOT_GATHER", "1") == "1"   # ... and the pool's backward inside that BN's reduction pass
-MASK_BITS = __import__("os").environ.get("OCR_RESNET_MASK_BITS", "0") == "1"   # tail mask as bits instead of the output tensor: measured SLOWER (byte stores +8 % on the writers, byte loads no faster in the latency-bound tail epilogue), off
+FUSE_FWD_ACT = _switch("OCR_RESNET_FUSE_FWD_ACT", False)
+FUSE_BWD_WIDE = _switch("OCR_RESNET_FUSE_BWD_WIDE")
+FUSE_ROOT_POOL = _switch("OCR_RESNET_FUSE_ROOT_POOL")   # root conv: BN + ReLU inside the max-pool that follows
+FUSE_ROOT_WGRAD = _switch("OCR_RESNET_FUSE_ROOT_WGRAD")   # root conv: BN-backward apply inside its weight gradient
+FUSE_ROOT_GATHER = _switch("OCR_RESNET_FUSE_ROOT_GATHER")   # ... and the pool's backward inside that BN's reduction pass
+MASK_BITS = _switch("OCR_RESNET_MASK_BITS", False)   # tail mask as bits instead of the output tensor: measured SLOWER (byte stores +8 % on the writers, byte loads no faster in the latency-bound tail epilogue), off
+MERGE_HEADS = _switch("OCR_RESNET_MERGE_HEADS")   # F_score + geo_map: one pass over the feature
+MERGE_REORDER = _switch("OCR_RESNET_MERGE_REORDER")   # 1x1 merge conv before the upsample
 
 
 class ConvBN:
@@ -128,54 +130,38 @@ def conv_bn_raw(g, x, cout, k, scope, *, stride=1, rate=1, is_training=True, wei
             ops.conv2d(d, x.data, w_fwd, y, None, part if is_training else None)
     c = ConvBN()
     c.y, c.gamma, c.beta, c.wv = y, gamma, beta, wv
-    c.scale, c.shift = g.empty((cout,), F32), g.empty((cout,), F32)
-    c.mean, c.invstd = g.empty((cout,), F32), g.empty((cout,), F32)
-    if is_training:
-        ops.bn_finalize(part, T, cout, float(n) * oh * ow, gamma.data, beta.data, BN_EPS, BN_DECAY, mm.data,
-                        mv.data, c.scale, c.shift, c.mean, c.invstd, stage)
-    else:
-        ops.bn_inference_params(gamma.data, beta.data, mm.data, mv.data, BN_EPS, c.scale, c.shift)
+    c.scale, c.shift, c.mean, c.invstd = _bn_params(g, cout, (gamma, beta, mm, mv),
+                                                    (part, T, float(n) * oh * ow, stage) if is_training else None)
 
     def backward_from(dy, fused=None):
         """dy: gradient of the conv output.  fused = (dz, y_bn, (A, B, C)): dy is still EMPTY — it is the batch-norm
         backward apply A*dz + B*y_bn + C, which the input-gradient convolution computes while loading its operand and
         writes into `dy` for the weight gradient (see `can_fuse_bwd`)."""
+        dd = _wgrad_desc(d)
         if fused is not None:
             dz_f, ybn_f, coef_f, relu_shift = fused
-            flags = 0
-            if x.grad is None:
-                x.grad = g.empty(x.shape)
-            else:
-                flags |= CONV_ACCUM_F16
-                x.bn_partial = None
-            last = False
-            if x.pending is not None and owner is not None and owner is x.pending_owner:
-                x.pending -= 1
-                assert x.pending >= 0, "more gradient contributions than the owning unit has consumers"
-                last = x.pending == 0
-            dg = ops.ConvDesc(d.n, d.oh, d.ow, d.cout, d.h, d.w, d.cin, 1, 1, 1, 1, 0, 0, 1, flags)
-            Tm = ops.conv2d_num_mtiles(dg)
+            flags = _open_input_grad(g, x)
+            last = _count_contribution(x, owner)
+            dg = _dgrad_desc(d, flags)
             if last and x.tail_ctx is not None and FUSE_TAIL:
                 # (as the unfused path below: the last contribution to a bottleneck output's gradient)
-                partial = g.empty((Tm, 2, d.cin), F32)
+                partial, Tm = _partial_rows(g, dg)
                 ops.conv2d_pw_bnbwd_tail(dg, dz_f, ybn_f, coef_f, relu_shift, dy, w_dg, x.grad, partial, x.tail_ctx, x.sub_grad)
                 x.sub_grad = None
                 x.tail_partial = (partial, Tm)
             elif x.bn_ctx is not None and not flags and FUSE_BN_REDUCE and relu_shift is None and x.pending is None:
-                partial = g.empty((Tm, 2, d.cin), F32)
+                partial, Tm = _partial_rows(g, dg)
                 ops.conv2d_pw_bnbwd_bnred(dg, dz_f, ybn_f, coef_f, dy, w_dg, x.grad, partial, x.bn_ctx)
                 x.bn_partial = (partial, Tm)
             else:
                 ops.conv2d_pw_bnbwd_tail(dg, dz_f, ybn_f, coef_f, relu_shift, dy, w_dg, x.grad)
-            dd = ops.ConvDesc(d.n, d.h, d.w, d.cin, d.oh, d.ow, d.cout, 1, 1, 1, 1, 0, 0, 0, 0)
             ops.conv2d_wgrad(dd, x_in, dy, wv.grad, g.ws_wgrad)
             return
         if strided and not s2d:
             dy_full = g.empty(y_full.shape)
             ops.maxpool_bwd(y_full, dy, 1, stride, (0, 0), dy_full, False)   # zero insertion
             dy = dy_full
-        dd = ops.ConvDesc(d.n, d.h, d.w, d.cin, d.oh, d.ow, d.cout, d.kh, d.kw, 1, d.dilation, d.pad_top,
-                          d.pad_left, 0, 0)
+
         def weight_gradient():
             if s2d:
                 dw22 = g.empty((2, 2, 4 * cin, cout), F32)
@@ -183,47 +169,32 @@ def conv_bn_raw(g, x, cout, k, scope, *, stride=1, rate=1, is_training=True, wei
                 ops.weights_s2d_grad(dw22, wv.grad)
             else:
                 ops.conv2d_wgrad(dd, x_in, dy, wv.grad, g.ws_wgrad)
+
         def input_gradient():
-            pt = d.dilation * (d.kh - 1) - d.pad_top
-            pl = d.dilation * (d.kw - 1) - d.pad_left
             if s2d:
                 # input gradient in the shuffled layout, then back to full resolution (added to what is there)
                 dxs = g.empty(x_in.shape)
-                dg = ops.ConvDesc(d.n, d.oh, d.ow, d.cout, d.h, d.w, d.cin, d.kh, d.kw, 1, d.dilation, pt, pl, 1, 0)
-                ops.conv2d(dg, dy, w_dg, dxs, None, None)
+                ops.conv2d(_dgrad_desc(d, 0), dy, w_dg, dxs, None, None)
                 had = x.grad is not None
                 if not had:
                     x.grad = g.empty(x.shape)
                 ops.depth_to_space(dxs, x.grad, had)
                 x.bn_partial = None
                 return
-            flags = 0
-            if x.grad is None:
-                x.grad = g.empty(x.shape)
-            else:
-                flags |= CONV_ACCUM_F16
-                x.bn_partial = None     # an earlier consumer's fused BN-backward sums no longer cover the full gradient
-            dg = ops.ConvDesc(d.n, d.oh, d.ow, d.cout, d.h, d.w, d.cin, d.kh, d.kw, 1, d.dilation, pt, pl, 1, flags)
-            last = False
-            if x.pending is not None and owner is not None and owner is x.pending_owner:
-                # only the owning unit's two contributions are counted (any other consumer of x was built
-                # later, runs earlier in the backward pass and has already added its share)
-                x.pending -= 1
-                assert x.pending >= 0, "more gradient contributions than the owning unit has consumers"
-                last = x.pending == 0
+            flags = _open_input_grad(g, x)
+            dg = _dgrad_desc(d, flags)
+            last = _count_contribution(x, owner)
             if last and x.tail_ctx is not None and k == 1 and FUSE_TAIL:
                 # x is the previous bottleneck's output and this is the last contribution to its gradient: store
                 # the gradient past its ReLU and emit the BN-backward sums of its last conv (ops.conv2d_bnred_tail)
-                Tm = ops.conv2d_num_mtiles(dg)
-                partial = g.empty((Tm, 2, d.cin), F32)
+                partial, Tm = _partial_rows(g, dg)
                 ops.conv2d_bnred_tail(dg, dy, w_dg, x.grad, partial, x.tail_ctx, x.sub_grad)
                 x.sub_grad = None
                 x.tail_partial = (partial, Tm)
             elif x.bn_ctx is not None and not flags and FUSE_BN_REDUCE:
                 # sole consumer of a conv+BN(+ReLU) output: this input-gradient kernel also emits that
                 # layer's BN-backward sums, so its backward skips the reduction pass (layers.py does the same)
-                Tm = ops.conv2d_num_mtiles(dg)
-                partial = g.empty((Tm, 2, d.cin), F32)
+                partial, Tm = _partial_rows(g, dg)
                 ops.conv2d_bnred(dg, dy, w_dg, x.grad, partial, x.bn_ctx)
                 x.bn_partial = (partial, Tm)
             else:
@@ -244,8 +215,7 @@ def conv_bn_raw(g, x, cout, k, scope, *, stride=1, rate=1, is_training=True, wei
                 return False
         elif not (FUSE_BN_REDUCE and x.grad is None and x.bn_ctx is not None and x.pending is None):
             return False
-        dg = ops.ConvDesc(d.n, d.oh, d.ow, d.cout, d.h, d.w, d.cin, 1, 1, 1, 1, 0, 0, 1, 0)
-        return _pw_fusable(dg)
+        return _pw_fusable(_dgrad_desc(d, 0))
     c.backward_from = backward_from
     c.can_fuse_bwd = can_fuse_bwd
     return c
@@ -284,11 +254,7 @@ def conv_bn_act(g, x, cout, k, scope, *, stride=1, rate=1, relu=True, is_trainin
         if a.bn_partial is not None and c.can_fuse_bwd(wide=True):
             # the sums are reduced already (the consumer's input-gradient epilogue): finalize them into the apply step's
             # coefficients and let this layer's own input-gradient convolution apply them (and the ReLU mask) on load
-            part_f, T_f = a.bn_partial
-            n_, h_, w_, c_ = c.y.shape
-            coef = (g.empty((c_,), F32), g.empty((c_,), F32), g.empty((c_,), F32))
-            ops.bn_bwd_coefficients(part_f, T_f, c_, float(n_) * h_ * w_, c.scale, c.mean, c.invstd, c.gamma.grad,
-                                    c.beta.grad, coef, ws)
+            coef = _bn_bwd_coef(g, (c.scale, c.mean, c.invstd, c.gamma, c.beta), *a.bn_partial, float(c.y.numel() // cout))
             a.bn_partial = None
             c.backward_from(dy, fused=(a.grad, c.y, coef, c.shift if relu else None))
             a.grad = None
@@ -328,13 +294,8 @@ def root_block(g, x4, scope="conv1", cout=64, is_training=True):
     mt = ops.conv2d_stem_num_mtiles(n, h, w)
     part, stage = g.ws_small.two(mt * 2 * cout * 4, ops.bn_reduce_workspace(mt, cout))
     ops.conv2d_stem(x4.data, w_stem, y, CONV_STATS if is_training else 0, None, part if is_training else None)
-    scale, shift = g.empty((cout,), F32), g.empty((cout,), F32)
-    mean, invstd = g.empty((cout,), F32), g.empty((cout,), F32)
-    if is_training:
-        ops.bn_finalize(part, mt, cout, float(n) * oh * ow, gamma.data, beta.data, BN_EPS, BN_DECAY, mm.data,
-                        mv.data, scale, shift, mean, invstd, stage)
-    else:
-        ops.bn_inference_params(gamma.data, beta.data, mm.data, mv.data, BN_EPS, scale, shift)
+    scale, shift, mean, invstd = _bn_params(g, cout, (gamma, beta, mm, mv),
+                                            (part, mt, float(n) * oh * ow, stage) if is_training else None)
     a = Act(g.empty(y.shape), name=scope)
 
     def fill():
@@ -352,7 +313,7 @@ def root_block(g, x4, scope="conv1", cout=64, is_training=True):
         if a.pool_grad is not None and a.grad is None:
             # the pool was the only contributor: its backward (the gather of the routed gradient) and this layer's BN
             # reduction are one pass — the gradient is summed while it is written for the weight gradient
-            coef = (g.empty((cout,), F32), g.empty((cout,), F32), g.empty((cout,), F32))
+            coef = _coef(g, cout)
             da = g.empty(y.shape)
             ops.bn_relu_bwd_reduce_pooled(y, scale, shift, mean, invstd, a.pool_grad, True, da, gamma.grad, beta.grad, coef, ws)
             ops.conv2d_stem_wgrad_bn(x4.data, da, y, shift, coef, True, wv.grad, ws)
@@ -366,7 +327,7 @@ def root_block(g, x4, scope="conv1", cout=64, is_training=True):
             return
         if FUSE_ROOT_WGRAD:
             # no input gradient: the weight gradient is the only reader of dy and applies the BN backward on load
-            coef = (g.empty((cout,), F32), g.empty((cout,), F32), g.empty((cout,), F32))
+            coef = _coef(g, cout)
             ops.bn_relu_bwd_reduce(y, scale, shift, mean, invstd, a.grad, True, gamma.grad, beta.grad, coef, ws)
             ops.conv2d_stem_wgrad_bn(x4.data, a.grad, y, shift, coef, True, wv.grad, ws)
         else:
@@ -430,8 +391,7 @@ def bottleneck(g, x, depth, depth_bottleneck, stride, scope, is_training=True):
             dy = g.empty(sc.y.shape)
             if sc.can_fuse_bwd(wide=True):
                 # reduction pass only; the apply step runs inside the projection's input-gradient convolution
-                c_ = sc.y.shape[-1]
-                coef = (g.empty((c_,), F32), g.empty((c_,), F32), g.empty((c_,), F32))
+                coef = _coef(g, depth)
                 ops.bn_relu_bwd_reduce(sc.y, sc.scale, sc.shift, sc.mean, sc.invstd, dz, False, sc.gamma.grad,
                                        sc.beta.grad, coef, ws)
                 sc.backward_from(dy, fused=(dz, sc.y, coef, None))
@@ -505,10 +465,8 @@ def bottleneck(g, x, depth, depth_bottleneck, stride, scope, is_training=True):
             dz = out.grad
             part_f, T_f = out.tail_partial
             if c3.can_fuse_bwd():
-                n_, h_, w_, c_ = c3.y.shape
-                coef = (g.empty((c_,), F32), g.empty((c_,), F32), g.empty((c_,), F32))
-                ops.bn_bwd_coefficients(part_f, T_f, c_, float(n_) * h_ * w_, c3.scale, c3.mean, c3.invstd,
-                                        c3.gamma.grad, c3.beta.grad, coef, ws)
+                coef = _bn_bwd_coef(g, (c3.scale, c3.mean, c3.invstd, c3.gamma, c3.beta), part_f, T_f,
+                                    float(c3.y.numel() // depth))
                 c3.backward_from(dy, fused=(dz, c3.y, coef, None))
             else:
                 ops.bn_relu_bwd_apply(c3.y, c3.scale, c3.shift, c3.mean, c3.invstd, dz, False, part_f, T_f,
@@ -588,13 +546,8 @@ def concat_conv_bn_relu(g, xa, xb, cout, scope, is_training=True):
     ops.conv2d(da, xa.data, wa_kc, y, None, None)
     db.flags = CONV_ACCUM_F16 | (CONV_STATS if is_training else 0)
     ops.conv2d(db, xb.data, wb_kc, y, None, part if is_training else None)
-    scale, shift = g.empty((cout,), F32), g.empty((cout,), F32)
-    mean, invstd = g.empty((cout,), F32), g.empty((cout,), F32)
-    if is_training:
-        ops.bn_finalize(part, mt, cout, float(n) * h * w, gamma.data, beta.data, BN_EPS, BN_DECAY, mm.data,
-                        mv.data, scale, shift, mean, invstd, stage)
-    else:
-        ops.bn_inference_params(gamma.data, beta.data, mm.data, mv.data, BN_EPS, scale, shift)
+    scale, shift, mean, invstd = _bn_params(g, cout, (gamma, beta, mm, mv),
+                                            (part, mt, float(n) * h * w, stage) if is_training else None)
     a = Act(g.empty(y.shape), name=scope)
     ops.bn_relu(y, scale, shift, True, 0, a.data, None)
 
@@ -607,19 +560,10 @@ def concat_conv_bn_relu(g, xa, xb, cout, scope, is_training=True):
             dd = ops.conv_desc((n, h, w, c), cout, 1, 1)
             ops.conv2d_wgrad(dd, x.data, dy, wv.grad[:, :, sl, :], g.ws_wgrad)
             if x.requires_grad:
-                flags = 0
-                if x.grad is None:
-                    x.grad = g.empty(x.shape)
-                else:
-                    flags = CONV_ACCUM_F16
-                dg = ops.ConvDesc(n, h, w, cout, h, w, c, 1, 1, 1, 1, 0, 0, 1, flags)
-                ops.conv2d(dg, dy, w_ck, x.grad, None, None)
+                ops.conv2d(_dgrad_desc(dd, _open_input_grad(g, x)), dy, w_ck, x.grad, None, None)
         a.grad = None
     g.record(backward, (wv, gamma, beta))
     return a
-
-
-MERGE_HEADS = __import__("os").environ.get("OCR_RESNET_MERGE_HEADS", "1") == "1"   # F_score + geo_map: one pass over the feature
 
 
 def sigmoid_heads(g, feat, couts, scopes):
@@ -686,9 +630,6 @@ def rbox_heads(g, feat, scopes, text_scale):
     return o0, o1
 
 
-MERGE_REORDER = __import__("os").environ.get("OCR_RESNET_MERGE_REORDER", "1") == "1"   # 1x1 merge conv before the upsample
-
-
 def unpool_concat_conv_bn_relu(g, lo, xb, cout, scope, is_training=True):
     """slim.conv2d(tf.concat([unpool(lo), xb], axis=-1), cout, 1) + BN + ReLU (nets/model_vgg_16.py:118-121) with the
     upsampled branch's share of the convolution taken BEFORE the resize: conv(unpool(lo), Wa) = unpool(conv(lo, Wa)) —
@@ -724,13 +665,8 @@ def unpool_concat_conv_bn_relu(g, lo, xb, cout, scope, is_training=True):
     T = ops.channel_stats_num_partials(n * h * w, cout)
     part, stage = g.ws_small.two(T * 2 * cout * 4, ops.bn_reduce_workspace(T, cout))
     ops.unpool_add_stats(t, y, part if is_training else None)
-    scale, shift = g.empty((cout,), F32), g.empty((cout,), F32)
-    mean, invstd = g.empty((cout,), F32), g.empty((cout,), F32)
-    if is_training:
-        ops.bn_finalize(part, T, cout, float(n) * h * w, gamma.data, beta.data, BN_EPS, BN_DECAY, mm.data,
-                        mv.data, scale, shift, mean, invstd, stage)
-    else:
-        ops.bn_inference_params(gamma.data, beta.data, mm.data, mv.data, BN_EPS, scale, shift)
+    scale, shift, mean, invstd = _bn_params(g, cout, (gamma, beta, mm, mv),
+                                            (part, T, float(n) * h * w, stage) if is_training else None)
     a = Act(g.empty(y.shape), name=scope)
     ops.bn_relu(y, scale, shift, True, 0, a.data, None)
 
@@ -746,13 +682,7 @@ def unpool_concat_conv_bn_relu(g, lo, xb, cout, scope, is_training=True):
             dd = ops.conv_desc((n, hh, ww, c), cout, 1, 1)
             ops.conv2d_wgrad(dd, x.data, d_out, wv.grad[:, :, sl, :], g.ws_wgrad)
             if x.requires_grad:
-                flags = 0
-                if x.grad is None:
-                    x.grad = g.empty(x.shape)
-                else:
-                    flags = CONV_ACCUM_F16
-                dg = ops.ConvDesc(n, hh, ww, cout, hh, ww, c, 1, 1, 1, 1, 0, 0, 1, flags)
-                ops.conv2d(dg, d_out, w_ck, x.grad, None, None)
+                ops.conv2d(_dgrad_desc(dd, _open_input_grad(g, x)), d_out, w_ck, x.grad, None, None)
         a.grad = None
     g.record(backward, (wv, gamma, beta))
     return a
