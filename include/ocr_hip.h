@@ -34,7 +34,8 @@ extern "C" {
  * augmentation (ocr_augment_u8_batch, ocr_augment_desc) and gradient accumulation (ocr_grad_accum_init, ocr_grad_accum_f32,
  * ocr_grad_accum_advance, ocr_grad_accum_state), ocr_conv2d_wgrad_variant (the name of the weight-gradient launch) and the
  * training summaries (ocr_tensor_stats_*, ocr_summary_image_u8), and the RBOX training labels with the post-NMS score
- * filter (ocr_icdar_rbox_labels, ocr_quad_mean_score). */
+ * filter (ocr_icdar_rbox_labels, ocr_quad_mean_score), and PixelLink's instance-balanced loss
+ * (ocr_pixellink_instance_weights, ocr_balanced_loss_*). */
 #define OCR_ABI_VERSION 7
 
 enum {
@@ -632,6 +633,60 @@ int ocr_softmax_loss_bwd_dyn(const ocr_softmax_loss_desc* d, const void* pixel_l
                              const void* link_logits, const void* pixel_labels, const void* link_labels,
                              const void* ohnm_threshold, const void* sums34, float grad_scale,
                              const float* loss_scale, void* d_pixel_logits, void* d_link_logits, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * PixelLink's INSTANCE-BALANCED loss (csrc/pixellink_balance.hip).  BUILD-DEFINED: the reference keeps only the remains
+ * of it — nets/pixellink.py:138-156 `OHNM_batch` takes a weight_mask and ignores it, the weighted pixel term (:161-168)
+ * and the W-gated link weights (:191-192) are commented out, what runs is the mean of pixel_rule 2.  This is the
+ * structure of that build_loss with the weights of the PixelLink paper (Deng et al. 2018, §3.3); PARITY with an upstream
+ * TensorFlow run IS UNPINNED (no such run exists to compare against).
+ *
+ * Weight map.  cover is ocr_poly_cover's, ignore uint8 [n][max_polys].  The owner of label cell (oy, ox) is bits 8-15
+ * of the cover word at the INTER_NEAREST source index of ocr_pixellink_labels (the same expression: cell for cell the
+ * cells that entry scores 1), owner j+1 = polygon j.  area int32 [n][max_polys] (zeroed by the entry): S_j = the number of
+ * label cells of the image owned by j, by integer atomics (deterministic).  Polygon j is live when ignore[j] == 0 and
+ * S_j >= 1; N = the number of live polygons of the image, S the sum of their areas.  weight f32 [n][new_h][new_w] =
+ * (float)((double)S / ((double)N * (double)S_j)) on the cells of a live owner — every live instance weighs S/N in
+ * total — and exactly 0 elsewhere (background, ignored polygons, polygons hidden completely by later ones, images
+ * without polygons).  OCR_ERR_UNSUPPORTED without a launch unless n, h, w, new_h, new_w >= 1, 1 <= max_polys <= 254,
+ * n <= 65535 and h, w <= 16384 (the bounds of ocr_poly_cover). */
+int ocr_pixellink_instance_weights(const void* cover_u32, const void* ignore_u8, int n, int max_polys, int h, int w,
+                                   int new_h, int new_w, void* area_i32, void* weight_f32, void* stream);
+/* The loss.  Tensors as ocr_softmax_loss_*; pixel_weights f32 [n][hw] (>= 0).  P = {w > 0}, Neg = {!(label > 0)}; a cell
+ * with label > 0 and w == 0 (ignored text) is in neither: it contributes nothing and its gradient is 0.
+ *   mining, per image: n_pos = |P|, k = (int)min((double)n_pos * (double)neg_ratio, (double)n_neg); n_pos == 0 or k <= 0:
+ *     threshold -1 (nothing mined); else the k-th smallest P(neg) over Neg (4-pass radix select on the float bits, the
+ *     det_exp score of ocr_softmax_loss_fwd bit for bit); a negative is mined when its score <= threshold (ties included)
+ *   pixel  W = w on P, 1 on mined negatives, 0 elsewhere; pixel = sum(CE W) / sum(W) over the batch, 0 when sum(W) == 0
+ *     (sum(W) = S + mined: the paper's (1 + r) S)
+ *   link d, on P only: Wp = w [link > 0], Wn = w [!(link > 0)]; link_d = sum(L Wp)/sum(Wp) + sum(L Wn)/sum(Wn), a
+ *     quotient with a zero denominator counts 0; L = CE, or the focal term of ocr_softmax_loss_desc when focal = 1
+ *   total = 2 pixel + sum_d link_d;  loss10 = [total, pixel, link_0..7];
+ *   sums34 = [sum CE W, sum W, then (sum L Wp, sum Wp, sum L Wn, sum Wn) x 8], block partials summed in double.
+ * Backward: the mined mask is a constant; EVERY element of both gradient tensors is written (zeros where nothing
+ * contributes).  OCR_ERR_INVALID_ARG: NULL pointers, n or hw < 1, neg_ratio negative or NaN, focal not 0 / 1;
+ * OCR_ERR_UNSUPPORTED: n * hw > INT32_MAX; OCR_ERR_WORKSPACE: ws_bytes below the query (which is 0 for sizes < 1). */
+typedef struct {
+  int32_t n, hw, focal;
+  float neg_ratio, alpha, gamma;
+} ocr_balanced_loss_desc;
+size_t ocr_balanced_loss_workspace(const ocr_balanced_loss_desc* d);
+int ocr_balanced_loss_fwd(const ocr_balanced_loss_desc* d, const void* pixel_logits, const void* link_logits,
+                          const void* pixel_labels, const void* link_labels, const void* pixel_weights,
+                          void* ohnm_threshold, void* sums34, void* loss10, void* workspace, size_t ws_bytes,
+                          void* stream);
+/* mask_u8 [n*hw] = 1 on the mined negatives and on P (W != 0) */
+int ocr_balanced_loss_selected(const ocr_balanced_loss_desc* d, const void* pixel_logits, const void* pixel_labels,
+                               const void* pixel_weights, const void* ohnm_threshold, void* mask_u8, void* stream);
+int ocr_balanced_loss_bwd(const ocr_balanced_loss_desc* d, const void* pixel_logits, const void* link_logits,
+                          const void* pixel_labels, const void* link_labels, const void* pixel_weights,
+                          const void* ohnm_threshold, const void* sums34, float grad_scale, void* d_pixel_logits,
+                          void* d_link_logits, void* stream);
+/* seed = grad_scale * *loss_scale, read on the device (see ocr_dice_loss_bwd_dyn) */
+int ocr_balanced_loss_bwd_dyn(const ocr_balanced_loss_desc* d, const void* pixel_logits, const void* link_logits,
+                              const void* pixel_labels, const void* link_labels, const void* pixel_weights,
+                              const void* ohnm_threshold, const void* sums34, float grad_scale, const float* loss_scale,
+                              void* d_pixel_logits, void* d_link_logits, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * f32 INFERENCE PRECISION (round 4; csrc/f32_infer.hip): the forward graph with f32 storage and arithmetic, the

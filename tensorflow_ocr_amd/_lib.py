@@ -38,6 +38,13 @@ class SoftmaxLossDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("n", "hw", "pixel_rule", "label_rule", "link_gate", "focal")] + \
                [(n, ctypes.c_float) for n in ("neg_ratio", "alpha", "gamma")]
 
+
+class BalancedLossDesc(ctypes.Structure):
+    """ocr_balanced_loss_desc (include/ocr_hip.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("n", "hw", "focal")] + \
+               [(n, ctypes.c_float) for n in ("neg_ratio", "alpha", "gamma")]
+
+
 TENSOR_STATS_BUCKETS = 1551
 
 

@@ -99,12 +99,21 @@ class PixelLinkNet(object):
         ops.softmax_pairs(self.pixel_cls.data, out)
         return out
 
-    def build_loss(self, pixel_labels, link_labels, do_summary=True, focal=None):
+    def build_loss(self, pixel_labels, link_labels, do_summary=True, focal=None, pixel_weights=None, neg_ratio=3.0):
         """nets/pixellink.py:88-263: adds (2 * mean pixel CE) and (sum of the 8 link losses) to the
-        LOSSES collection; `focal=(alpha, gamma)` swaps the link CE for the focal loss."""
+        LOSSES collection; `focal=(alpha, gamma)` swaps the link CE for the focal loss.
+
+        `pixel_weights` [n,h,w] (the map of `pixellink_fn.generate_rbox_batch(weights=True)`) switches on the paper's
+        instance-balanced loss the reference left commented out (:138-168, :191-192; build-defined, `losses.balanced_loss`):
+        weighted text pixels, `neg_ratio` (config.max_neg_pos_ratio, :116) mined negatives per positive, links weighted on
+        text pixels.  None: the reference's mean, unchanged."""
         g = self.g
-        s = losses.softmax_loss(g, self.pixel_cls, self.link_cls, pixel_labels, link_labels,
-                                pixel_rule=2, label_rule=1, link_gate=False, focal=focal)
+        if pixel_weights is None:
+            s = losses.softmax_loss(g, self.pixel_cls, self.link_cls, pixel_labels, link_labels,
+                                    pixel_rule=2, label_rule=1, link_gate=False, focal=focal)
+        else:
+            s = losses.balanced_loss(g, self.pixel_cls, self.link_cls, pixel_labels, link_labels, pixel_weights,
+                                     focal=focal, neg_ratio=neg_ratio)
         g.collections["losses"].pop()        # replaced by the two reference entries
         g.collections["losses"].append(_LossTerm(s, lambda v: 2.0 * v[1]))
         g.collections["losses"].append(_LossTerm(s, lambda v: v[2:10].sum()))

@@ -834,6 +834,45 @@ def softmax_loss_bwd_dyn(desc, pixel_logits, link_logits, pixel_labels, link_lab
            ptr(link_labels), ptr(thr), ptr(sums34), c_float(grad_scale), ptr(loss_scale), ptr(d_pixel), ptr(d_link), _st())
 
 
+def _balanced_check(desc, pixel_logits, link_logits, pixel_labels, link_labels, pixel_weights):
+    px = desc.n * desc.hw
+    if pixel_logits.numel() != 2 * px or pixel_labels.numel() != px or pixel_weights.numel() != px or \
+            (link_logits is not None and (link_logits.numel() != 16 * px or link_labels.numel() != 8 * px)):
+        raise ValueError("balanced loss: tensors do not match n * hw = %d" % px)
+
+
+def balanced_loss_fwd(desc, pixel_logits, link_logits, pixel_labels, link_labels, pixel_weights, thr, sums34, loss10, ws):
+    """PixelLink's instance-balanced loss (include/ocr_hip.h: ocr_balanced_loss_fwd); pixel_weights f32 [n, hw]."""
+    _balanced_check(desc, pixel_logits, link_logits, pixel_labels, link_labels, pixel_weights)
+    nbytes = L.call_size("ocr_balanced_loss_workspace", byref(desc))
+    buf = ws.get(nbytes)
+    L.call("ocr_balanced_loss_fwd", byref(desc), ptr(pixel_logits), ptr(link_logits), ptr(pixel_labels),
+           ptr(link_labels), ptr(pixel_weights), ptr(thr), ptr(sums34), ptr(loss10), ptr(buf), c_size_t(nbytes), _st())
+
+
+def balanced_loss_selected(desc, pixel_logits, pixel_labels, pixel_weights, thr, mask_u8):
+    _balanced_check(desc, pixel_logits, None, pixel_labels, None, pixel_weights)
+    L.call("ocr_balanced_loss_selected", byref(desc), ptr(pixel_logits), ptr(pixel_labels), ptr(pixel_weights), ptr(thr),
+           ptr(mask_u8), _st())
+
+
+def balanced_loss_bwd(desc, pixel_logits, link_logits, pixel_labels, link_labels, pixel_weights, thr, sums34, grad_scale,
+                      d_pixel, d_link):
+    _balanced_check(desc, pixel_logits, link_logits, pixel_labels, link_labels, pixel_weights)
+    L.call("ocr_balanced_loss_bwd", byref(desc), ptr(pixel_logits), ptr(link_logits), ptr(pixel_labels),
+           ptr(link_labels), ptr(pixel_weights), ptr(thr), ptr(sums34), c_float(grad_scale), ptr(d_pixel), ptr(d_link),
+           _st())
+
+
+def balanced_loss_bwd_dyn(desc, pixel_logits, link_logits, pixel_labels, link_labels, pixel_weights, thr, sums34,
+                          grad_scale, loss_scale, d_pixel, d_link):
+    """balanced_loss_bwd with the seed grad_scale * loss_scale[0], `loss_scale` a DEVICE f32 (LossScaleState.scale_ptr)."""
+    _balanced_check(desc, pixel_logits, link_logits, pixel_labels, link_labels, pixel_weights)
+    L.call("ocr_balanced_loss_bwd_dyn", byref(desc), ptr(pixel_logits), ptr(link_logits), ptr(pixel_labels),
+           ptr(link_labels), ptr(pixel_weights), ptr(thr), ptr(sums34), c_float(grad_scale), ptr(loss_scale),
+           ptr(d_pixel), ptr(d_link), _st())
+
+
 # ------------------------------------------------------------------ heads, batched (one launch per kernel kind)
 def _struct(name, fields):
     return type(name, (ctypes.Structure,), {"_fields_": fields})
@@ -1161,6 +1200,18 @@ def pixellink_labels(cover, new_h, new_w, score, link):
     n, h, w = cover.shape
     L.call("ocr_pixellink_labels", ptr(cover), c_int(n), c_int(h), c_int(w), c_int(new_h), c_int(new_w),
            ptr(score), ptr(link), _st())
+
+
+def pixellink_instance_weights(cover, ignore, new_h, new_w, area, weight):
+    """Instance-balanced weight map of the label cells (include/ocr_hip.h: ocr_pixellink_instance_weights): cover int32
+    [n,h,w] (ocr_poly_cover), ignore uint8 [n,P] -> area int32 [n,P] (cells owned per polygon), weight f32 [n,new_h,new_w]."""
+    n, h, w = cover.shape
+    P = ignore.shape[1]
+    if tuple(ignore.shape) != (n, P) or ignore.dtype != torch.uint8 or tuple(area.shape) != (n, P) or \
+            area.dtype != torch.int32 or weight.numel() != n * new_h * new_w or weight.dtype != torch.float32:
+        raise ValueError("pixellink_instance_weights: tensors do not match n, max_polys, new_h, new_w")
+    L.call("ocr_pixellink_instance_weights", ptr(cover), ptr(ignore), c_int(n), c_int(P), c_int(h), c_int(w),
+           c_int(new_h), c_int(new_w), ptr(area), ptr(weight), _st())
 
 
 def resize_linear_u8(src_u8, dst_f32):

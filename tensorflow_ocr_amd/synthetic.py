@@ -6,7 +6,9 @@ direction order left, left_down, left_up, right, right_down, right_up, up, down)
 import numpy as np
 
 
-def make_batch(rng, n, size, rects=8):
+def make_batch(rng, n, size, rects=8, return_ids=False):
+    """return_ids=True adds a fifth value, the int32 [n, size/4, size/4] map of rectangle numbers (0: background, k + 1:
+    rectangle k, later ones on top) the labels were made from: the instances of the instance-balanced loss."""
     q4 = size // 4
     images = rng.uniform(0, 255, size=(n, size, size, 3)).astype(np.float32)
     ids = np.zeros((n, q4, q4), np.int32)
@@ -25,6 +27,8 @@ def make_batch(rng, n, size, rects=8):
         nb = pad[:, 1 + dy:1 + dy + q4, 1 + dx:1 + dx + q4]
         link[..., d] = ((ids > 0) & ((nb == ids) | (nb == -1))).astype(np.float32)
     mask = np.ones((n, q4, q4, 1), np.float32)
+    if return_ids:
+        return images, pixel, link, mask, ids
     return images, pixel, link, mask
 
 

@@ -223,9 +223,14 @@ def tf_pixellink_get_rbox(img_size, xs, ys, bboxes, ignored, graph=None):
     return s[0], l[0], torch.from_numpy(sb[0]).to(s.device)
 
 
-def generate_rbox_batch(h, w, xs_list, ys_list, bboxes_list, ignored_list, graph=None):
+def generate_rbox_batch(h, w, xs_list, ys_list, bboxes_list, ignored_list, graph=None, weights=False):
     """generate_rbox for a batch: device tensors score [n,h/4,w/4], link [n,h/4,w/4,8]; show_bboxes
-    [n,200,4] stays a NumPy copy of the inputs (:66,77)."""
+    [n,200,4] stays a NumPy copy of the inputs (:66,77).
+
+    weights=True (not in the reference: the input of `PixelLinkNet.build_loss(pixel_weights=...)`) adds a fourth value,
+    the instance-balanced weight map f32 [n,h/4,w/4] of `ops.pixellink_instance_weights`: every text instance that is
+    not `ignored` and owns at least one label cell weighs the same in total, ignored ones 0.  The `ignored` flags go
+    into that map only: score and link maps are the reference's, whatever they say."""
     import numpy as np
     g = graph or get_default_graph()
     h, w = int(h), int(w)
@@ -256,7 +261,16 @@ def generate_rbox_batch(h, w, xs_list, ys_list, bboxes_list, ignored_list, graph
     score = torch.empty((n, nh, nw), dtype=F32, device=dev)
     link = torch.empty((n, nh, nw, 8), dtype=F32, device=dev)
     ops.pixellink_labels(cover, nh, nw, score, link)
-    return score, link, show_bboxes
+    if not weights:
+        return score, link, show_bboxes
+    ignore = np.zeros((n, P), np.uint8)
+    for b in range(n):
+        ig = np.asarray(ignored_list[b]).reshape(-1)
+        ignore[b, :len(ig)] = ig != 0
+    area = torch.empty((n, P), dtype=torch.int32, device=dev)
+    weight = torch.empty((n, nh, nw), dtype=F32, device=dev)
+    ops.pixellink_instance_weights(cover, torch.from_numpy(ignore).to(dev), nh, nw, area, weight)
+    return score, link, show_bboxes, weight
 
 
 def east_pixel_detect(score_map, geo_map, score_map_thresh=0.8, link_thresh=0.8, graph=None):

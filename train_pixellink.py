@@ -62,7 +62,21 @@ def parse(argv=None):
     # flat buffers (summary.TensorStats).  0 = off: no event file.
     ap.add_argument('--save_summary_steps', type=int, default=0)
     ap.add_argument('--summary_variables', action='store_true')
+    # not a reference flag: the pixel loss.  'mean' is what the reference's build_loss computes (nets/pixellink.py:160, the
+    # mean CE over all pixels); 'instance_balanced' is the paper's loss the reference left commented out (:138-168,
+    # :191-192): every text instance weighs the same, --max_neg_pos_ratio hardest negatives per positive are mined, `###`
+    # regions train nothing (losses.balanced_loss; build-defined).
+    ap.add_argument('--pixel_loss', choices=('mean', 'instance_balanced'), default='mean')
+    # config.max_neg_pos_ratio (nets/pixellink.py:116); read by --pixel_loss instance_balanced only
+    ap.add_argument('--max_neg_pos_ratio', type=_neg_ratio_arg, default=3.0)
     return ap.parse_args(argv)
+
+
+def _neg_ratio_arg(text):
+    v = float(text)
+    if not v >= 0.0:
+        raise argparse.ArgumentTypeError('--max_neg_pos_ratio must be a number >= 0, got %r' % text)
+    return v
 
 
 def _accumulate_steps_arg(text):
@@ -103,7 +117,8 @@ INPUT_NORM = (120.0, 60.0)
 
 
 def dataset_batches(FLAGS, g, batch, rank):
-    """ICDAR directory -> (images [B,H,W,3] f32, pixel labels [B,H/4,W/4], link labels [B,H/4,W/4,8])."""
+    """ICDAR directory -> (images [B,H,W,3] f32, pixel labels [B,H/4,W/4], link labels [B,H/4,W/4,8]) and, with
+    --pixel_loss instance_balanced, the weight map [B,H/4,W/4] (the `###` tags zero their instances there)."""
     from tensorflow_ocr_amd.datasets import icdar
     from tensorflow_ocr_amd.tool import pixellink_fn
     H, W = FLAGS.train_image_height, FLAGS.train_image_width
@@ -133,9 +148,27 @@ def dataset_batches(FLAGS, g, batch, rank):
                     images = icdar.resize_images(ims, H, graph=g)
                 else:
                     raise SystemExit('square train size only (resize_images)')
-                score, link, _ = pixellink_fn.generate_rbox_batch(H, W, xs_l, ys_l, bb_l, ig_l, graph=g)
-                yield images, score, link
+                if FLAGS.pixel_loss == 'instance_balanced':
+                    score, link, _, weight = pixellink_fn.generate_rbox_batch(H, W, xs_l, ys_l, bb_l, ig_l, graph=g,
+                                                                              weights=True)
+                    yield images, score, link, weight
+                else:
+                    score, link, _ = pixellink_fn.generate_rbox_batch(H, W, xs_l, ys_l, bb_l, ig_l, graph=g)
+                    yield images, score, link
                 ims, xs_l, ys_l, bb_l, ig_l = [], [], [], [], []
+
+
+def synthetic_weights(ids, device, rects=8):
+    """The instance-balanced weight map of a synthetic batch: `ids` (synthetic.make_batch(return_ids=True)) is its own
+    label-resolution owner map, so `ids * 257` is a cover raster (first = last = owner) and the weights entry runs on it
+    without resampling."""
+    from tensorflow_ocr_amd import ops
+    n, h, w = ids.shape
+    cover = torch.from_numpy(ids * 257).to(device=device, dtype=torch.int32)
+    area = torch.empty((n, rects), dtype=torch.int32, device=device)
+    weight = torch.empty((n, h, w), dtype=torch.float32, device=device)
+    ops.pixellink_instance_weights(cover, torch.zeros((n, rects), dtype=torch.uint8, device=device), h, w, area, weight)
+    return weight
 
 
 def _window(step, K, next_batch):
@@ -173,9 +206,12 @@ def main():
 
     g = Graph(device, loss_scale=FLAGS.loss_scale, seed=1)
 
-    def forward_loss(gr, im, pixel_labels, link_labels):
+    balanced = FLAGS.pixel_loss == 'instance_balanced'
+
+    def forward_loss(gr, im, pixel_labels, link_labels, pixel_weights=None):
         net = pixellink.PixelLinkNet(im, graph=gr, input_norm=INPUT_NORM)   # raw images in
-        return net.build_loss(pixel_labels, link_labels)                 # 2*pixel + link (two LOSSES, :263)
+        return net.build_loss(pixel_labels, link_labels, pixel_weights=pixel_weights,   # 2*pixel + link (two LOSSES, :263)
+                              neg_ratio=FLAGS.max_neg_pos_ratio)
 
     def make_opt(gr):
         opt = MomentumOptimizer(gr, base_lr=FLAGS.learning_rate, momentum=FLAGS.momentum,
@@ -201,8 +237,10 @@ def main():
         if feeder is not None:
             last[0] = next(feeder)
         else:
-            im, px, lk, _ = synthetic.make_batch(rng, batch_size_per_gpu, FLAGS.train_image_height)
+            im, px, lk, _, ids = synthetic.make_batch(rng, batch_size_per_gpu, FLAGS.train_image_height, return_ids=True)
             last[0] = [torch.from_numpy(a).to(device, non_blocking=True) for a in (im, px[..., 0], lk)]
+            if balanced:
+                last[0].append(synthetic_weights(ids, device))
         return last[0]
     summaries = None
     for it in range(FLAGS.max_number_of_steps):
