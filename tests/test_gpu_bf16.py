@@ -131,6 +131,26 @@ def test_bf16_bn_pool_matrix(device):
     assert m and int(m.group(1)) == B.N_TESTS and "failed" not in r.stdout, tail
 
 
+def test_bf16_optim_matrix(device):
+    """tests/test_gpu_optim_matrix.py (every entry of optim.hip and s2d.hip against float64) on the bf16 library: every
+    case passes; the pack and space-to-depth rows then round to bfloat16, the f32 rows are the same code."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    try:
+        import test_gpu_optim_matrix as P
+    finally:
+        sys.path.pop(0)
+    env = dict(os.environ, OCR_STORAGE="bf16")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-s", "-m", "gpu", "-p", "no:cacheprovider",
+                        os.path.join(ROOT, "tests", "test_gpu_optim_matrix.py")],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    tail = (r.stdout + r.stderr)[-3000:]
+    import re
+    print("\n".join(re.findall(r"optim .*", r.stdout)))
+    assert r.returncode == 0, tail
+    m = re.search(r"(\d+) passed", r.stdout)
+    assert m and int(m.group(1)) == P.N_TESTS and "failed" not in r.stdout, tail
+
+
 def test_bf16_resnet50_east_640_batch64_parity(device):
     """BASELINE configs[3] as quoted (bf16, batch 64, 640^2): n = 64 replicated == n = 2 in the bf16 library."""
     env = dict(os.environ, OCR_STORAGE="bf16")
