@@ -80,7 +80,8 @@ def main():
     torch.cuda.synchronize()
     plan = step.plan
     assert plan is not None, "the step did not record a plan"
-    from tensorflow_ocr_amd import _lib
+    from tensorflow_ocr_amd import _lib, step_plan
+    kinds = step_plan.kinds(plan)
     times = [[] for _ in plan]
     for _ in range(args.reps):
         evs = []
@@ -88,14 +89,13 @@ def main():
             if src is not dst:
                 dst.copy_(src, non_blocking=True)
         for i, e in enumerate(plan):
-            if e[0] in ("fork", "join"):          # train.schedule_guests' markers: this walk is serial, one stream
+            if kinds[i] in ("fork", "join"):      # train.schedule_guests' markers: this walk is serial, one stream
                 continue
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
+            if kinds[i] == "xchg":
+                continue
             if e[0] == "c":
-                tag = e[4]
-                if tag is not None and tag[0] == "xchg":
-                    continue
                 rc = e[1](*e[2])
                 if rc != 0:
                     _lib.check(rc, e[3])
@@ -113,11 +113,11 @@ def main():
         us = float(np.median(times[i]))
         row = {"i": i, "us": round(us, 1), "call": e[3] if e[0] == "c" else "py:" + (e[2] if len(e) > 2 and isinstance(e[2], str) else "hook")}
         if e[0] == "c":
-            tag = e[4]
-            if tag is not None:
-                row["variant"], row["phase"] = tag[0], (tag[2] if len(tag) > 2 else "")
-                if len(tag) > 1 and isinstance(tag[1], float) and tag[1] > 0:
-                    row["tflops"] = round(tag[1] / us / 1e6, 1)
+            if kinds[i] != "c":
+                row["variant"], row["phase"] = kinds[i], step_plan.note(e)
+                amount = step_plan.amount(e)                 # FLOP (a guest's bytes: TB/s under the same key)
+                if isinstance(amount, float) and amount > 0:
+                    row["tflops"] = round(amount / us / 1e6, 1)
             d = desc_of(e[2])
             if d is not None:
                 row["conv"] = "%dx%d %d->%d k%d s%d f%d" % (d["h"], d["w"], d["cin"], d["cout"], d["kh"], d["stride"], d["flags"])

@@ -16,6 +16,8 @@ complete, ~60 % of the bytes) travel under the conv1-conv4 backward.
 import torch
 import torch.distributed as td
 
+from . import step_plan
+
 
 def init_process_group_from_env(backend=None, force=False):
     """Reads RANK / WORLD_SIZE / LOCAL_RANK / MASTER_* (torch.distributed.run contract; also what
@@ -344,7 +346,7 @@ class GradientAllReduce:
         s, e = self.buckets[bi]
         buf = self.store.flat_grad[s:e]
         if self.accum is not None and not self.accumulated[bi]:
-            # abi mode: a C entry of the plan, tagged ("accum",), replayed in every phase; torch mode: the recorded host
+            # abi mode: a C entry of the plan, tagged step_plan.accum_tag(), replayed in every phase; torch mode: the recorded host
             # callback re-runs this call, so it must not ALSO enter the plan (as the scale in `finish`)
             self.accumulated[bi] = True
             self.accum.run(s, e, record=self.mode == "abi")
@@ -381,14 +383,14 @@ class GradientAllReduce:
 
     @staticmethod
     def _xcall(name, *args, kind=None, when=None):
-        """A C-ABI call of the exchange, tagged ("xchg", kind, when) in a recorded plan: kind "rccl" / "proxy" = the two
+        """A C-ABI call of the exchange, tagged step_plan.xchg_tag(kind, when) in a recorded plan: kind "rccl" / "proxy" = the two
         alternative comm-stream launches of a bucket, "finish" = the compute stream's wait for a bucket, None = event
-        plumbing; when "early" / "late" = the placement the entry belongs to when the plan holds both (train.TrainStep.
-        _replay runs the entries of the placement `overlap` names), None = always."""
+        plumbing; when "early" / "late" = the placement the entry belongs to when the plan holds both (step_plan.run_plan
+        runs the entries of the placement `overlap` names), None = always."""
         from . import _lib as L
         L.call(name, *args)
         if L.RECORDER is not None:
-            L.RECORDER.tag_last(("xchg", kind, when))
+            L.RECORDER.tag_last(step_plan.xchg_tag(kind, when))
 
     def finish(self):
         """Fire whatever has not been fired (variables without a gradient this step), wait for all

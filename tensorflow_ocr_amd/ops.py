@@ -10,7 +10,7 @@ from ctypes import byref, c_double, c_float, c_int, c_int64, c_size_t
 
 import torch
 
-from . import _lib as L
+from . import _lib as L, step_plan
 from ._lib import ConvDesc, CONV_ACCUM_F16, CONV_BIAS, CONV_RELU, CONV_STATS, ptr
 
 F16, F32 = (torch.bfloat16 if L.STORAGE == "bf16" else torch.float16), torch.float32
@@ -98,7 +98,7 @@ def _conv_call(fn, d, *args, phase, pwx=False, timed=False):
         v = conv2d_variant(d)
         if pwx:
             v = v.replace("conv_pw_kernel", "conv_pwx_kernel")
-        tag = (v, 2.0 * d.n * d.oh * d.ow * d.cout * d.cin * d.kh * d.kw, phase)
+        tag = step_plan.kernel_tag(v, 2.0 * d.n * d.oh * d.ow * d.cout * d.cin * d.kh * d.kw, phase)
     events = None
     if timed and KERNEL_TIMING is not None:
         events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -263,7 +263,7 @@ def bn_bwd_coefficients_pre(partial, T, c, count, scale, save_mean, save_invstd,
     weight-gradient grid they would hold the guest back for that grid's whole launch)."""
     bn_bwd_coefficients(partial, T, c, count, scale, save_mean, save_invstd, dgamma, dbeta, coef, ws)
     if L.RECORDER is not None:
-        L.RECORDER.tag_last(("pre",))
+        L.RECORDER.tag_last(step_plan.pre_tag())
 
 
 def bn_relu_bwd_apply_affine(y, da, scale, shift, coef_b, coef_c, relu, dy):
@@ -271,7 +271,7 @@ def bn_relu_bwd_apply_affine(y, da, scale, shift, coef_b, coef_c, relu, dy):
     L.call("ocr_bn_relu_bwd_apply_affine_f16", ptr(y), ptr(da), ptr(scale), ptr(shift), ptr(coef_b), ptr(coef_c),
            c_int(n), c_int(h), c_int(w), c_int(c), c_int(int(relu)), ptr(dy), c_int(0), _st())
     if L.RECORDER is not None:
-        L.RECORDER.tag_last(("guest", 6.0 * n * h * w * c))           # bytes: y + da read, dy written
+        L.RECORDER.tag_last(step_plan.guest_tag(6.0 * n * h * w * c))           # bytes: y + da read, dy written
 
 
 def bn_relu_pool_bwd_idx_apply_affine(y, argmax, da_pool, coef, relu, dy):
@@ -279,7 +279,7 @@ def bn_relu_pool_bwd_idx_apply_affine(y, argmax, da_pool, coef, relu, dy):
     L.call("ocr_bn_relu_pool_bwd_idx_apply_affine_f16", ptr(y), ptr(argmax), ptr(da_pool), ptr(coef[0]), ptr(coef[1]),
            ptr(coef[2]), c_int(n), c_int(h), c_int(w), c_int(c), c_int(int(relu)), ptr(dy), c_int(0), _st())
     if L.RECORDER is not None:
-        L.RECORDER.tag_last(("guest", 4.75 * n * h * w * c))          # y read + dy written + the pooled gradient and index
+        L.RECORDER.tag_last(step_plan.guest_tag(4.75 * n * h * w * c))          # y read + dy written + the pooled gradient and index
 
 
 def conv2d_wgrad_variant(d):
@@ -307,17 +307,17 @@ def conv2d_wgrad(d, x, dy, dw, ws, alloc=None):
             # a host only if a guest's 56 registers per lane fit beside it (a kernel that fills the file would
             # time-slice with the guest); otherwise it stays where it was recorded
             room = L.call_int("ocr_conv2d_wgrad_guest_room", byref(d))
-            L.RECORDER.tag_last(("side", flops) if room >= 56 else ("side",))
+            L.RECORDER.tag_last(step_plan.side_tag(flops if room >= 56 else None))
         L.call("ocr_conv2d_wgrad_reduce_f32", byref(d), ptr(buf), ptr(dw), _st())
         if L.RECORDER is not None:
-            L.RECORDER.tag_last(("reduce",))
+            L.RECORDER.tag_last(step_plan.reduce_tag())
         return
     buf = ws.get(nbytes)
     L.call("ocr_conv2d_wgrad_f16", byref(d), ptr(x), ptr(dy), ptr(dw), ptr(buf), c_size_t(nbytes), _st())
     if L.RECORDER is not None:
         # (the one-call form shares the tower's slab workspace with the next weight gradient: it stays where it was
         # recorded — train.schedule_guests holds back only the split form above)
-        L.RECORDER.tag_last(("side",))
+        L.RECORDER.tag_last(step_plan.side_tag())
 
 
 def space_to_depth(x, xs):
@@ -339,7 +339,7 @@ def weights_s2d_grad(dw22, dw33):
     _, _, cin, cout = dw33.shape
     L.call("ocr_weights_s2d_grad_f32", ptr(dw22), c_int(cin), c_int(cout), ptr(dw33), _st())
     if L.RECORDER is not None:
-        L.RECORDER.tag_last(("side",))      # reads what the weight-gradient launch before it wrote: same stream
+        L.RECORDER.tag_last(step_plan.side_tag())      # reads what the weight-gradient launch before it wrote: same stream
 
 
 def conv2d_first_num_mtiles(n, h, w):
@@ -448,7 +448,7 @@ def bn_relu_bwd_reduce_rows(y, da_full, scale, shift, save_mean, save_invstd, re
            _st())
     if L.RECORDER is not None:
         # (its grid is one workgroup per CU wherever it runs: the row count must not depend on the placement)
-        L.RECORDER.tag_last(("guest", (4.0 if not pooled else 4.75) * n * h * w * c, "as_is"))
+        L.RECORDER.tag_last(step_plan.guest_tag((4.0 if not pooled else 4.75) * n * h * w * c, as_is=True))
     return part, T
 
 
@@ -458,7 +458,7 @@ def bn_relu_poolfull_bwd_apply_affine(y, da_full, da_pool, argmax, scale, shift,
     L.call("ocr_bn_relu_poolfull_bwd_apply_affine_f16", ptr(y), ptr(da_full), ptr(da_pool), ptr(argmax), ptr(scale), ptr(shift),
            ptr(coef[1]), ptr(coef[2]), c_int(n), c_int(h), c_int(w), c_int(c), c_int(int(relu)), ptr(dy), c_int(0), _st())
     if L.RECORDER is not None:
-        L.RECORDER.tag_last(("guest", 6.75 * n * h * w * c))          # y + da_full read, dy written, pooled gradient + index
+        L.RECORDER.tag_last(step_plan.guest_tag(6.75 * n * h * w * c))          # y + da_full read, dy written, pooled gradient + index
 
 
 def bn_relu_bwd_reduce_pooled(y, scale, shift, save_mean, save_invstd, pooled, relu, da_out, dgamma, dbeta, coef, ws):

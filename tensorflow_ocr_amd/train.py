@@ -5,14 +5,22 @@ train_pixellink.py:179-194,222-243 (sum of pre-divided gradients -> Momentum).
 One process drives one GPU ("tower"); the cross-tower gradient mean of `average_gradients`
 (multigpu_train.py:70-85) is an RCCL all-reduce over the flat gradient buffer, issued by
 `dist.GradientAllReduce` on a side stream.
+
+The recorded step's plan — its tags, `schedule_guests`, the replay walk — is `step_plan`; the names below are imported
+so that `train.schedule_guests` and the switches `train.GUEST_*` stay what callers read and set: TrainStep passes
+THIS module's switch values to the scheduler.
 """
+import contextlib
+import ctypes
 import math
 
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, step_plan
 from .graph import F32
+from .step_plan import (GUEST_BALANCE, GUEST_COVER, GUEST_MIN_US, GUEST_PAIRED_GRID, USE_GUESTS, XCHG_AT_FORK,  # noqa: F401
+                        _VIEW_OPS, _record_audit, schedule_guests)
 
 def exponential_decay(learning_rate, global_step, decay_steps=5000, decay_rate=0.94, staircase=True):
     """tf.train.exponential_decay (multigpu_train.py:104)."""
@@ -155,7 +163,7 @@ class GradAccum:
             from . import _lib
             ops.grad_accum(g, a, self.state)
             if _lib.RECORDER is not None:
-                _lib.RECORDER.tag_last(("accum",))
+                _lib.RECORDER.tag_last(step_plan.accum_tag())
         elif self.k == 1:
             pass
         elif self.micro >= self.k - 1:
@@ -170,7 +178,7 @@ class GradAccum:
             from . import _lib
             ops.grad_accum_advance(self.state)
             if _lib.RECORDER is not None:
-                _lib.RECORDER.tag_last(("accum", "advance"))
+                _lib.RECORDER.tag_last(step_plan.accum_tag(advance=True))
         else:
             self.state[ops.GA_MICRO] = (self.micro + 1) % self.k
             if self.micro + 1 >= self.k:
@@ -343,228 +351,6 @@ class MomentumOptimizer(_ClipReadout):
         self.global_step += 1
 
 
-_VIEW_OPS = frozenset((
-    "empty", "empty_like", "empty_strided", "new_empty", "new_empty_strided", "view", "_unsafe_view", "reshape",
-    "_reshape_alias", "slice", "select", "permute", "transpose", "t", "as_strided", "detach", "alias", "unsqueeze",
-    "squeeze", "expand", "narrow", "unbind", "split", "split_with_sizes", "unfold", "view_as_real", "lift_fresh",
-    "is_pinned", "_has_compatible_shallow_copy_type", "size", "stride", "sym_size", "sym_stride", "numel", "dim"))
-
-
-def _record_audit():
-    """Dispatch mode for the RECORDED step: the plan holds C-ABI calls only, so a torch operator that
-    launches device work inside `forward_loss` (arithmetic on an input, a dtype cast, a `zeros`) would
-    run once, at record time, and every replayed step would read its stale result.  Collects the names
-    of such operators so `TrainStep` can refuse the recording; views and allocations are fine."""
-    from torch.utils._python_dispatch import TorchDispatchMode
-
-    class Audit(TorchDispatchMode):
-        def __init__(self):
-            super().__init__()
-            self.offenders = []
-
-        def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-            out = func(*args, **(kwargs or {}))
-            name = func.overloadpacket.__name__ if hasattr(func, "overloadpacket") else str(func)
-            if name not in _VIEW_OPS:
-                flat = list(args) + list((kwargs or {}).values()) + (list(out) if isinstance(out, (tuple, list)) else [out])
-                if any(isinstance(t, torch.Tensor) and t.is_cuda for t in flat):
-                    self.offenders.append(name)
-            return out
-    return Audit()
-
-
-USE_GUESTS = __import__("os").environ.get("OCR_GUEST_STREAM", "1") == "1"
-
-
-GUEST_COVER = float(__import__("os").environ.get("OCR_GUEST_COVER", "2.1"))
-GUEST_PAIRED_GRID = int(__import__("os").environ.get("OCR_GUEST_PAIRED_GRID", "256"))
-GUEST_MIN_US = float(__import__("os").environ.get("OCR_GUEST_MIN_US", "40"))
-# a completed bucket's exchange entries at the NEXT fork instead of right behind the join that followed its last weight
-# gradient (VERDICT r5 item 7c): the comm kernel then starts beside held-back weight gradients (456 of 512 registers: the
-# only kernels of the step it can share a CU with) instead of beside the next input-gradient launch (512: it cannot).
-# Measured with the one-GPU stand-ins (bench.py exchange.proxy_at_fork): 1.34 -> 1.23 ms of the stand-in's 1.10-1.19 ms
-# exposed per step, either footprint; on.  (Issuing an exchange entry later than recorded is always correct.)
-XCHG_AT_FORK = __import__("os").environ.get("OCR_XCHG_AT_FORK", "1") == "1"
-# hosts shared out with the guests still to come in view (round 6): the greedy choice covered conv2_1's apply pass with two
-# weight gradients (791 us for a 577 us pass) and left conv1_2's pooled pass — the last and largest — 306 us of host for 585,
-# 0.28 ms exposed on the critical path (profiles/r05_guest_pairs_trace.txt).  0: the round-5 greedy choice (A/B).
-GUEST_BALANCE = __import__("os").environ.get("OCR_GUEST_BALANCE", "1") == "1"
-
-
-def schedule_guests(entries, cover=None, min_us=None, xchg_at_fork=None, balance=None):
-    """Run the HBM-bound batch-norm backward passes of the recorded step as GUESTS beside its weight gradients
-    (csrc/guest_bn.hip; measured rates: profiles/r05_guest_pairs.json).
-
-    Recorded order (layers._conv_backward, layers.conv2d): ... coefficients(L) ["pre"], apply(L) ["guest", bytes],
-    dgrad(L), wgrad(L) = slab kernel ["side", FLOP] + slab sum ["reduce"], [exchange entries of the bucket that wgrad(L)
-    completed], coefficients(L-1), apply(L-1), ...  The chain apply -> dgrad -> apply is the critical path; a weight
-    gradient depends on its layer's apply pass only, and nothing but the optimiser (and the exchange) waits for it.
-    So weight gradients are HELD BACK and spent as hosts: at every guest the plan forks, the guest goes to the second
-    stream, and held-back slab kernels go to the main stream — chosen, oldest first, so that their estimated time
-    covers `cover` x the guest's stand-alone time without overshooting it by much (beside a host a guest moves ~0.42 of
-    its stand-alone rate, the host keeps ~0.9 of its own: small guests take small hosts, the deep layers' weight
-    gradients — little HBM traffic of their own — are left for the large passes of conv2 / conv1, which come last) —
-    then the plan joins: the next input-gradient kernel owns the whole register file and would only time-slice with a
-    straggler.  The slab sums (and whatever was recorded behind them: a re-layout of the gradient, the exchange entries
-    of the bucket it completed) follow the join: alone they take 13 us, beside a streaming guest 60-370.  A guest's
-    waves (<= 56 registers per lane) are placed beside the weight gradient's resident workgroups (456 of 512).  What is
-    still held back when something needs the gradients (the exchange's closing entries, the optimiser, any host
-    callback) is issued there, in order; a guest with nothing to run beside stays on the main stream.  Exchange entries
-    issued later than recorded are always correct: they order the comm stream behind the compute stream at that
-    point."""
-    cover = GUEST_COVER if cover is None else cover
-    min_us = GUEST_MIN_US if min_us is None else min_us
-    xchg_at_fork = XCHG_AT_FORK if xchg_at_fork is None else xchg_at_fork
-    balance = GUEST_BALANCE if balance is None else balance
-    out, pending, i, n = [], [], 0, len(entries)
-    deferred = []                # exchange entries of hosts already run, waiting for the next fork (xchg_at_fork)
-
-    def tag(e):
-        return e[4] if (e[0] == "c" and e[4] is not None) else (None,)
-
-    def travels(e):            # an exchange entry that belongs to the weight gradient in front of it
-        t = tag(e)
-        if t[0] == "accum":    # a bucket's accumulate call (GradAccum.run): in front of its exchange entries, and like them
-            return len(t) < 2  # it reads every weight gradient recorded before it; the step's one advance call does not travel
-        return t[0] == "xchg" and (len(t) < 2 or t[1] != "finish") and (len(t) < 3 or t[2] in (None, "early"))
-
-    def guest_ahead(i0):             # is there a guest behind entry i0, before anything that needs the gradients?
-        for q in range(i0 + 1, n):
-            eq = entries[q]
-            tq = tag(eq)
-            if tq[0] == "guest":
-                return True
-            if eq[0] != "c" or (tq[0] in ("xchg", "accum") and not travels(eq)):
-                return False
-        return False
-
-    def outlook(i0):
-        """(what the guests from entry i0 on want of hosts, us; what the weight gradients recorded behind i0 and in front of
-        the last of those guests will supply, us)"""
-        last = None
-        for q in range(i0, n):
-            tq = tag(entries[q])
-            if tq[0] == "guest" and len(tq) > 1 and tq[1] / 5.0e6 >= min_us:
-                last = q
-        want = supply = 0.0
-        if last is not None:
-            for q in range(i0, last + 1):
-                tq = tag(entries[q])
-                if tq[0] == "guest" and len(tq) > 1 and tq[1] / 5.0e6 >= min_us:
-                    want += cover * tq[1] / 5.0e6
-                elif tq[0] == "side" and len(tq) >= 2 and q > i0:
-                    supply += tq[1] / 1.3e9
-        return want, supply
-
-    def flush():
-        out.extend(deferred)         # (recorded before anything still pending: their buckets are complete)
-        del deferred[:]
-        for head, tail, _ in pending:
-            out.append(head)
-            out.extend(tail)
-        del pending[:]
-    while i < n:
-        e = entries[i]
-        t = tag(e)
-        if t[0] == "side" and len(t) < 2:
-            out.append(e)                    # a weight gradient that cannot host (ops.conv2d_wgrad): stays in place
-            i += 1
-            continue
-        if t[0] == "side" and not guest_ahead(i):
-            out.extend(deferred)             # (no fork will come for them either)
-            del deferred[:]
-            out.append(e)                    # no guest left to host (a net without batch norm: every call stays in place,
-            i += 1                           # and the exchange sees its buckets as early as it was recorded)
-            continue
-        if t[0] == "side":
-            us = t[1] / 1.3e9                                     # FLOP at 1.3 PFLOP/s, in us
-            j = i + 1
-            while j < n and (tag(entries[j])[0] == "reduce" or (tag(entries[j])[0] == "side" and len(tag(entries[j])) < 2)
-                             or travels(entries[j])):
-                j += 1
-            pending.append((e, entries[i + 1:j], us))
-            i = j
-            continue
-        if t[0] == "guest":
-            alone = (t[1] / 5.0e6) if len(t) > 1 else 0.0                  # bytes at 5 TB/s, in us
-            if pending and alone >= min_us:          # (a fork + join costs the main queue ~25 us of idle time)
-                need = cover * alone
-                # a host that carries exchange entries (its weight gradient completed a bucket) may only go once every
-                # weight gradient recorded before it has gone: the bucket's all-reduce reads all of them
-                def closes_bucket(k):
-                    return any(tag(x)[0] in ("xchg", "accum") for x in pending[k][1])
-                take, acc, skipped = [], 0.0, False
-                if balance and len(pending) <= 12:
-                    # what is exposed of a guest is what its hosts do not cover, and every host a guest can use the later
-                    # guests can use too: when the guests still to come want more than all hosts can give, each gets its
-                    # SHARE (target), and the subset of the pending hosts whose sum is closest to the target goes — a miss
-                    # either way costs a guest (this one or a later one) the same; with hosts to spare, covering counts
-                    want, supply = outlook(i)
-                    have = sum(us for _, _, us in pending) + supply
-                    scarce = have < want
-                    target = need * have / want if scarce else need
-                    best = None
-                    for m in range(1, 1 << len(pending)):
-                        ks = [k for k in range(len(pending)) if m >> k & 1]
-                        if any(closes_bucket(k) and any(j not in ks for j in range(k)) for k in ks):
-                            continue
-                        tot = sum(pending[k][2] for k in ks)
-                        miss = abs(tot - target) if scarce else (2.0 * (target - tot) if tot < target else 0.25 * (tot - target))
-                        key = (miss, len(ks), ks)
-                        if best is None or key < best[0]:
-                            best = (key, ks, tot)
-                    if best is not None and best[2] <= 3.0 * need:
-                        take, acc = best[1], best[2]
-                else:
-                    for k, (_, _, us) in enumerate(pending):                  # oldest first, no large overshoot
-                        if acc >= 0.85 * need:
-                            break
-                        if acc + us <= 1.3 * need and not (skipped and closes_bucket(k)):
-                            take.append(k)
-                            acc += us
-                        else:
-                            skipped = True
-                if not take:
-                    ok = [q for q in range(len(pending)) if q == 0 or not closes_bucket(q)]
-                    k = min(ok, key=lambda q: pending[q][2])
-                    if pending[k][2] <= 3.0 * need:
-                        take = [k]
-                if take:
-                    g = list(e)
-                    g[4] = ("guest", t[1] if len(t) > 1 else 0.0, "paired")
-                    # the guest entry points' `max_workgroups` (second to last argument): one workgroup per CU beside hosts
-                    if len(e[2]) >= 2 and t[-1] != "as_is":
-                        g[2] = tuple(e[2][:-2]) + (__import__("ctypes").c_int(GUEST_PAIRED_GRID),) + (e[2][-1],)
-                    out.append(["fork"])
-                    out.extend(deferred)          # the exchange of buckets completed by EARLIER hosts starts with these hosts
-                    del deferred[:]
-                    out.append(g)
-                    hosts = [pending[k] for k in take]
-                    for k in reversed(take):
-                        del pending[k]
-                    for head, _, _ in hosts:
-                        out.append(head)
-                    out.append(["join"])
-                    for _, tail, _ in hosts:
-                        for te in tail:
-                            (deferred if (xchg_at_fork and tag(te)[0] == "xchg") else out).append(te)
-                    i += 1
-                    continue
-            out.append(e)
-            i += 1
-            continue
-        if e[0] != "c" or t[0] in ("xchg", "accum"):
-            # host callbacks (optimiser, torch-mode exchange), the exchange's closing entries — and an exchange entry that
-            # TRAVELS behind a weight gradient which stayed in place (one that cannot host, or conv1_1's sums form): its
-            # bucket's all-reduce reads every weight gradient recorded before it, the held-back ones included.  An accumulate
-            # call (GradAccum.run) reads them too: the whole-buffer one behind backward, a bucket's in front of its exchange
-            flush()
-        out.append(e)
-        i += 1
-    flush()
-    return out
-
-
 class TrainStep:
     """One data-parallel training step of `multigpu_train.py`'s hot loop (:118-142,171-174) for
     this process's tower: forward -> loss -> backward (gradient buckets all-reduced while the rest
@@ -617,7 +403,8 @@ class TrainStep:
         self.reducer = None
         self.replay = replay
         self.steps = 0
-        self.plan = None
+        self.plan = None                  # the list of entries replayed (bench.py reads it); plan_kinds: step_plan.kinds of it
+        self.plan_kinds = None
         self.static_batch = None
         self.loss = None
         self.guest_stream = self.guest_ptr = self.guest_event = None      # schedule_guests: the paired guest passes' stream
@@ -695,7 +482,7 @@ class TrainStep:
                 # the call before this one ran at the same store version and refreshed the lazily packed operands (conv1_1's
                 # among them); recorded as it stands, this step would hold no refresh of them and replay stale weights
                 g.stale_lazy_packs()
-        audit = _record_audit() if record else __import__("contextlib").nullcontext()
+        audit = _record_audit() if record else contextlib.nullcontext()
         try:
             with audit:
                 loss = self.forward_loss(g, *batch)
@@ -727,7 +514,7 @@ class TrainStep:
             rec.py(self._repack)
             rec.entries[-1].append("repack")
             self.recorded = rec.entries                       # (kept: reschedule() derives another plan from the same recording)
-            self.plan = schedule_guests(rec.entries) if USE_GUESTS else rec.entries
+            self._set_plan(self._schedule(rec.entries) if USE_GUESTS else rec.entries)
             self.static_batch = list(batch)
             self.keepalive, g.keepalive = g.keepalive, None
             g.reset_tape()
@@ -737,7 +524,17 @@ class TrainStep:
     def reschedule(self, **kw):
         """Another guest / exchange placement of the SAME recorded step (schedule_guests keywords): bench.py's A/B arms."""
         if self.plan is not None and USE_GUESTS:
-            self.plan = schedule_guests(self.recorded, **kw)
+            self._set_plan(self._schedule(self.recorded, **kw))
+
+    def _schedule(self, entries, **kw):
+        """schedule_guests under this module's switches (a caller's keywords first)."""
+        sw = dict(cover=GUEST_COVER, min_us=GUEST_MIN_US, xchg_at_fork=XCHG_AT_FORK, balance=GUEST_BALANCE,
+                  paired_grid=GUEST_PAIRED_GRID)
+        sw.update((k, v) for k, v in kw.items() if v is not None)
+        return schedule_guests(entries, **sw)
+
+    def _set_plan(self, plan):
+        self.plan, self.plan_kinds = plan, step_plan.kinds(plan)
 
     def _repack(self):
         """Batched re-pack of the [tap][cout][cin] / [tap][cin][cout] operand copies from the f32 masters, stamped
@@ -748,75 +545,21 @@ class TrainStep:
         self._packed_version = self.g.store.version
 
     def _replay(self, batch):
-        import ctypes
-        from . import _lib, ops
         if self.g.store.version != self._packed_version:
             self._repack()
         for dst, src in zip(self.static_batch, batch):
             if src is not dst:
                 dst.copy_(src, non_blocking=True)
-        timing = ops.KERNEL_TIMING
-        main = torch.cuda.current_stream()
-        bwd_marked = False
         closing = self.accum is None or self.accum.closing
         self.reducer.closing = closing      # (torch mode: the exchange's host callbacks ask it)
-        for e in self.plan:
-            if e[0] == "fork":
-                # a weight gradient and the guest pass paired with it (schedule_guests): the guest stream starts here
-                if self.guest_stream is None:
-                    self.guest_stream = torch.cuda.Stream()
-                    self.guest_ptr = ctypes.c_void_p(self.guest_stream.cuda_stream)
-                    self.guest_event = torch.cuda.Event()
-                self.guest_event.record(main)
-                self.guest_stream.wait_event(self.guest_event)
-                continue
-            if e[0] == "join":
-                main.wait_stream(self.guest_stream)
-                continue
-            if e[0] == "c":
-                tag = e[4]
-                if tag is not None and tag[0] == "guest" and tag[-1] == "paired":
-                    rc = e[1](*(e[2][:-1] + (self.guest_ptr,)))
-                    if rc != 0:
-                        _lib.check(rc, e[3])
-                    continue
-                if tag is not None and tag[0] == "xchg":
-                    # the gradient exchange as C-ABI calls (dist.GradientAllReduce, abi mode); once per window
-                    if self.reducer.enabled and closing:
-                        kind = tag[1] if len(tag) > 1 else None
-                        when = tag[2] if len(tag) > 2 else None
-                        # a bucket's comm-stream launch: the RCCL all-reduce OR its one-GPU stand-in (dist: proxy)
-                        if (kind == "proxy" and not self.reducer.use_proxy) or (kind == "rccl" and self.reducer.use_proxy):
-                            continue
-                        # a plan that holds both placements of the exchange (under backward / after it) runs one
-                        if when is not None and when != ("early" if self.reducer.overlap else "late"):
-                            continue
-                        if (kind == "finish" or when == "late") and self.backward_end_event is not None and not bwd_marked:
-                            self.backward_end_event.record(main)      # end of backward on the compute stream
-                            bwd_marked = True
-                        rc = e[1](*e[2])
-                        if rc != 0:
-                            _lib.check(rc, e[3])
-                    continue
-            if e[0] == "c":
-                tag = e[4]
-                if timing is not None and tag is not None and len(tag) > 2 and tag[0] not in ("side", "guest", "xchg"):      # (kernel instantiation, FLOP, phase)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    rc = e[1](*e[2])
-                    e1.record()
-                    timing.append((tag[0], tag[1], tag[2] if len(tag) > 2 else "", e0, e1))
-                else:
-                    rc = e[1](*e[2])
-                if rc != 0:
-                    _lib.check(rc, e[3])
-            else:
-                if not closing and len(e) > 2 and e[2] in ("opt", "repack"):
-                    continue                                      # a micro-step inside its window: gradients only
-                if len(e) > 2 and e[2] == "opt" and self.backward_end_event is not None and not bwd_marked:
-                    self.backward_end_event.record(main)          # (no exchange in this step: backward ends here)
-                    bwd_marked = True
-                e[1]()
+        if self.guest_stream is None and "fork" in self.plan_kinds:
+            # a weight gradient and the guest pass paired with it (schedule_guests) run on two streams
+            self.guest_stream = torch.cuda.Stream()
+            self.guest_ptr = ctypes.c_void_p(self.guest_stream.cuda_stream)
+            self.guest_event = torch.cuda.Event()
+        step_plan.run_plan(self.plan, self.plan_kinds, step_plan.Replay(
+            torch.cuda.current_stream(), self.guest_stream, self.guest_ptr, self.guest_event, self.reducer, closing,
+            self.backward_end_event, ops.KERNEL_TIMING))
         if self.accum is not None:
             self.accum.micro = (self.accum.micro + 1) % self.accum.k      # the plan's advance entry has moved the device's
         return self.loss

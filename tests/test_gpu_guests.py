@@ -1,11 +1,14 @@
 """The GUEST forms of the batch-norm backward apply passes (csrc/guest_bn.hip; reference: the gradient of slim.batch_norm
 + ReLU under nets/model_vgg_16.py:144, nets/vgg.py:14-39) against the general kernels they stand in for and against a
 float64 restatement, and the recorded step's pairing of each with the weight gradient it runs beside."""
+import json
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import ocr_oracle as O
+from test_step_plan_host import GOLDEN, canonical
 
 pytestmark = pytest.mark.gpu
 BF16 = O.STORAGE == torch.bfloat16
@@ -226,7 +229,7 @@ def test_recorded_step_pairs_every_guest_with_a_weight_gradient(device, monkeypa
     (two streams) gives the parameters of the eager step (one stream) bit for bit."""
     from tensorflow_ocr_amd.graph import Graph
     from tensorflow_ocr_amd.nets import model_vgg_16 as M
-    from tensorflow_ocr_amd import train
+    from tensorflow_ocr_amd import step_plan, train
     from tensorflow_ocr_amd.train import AdamOptimizer, TrainStep
     monkeypatch.setattr(train, "GUEST_MIN_US", 0.0)          # (at this size every pass is shorter than the pairing threshold)
     rng = np.random.default_rng(0)
@@ -246,7 +249,12 @@ def test_recorded_step_pairs_every_guest_with_a_weight_gradient(device, monkeypa
         outs.append(g.store.flat.clone())
         if replay:
             plan = step.plan
-            kinds = [e[0] if e[0] != "c" else (e[4][0] if e[4] is not None else "c") for e in plan]
+            kinds = step_plan.kinds(plan)
+            if not BF16:
+                # the scheduler on a real recording: the plan the commit it was split out of made of this step
+                # (tests/golden/make_guest_plans.py --vgg; the layer trace pins the unscheduled recording only)
+                with open(GOLDEN) as f:
+                    assert canonical(plan) == json.load(f)["vgg_2x128"]
             forks = [i for i, k in enumerate(kinds) if k == "fork"]
             assert len(forks) >= 8, kinds                        # conv1_2 ... conv5_2 and fc6, minus guests left without a host
             for i in forks:
