@@ -1073,6 +1073,45 @@ int ocr_quad_iou(const void* dets_i32, int nd, const void* gts_i32, int ng, int 
 int ocr_quad_mean_score(const void* quads_f32, int k, const void* score_f32, int h, int w, float inv_scale,
                         void* mean_f32, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Held-out evaluation of a batch on the device (csrc/eval_match.hip): LANMS output -> detection list -> the reference's
+ * matching (tool/bboxes.py:171-240) -> running counters, without a host synchronisation.  f32 and integers.
+ * Status (all entries): OCR_ERR_INVALID_ARG for a null required pointer or a non-positive extent, OCR_ERR_UNSUPPORTED
+ * for max_d > 1024, max_g > 254, n > 65535 or a mask side beyond 32768, OCR_ERR_WORKSPACE for ws_bytes below
+ * ocr_eval_match_workspace; nothing is written on error.
+ *
+ * ocr_eval_collect: per image i < n the rows j < n_keep[i] of keep_idx [n][max_k] (indices into merged [n][max_k][9],
+ * ocr_lanms's outputs) with passed[i][j] != 0 (passed u8 [n][max_k], the box_thresh mask; NULL: every row passes; a row
+ * whose index lies outside [0, max_k) is dropped).  inv_ratio f32 [n][2] = (ratio_w, ratio_h), the resize ratios that
+ * are divided out again: a vertex is int32(trunc(x / ratio_w)), int32(trunc(y / ratio_h)) with the IEEE f32 division
+ * (no reciprocal); a non-finite quotient gives 0, a magnitude of 2^22 or more is clamped there (ocr_quad_mean_score's
+ * rule).  The rows come out in DESCENDING score (merged[..][8]) order, equal scores in keep order, NaN scores last:
+ * np.argsort(-score, kind="stable").  A row's slot is its rank (counted, no atomic counter): the order does not depend
+ * on scheduling.  dets int32 [n][max_d][4][2], det_score f32 [n][max_d], nd int32 [n] = min(nd_total, max_d), nd_total
+ * int32 [n] = the number of passing rows; when it exceeds max_d the first max_d rows of the sorted order are written
+ * and the caller is expected to raise.  Nothing is written at or beyond row nd[i]. */
+int ocr_eval_collect(const void* merged_f32, const void* keep_idx_i32, const void* n_keep_i32, const void* passed_u8,
+                     const void* inv_ratio_f32, int n, int max_k, int max_d, void* dets_i32, void* det_score_f32,
+                     void* nd_i32, void* nd_total_i32, void* stream);
+/* ocr_eval_match_batch: bboxes_matching for n images in one call.  dets int32 [n][max_d][4][2] with nd [n] rows in
+ * matching order (descending score), gts int32 [n][max_g][4][2] with ng [n] rows, gignored u8 [n][max_g]; counts outside
+ * [0, max_d] / [0, max_g] are clamped.  Per pair inter = |A and B|, union = |A or B| of the rasters ocr_quad_iou counts,
+ * clipped to [0, mask_h) x [0, mask_w) (any mask that holds every vertex gives the reference's counts); Jaccard =
+ * f32(f64(inter) / f64(union)), NaN for an empty union.  Per image, detections in order: idxmax = np.argmax of the row
+ * (first maximum; a NaN is the maximum, the first NaN wins), match = jaccard[idxmax] > threshold in f32 (false for NaN),
+ *   tp = not ignored[idxmax] and match and not matched[idxmax]
+ *   fp = not ignored[idxmax] and (matched[idxmax] or not match)
+ *   matched[idxmax] |= not ignored[idxmax] and match
+ * BUILD-DEFINED: ng[i] = 0, where the reference raises (argmax of an empty row): every detection of that image is a
+ * false positive.  tp, fp u8 [n][max_d], zero at and beyond nd[i].  record int64 [4] = {ground truths not ignored, tp,
+ * fp, detections} is ADDED TO (integer atomics), so one record serves a whole pass; ocr_eval_record_init zeroes it.
+ * Workspace: the pair counts, ocr_eval_match_workspace(n, max_d, max_g) bytes (0 for a non-positive extent). */
+size_t ocr_eval_match_workspace(int n, int max_d, int max_g);
+int ocr_eval_match_batch(const void* dets_i32, const void* nd_i32, const void* gts_i32, const void* ng_i32,
+                         const void* gignored_u8, int n, int max_d, int max_g, float threshold, int mask_h, int mask_w,
+                         void* tp_u8, void* fp_u8, void* record_i64, void* workspace, size_t ws_bytes, void* stream);
+int ocr_eval_record_init(void* record_i64, void* stream);
+
 /* Strided 3x3 convolutions of ResNet-v1 (nets/resnet_utils.py:85-122 conv2d_same with stride 2) as one
  * stride-1 2x2 convolution over a space-to-depth copy: xs[n][Y][X][(a*2+b)*c + ch] = x[n][2Y+a][2X+b][ch]
  * (h, w even; c a multiple of 8), weights w22 f32 [2][2][4c][k] from w33 f32 [3][3][c][k] (zero where a tap

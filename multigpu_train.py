@@ -16,7 +16,9 @@ with an empty directory) batches are synthetic (`tensorflow_ocr_amd.synthetic`).
 `--summary_variables`, per-variable histograms) to a TensorBoard event file in `--checkpoint_path`.  `--augment east`
 `--net east --geometry RBOX` trains EAST's RBOX heads (`model_vgg_16.model_rbox` / `loss_rbox`, distances x `--text_scale`)
 on RBOX label maps made on the device from the same ICDAR polygons (or `synthetic.rbox_labels` without data) — the head
-`test.py --geometry RBOX` runs.  `--augment east`
+`test.py --geometry RBOX` runs; with `--eval_data_path DIR --eval_steps N` rank 0 evaluates that directory (images +
+gt_*.txt) between steps every N optimiser steps, on the device and outside the recorded step (tensorflow_ocr_amd/evaluate.py),
+and reports precision / recall / hmean.  `--augment east`
 (or `pixellink`, or key=value,...) turns on the augmentation the reference keeps disabled
 (datasets/icdar.py:576-615), warped on the device in one launch per batch.  The stdout line
 format is the reference's (:183-184)."""
@@ -66,9 +68,25 @@ def parse(argv=None):
     ap.add_argument('--geometry', choices=['link', 'RBOX'], default='link')
     ap.add_argument('--text_scale', type=int, default=512, help="RBOX only: the distance scale of the geometry head "
                     "(the reference's nets/model.py flag)")
+    # not reference flags: held-out evaluation between steps (tensorflow_ocr_amd.evaluate.TrainEval), --net east --geometry
+    # RBOX only.  Every --eval_steps optimiser steps (0 = off) rank 0 runs the images of --eval_data_path (images + gt_*.txt,
+    # at most --eval_max_images of them) through forward -> decode -> LANMS -> matching on the device and reports precision /
+    # recall / hmean; --eval_weights: ema = the moving averages test.py restores, raw = the weights being trained
+    ap.add_argument('--eval_data_path', type=str, default=None, metavar='DIR')
+    ap.add_argument('--eval_steps', type=int, default=0, metavar='N')
+    ap.add_argument('--eval_max_images', type=int, default=None, metavar='M')
+    ap.add_argument('--eval_weights', choices=['ema', 'raw'], default='ema')
     FLAGS = ap.parse_args(argv)
     if FLAGS.geometry == 'RBOX' and FLAGS.net != 'east':
         ap.error('--geometry RBOX needs --net east (the RBOX heads sit on the EAST merge branch)')
+    if FLAGS.eval_steps < 0 or (FLAGS.eval_max_images is not None and FLAGS.eval_max_images < 1):
+        ap.error('--eval_steps must not be negative and --eval_max_images must be positive')
+    if FLAGS.eval_steps > 0 and not FLAGS.eval_data_path:
+        ap.error('--eval_steps needs --eval_data_path')
+    if (FLAGS.eval_steps > 0 or FLAGS.eval_data_path) and not (FLAGS.net == 'east' and FLAGS.geometry == 'RBOX'):
+        ap.error('--eval_data_path / --eval_steps need --net east --geometry RBOX (the evaluation decodes RBOX maps)')
+    if FLAGS.eval_weights == 'ema' and FLAGS.eval_steps > 0 and not FLAGS.moving_average_decay:
+        ap.error('--eval_weights ema needs a --moving_average_decay')
     return FLAGS
 
 
@@ -239,8 +257,9 @@ def _train_loop(FLAGS, g, step, feeder, rng, rank, world, device, start):
         # summary_writer = tf.summary.FileWriter(FLAGS.checkpoint_path, ...) (multigpu_train.py:145)
         from tensorflow_ocr_amd.summary import TrainingSummaries
         summaries = TrainingSummaries(FLAGS.checkpoint_path, step, variables=FLAGS.summary_variables)
+    train_eval = make_train_eval(FLAGS, g, step) if rank == 0 else None
     try:
-        _steps(FLAGS, g, step, opt, K, next_batch, last, summaries, rank, world, start)
+        _steps(FLAGS, g, step, opt, K, next_batch, last, summaries, rank, world, start, train_eval)
     finally:
         if summaries is not None:
             summaries.close()
@@ -260,12 +279,39 @@ def _write_summaries(summaries, g, opt, loss, batch):
                                                ('geo_map_0', geo_maps[0][..., 0:1])])
 
 
-def _steps(FLAGS, g, step, opt, K, next_batch, last, summaries, rank, world, start):
+def make_train_eval(FLAGS, g, step, blocks=None):
+    """The between-steps evaluation of --eval_data_path / --eval_steps (None when off): model_rbox in inference mode on
+    the training graph — batch norm on the moving statistics — with the weights --eval_weights names.  `blocks`: a smaller
+    trunk (tests)."""
+    if not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
+        return None
+    from tensorflow_ocr_amd import evaluate
+    from tensorflow_ocr_amd.nets import model_vgg_16
+
+    def network(gr, im):
+        return model_vgg_16.model_rbox(im, is_training=False, text_scale=FLAGS.text_scale, graph=gr, blocks=blocks)
+    return evaluate.TrainEval(g, step, network, FLAGS.eval_data_path, FLAGS.eval_steps, max_images=FLAGS.eval_max_images,
+                              weights=FLAGS.eval_weights, batch_size=FLAGS.batch_size_per_gpu)
+
+
+def _evaluate(train_eval, summaries, opt):
+    """One pass between two steps (rank 0; the other ranks meet it at the next exchange): the line test.py prints, and
+    eval/precision, eval/recall, eval/hmean in the event file where one is open."""
+    from tensorflow_ocr_amd import evaluate
+    res = train_eval.run()
+    print('Step {:06d}, '.format(opt.global_step) + evaluate.format_line(res), flush=True)
+    if summaries is not None:
+        train_eval.write(summaries.writer, opt.global_step)
+
+
+def _steps(FLAGS, g, step, opt, K, next_batch, last, summaries, rank, world, start, train_eval=None):
     from tensorflow_ocr_amd import checkpoint, dist
     for it in range(FLAGS.max_steps):
         loss = _window(step, K, next_batch)
         if summaries is not None and it % FLAGS.save_summary_steps == 0:
             _write_summaries(summaries, g, opt, loss, last[0])
+        if train_eval is not None and train_eval.due(it + 1):
+            _evaluate(train_eval, summaries, opt)
         if it % 10 == 0:
             ml = loss.item()
             # the stop decision is collective: a rank leaving alone would strand the others in the

@@ -1,0 +1,250 @@
+"""Held-out evaluation on the device: precision / recall / F-measure of a detector over a directory of images and
+`gt_*.txt` files (the ICDAR layout datasets/icdar.py reads), one chain per batch
+
+    forward -> rbox.detect_device (decode, LANMS, mean-score mask) -> ocr_eval_collect -> bboxes.bboxes_matching_batch
+
+with the counters of tool/metrics.py on the device (`metrics.DeviceTpFp`): the host reads them once per pass.  The
+matching rule is the reference's (tool/bboxes.py:171-240, rasterised IoU), NOT the official ICDAR-2015 polygon-IoU
+protocol; ground truths are matched in ORIGINAL image coordinates, detections are divided by the resize ratios as test.py
+divides them; `###` (or `*`) marks an ignored ground truth (icdar.load_annoataion).  RBOX geometry only: the link
+geometry's contour path ends on the host (pixellink_fn.find_contour_boxes)."""
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+from .graph import get_default_graph
+
+IMAGE_EXTS = ('jpg', 'png', 'jpeg', 'JPG', 'npy')
+
+
+def resize_rule(h, w, max_side_len=3000):
+    """test.py:92-121: the size an h x w image is resized to — the longer side limited to max_side_len, both sides
+    multiples of 32 (already-multiples stay, others become (x // 32 - 1) * 32).  Returns (resize_h, resize_w)."""
+    resize_w, resize_h = w, h
+    if max(resize_h, resize_w) > max_side_len:
+        ratio = float(max_side_len) / resize_h if resize_h > resize_w else float(max_side_len) / resize_w
+    else:
+        ratio = 1.
+    resize_h = int(resize_h * ratio)
+    resize_w = int(resize_w * ratio)
+    resize_h = resize_h if resize_h % 32 == 0 else (resize_h // 32 - 1) * 32
+    resize_w = resize_w if resize_w % 32 == 0 else (resize_w // 32 - 1) * 32
+    if resize_h <= 0 or resize_w <= 0:
+        raise ValueError('image too small for the reference sizing rule: %dx%d' % (h, w))
+    return int(resize_h), int(resize_w)
+
+
+def list_images(data):
+    """The images under `data` (test.py:76-90 plus .npy arrays), in name order."""
+    files = []
+    for parent, _, filenames in os.walk(data):
+        for filename in sorted(filenames):
+            if filename.endswith(IMAGE_EXTS):
+                files.append(os.path.join(parent, filename))
+    return sorted(files)
+
+
+def load_ground_truth(im_fn, gt_path=None):
+    """(polys int32 [k,4,2], ignored bool [k]) of gt_<stem>.txt — beside the image, or under `gt_path` — in original image
+    pixels (coordinates truncated as the reference's matcher casts them), or None when the file does not exist."""
+    from .datasets import icdar
+    p = icdar.txt_name(im_fn)
+    if gt_path is not None:
+        p = os.path.join(gt_path, os.path.basename(p))
+    if not os.path.exists(p):
+        return None
+    polys, tags = icdar.load_annoataion(p)
+    polys = np.asarray(polys, np.float32).reshape(-1, 4, 2)
+    return polys.astype(np.int32), np.asarray(tags, bool).reshape(-1)
+
+
+def format_line(result):
+    return 'precision %.4f recall %.4f hmean %.4f (gt %d det %d)' % (
+        result['precision'], result['recall'], result['hmean'], result['num_gt'], result['num_det'])
+
+
+class Evaluator:
+    """Evaluator(graph, forward, data): `forward(x)` takes a device f32 [n,H,W,3] batch (0..255, RGB) and returns the
+    (score [n,H/4,W/4,1], geometry [n,H/4,W/4,5]) maps of model_rbox (tensors or head handles) as a pure launch sequence;
+    `data` is a directory of images with gt_<stem>.txt beside them, or under `gt_path` (an image without one is skipped).
+    Images are resized by test.py's rule and batched by resized shape, at most `batch_size` per chain.  `run()` makes one pass and returns
+    {'precision', 'recall', 'hmean', 'num_gt', 'tp', 'fp', 'num_det', 'images'}; it reads the device once at its end: the
+    record, and the two overflow counts (pixels over max_k, detections over max_d), either of which raises ValueError."""
+
+    def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, score_map_thresh=0.8,
+                 nms_thres=0.2, box_thresh=None, max_k=None, max_d=ops.EVAL_MAX_D, max_side_len=3000, gt_path=None):
+        from .tool import metrics
+        self.g = graph or get_default_graph()
+        self.forward = forward
+        if not os.path.isdir(data):
+            raise FileNotFoundError('no evaluation directory %r' % (data,))
+        files = [(f, load_ground_truth(f, gt_path)) for f in list_images(data)]
+        self.samples = [(f, gt) for f, gt in files if gt is not None]
+        if max_images:
+            self.samples = self.samples[:int(max_images)]
+        if not self.samples:
+            raise FileNotFoundError('no image with a gt_*.txt under %r' % (data,))
+        too_many = [f for f, (polys, _) in self.samples if len(polys) > ops.EVAL_MAX_G]
+        if too_many:
+            raise ValueError('more than %d ground truths in %s' % (ops.EVAL_MAX_G, too_many[0]))
+        if not 1 <= int(max_d) <= ops.EVAL_MAX_D:
+            raise ValueError('max_d must be in [1, %d]' % ops.EVAL_MAX_D)
+        self.batch_size = max(1, int(batch_size))
+        self.matching_threshold = float(matching_threshold)
+        self.score_map_thresh, self.nms_thres, self.box_thresh = float(score_map_thresh), float(nms_thres), box_thresh
+        self.max_k, self.max_d, self.max_side_len = max_k, int(max_d), max_side_len
+        self.acc = metrics.DeviceTpFp(self.g)
+        self.last = None          # the device tensors of the last chain (tests and the cost script look at them)
+
+    # -- one chain -------------------------------------------------------------------------------
+    def _upload(self, batch):
+        """batch: [(image uint8 [h,w,3], polys, ignored)] of one resized shape -> x, inv_ratio, gts, ng, gignored, mask_hw"""
+        dev = self.g.device
+        n = len(batch)
+        rh, rw = resize_rule(batch[0][0].shape[0], batch[0][0].shape[1], self.max_side_len)
+        x = torch.empty((n, rh, rw, 3), dtype=torch.float32, device=dev)
+        max_g = max([len(p) for _, p, _ in batch] + [1])
+        gts = np.zeros((n, max_g, 4, 2), np.int32)
+        ng = np.zeros((n,), np.int32)
+        gign = np.zeros((n, max_g), np.uint8)
+        ratio = np.zeros((n, 2), np.float32)
+        extent = 1
+        for i, (im, polys, ignored) in enumerate(batch):
+            h, w, _ = im.shape
+            ops.resize_linear_u8(torch.from_numpy(np.ascontiguousarray(im, dtype=np.uint8)).to(dev), x[i])
+            ratio[i] = (rw / float(w), rh / float(h))                       # (ratio_w, ratio_h) of test.py:127
+            k = len(polys)
+            gts[i, :k], ng[i], gign[i, :k] = polys, k, ignored
+            extent = max(extent, h, w, int(polys.max()) + 1 if k else 1)
+        # any mask that holds every vertex gives the reference's counts; twice the extent leaves room for detections that
+        # overhang the image, and bounds what a wild quad can cost
+        side = int(min(32768, 2 * extent + 10))
+        up = lambda a: torch.from_numpy(a).to(dev)
+        return x, up(ratio), up(gts), up(ng), up(gign), (side, side)
+
+    def _chain(self, batch):
+        from .tool import bboxes, rbox
+        g = self.g
+        x, inv_ratio, gts, ng, gign, mask_hw = self._upload(batch)
+        f_score, f_geometry = self.forward(x)
+        merged, keep, n_keep, passed, total = rbox.detect_device(f_score, f_geometry, self.score_map_thresh, self.nms_thres,
+                                                                 self.max_k, graph=g, box_thresh=self.box_thresh)
+        n, max_k = merged.shape[:2]
+        dets = torch.empty((n, self.max_d, 4, 2), dtype=torch.int32, device=g.device)
+        det_score = torch.empty((n, self.max_d), dtype=torch.float32, device=g.device)
+        nd = torch.empty((n,), dtype=torch.int32, device=g.device)
+        nd_total = torch.empty_like(nd)
+        ops.eval_collect(merged, keep, n_keep, None if passed is None else passed.to(torch.uint8), inv_ratio, dets,
+                         det_score, nd, nd_total)
+        tp, fp, _ = bboxes.bboxes_matching_batch(dets, nd, gts, ng, gign, self.matching_threshold, record=self.acc.record,
+                                                 graph=g, mask_hw=mask_hw)
+        self.last = dict(dets=dets, det_score=det_score, nd=nd, nd_total=nd_total, tp=tp, fp=fp, gts=gts, ng=ng)
+        return total - max_k, nd_total - self.max_d          # > 0: overflow (device tensors, read at the end of the pass)
+
+    # -- one pass --------------------------------------------------------------------------------
+    def run(self):
+        from .datasets import icdar
+        from .tool import metrics
+        self.acc.reset()
+        over_k, over_d, buckets = [], [], {}
+
+        def flush(items):
+            a, b = self._chain(items)
+            over_k.append(a)
+            over_d.append(b)
+        for im_fn, (polys, ignored) in self.samples:
+            im = icdar.read_image_rgb(im_fn)
+            key = tuple(im.shape[:2])
+            items = buckets.setdefault(key, [])
+            items.append((im, polys, ignored))
+            if len(items) == self.batch_size:
+                flush(buckets.pop(key))
+        for key in sorted(buckets):
+            flush(buckets[key])
+        num_gt, tp, fp, n_det = self.acc.value()                            # the single read of the record
+        worst_k, worst_d = torch.stack([torch.cat(over_k).max(), torch.cat(over_d).max()]).cpu().tolist()
+        if worst_k > 0:
+            raise ValueError('an image selected %d pixels more than max_k: raise max_k or the score threshold' % worst_k)
+        if worst_d > 0:
+            raise ValueError('an image kept %d detections more than max_d = %d' % (worst_d, self.max_d))
+        precision, recall = metrics.precision_recall(num_gt, tp, fp)
+        hmean = metrics.fmean(precision, recall) if precision + recall > 0 else 0.0
+        return {'precision': precision, 'recall': recall, 'hmean': hmean, 'num_gt': num_gt, 'tp': tp, 'fp': fp,
+                'num_det': n_det, 'images': len(self.samples)}
+
+
+class EmaWeights:
+    """Context manager: the optimiser's EMA shadows stand in the variable store for the duration (the weights test.py
+    restores), the raw weights come back bit for bit afterwards.  The store's version moves both times, so every pack
+    follows (a recorded TrainStep re-packs before its next replay).  Nothing of this is part of the recorded step."""
+
+    def __init__(self, graph, opt):
+        self.st, self.ema = graph.store, getattr(opt, 'ema', None)
+        if self.ema is None:
+            raise ValueError('the optimiser keeps no moving averages (moving_average_decay): evaluate the raw weights')
+        self.saved = None
+
+    def __enter__(self):
+        self.saved = self.st.flat.clone()
+        self.st.flat.copy_(self.ema)
+        self.st.version += 1
+        return self
+
+    def __exit__(self, *exc):
+        self.st.flat.copy_(self.saved)
+        self.saved = None
+        self.st.version += 1
+        return False
+
+
+class TrainEval:
+    """Evaluation inside a training run (multigpu_train.py --eval_data_path / --eval_steps): every `every` optimiser steps
+    one `Evaluator` pass BETWEEN steps — nothing of it is part of the recorded step plan, whose call list is the same with
+    and without it.  The network runs in inference mode on the training graph (batch norm on the moving statistics, eager
+    launches) with the EMA shadows (`weights='ema'`, what test.py restores) or the raw weights; the raw weights are back
+    bit for bit before the next step.  `network(graph, images)` -> (score, geometry); `opt` is read when a pass runs
+    (the optimiser exists only after the step was built).  `last` holds the latest result."""
+
+    def __init__(self, graph, step, network, data, every, max_images=None, weights='ema', batch_size=8, **evaluator_kw):
+        if weights not in ('ema', 'raw'):
+            raise ValueError("weights must be 'ema' or 'raw'")
+        if int(every) < 1:
+            raise ValueError('every must be positive')
+        self.g, self.step, self.network = graph, step, network
+        self.every, self.weights = int(every), weights
+        self.evaluator = Evaluator(graph, self._forward, data, batch_size=batch_size, max_images=max_images, **evaluator_kw)
+        self.last = None
+        self.passes = 0
+
+    def _forward(self, x):
+        out = self.network(self.g, x)
+        self.g.reset_tape()
+        return out
+
+    def due(self, optimiser_steps):
+        return optimiser_steps > 0 and optimiser_steps % self.every == 0
+
+    def run(self):
+        from . import _lib
+        if _lib.RECORDER is not None:
+            raise RuntimeError('evaluation inside a recorded step')
+        if self.weights == 'ema':
+            with EmaWeights(self.g, self.step.opt):
+                self.last = self.evaluator.run()
+        else:
+            self.last = self.evaluator.run()
+            self.g.store.version += 1       # the inference forward refreshed lazy packs: none may count as current below
+        # the packs are now where an optimiser step leaves them (TrainStep._eager): the batched ones re-packed from the
+        # raw weights, the lazy ones out of date — so a step recorded next holds exactly the calls it holds without an
+        # evaluation, and a replayed one finds nothing to re-pack
+        self.step._repack()
+        self.passes += 1
+        return self.last
+
+    def write(self, writer, global_step):
+        """eval/precision, eval/recall, eval/hmean of the latest pass as one event of a summary.FileWriter."""
+        for k in ('precision', 'recall', 'hmean'):
+            writer.add_scalar('eval/' + k, self.last[k])
+        writer.flush_step(global_step)

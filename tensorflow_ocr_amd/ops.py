@@ -1245,6 +1245,58 @@ def quad_iou(dets, gts, mask_h, mask_w, inter, uni):
            ptr(inter), ptr(uni), _st())
 
 
+# ------------------------------------------------------------------ held-out evaluation on the device (csrc/eval_match.hip)
+EVAL_MAX_D, EVAL_MAX_G = 1024, 254      # the most detections / ground truths per image the matcher takes
+
+
+def eval_collect(merged, keep_idx, n_keep, passed, inv_ratio, dets, det_score, nd, nd_total):
+    """LANMS output (merged f32 [n,max_k,9], keep_idx int32 [n,max_k], n_keep int32 [n]; passed uint8 [n,max_k] or None) ->
+    dets int32 [n,max_d,4,2] (kept quads / the resize ratios inv_ratio f32 [n,2] = (ratio_w, ratio_h), truncated), det_score
+    f32 [n,max_d], in descending score order; nd = min(nd_total, max_d), nd_total int32 [n] (include/ocr_hip.h)."""
+    n, max_k, _ = merged.shape
+    max_d = dets.shape[1]
+    if tuple(keep_idx.shape) != (n, max_k) or n_keep.numel() != n or tuple(inv_ratio.shape) != (n, 2) or \
+            tuple(dets.shape) != (n, max_d, 4, 2) or tuple(det_score.shape) != (n, max_d) or nd.numel() != n or \
+            nd_total.numel() != n or (passed is not None and (tuple(passed.shape) != (n, max_k) or passed.dtype != torch.uint8)):
+        raise ValueError("eval_collect: tensors do not match n, max_k, max_d")
+    if merged.dtype != torch.float32 or keep_idx.dtype != torch.int32 or n_keep.dtype != torch.int32 or \
+            inv_ratio.dtype != torch.float32 or dets.dtype != torch.int32 or det_score.dtype != torch.float32 or \
+            nd.dtype != torch.int32 or nd_total.dtype != torch.int32:
+        raise ValueError("eval_collect: merged / inv_ratio / det_score f32, the index and count tensors int32")
+    for t in (merged, keep_idx, n_keep, inv_ratio, dets, det_score, nd, nd_total) + (() if passed is None else (passed,)):
+        if not t.is_contiguous():
+            raise ValueError("eval_collect: contiguous tensors only")
+    L.call("ocr_eval_collect", ptr(merged), ptr(keep_idx), ptr(n_keep), ptr(passed), ptr(inv_ratio), c_int(n), c_int(max_k),
+           c_int(max_d), ptr(dets), ptr(det_score), ptr(nd), ptr(nd_total), _st())
+
+
+def eval_match_batch(dets, nd, gts, ng, gignored, threshold, mask_h, mask_w, tp, fp, record, ws):
+    """bboxes_matching of n images in one call: dets int32 [n,max_d,4,2] / nd int32 [n] in matching order, gts int32
+    [n,max_g,4,2] / ng int32 [n], gignored uint8 [n,max_g] -> tp, fp uint8 [n,max_d]; record int64 [4] is added to."""
+    n, max_d = dets.shape[:2]
+    max_g = gts.shape[1]
+    if tuple(dets.shape) != (n, max_d, 4, 2) or tuple(gts.shape) != (n, max_g, 4, 2) or nd.numel() != n or ng.numel() != n or \
+            tuple(gignored.shape) != (n, max_g) or tuple(tp.shape) != (n, max_d) or tuple(fp.shape) != (n, max_d) or \
+            record.numel() != 4:
+        raise ValueError("eval_match_batch: tensors do not match n, max_d, max_g")
+    if dets.dtype != torch.int32 or gts.dtype != torch.int32 or nd.dtype != torch.int32 or ng.dtype != torch.int32 or \
+            gignored.dtype != torch.uint8 or tp.dtype != torch.uint8 or fp.dtype != torch.uint8 or record.dtype != torch.int64:
+        raise ValueError("eval_match_batch: quads and counts int32, flags uint8, record int64")
+    for t in (dets, nd, gts, ng, gignored, tp, fp, record):
+        if not t.is_contiguous():
+            raise ValueError("eval_match_batch: contiguous tensors only")
+    nbytes = L.call_size("ocr_eval_match_workspace", c_int(n), c_int(max_d), c_int(max_g))
+    buf = ws.get(nbytes)
+    L.call("ocr_eval_match_batch", ptr(dets), ptr(nd), ptr(gts), ptr(ng), ptr(gignored), c_int(n), c_int(max_d), c_int(max_g),
+           c_float(threshold), c_int(mask_h), c_int(mask_w), ptr(tp), ptr(fp), ptr(record), ptr(buf), c_size_t(nbytes), _st())
+
+
+def eval_record_init(record):
+    if record.numel() != 4 or record.dtype != torch.int64 or not record.is_contiguous():
+        raise ValueError("eval_record_init: record is int64 [4]")
+    L.call("ocr_eval_record_init", ptr(record), _st())
+
+
 # -------------------------------------------------------------------------- optimiser
 def adam_step(w, g, m, v, ema, n_reg, lr_t, beta1, beta2, eps, wd, inv_scale, ema_decay):
     L.call("ocr_adam_step", ptr(w), ptr(g), ptr(m), ptr(v), ptr(ema), c_int64(w.numel()),

@@ -3,7 +3,8 @@ with RASTERISED IoU (`bboxes_matching` :171-240, `bboxes_jaccard` :242-245, `np_
 :246-283).  The reference draws each pair of quadrangles into 0/1 masks with cv2 and counts pixels on
 the host, once per detection inside a tf.while_loop; here all pairs of an image are counted in one
 launch (ocr_quad_iou) and the sequential greedy matching — O(detections) scalar work — stays on the
-host exactly as written."""
+host exactly as written.  `bboxes_matching_batch` is the same rule for a whole batch with the greedy pass on the device
+too (ocr_eval_match_batch: no synchronisation, the totals added to a device record)."""
 import numpy as np
 import torch
 
@@ -38,6 +39,30 @@ def np_bboxes_jaccard(bbox, gxs, gys, graph=None):
 
 
 bboxes_jaccard = np_bboxes_jaccard          # :242-245 (the tf.py_func wrapper)
+
+
+def bboxes_matching_batch(dets, nd, gts, ng, gignored, matching_threshold=0.5, record=None, graph=None, mask_hw=None):
+    """`bboxes_matching` for a batch, on the device and without a synchronisation (ocr_eval_match_batch): one grid counts
+    the pairs of every image, one workgroup per image walks its detections.  All operands are DEVICE tensors:
+    dets int32 [n,max_d,4,2] with nd int32 [n] rows per image in matching order (descending score), gts int32
+    [n,max_g,4,2] with ng int32 [n] rows, gignored uint8 / bool [n,max_g].  record: int64 [4] device tensor that {ground
+    truths not ignored, tp, fp, detections} are ADDED to (`metrics.DeviceTpFp.record`); None: a fresh zeroed one.
+    mask_hw: the (h, w) the rasters are clipped to; any mask holding every vertex gives the reference's counts
+    (its own masks are `max coordinate + 10`); default 32768 x 32768, the largest — a pair costs its bounding box, not
+    the mask.  An image without ground truths makes every detection a false positive (the reference raises there).
+    Returns (tp, fp, record): uint8 [n,max_d] (zero beyond nd) and the record."""
+    g = graph or get_default_graph()
+    n, max_d = dets.shape[:2]
+    if gignored.dtype == torch.bool:
+        gignored = gignored.to(torch.uint8)
+    if record is None:
+        record = torch.empty((4,), dtype=torch.int64, device=g.device)
+        ops.eval_record_init(record)
+    mask_h, mask_w = (32768, 32768) if mask_hw is None else (int(mask_hw[0]), int(mask_hw[1]))
+    tp = torch.empty((n, max_d), dtype=torch.uint8, device=g.device)
+    fp = torch.empty_like(tp)
+    ops.eval_match_batch(dets, nd, gts, ng, gignored, float(matching_threshold), mask_h, mask_w, tp, fp, record, g.workspace())
+    return tp, fp, record
 
 
 def bboxes_matching(bboxes, gxs, gys, gignored, matching_threshold=0.5, scope=None, graph=None):

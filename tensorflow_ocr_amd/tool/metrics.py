@@ -29,6 +29,32 @@ class streaming_tp_fp_arrays:
         return self.v_num_gbboxes, self.v_tp, self.v_fp
 
 
+class DeviceTpFp:
+    """`streaming_tp_fp_arrays` with the running totals on the device: owns the int64 [4] record {ground truths not
+    ignored, tp, fp, detections} that `bboxes.bboxes_matching_batch(..., record=acc.record)` adds to, batch after batch,
+    without a synchronisation.  `value()` is the single host read of a pass: (num_gbboxes, tp, fp, n_det) as Python
+    ints — `precision_recall(num_gbboxes, tp, fp)` and `fmean` apply to them unchanged (they only sum tp and fp).
+    `reads` counts the calls of `value()`."""
+
+    def __init__(self, graph=None):
+        import torch
+        from .. import ops
+        from ..graph import get_default_graph
+        self.g = graph or get_default_graph()
+        self.record = torch.empty((4,), dtype=torch.int64, device=self.g.device)
+        self.reads = 0
+        self._init = ops.eval_record_init
+        self.reset()
+
+    def reset(self):
+        self._init(self.record)
+
+    def value(self):
+        self.reads += 1
+        num_gt, tp, fp, n_det = (int(v) for v in self.record.cpu().tolist())
+        return num_gt, tp, fp, n_det
+
+
 def precision_recall(num_gbboxes, tp, fp, scope=None):
     """tool/metrics.py:67-79 -> (precision, recall)."""
     tp = float(np.sum(np.asarray(tp, np.float32)))

@@ -64,12 +64,11 @@ def quad_mean_scores(quads, valid, score, graph=None):
     return means
 
 
-def detect(score_map, geo_map, score_map_thresh=0.8, nms_thres=0.2, max_k=None, graph=None, box_thresh=None):
-    """decode + lanms.lanms_batch on the device, one synchronisation at the end.  Returns one [m, 9] array of kept quads
-    (merged coordinates, summed scores) per image.  Raises ValueError when an image selects more than max_k pixels:
-    candidates are never dropped silently.  box_thresh: None = no filter; a number = only the kept quads whose mean
-    score over their raster (quad_mean_scores) is STRICTLY above it, EAST's `box_thresh` (0.1 there); the means are
-    computed on the device in front of the same single synchronisation."""
+def detect_device(score_map, geo_map, score_map_thresh=0.8, nms_thres=0.2, max_k=None, graph=None, box_thresh=None):
+    """The device part of `detect`: decode + lanms.lanms_batch (+ the mean-score mask of box_thresh), NO synchronisation.
+    Returns device tensors (merged f32 [n,max_k,9], keep int32 [n,max_k], n_keep int32 [n], passed bool [n,max_k] or None,
+    total int32 [n]): image i's kept quads are merged[i][keep[i, :n_keep[i]]], of which passed[i, :n_keep[i]] survive the
+    filter; total[i] > max_k means candidates were dropped, which the caller must turn into an error once it reads it."""
     g = graph or get_default_graph()
     boxes, counts, total = decode(score_map, geo_map, score_map_thresh, 4.0, max_k, graph=g)
     if boxes.shape[1] > LANMS_MAX_K:
@@ -83,10 +82,20 @@ def detect(score_map, geo_map, score_map_thresh=0.8, nms_thres=0.2, max_k=None, 
         idx = torch.where(valid, keep, torch.zeros_like(keep)).long().clamp_(0, k - 1)
         kept = torch.gather(merged[..., :8], 1, idx[..., None].expand(-1, -1, 8))
         passed = valid & (quad_mean_scores(kept, valid, score.reshape(n, h, w), graph=g) > float(box_thresh))
+    return merged, keep, n_keep, passed, total
+
+
+def detect(score_map, geo_map, score_map_thresh=0.8, nms_thres=0.2, max_k=None, graph=None, box_thresh=None):
+    """decode + lanms.lanms_batch on the device, one synchronisation at the end.  Returns one [m, 9] array of kept quads
+    (merged coordinates, summed scores) per image.  Raises ValueError when an image selects more than max_k pixels:
+    candidates are never dropped silently.  box_thresh: None = no filter; a number = only the kept quads whose mean
+    score over their raster (quad_mean_scores) is STRICTLY above it, EAST's `box_thresh` (0.1 there); the means are
+    computed on the device in front of the same single synchronisation."""
+    merged, keep, n_keep, passed, total = detect_device(score_map, geo_map, score_map_thresh, nms_thres, max_k, graph, box_thresh)
     total_h = total.cpu().numpy()                               # the single sync: everything below is already computed
-    if (total_h > boxes.shape[1]).any():
+    if (total_h > merged.shape[1]).any():
         raise ValueError("%s pixels above the threshold, max_k = %d: raise max_k or the threshold"
-                         % (total_h.tolist(), boxes.shape[1]))
+                         % (total_h.tolist(), merged.shape[1]))
     n_keep_h = n_keep.cpu().numpy()
     merged_h, keep_h = merged.cpu().numpy(), keep.cpu().numpy()
     out = [merged_h[i][keep_h[i, :n_keep_h[i]]] for i in range(len(total_h))]

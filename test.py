@@ -6,7 +6,9 @@ heads), softmax scores, the script's own `pixel_detect`, one `cv2.minAreaRect` b
 
 `--geometry RBOX` runs the geometry the default checkpoint path is named for instead: `model_vgg_16.model_rbox`
 (score, four distances x `--text_scale`, angle), per-pixel quads in raster order, locality-aware NMS, all on the device
-(`main_rbox`); the default `--geometry link` is the path described above, unchanged.
+(`main_rbox`); the default `--geometry link` is the path described above, unchanged.  With `--gt_path DIR` (RBOX only) the
+detections are then matched against the `gt_<name>.txt` files there on the device (tensorflow_ocr_amd/evaluate.py) and one
+line `precision .. recall .. hmean .. (gt .. det ..)` is printed.
 
     python test.py --test_data_path ./exhibition --checkpoint_path /tmp/east_icdar2015_resnet_v1_50_rbox/ --output_dir /tmp/res/
 
@@ -44,7 +46,14 @@ def parse(argv=None):
                     "(the reference's nets/model.py flag)")
     ap.add_argument('--box_thresh', type=float, default=None, help="RBOX only: after the NMS keep only the quads whose mean "
                     "score over their raster is above this (EAST's eval.py uses 0.1).  Default: no filter")
-    return ap.parse_args(argv)
+    ap.add_argument('--gt_path', type=str, default=None, metavar='DIR', help="RBOX only: a directory of gt_<name>.txt files "
+                    "(ICDAR layout, ### = ignored).  After the run the detections are matched against them on the device "
+                    "(tensorflow_ocr_amd.evaluate: the reference's raster-IoU rule, not the official ICDAR protocol) and one "
+                    "line `precision .. recall .. hmean .. (gt .. det ..)` is printed")
+    FLAGS = ap.parse_args(argv)
+    if FLAGS.gt_path is not None and FLAGS.geometry != 'RBOX':
+        ap.error('--gt_path needs --geometry RBOX (the link geometry\'s contour decode ends on the host)')
+    return FLAGS
 
 
 # --fold-bn when the flag is not given: on where the folded graph measured faster than the unfolded one at this script's
@@ -108,19 +117,10 @@ def resize_image(im, max_side_len=3000, graph=None):
     image as a DEVICE float32 [H,W,3] tensor and (ratio_h, ratio_w)."""
     from tensorflow_ocr_amd import ops
     from tensorflow_ocr_amd.graph import get_default_graph
+    from tensorflow_ocr_amd.evaluate import resize_rule
     g = graph or get_default_graph()
     h, w, _ = im.shape
-    resize_w, resize_h = w, h
-    if max(resize_h, resize_w) > max_side_len:
-        ratio = float(max_side_len) / resize_h if resize_h > resize_w else float(max_side_len) / resize_w
-    else:
-        ratio = 1.
-    resize_h = int(resize_h * ratio)
-    resize_w = int(resize_w * ratio)
-    resize_h = resize_h if resize_h % 32 == 0 else (resize_h // 32 - 1) * 32
-    resize_w = resize_w if resize_w % 32 == 0 else (resize_w // 32 - 1) * 32
-    if resize_h <= 0 or resize_w <= 0:
-        raise ValueError('image too small for the reference sizing rule: %dx%d' % (h, w))
+    resize_h, resize_w = resize_rule(h, w, max_side_len)          # the sizing rule, shared with the evaluator
     src = torch.from_numpy(np.ascontiguousarray(im, dtype=np.uint8)).to(g.device)
     out = torch.empty((int(resize_h), int(resize_w), 3), dtype=torch.float32, device=g.device)
     ops.resize_linear_u8(src, out)
@@ -193,6 +193,12 @@ def main_rbox(FLAGS):
                 box = box.astype(np.int32)
                 f.write('{},{},{},{},{},{},{},{}\r\n'.format(box[0, 0], box[0, 1], box[1, 0], box[1, 1],
                                                             box[2, 0], box[2, 1], box[3, 0], box[3, 1]))
+    if FLAGS.gt_path is not None:
+        # a second pass over the same images with the restored weights: forward -> decode -> LANMS -> filter -> match
+        # per batch on the device, one read of the counters at its end
+        from tensorflow_ocr_amd import evaluate
+        ev = evaluate.Evaluator(g, forward, FLAGS.test_data_path, gt_path=FLAGS.gt_path, box_thresh=FLAGS.box_thresh)
+        print(evaluate.format_line(ev.run()), flush=True)
 
 
 def main():
