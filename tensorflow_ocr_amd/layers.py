@@ -1,4 +1,5 @@
-"""slim-style layers (conv2d [+batch_norm] [+relu] [+max_pool2d], heads) driving the HIP kernels.
+"""slim-style layers (conv2d [+batch_norm] [+relu] [+max_pool2d]) driving the HIP kernels; the fuse heads on top of
+them are in head_layers.py.
 
 Each function runs the forward kernels immediately and records ONE backward closure on the
 graph's tape.  Variable names follow tf.contrib.slim so checkpoints/state-dicts line up with
@@ -10,7 +11,7 @@ import os
 import torch
 
 from . import ops
-from .graph import Act, F16, F32, constant, variance_scaling, xavier_uniform
+from .graph import Act, F16, F32, constant, variance_scaling
 from ._lib import CONV_ACCUM_F16, CONV_BIAS, CONV_RELU, CONV_STATS
 
 BN_DECAY = 0.997
@@ -43,7 +44,6 @@ FUSE_FIRST_WGRAD = _switch("OCR_FUSE_FIRST_WGRAD")    # measurement switch
 # conv1_1's weight gradient from SUMS (csrc/conv_first.hip: first_wgrad_sums_kernel): conv1_2's input-gradient launch
 # leaves S1 = V^T dz instead of the 1 GiB gradient, dW = A .* S1 + B .* (M W) + C .* m
 FIRST_WGRAD_SUMS = _switch("OCR_FIRST_WGRAD_SUMS")
-BATCH_HEADS = _switch("OCR_BATCH_HEADS")    # one launch per kernel kind over the head sources
 
 
 def _bn_vars(g, C):
@@ -432,6 +432,14 @@ def _open_input_grad(g, x):
     return CONV_ACCUM_F16
 
 
+def _grad_buffer(g, x):
+    """-> (x.grad, whether the caller accumulates into it): allocated here when this is the first contribution."""
+    acc = x.grad is not None
+    if not acc:
+        x.grad = g.empty(x.shape)
+    return x.grad, acc
+
+
 def _count_contribution(x, owner):
     """-> whether this is the LAST gradient contribution to a bottleneck output.  Only the owning unit's two are counted
     (any other consumer of x was built later, runs earlier in the backward pass and has added its share)."""
@@ -543,11 +551,9 @@ def max_pool2d(g, x, k, stride, scope="pool", bias_relu=None):
             x.pool_grad = (out.grad, argmax, k, stride, (pt, pl))
             out.grad = None
             return
-        acc = x.grad is not None
-        if not acc:
-            x.grad = g.empty(x.shape)
+        dx, acc = _grad_buffer(g, x)
         # (with the forward's index tensor the backward never reads x: do not force a deferred x into existence)
-        ops.maxpool_bwd(x._data if argmax is not None else x.data, out.grad, k, stride, (pt, pl), x.grad, acc,
+        ops.maxpool_bwd(x._data if argmax is not None else x.data, out.grad, k, stride, (pt, pl), dx, acc,
                         argmax=argmax, in_shape=x.shape)
         out.grad = None
     g.record(backward)
@@ -568,383 +574,3 @@ def prep_images(g, images, means=(123.68, 116.78, 103.94), div=1.0):
     x4 = g.empty((n, h, w, 4))
     ops.prep_images(images, x4, means, div)
     return Act(x4, requires_grad=False, name="images")
-
-
-# ---------------------------------------------------------------------------- fuse heads
-class SmallAct:
-    """f32 [n,h,w,C] head tensor."""
-    __slots__ = ("data", "grad")
-
-    def __init__(self, data):
-        self.data = data
-        self.grad = None
-
-
-def _head_vars(g, names, cin, couts, mode, initializer=None):
-    """One merged parameter per head source, its columns mapping onto the reference variables `names`
-    -> (weights [cin, sum(couts)], BN variables | None, biases | None)."""
-    C = sum(couts)
-    with g.variable_scope("+".join(names)):
-        init = _merged_init(g, cin, couts, None if mode == "bn" else (initializer or xavier_uniform))
-        wv = g.get_variable("weights", (cin, C), init, regularized=True)
-        if mode == "bn":
-            return wv, _bn_vars(g, C), None
-        return wv, None, g.get_variable("biases", (C,), constant(0.0))
-
-
-def _small_packs(g, wv, cin):
-    """f16 operand layouts of a merged head weight, padded to 32 columns: forward [32][cin] and dgrad [cin][32]."""
-    def mk(old):
-        if old is None:
-            old = (g.empty((32, cin)), g.empty((cin, 32)))
-        ops.pack_weights_small(wv.data, old[0], old[1])
-        return old
-    return g.packed(wv, "small", mk)
-
-
-def _small_stats(g, z, C):
-    """Batch statistics of an f32 head tensor [..., C]: the `stats` of _bn_params."""
-    P = z.numel() // C
-    T = ops.sc_num_partials(P, C)
-    part, stage = g.ws_small.two(T * 2 * C * 4, ops.bn_reduce_workspace(T, C))
-    ops.sc_stats(z, C, part)
-    return part, T, float(P), stage
-
-
-def _pointwise_vars(g, scope, c, mode, initializer=None):
-    """One predication convolution's (weights [1,1,c,c], BN variables | None, biases | None)."""
-    with g.variable_scope(scope):
-        init = variance_scaling(g.rng) if mode == "bn" else (initializer or xavier_uniform)(g.rng)
-        wv = g.get_variable("weights", (1, 1, c, c), init, regularized=True)
-        if mode == "bn":
-            return wv, _bn_vars(g, c), None
-        return wv, None, g.get_variable("biases", (c,), constant(0.0))
-
-
-def head_conv_bn(g, feat, names, couts, is_training=True, relu=True):
-    """The BN'd 1x1 fuse convs that several heads apply to ONE feature map, evaluated in a single
-    pass over the feature: slim.conv2d(feat, c, 1) for c in couts (nets/model_vgg_16.py:160-172).
-    Returns (z, scale, shift, ctx): z = raw conv output [n,h,w,sum(couts)] f32."""
-    n, h, w, cin = feat.shape
-    C = sum(couts)
-    ws = g.workspace()
-    wv, bn_vars, _ = _head_vars(g, names, cin, couts, "bn")
-    gamma, beta = bn_vars[:2]
-    w_kc32, w_ck32 = _small_packs(g, wv, cin)
-    z = g.empty((n, h, w, C), F32)
-    if g.precision == "f32":
-        from . import layers_f32
-        layers_f32.head_conv(g, feat, wv, C, z)
-    else:
-        ops.conv1x1_small(feat.data, w_kc32, C, z)
-    scale, shift, mean, invstd = _bn_params(g, C, bn_vars, _small_stats(g, z, C) if is_training else None)
-    out = SmallAct(z)   # grad of out = gradient w.r.t. relu(bn(z))
-
-    def backward():
-        if out.grad is None:
-            return
-        dz = g.empty(z.shape, F32)
-        ops.sc_bn_bwd(z, scale, shift, mean, invstd, out.grad, relu, gamma.grad, beta.grad, dz, ws)
-        ops.conv1x1_small_wgrad(feat.data, dz, C, wv.grad, ws)
-        if feat.requires_grad:
-            acc = feat.grad is not None
-            if not acc:
-                feat.grad = g.empty(feat.shape)
-            ops.conv1x1_small_dgrad(dz, w_ck32, C, feat.grad, acc)
-        out.grad = None
-    g.record(backward, (wv, gamma, beta))
-    return out, scale, shift
-
-
-def head_conv_bias(g, feat, names, couts, initializer=None):
-    """PixelLinkNet's fuse convs on one feature map — slim.conv2d(feat, c, [1,1], activation_fn=None)
-    with biases, no normaliser (nets/pixellink.py:58-67) — merged into one pass over the feature.
-    Returns (z, None, None) in the triple form `fuse` consumes."""
-    n, h, w, cin = feat.shape
-    C = sum(couts)
-    ws = g.workspace()
-    wv, _, bias = _head_vars(g, names, cin, couts, "bias", initializer)
-    w_kc32, w_ck32 = _small_packs(g, wv, cin)
-    z = g.empty((n, h, w, C), F32)
-    if g.precision == "f32":
-        from . import layers_f32
-        layers_f32.head_conv(g, feat, wv, C, z, bias)
-    else:
-        ops.conv1x1_small(feat.data, w_kc32, C, z, bias.data)
-    out = SmallAct(z)
-
-    def backward():
-        if out.grad is None:
-            return
-        ops.sc_colsum(out.grad, C, bias.grad, ws)
-        ops.conv1x1_small_wgrad(feat.data, out.grad, C, wv.grad, ws)
-        if feat.requires_grad:
-            acc = feat.grad is not None
-            if not acc:
-                feat.grad = g.empty(feat.shape)
-            ops.conv1x1_small_dgrad(out.grad, w_ck32, C, feat.grad, acc)
-        out.grad = None
-    g.record(backward, (wv, bias))
-    return out, None, None
-
-
-def head_group(g, feats, names_list, couts, *, mode="bn", is_training=True, relu=True, initializer=None):
-    """The fuse convs of ALL head sources (nets/model_vgg_16.py:160-172: fc7, conv5_3, conv4_3, conv3_3; nets/pixellink.py:
-    58-67; nets/model.py:129-141) with one launch per kernel kind over the sources instead of one per source: per feature map
-    the same merged 1x1 convolution (+ batch-norm statistics | + biases) as head_conv_bn / head_conv_bias, same variables in
-    the same order.  Returns the list of (z SmallAct, scale, shift) triples `fuse` consumes (scale = shift = None for
-    mode="bias").  OCR_BATCH_HEADS=0 (or the f32 verification precision) runs the per-source forms."""
-    if not BATCH_HEADS or g.precision == "f32" or len(feats) > 4:
-        out = []
-        for f, nm in zip(feats, names_list):
-            out.append(head_conv_bn(g, f, nm, couts, is_training=is_training, relu=relu) if mode == "bn" else
-                       head_conv_bias(g, f, nm, couts, initializer=initializer))
-        return out
-    C = sum(couts)
-    ws = g.workspace()
-    srcs = []
-    for feat, names in zip(feats, names_list):
-        n, h, w, cin = feat.shape
-        wv, bn_vars, bias = _head_vars(g, names, cin, couts, mode, initializer)
-        gamma, beta, mm, mv = bn_vars or (None,) * 4
-        w_kc32, w_ck32 = _small_packs(g, wv, cin)
-        srcs.append(dict(feat=feat, P=n * h * w, cin=cin, wv=wv, bias=bias, gamma=gamma, beta=beta, mm=mm, mv=mv,
-                         w_kc32=w_kc32, w_ck32=w_ck32, z=g.empty((n, h, w, C), F32)))
-    train_bn = mode == "bn" and is_training
-    for s in srcs:
-        if mode == "bn":
-            s["scale"], s["shift"], s["mean"], s["invstd"] = _bn_buffers(g, C)
-        if train_bn:
-            s["T"] = ops.conv1x1_small_batch_rows(s["P"])
-            s["part"] = g.empty((s["T"], 2, C), F32)
-    ops.conv1x1_small_batch([(s["feat"].data, s["w_kc32"], s["bias"].data if s["bias"] is not None else None, s["z"],
-                              s.get("part")) for s in srcs])
-    if train_bn:
-        ops.bn_finalize_batch([(s["part"], s["T"], C, float(s["P"]), s["gamma"].data, s["beta"].data, s["mm"].data,
-                                s["mv"].data, s["scale"], s["shift"], s["mean"], s["invstd"]) for s in srcs],
-                              BN_EPS, BN_DECAY)
-    elif mode == "bn":
-        for s in srcs:
-            ops.bn_inference_params(s["gamma"].data, s["beta"].data, s["mm"].data, s["mv"].data, BN_EPS, s["scale"], s["shift"])
-    for s in srcs:
-        s["out"] = SmallAct(s["z"])          # grad of out = gradient w.r.t. relu(bn(z)) (bn) / z (bias)
-
-    def backward():
-        live = [s for s in srcs if s["out"].grad is not None]
-        if not live:
-            return
-        if mode == "bn":
-            if not is_training:
-                raise NotImplementedError("backward through inference-mode batch norm")
-            items = []
-            for s in live:
-                s["dz"] = g.empty(s["z"].shape, F32)
-                T = ops.sc_num_partials(s["P"], C)
-                items.append((s["z"], s["scale"], s["shift"], s["mean"], s["invstd"], s["out"].grad, s["gamma"].grad,
-                              s["beta"].grad, s["dz"], g.empty((T, 2, C), F32), relu))
-            ops.sc_bn_bwd_batch(items)
-        else:
-            items = []
-            for s in live:
-                s["dz"] = s["out"].grad
-                T = ops.sc_num_partials(s["P"], C)
-                items.append((s["dz"], s["bias"].grad, g.empty((T + 1, 2, C), F32)))
-            ops.sc_colsum_batch(items)
-        # the batched MFMA kernel: 128-channel blocks, 32-bit buffer offsets (heads.hip: P * cin * 2 and P * C * 4 below
-        # 2 GiB); anything else — a 256-channel map beyond 4.19 M pixels, say — keeps the per-map kernel, which has no limit
-        def is_wide(s):
-            return s["cin"] % 128 == 0 and s["P"] * s["cin"] * 2 < (1 << 31) and s["P"] * C * 4 < (1 << 31)
-        wide = [s for s in live if is_wide(s)]
-        if wide:
-            ops.conv1x1_small_wgrad_batch([
-                (s["feat"].data, s["dz"], s["wv"].grad,
-                 g.empty((ops.conv1x1_small_wgrad_batch_slab_bytes(s["P"], s["cin"]),), torch.uint8)) for s in wide])
-        for s in live:
-            if not is_wide(s):
-                ops.conv1x1_small_wgrad(s["feat"].data, s["dz"], C, s["wv"].grad, ws)
-        items = []
-        for s in live:
-            feat = s["feat"]
-            if feat.requires_grad:
-                acc = feat.grad is not None
-                if not acc:
-                    feat.grad = g.empty(feat.shape)
-                items.append((s["dz"], s["w_ck32"], feat.grad, acc))
-        if items:
-            ops.conv1x1_small_dgrad_batch(items)
-        for s in live:
-            s["out"].grad = None
-            s["dz"] = None
-    produces = []
-    for s in srcs:
-        produces += [s["wv"]] + ([s["gamma"], s["beta"]] if mode == "bn" else [s["bias"]])
-    g.record(backward, produces)
-    return [(s["out"], s.get("scale") if mode == "bn" else None, s.get("shift") if mode == "bn" else None) for s in srcs]
-
-
-def pointwise_pair(g, x, scopes, *, mode="bn", is_training=True, relu=True, initializer=None):
-    """The two predication convolutions on the fused 18-channel head tensor — pixel (2 -> 2 on channels 0..1) and link
-    (16 -> 16 on channels 2..17): `pointwise_bn` x 2 (nets/model_vgg_16.py:166,173: conv + BN + ReLU) or `pointwise_bias`
-    x 2 (nets/pixellink.py:61,67, nets/model.py:139-141: conv + biases, linear) — as ONE pass over the tensor per
-    direction, same variables in the same order.  Returns (pixel SmallAct [n,h,w,2], link SmallAct [n,h,w,16])."""
-    n, h, w, C = x.data.shape
-    if not BATCH_HEADS or g.precision == "f32" or C != 18:
-        if mode == "bn":
-            return (pointwise_bn(g, x, 0, 2, scopes[0], is_training=is_training, relu=relu),
-                    pointwise_bn(g, x, 2, 16, scopes[1], is_training=is_training, relu=relu))
-        return (pointwise_bias(g, x, 0, 2, scopes[0], initializer=initializer),
-                pointwise_bias(g, x, 2, 16, scopes[1], initializer=initializer))
-    P = n * h * w
-    ws = g.workspace()
-    hd = []
-    for scope, c in zip(scopes, (2, 16)):
-        wv, bn_vars, bias = _pointwise_vars(g, scope, c, mode, initializer)
-        gamma, beta, mm, mv = bn_vars or (None,) * 4
-        hd.append(dict(c=c, wv=wv, bias=bias, gamma=gamma, beta=beta, mm=mm, mv=mv, z=g.empty((n, h, w, c), F32)))
-    a, b = hd
-    train_bn = mode == "bn" and is_training
-    if train_bn:
-        T = ops.sc_pointwise_pair_num_partials(P)
-        for d in hd:
-            d["part"] = g.empty((T, 2, d["c"]), F32)
-    ops.sc_pointwise_pair_fwd(x.data, a["wv"].data, a["bias"].data if a["bias"] is not None else None, b["wv"].data,
-                              b["bias"].data if b["bias"] is not None else None, a["z"], b["z"], a.get("part"), b.get("part"))
-    if mode == "bn":
-        for d in hd:
-            d["scale"], d["shift"], d["mean"], d["invstd"] = _bn_buffers(g, d["c"])
-        if train_bn:
-            ops.bn_finalize_batch([(d["part"], T, d["c"], float(P), d["gamma"].data, d["beta"].data, d["mm"].data,
-                                    d["mv"].data, d["scale"], d["shift"], d["mean"], d["invstd"]) for d in hd],
-                                  BN_EPS, BN_DECAY)
-        else:
-            for d in hd:
-                ops.bn_inference_params(d["gamma"].data, d["beta"].data, d["mm"].data, d["mv"].data, BN_EPS, d["scale"], d["shift"])
-        for d in hd:
-            d["out"] = SmallAct(g.empty((n, h, w, d["c"]), F32))
-        ops.sc_act_batch([(d["z"], d["scale"], d["shift"], d["out"].data) for d in hd], relu)
-    else:
-        for d in hd:
-            d["out"] = SmallAct(d["z"])
-
-    def backward():
-        if a["out"].grad is None and b["out"].grad is None:
-            return
-        for d in hd:
-            if d["out"].grad is None:                       # a head the loss did not read: its gradient is zero
-                d["out"].grad = g.empty(d["out"].data.shape, F32)
-                ops.fill_(d["out"].grad, 0.0)
-        if mode == "bn":
-            if not is_training:
-                raise NotImplementedError("backward through inference-mode batch norm")
-            items = []
-            for d in hd:
-                d["dz"] = g.empty(d["z"].shape, F32)
-                Tb = ops.sc_num_partials(P, d["c"])
-                items.append((d["z"], d["scale"], d["shift"], d["mean"], d["invstd"], d["out"].grad, d["gamma"].grad,
-                              d["beta"].grad, d["dz"], g.empty((Tb, 2, d["c"]), F32), relu))
-            ops.sc_bn_bwd_batch(items)
-        else:
-            for d in hd:
-                d["dz"] = d["out"].grad
-        if x.grad is not None:
-            raise RuntimeError("the fused head tensor already carries a gradient (pointwise_pair writes all of it)")
-        x.grad = g.empty(x.data.shape, F32)
-        ops.sc_pointwise_pair_bwd(x.data, a["dz"], b["dz"], a["wv"].data, b["wv"].data, x.grad, a["wv"].grad,
-                                  a["bias"].grad if a["bias"] is not None else None, b["wv"].grad,
-                                  b["bias"].grad if b["bias"] is not None else None, ws)
-        for d in hd:
-            d["out"].grad = None
-            d["dz"] = None
-    produces = []
-    for d in hd:
-        produces += [d["wv"]] + ([d["gamma"], d["beta"]] if mode == "bn" else [d["bias"]])
-    g.record(backward, produces)
-    return a["out"], b["out"]
-
-
-def pointwise_bias(g, x, xo, c, scope, initializer=None):
-    """text_predication / link_predication: 1x1 conv with biases and no activation on a channel
-    slice of the fused head tensor (nets/pixellink.py:61,67).  Returns contiguous logits."""
-    n, h, w, C = x.data.shape
-    ws = g.workspace()
-    wv, _, bias = _pointwise_vars(g, scope, c, "bias", initializer)
-    out = SmallAct(g.empty((n, h, w, c), F32))
-    ops.sc_pointwise_fwd(x.data, xo, c, wv.data, out.data, 0, c, bias.data)
-
-    def backward():
-        if out.grad is None:
-            return
-        ops.sc_pointwise_wgrad(x.data, xo, c, out.grad, 0, c, wv.grad, bias.grad, ws)
-        if x.grad is None:
-            x.grad = g.empty(x.data.shape, F32)
-            ops.fill_(x.grad, 0.0)
-        ops.sc_pointwise_dgrad(out.grad, 0, c, wv.data, x.grad, xo, c)
-        out.grad = None
-    g.record(backward, (wv, bias))
-    return out
-
-
-def _merged_init(g, cin, couts, base=None):
-    base = base or variance_scaling
-
-    def init(shape):
-        import numpy as np
-        cols = [base(g.rng)((1, 1, cin, c)).reshape(cin, c) for c in couts]
-        return np.concatenate(cols, axis=1)
-    return init
-
-
-def fuse(g, shape, a=None, b=None, prev=None, relu=True):
-    """out = relu(bn(a.z)) + relu(bn(b.z)) + unpool(prev)   (any subset) on f32 head tensors.
-    a, b: (SmallAct z, scale, shift) triples from head_conv_bn; prev: SmallAct at half resolution."""
-    out = SmallAct(g.empty(shape, F32))
-    za, sa, ha = (a[0].data, a[1], a[2]) if a is not None else (None, None, None)
-    zb, sb, hb = (b[0].data, b[1], b[2]) if b is not None else (None, None, None)
-    ops.sc_fuse(out.data, za, sa, ha, zb, sb, hb, prev.data if prev is not None else None, relu)
-
-    def backward():
-        if out.grad is None:
-            return
-        # the add fans the same gradient out to every branch; the BN/ReLU part of a and b is
-        # differentiated inside head_conv_bn's closure
-        for br in (a, b):
-            if br is not None:
-                if br[0].grad is not None:
-                    raise RuntimeError("head tensor used twice")
-                br[0].grad = out.grad
-        if prev is not None:
-            dprev = g.empty(prev.data.shape, F32)
-            ops.sc_unpool_bwd(out.grad, dprev)
-            prev.grad = dprev
-        out.grad = None
-    g.record(backward)
-    return out
-
-
-def pointwise_bn(g, x, xo, c, scope, is_training=True, relu=True):
-    """Final predication conv on a channel slice of a head tensor:
-    out = relu(bn(conv1x1(x[..., xo:xo+c], c)))   (pixel_cls / link_cls,
-    nets/model_vgg_16.py:166,173).  Returns a contiguous SmallAct [n,h,w,c]."""
-    n, h, w, C = x.data.shape
-    ws = g.workspace()
-    wv, bn_vars, _ = _pointwise_vars(g, scope, c, "bn")
-    gamma, beta = bn_vars[:2]
-    z = g.empty((n, h, w, c), F32)
-    ops.sc_pointwise_fwd(x.data, xo, c, wv.data, z, 0, c)
-    scale, shift, mean, invstd = _bn_params(g, c, bn_vars, _small_stats(g, z, c) if is_training else None)
-    out = SmallAct(g.empty((n, h, w, c), F32))
-    ops.sc_fuse(out.data, z, scale, shift, relu=relu)
-
-    def backward():
-        if out.grad is None:
-            return
-        dz = g.empty(z.shape, F32)
-        ops.sc_bn_bwd(z, scale, shift, mean, invstd, out.grad, relu, gamma.grad, beta.grad, dz, ws)
-        ops.sc_pointwise_wgrad(x.data, xo, c, dz, 0, c, wv.grad, None, ws)
-        if x.grad is None:
-            x.grad = g.empty(x.data.shape, F32)
-            ops.fill_(x.grad, 0.0)
-        ops.sc_pointwise_dgrad(dz, 0, c, wv.data, x.grad, xo, c)
-        out.grad = None
-    g.record(backward, (wv, gamma, beta))
-    return out

@@ -6,7 +6,7 @@ EAST's RBOX geometry (reference nets/model.py:76-80) on the merge branch of `mod
 import numpy as np
 import torch
 
-from .. import layers, ops
+from .. import head_layers, layers, ops
 from ..graph import F32, get_default_graph
 from . import vgg
 
@@ -15,7 +15,7 @@ def unpool(inputs, graph=None):
     """tf.image.resize_bilinear x2, legacy sampling (nets/model_vgg_16.py:15-16)."""
     g = graph or get_default_graph()
     n, h, w, c = inputs.data.shape
-    return layers.fuse(g, (n, 2 * h, 2 * w, c), prev=inputs)
+    return head_layers.fuse(g, (n, 2 * h, 2 * w, c), prev=inputs)
 
 
 def mean_image_subtraction(images, means=(123.68, 116.78, 103.94), graph=None):
@@ -63,11 +63,10 @@ def model(images, weight_decay=1e-5, is_training=True, graph=None, blocks=None):
     """nets/model_vgg_16.py:85-136: ResNet-v1-50 + the EAST feature-merging branch
     h_i = conv3x3(conv1x1(concat(unpool(h_{i-1}), f_i))), widths 128/64/32, one more 3x3, then
     F_score = sigmoid(conv1x1 -> 1), geo_map = sigmoid(conv1x1 -> 8)."""
-    from .. import resnet_layers as R
     g = graph or get_default_graph()
     gi, names = _merge_branch(images, weight_decay, is_training, g, blocks)
     with g.variable_scope('feature_fusion'):
-        F_score, geo_map = R.sigmoid_heads(g, gi, (1, 8), (next(names), next(names)))
+        F_score, geo_map = head_layers.sigmoid_heads(g, gi, (1, 8), (next(names), next(names)))
     return F_score, geo_map
 
 
@@ -78,11 +77,10 @@ def model_rbox(images, weight_decay=1e-5, is_training=True, text_scale=512, grap
     (angle): slim's auto-naming order, so an RBOX checkpoint maps by name.  `text_scale` defaults to the reference flag
     (nets/model.py:6).  Returns (F_score [N,H/4,W/4,1], F_geometry [N,H/4,W/4,5]); `graph.end_points['feature_fusion']` is the
     merge branch's output the heads read."""
-    from .. import resnet_layers as R
     g = graph or get_default_graph()
     gi, names = _merge_branch(images, weight_decay, is_training, g, blocks)
     with g.variable_scope('feature_fusion'):
-        F_score, F_geometry = R.rbox_heads(g, gi, (next(names), next(names), next(names)), text_scale)
+        F_score, F_geometry = head_layers.rbox_heads(g, gi, (next(names), next(names), next(names)), text_scale)
     return F_score, F_geometry
 
 
@@ -97,14 +95,14 @@ def model_vgg(images, weight_decay=1e-5, is_training=True, graph=None):
         # slim auto-names: pixel convs Conv..Conv_4, link convs Conv_5..Conv_9
         srcs = [('fc7', ('Conv', 'Conv_5')), ('conv5_3', ('Conv_1', 'Conv_6')),
                 ('conv4_3', ('Conv_2', 'Conv_7')), ('conv3_3', ('Conv_3', 'Conv_8'))]
-        trip = layers.head_group(g, [end_points[key] for key, _ in srcs], [names for _, names in srcs], (2, 16),
-                                 mode="bn", is_training=is_training)
+        trip = head_layers.head_group(g, [end_points[key] for key, _ in srcs], [names for _, names in srcs], (2, 16),
+                                      mode="bn", is_training=is_training)
         heads = {key: t for (key, _), t in zip(srcs, trip)}
         n, h, w, _ = end_points['fc7'].shape
-        s1 = layers.fuse(g, (n, h, w, 18), a=heads['fc7'], b=heads['conv5_3'])
-        s2 = layers.fuse(g, (n, 2 * h, 2 * w, 18), a=heads['conv4_3'], prev=s1)
-        s3 = layers.fuse(g, (n, 4 * h, 4 * w, 18), a=heads['conv3_3'], prev=s2)
-        pixel_cls, link_cls = layers.pointwise_pair(g, s3, ('Conv_4', 'Conv_9'), mode="bn", is_training=is_training)
+        s1 = head_layers.fuse(g, (n, h, w, 18), a=heads['fc7'], b=heads['conv5_3'])
+        s2 = head_layers.fuse(g, (n, 2 * h, 2 * w, 18), a=heads['conv4_3'], prev=s1)
+        s3 = head_layers.fuse(g, (n, 4 * h, 4 * w, 18), a=heads['conv3_3'], prev=s2)
+        pixel_cls, link_cls = head_layers.pointwise_pair(g, s3, ('Conv_4', 'Conv_9'), mode="bn", is_training=is_training)
     return pixel_cls, link_cls
 
 

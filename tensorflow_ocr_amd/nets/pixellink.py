@@ -7,7 +7,7 @@ Variable scopes follow the reference: `vgg/conv1/conv1_1/{weights,biases}` ...,
 map are one merged parameter internally; `checkpoint.internal_to_tf` splits it)."""
 import torch
 
-from .. import layers, losses, ops
+from .. import head_layers, layers, losses, ops
 from ..graph import F32, constant, get_default_graph, xavier_uniform
 from . import vgg
 
@@ -58,7 +58,7 @@ class PixelLinkNet(object):
 
     def unpool(self, inputs):
         n, h, w, c = inputs.data.shape
-        return layers.fuse(self.g, (n, 2 * h, 2 * w, c), prev=inputs)
+        return head_layers.fuse(self.g, (n, 2 * h, 2 * w, c), prev=inputs)
 
     def _build_network(self):
         g = self.g
@@ -81,15 +81,15 @@ class PixelLinkNet(object):
     def _add_pixellink_layers(self, basenet, end_points):
         g = self.g
         srcs = [('fc7', 'stage_6'), ('conv5_3', 'stage_5'), ('conv4_3', 'stage_4'), ('conv3_3', 'stage_3')]
-        trip = layers.head_group(g, [end_points[key] for key, _ in srcs],
-                                 [(st + '_pixel_fuse', st + '_link_fuse') for _, st in srcs], (2, 16), mode="bias",
-                                 initializer=xavier_uniform)
+        trip = head_layers.head_group(g, [end_points[key] for key, _ in srcs],
+                                      [(st + '_pixel_fuse', st + '_link_fuse') for _, st in srcs], (2, 16), mode="bias",
+                                      initializer=xavier_uniform)
         heads = {key: t for (key, _), t in zip(srcs, trip)}
         n, h, w, _ = end_points['fc7'].shape
-        s1 = layers.fuse(g, (n, h, w, 18), a=heads['fc7'], b=heads['conv5_3'])
-        s2 = layers.fuse(g, (n, 2 * h, 2 * w, 18), a=heads['conv4_3'], prev=s1)
-        s3 = layers.fuse(g, (n, 4 * h, 4 * w, 18), a=heads['conv3_3'], prev=s2)
-        self.pixel_cls, self.link_cls = layers.pointwise_pair(g, s3, ('text_predication', 'link_predication'), mode="bias")
+        s1 = head_layers.fuse(g, (n, h, w, 18), a=heads['fc7'], b=heads['conv5_3'])
+        s2 = head_layers.fuse(g, (n, 2 * h, 2 * w, 18), a=heads['conv4_3'], prev=s1)
+        s3 = head_layers.fuse(g, (n, 4 * h, 4 * w, 18), a=heads['conv3_3'], prev=s2)
+        self.pixel_cls, self.link_cls = head_layers.pointwise_pair(g, s3, ('text_predication', 'link_predication'), mode="bias")
         return self.pixel_cls, self.link_cls
 
     @property

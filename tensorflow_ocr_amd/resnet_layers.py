@@ -14,7 +14,7 @@ import torch
 from . import ops
 from .graph import Act, F32, constant, variance_scaling
 from .layers import (FUSE_BN_REDUCE, _bn_bwd_coef, _bn_params, _bn_vars, _coef, _count_contribution, _dgrad_desc,
-                     _open_input_grad, _packs, _partial_rows, _switch, _wgrad_desc)
+                     _grad_buffer, _open_input_grad, _packs, _partial_rows, _switch, _wgrad_desc, max_pool2d)
 from ._lib import CONV_ACCUM_F16, CONV_STATS
 
 USE_S2D = _switch("OCR_RESNET_S2D")     # measurement switch (A/B against the subsample form)
@@ -32,7 +32,6 @@ FUSE_ROOT_POOL = _switch("OCR_RESNET_FUSE_ROOT_POOL")   # root conv: BN + ReLU i
 FUSE_ROOT_WGRAD = _switch("OCR_RESNET_FUSE_ROOT_WGRAD")   # root conv: BN-backward apply inside its weight gradient
 FUSE_ROOT_GATHER = _switch("OCR_RESNET_FUSE_ROOT_GATHER")   # ... and the pool's backward inside that BN's reduction pass
 MASK_BITS = _switch("OCR_RESNET_MASK_BITS", False)   # tail mask as bits instead of the output tensor: measured SLOWER (byte stores +8 % on the writers, byte loads no faster in the latency-bound tail epilogue), off
-MERGE_HEADS = _switch("OCR_RESNET_MERGE_HEADS")   # F_score + geo_map: one pass over the feature
 MERGE_REORDER = _switch("OCR_RESNET_MERGE_REORDER")   # 1x1 merge conv before the upsample
 
 
@@ -175,10 +174,7 @@ def conv_bn_raw(g, x, cout, k, scope, *, stride=1, rate=1, is_training=True, wei
                 # input gradient in the shuffled layout, then back to full resolution (added to what is there)
                 dxs = g.empty(x_in.shape)
                 ops.conv2d(_dgrad_desc(d, 0), dy, w_dg, dxs, None, None)
-                had = x.grad is not None
-                if not had:
-                    x.grad = g.empty(x.shape)
-                ops.depth_to_space(dxs, x.grad, had)
+                ops.depth_to_space(dxs, *_grad_buffer(g, x))
                 x.bn_partial = None
                 return
             flags = _open_input_grad(g, x)
@@ -349,8 +345,6 @@ def bottleneck(g, x, depth, depth_bottleneck, stride, scope, is_training=True):
     shortcut's batch norm is applied inside that same expression and never stored, the output's ReLU mask travels to
     the backward pass as bits, and conv3's batch-norm backward apply runs inside conv3's input-gradient convolution
     (FUSE_BWD)."""
-    from .layers import max_pool2d
-    import torch
     depth_in = x.shape[-1]
     ws = g.workspace()
     owner = object()                       # identifies this unit's own consumers of x (conv1, shortcut)
@@ -427,10 +421,8 @@ def bottleneck(g, x, depth, depth_bottleneck, stride, scope, is_training=True):
                     if x.grad is None and x.pending == 2 and stride == 2:
                         x.sub_grad = shortcut.grad
                     else:                            # someone else contributed already: materialise
-                        acc = x.grad is not None
-                        if not acc:
-                            x.grad = g.empty(x.shape)
-                        ops.maxpool_bwd(x.data, shortcut.grad, 1, stride, (0, 0), x.grad, acc, in_shape=x.shape)
+                        dx, acc = _grad_buffer(g, x)
+                        ops.maxpool_bwd(x.data, shortcut.grad, 1, stride, (0, 0), dx, acc, in_shape=x.shape)
                     x.pending -= 1
                     shortcut.grad = None
                 g.record(sub_back)
@@ -507,13 +499,40 @@ def unpool(g, x):
     def backward():
         if out.grad is None or not x.requires_grad:
             return
-        acc = x.grad is not None
-        if not acc:
-            x.grad = g.empty(x.shape)
-        ops.unpool_bwd_f16(out.grad, x.grad, acc)
+        ops.unpool_bwd_f16(out.grad, *_grad_buffer(g, x))
         out.grad = None
     g.record(backward)
     return out
+
+
+def _cat_vars(g, scope, ca, cb, cout):
+    """The merge convolution's ONE variable `<scope>/weights` [1,1,ca+cb,cout] as in the reference, its batch-norm
+    variables, and the two branches' operand packs (wa_kc, wa_ck, wb_kc, wb_ck)."""
+    with g.variable_scope(scope):
+        wv = g.get_variable("weights", (1, 1, ca + cb, cout), variance_scaling(g.rng), regularized=True)
+        bn_vars = _bn_vars(g, cout)
+
+    def mk(old):
+        if old is None:
+            old = [g.empty((1, cout, ca)), g.empty((1, ca, cout)), g.empty((1, cout, cb)), g.empty((1, cb, cout))]
+        ops.pack_weights(wv.data[:, :, :ca, :], old[0], old[1])
+        ops.pack_weights(wv.data[:, :, ca:, :], old[2], old[3])
+        return old
+    return wv, bn_vars, g.packed(wv, "cat", mk)
+
+
+def _cat_backward(g, wv, branches):
+    """The merge convolution's weight gradient and input gradient branch by branch; branches: (input Act, its input-
+    gradient pack, gradient of its share of the convolution's output), in the concat's channel order."""
+    cout = wv.shape[-1]
+    lo = 0
+    for x, w_ck, dy in branches:
+        c = x.shape[-1]
+        dd = ops.conv_desc(x.shape, cout, 1, 1)
+        ops.conv2d_wgrad(dd, x.data, dy, wv.grad[:, :, lo:lo + c, :], g.ws_wgrad)
+        if x.requires_grad:
+            ops.conv2d(_dgrad_desc(dd, _open_input_grad(g, x)), dy, w_ck, x.grad, None, None)
+        lo += c
 
 
 def concat_conv_bn_relu(g, xa, xb, cout, scope, is_training=True):
@@ -525,18 +544,9 @@ def concat_conv_bn_relu(g, xa, xb, cout, scope, is_training=True):
         return layers_f32.concat_conv_bn_relu(g, xa, xb, cout, scope, is_training=is_training)
     n, h, w, ca = xa.shape
     cb = xb.shape[-1]
-    with g.variable_scope(scope):
-        wv = g.get_variable("weights", (1, 1, ca + cb, cout), variance_scaling(g.rng), regularized=True)
-        gamma, beta, mm, mv = _bn_vars(g, cout)
+    wv, bn_vars, (wa_kc, wa_ck, wb_kc, wb_ck) = _cat_vars(g, scope, ca, cb, cout)
+    gamma, beta = bn_vars[:2]
     ws = g.workspace()
-
-    def mk(old):
-        if old is None:
-            old = [g.empty((1, cout, ca)), g.empty((1, ca, cout)), g.empty((1, cout, cb)), g.empty((1, cb, cout))]
-        ops.pack_weights(wv.data[:, :, :ca, :], old[0], old[1])
-        ops.pack_weights(wv.data[:, :, ca:, :], old[2], old[3])
-        return old
-    wa_kc, wa_ck, wb_kc, wb_ck = g.packed(wv, "cat", mk)
     da = ops.conv_desc((n, h, w, ca), cout, 1, 1)
     db = ops.conv_desc((n, h, w, cb), cout, 1, 1)
     y = g.empty((n, h, w, cout))
@@ -546,8 +556,7 @@ def concat_conv_bn_relu(g, xa, xb, cout, scope, is_training=True):
     ops.conv2d(da, xa.data, wa_kc, y, None, None)
     db.flags = CONV_ACCUM_F16 | (CONV_STATS if is_training else 0)
     ops.conv2d(db, xb.data, wb_kc, y, None, part if is_training else None)
-    scale, shift, mean, invstd = _bn_params(g, cout, (gamma, beta, mm, mv),
-                                            (part, mt, float(n) * h * w, stage) if is_training else None)
+    scale, shift, mean, invstd = _bn_params(g, cout, bn_vars, (part, mt, float(n) * h * w, stage) if is_training else None)
     a = Act(g.empty(y.shape), name=scope)
     ops.bn_relu(y, scale, shift, True, 0, a.data, None)
 
@@ -556,78 +565,10 @@ def concat_conv_bn_relu(g, xa, xb, cout, scope, is_training=True):
             return
         dy = g.empty(y.shape)
         ops.bn_relu_bwd(y, scale, shift, mean, invstd, a.grad, None, True, 0, gamma.grad, beta.grad, dy, ws)
-        for x, c, w_ck, sl in ((xa, ca, wa_ck, slice(0, ca)), (xb, cb, wb_ck, slice(ca, ca + cb))):
-            dd = ops.conv_desc((n, h, w, c), cout, 1, 1)
-            ops.conv2d_wgrad(dd, x.data, dy, wv.grad[:, :, sl, :], g.ws_wgrad)
-            if x.requires_grad:
-                ops.conv2d(_dgrad_desc(dd, _open_input_grad(g, x)), dy, w_ck, x.grad, None, None)
+        _cat_backward(g, wv, ((xa, wa_ck, dy), (xb, wb_ck, dy)))
         a.grad = None
     g.record(backward, (wv, gamma, beta))
     return a
-
-
-def sigmoid_heads(g, feat, couts, scopes):
-    """The two sigmoid heads on the merge branch's output (nets/model_vgg_16.py:129-131: F_score = conv1x1 -> 1,
-    geo_map = conv1x1 -> 8, both sigmoid, biases, no normaliser) as ONE merged 1x1 convolution over the feature
-    (layers.head_conv_bias: variable `<scope0>+<scope1>/weights` [cin, 1+8], split back into the reference's two by
-    checkpoint.internal_to_tf) — one pass over the 105 MB feature for the forward, the weight gradient and the input
-    gradient instead of two each.  Returns the two activation handles."""
-    from .layers import SmallAct, head_conv_bias
-    if g.precision == "f32" or not MERGE_HEADS:
-        return tuple(sigmoid_head(g, feat, c, s) for c, s in zip(couts, scopes))
-    z, _, _ = head_conv_bias(g, feat, tuple(scopes), tuple(couts))
-    n, h, w, _ = z.data.shape
-    o0 = SmallAct(g.empty((n, h, w, couts[0]), F32))
-    o1 = SmallAct(g.empty((n, h, w, couts[1]), F32))
-    ops.sc_sigmoid_split(z.data, couts[0], o0.data, o1.data)
-
-    def backward():
-        if o0.grad is None and o1.grad is None:
-            return
-        z.grad = g.empty(z.data.shape, F32)
-        ops.sc_sigmoid_split_bwd(o0.data, o0.grad, o1.data, o1.grad, z.grad)
-        o0.grad = o1.grad = None
-    g.record(backward)
-    return o0, o1
-
-
-def rbox_heads(g, feat, scopes, text_scale):
-    """EAST's RBOX heads on the merge branch's output (reference nets/model.py:76-80): F_score = sigmoid(conv1x1 -> 1),
-    four distances = sigmoid(conv1x1 -> 4) * text_scale, angle = (sigmoid(conv1x1 -> 1) - 0.5) * pi/2, as ONE merged 1x1
-    convolution (layers.head_conv_bias: variable `<s0>+<s1>+<s2>/weights` [cin, 1+4+1], split back into the reference's
-    three by checkpoint.internal_to_tf) and one f32 activation kernel (ops.rbox_head_fwd).  Returns the handles
-    (F_score [n,h,w,1], F_geometry [n,h,w,5]).  With the f32 inference precision or OCR_RESNET_MERGE_HEADS=0: one
-    convolution per head, the same activation kernel on their concatenation."""
-    import torch
-    from .layers import SmallAct, head_conv_bias
-    couts = (1, 4, 1)
-    if g.precision == "f32" or not MERGE_HEADS:
-        if g.keepalive is not None:
-            # the columns are gathered / scattered by torch copies, which a recorded step plan does not replay
-            raise NotImplementedError("rbox_heads with OCR_RESNET_MERGE_HEADS=0 cannot run inside a recorded step")
-        zs = [head_conv_bias(g, feat, (s,), (c,))[0] for s, c in zip(scopes, couts)]
-        z = SmallAct(torch.cat([t.data for t in zs], dim=-1))
-    else:
-        zs = None
-        z, _, _ = head_conv_bias(g, feat, tuple(scopes), couts)
-    n, h, w, _ = z.data.shape
-    o0 = SmallAct(g.empty((n, h, w, 1), F32))
-    o1 = SmallAct(g.empty((n, h, w, 5), F32))
-    ops.rbox_head_fwd(z.data, float(text_scale), o0.data, o1.data)
-
-    def backward():
-        if o0.grad is None and o1.grad is None:
-            return
-        z.grad = g.empty(z.data.shape, F32)
-        ops.rbox_head_bwd(o0.data, o0.grad, o1.data, o1.grad, float(text_scale), z.grad)
-        if zs is not None:
-            o = 0
-            for t, c in zip(zs, couts):
-                t.grad = z.grad[..., o:o + c].contiguous()
-                o += c
-        o0.grad = o1.grad = None
-    g.record(backward)
-    return o0, o1
 
 
 def unpool_concat_conv_bn_relu(g, lo, xb, cout, scope, is_training=True):
@@ -642,18 +583,9 @@ def unpool_concat_conv_bn_relu(g, lo, xb, cout, scope, is_training=True):
     n, lh, lw, ca = lo.shape
     _, h, w, cb = xb.shape
     assert (h, w) == (2 * lh, 2 * lw)
-    with g.variable_scope(scope):
-        wv = g.get_variable("weights", (1, 1, ca + cb, cout), variance_scaling(g.rng), regularized=True)
-        gamma, beta, mm, mv = _bn_vars(g, cout)
+    wv, bn_vars, (wa_kc, wa_ck, wb_kc, wb_ck) = _cat_vars(g, scope, ca, cb, cout)
+    gamma, beta = bn_vars[:2]
     ws = g.workspace()
-
-    def mk(old):
-        if old is None:
-            old = [g.empty((1, cout, ca)), g.empty((1, ca, cout)), g.empty((1, cout, cb)), g.empty((1, cb, cout))]
-        ops.pack_weights(wv.data[:, :, :ca, :], old[0], old[1])
-        ops.pack_weights(wv.data[:, :, ca:, :], old[2], old[3])
-        return old
-    wa_kc, wa_ck, wb_kc, wb_ck = g.packed(wv, "cat", mk)
     da = ops.conv_desc((n, lh, lw, ca), cout, 1, 1)
     db = ops.conv_desc((n, h, w, cb), cout, 1, 1)
     t = g.empty((n, lh, lw, cout))
@@ -665,8 +597,7 @@ def unpool_concat_conv_bn_relu(g, lo, xb, cout, scope, is_training=True):
     T = ops.channel_stats_num_partials(n * h * w, cout)
     part, stage = g.ws_small.two(T * 2 * cout * 4, ops.bn_reduce_workspace(T, cout))
     ops.unpool_add_stats(t, y, part if is_training else None)
-    scale, shift, mean, invstd = _bn_params(g, cout, (gamma, beta, mm, mv),
-                                            (part, T, float(n) * h * w, stage) if is_training else None)
+    scale, shift, mean, invstd = _bn_params(g, cout, bn_vars, (part, T, float(n) * h * w, stage) if is_training else None)
     a = Act(g.empty(y.shape), name=scope)
     ops.bn_relu(y, scale, shift, True, 0, a.data, None)
 
@@ -677,29 +608,7 @@ def unpool_concat_conv_bn_relu(g, lo, xb, cout, scope, is_training=True):
         ops.bn_relu_bwd(y, scale, shift, mean, invstd, a.grad, None, True, 0, gamma.grad, beta.grad, dy, ws)
         dt = g.empty(t.shape)
         ops.unpool_bwd_f16(dy, dt, False)                # gradient of conv(lo, Wa): the resize's transpose on cout channels
-        for x, c, w_ck, sl, d_out, (hh, ww) in ((lo, ca, wa_ck, slice(0, ca), dt, (lh, lw)),
-                                                (xb, cb, wb_ck, slice(ca, ca + cb), dy, (h, w))):
-            dd = ops.conv_desc((n, hh, ww, c), cout, 1, 1)
-            ops.conv2d_wgrad(dd, x.data, d_out, wv.grad[:, :, sl, :], g.ws_wgrad)
-            if x.requires_grad:
-                ops.conv2d(_dgrad_desc(dd, _open_input_grad(g, x)), d_out, w_ck, x.grad, None, None)
+        _cat_backward(g, wv, ((lo, wa_ck, dt), (xb, wb_ck, dy)))
         a.grad = None
     g.record(backward, (wv, gamma, beta))
     return a
-
-
-def sigmoid_head(g, feat, cout, scope):
-    """slim.conv2d(feat, cout, 1, activation_fn=tf.nn.sigmoid, normalizer_fn=None) (model_vgg_16.py:129-131)."""
-    from .layers import SmallAct, head_conv_bias
-    z, _, _ = head_conv_bias(g, feat, (scope,), (cout,))
-    out = SmallAct(g.empty(z.data.shape, F32))
-    ops.sc_sigmoid(z.data, out.data)
-
-    def backward():
-        if out.grad is None:
-            return
-        z.grad = g.empty(z.data.shape, F32)
-        ops.sc_sigmoid_bwd(out.data, out.grad, z.grad)
-        out.grad = None
-    g.record(backward)
-    return out

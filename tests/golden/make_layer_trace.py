@@ -1,5 +1,5 @@
-"""Records tests/golden/layer_trace.json: what the Python layer modules (tensorflow_ocr_amd/layers.py, resnet_layers.py)
-LAUNCH for a table of small builds — the flat list of C-ABI calls of one eager step under `_lib.Recorder`, made
+"""Records tests/golden/layer_trace.json: what the Python layer modules (tensorflow_ocr_amd/layers.py, resnet_layers.py,
+head_layers.py) LAUNCH for a table of small builds — the flat list of C-ABI calls of one eager step under `_lib.Recorder`, made
 independent of addresses — and, for the training builds, the bits of two training steps.  tests/test_gpu_layer_trace.py
 re-records every build and requires the same list and the same bits: run this on the commit whose launches are to be
 kept, BEFORE changing the host code above the C ABI.  Needs the GPU.
@@ -48,6 +48,13 @@ BUILDS = {"vgg": ("vgg", "train", {}), "pixellink": ("pixellink", "train", {}), 
 for _net in ("vgg", "resnet"):
     for _sw in SWITCHES:
         BUILDS["%s,%s=0" % (_net, _sw)] = (_net, "train", {_sw: "0"})
+# head paths that the table above does not reach: the per-source bias forms, the two single sigmoid heads, the merge
+# convolution on the upsampled tensor, and the RBOX heads' forward (their backward: tests/test_gpu_rbox.py)
+MERGE_SWITCHES = ["OCR_RESNET_MERGE_HEADS", "OCR_RESNET_MERGE_REORDER"]
+BUILDS["pixellink,OCR_BATCH_HEADS=0"] = ("pixellink", "train", {"OCR_BATCH_HEADS": "0"})
+for _sw in MERGE_SWITCHES:
+    BUILDS["resnet,%s=0" % _sw] = ("resnet", "train", {_sw: "0"})
+BUILDS["rbox"] = ("rbox", "infer", {})
 
 
 # ------------------------------------------------------------------------------------------------ canonical form
@@ -183,6 +190,8 @@ def child(name, batch, size):
                 M.model_vgg(data[0], is_training=False, graph=g)
             elif net == "resnet":
                 M.model(data[0], is_training=False, graph=g)
+            elif net == "rbox":
+                M.model_rbox(data[0], is_training=False, graph=g)
             else:
                 # (PixelLinkNet has no is_training argument — its layers have no batch norm: the forward alone)
                 from tensorflow_ocr_amd.nets import pixellink
@@ -204,7 +213,7 @@ def child(name, batch, size):
 def run_build(name, batch, size, storage="f16"):
     """One build in a fresh interpreter -> the child's dict."""
     env = dict(os.environ, OCR_STORAGE=storage)
-    for sw in SWITCHES:
+    for sw in SWITCHES + MERGE_SWITCHES:
         env.pop(sw, None)
     env.update(BUILDS[name][2])
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, str(batch), str(size)], cwd=ROOT, env=env,

@@ -66,7 +66,7 @@ def test_ohnm_single_image_on_signed_scores(device, hw, n_pos):
 
 def test_ohnm_batch_exact_and_equals_the_loss_kernels_mask(device):
     """OHNM_batch on P(neg) computed with the shared deterministic exp = the mask the fused loss mines."""
-    from tensorflow_ocr_amd import layers
+    from tensorflow_ocr_amd import head_layers
     from tensorflow_ocr_amd.graph import Graph
     from tensorflow_ocr_amd.nets import model as M
     g = Graph(device)
@@ -81,8 +81,8 @@ def test_ohnm_batch_exact_and_equals_the_loss_kernels_mask(device):
     want = O.ohnm_batch(scores, pos, neg)
     assert np.array_equal(got, want) and got[3].sum() == 0
     # the same selection comes out of the training loss (nets/model.py: loss -> ocr_softmax_loss_selected)
-    px = layers.SmallAct(torch.from_numpy(logits).to(device))
-    lk = layers.SmallAct(torch.from_numpy(rng.standard_normal((n, h, w, 16)).astype(np.float32)).to(device))
+    px = head_layers.SmallAct(torch.from_numpy(logits).to(device))
+    lk = head_layers.SmallAct(torch.from_numpy(rng.standard_normal((n, h, w, 16)).astype(np.float32)).to(device))
     res = M.loss(label, px, (rng.random((n, h, w, 8)) < 0.5).astype(np.float32), lk, None, graph=g)
     assert np.array_equal(res.selected_mask().cpu().numpy().reshape(n, -1).astype(np.float32), want)
     # a batch_size below the tensor's (the reference passes a literal 14): the first rows only
@@ -90,7 +90,7 @@ def test_ohnm_batch_exact_and_equals_the_loss_kernels_mask(device):
 
 
 def test_cal_link_loss_value_slices_and_gradient(device):
-    from tensorflow_ocr_amd import layers
+    from tensorflow_ocr_amd import head_layers
     from tensorflow_ocr_amd.graph import Graph
     from tensorflow_ocr_amd.nets import model_vgg_16 as MV
     g = Graph(device, loss_scale=1.0)
@@ -109,15 +109,15 @@ def test_cal_link_loss_value_slices_and_gradient(device):
     pr = torch.from_numpy(link_pred[..., 4:6].copy()).requires_grad_(True)
     want = O.cal_link_loss(torch.from_numpy(link_gt[..., 2]), pr, torch.from_numpy(W))
     want.backward()
-    hd = layers.SmallAct(torch.from_numpy(link_pred[..., 4:6].copy()).to(device))
+    hd = head_layers.SmallAct(torch.from_numpy(link_pred[..., 4:6].copy()).to(device))
     got = MV.cal_link_loss(link_gt[..., 2], hd, W, graph=g)
     g.backward()
     assert abs(got.item() - float(want)) <= 1e-5
     assert np.abs(hd.grad.cpu().numpy() - pr.grad.numpy()).max() <= 1e-6
     # ohem_loss = 2 L_pixel + sum of the eight cal_link_loss terms with W_pixel = (label == 1) (:243-282)
     label = (rng.random((n, h, w, 1)) < 0.3).astype(np.float32)
-    px = layers.SmallAct(torch.from_numpy(rng.standard_normal((n, h, w, 2)).astype(np.float32)).to(device))
-    lk = layers.SmallAct(pr_d)
+    px = head_layers.SmallAct(torch.from_numpy(rng.standard_normal((n, h, w, 2)).astype(np.float32)).to(device))
+    lk = head_layers.SmallAct(pr_d)
     g.reset_tape()
     full = MV.ohem_loss(label, px, link_gt, lk, None, graph=g)
     terms = [MV.cal_link_loss(gt_d[..., d:d + 1], pr_d[..., 2 * d:2 * d + 2], label.reshape(-1), graph=g).item() for d in range(8)]

@@ -244,16 +244,16 @@ def test_sc_act_batch(device):
 
 @pytest.mark.parametrize("net", ["model_vgg", "pixellink"])
 def test_whole_step_batched_heads_vs_per_map_heads(device, net, monkeypatch):
-    """The same net, same weights, same batch, with layers.BATCH_HEADS on and off: outputs, loss and every gradient agree to
+    """The same net, same weights, same batch, with head_layers.BATCH_HEADS on and off: outputs, loss and every gradient agree to
     the summation-order differences of the head statistics / weight gradients (the trunk is untouched)."""
     from oracle import ocr_oracle as O
-    from tensorflow_ocr_amd import layers
+    from tensorflow_ocr_amd import head_layers
     from tensorflow_ocr_amd.graph import Graph
     rng = np.random.default_rng(11)
     images, pixel, link, mask = O.synthetic_batch(rng, 2, 128)
     res = {}
     for batched in (True, False):
-        monkeypatch.setattr(layers, "BATCH_HEADS", batched)
+        monkeypatch.setattr(head_layers, "BATCH_HEADS", batched)
         g = Graph(device, loss_scale=128.0, seed=3)
         if net == "model_vgg":
             from tensorflow_ocr_amd.nets import model_vgg_16 as M
@@ -331,9 +331,9 @@ def test_sigmoid_split_and_its_gradient(device):
 
 
 def test_merged_sigmoid_heads_equal_the_two_heads(device):
-    """resnet_layers.sigmoid_heads (one merged 1x1 convolution for F_score + geo_map) against two sigmoid_head calls with
+    """head_layers.sigmoid_heads (one merged 1x1 convolution for F_score + geo_map) against two sigmoid_head calls with
     the same weights: activations bit for bit (same kernel, same per-output arithmetic), gradients to f32 summation order."""
-    from tensorflow_ocr_amd import checkpoint, resnet_layers as R
+    from tensorflow_ocr_amd import checkpoint, head_layers as R
     from tensorflow_ocr_amd.graph import Act, F16, Graph
     rng = np.random.default_rng(32)
     n, h, w, cin = 2, 24, 40, 32

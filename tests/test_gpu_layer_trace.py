@@ -1,10 +1,10 @@
 """GPU: what the Python layer modules launch, build by build, against tests/golden/layer_trace.json.
 
-tensorflow_ocr_amd/layers.py and resnet_layers.py decide which C-ABI entries a step calls, in which order and on which
-tensors.  tests/golden/make_layer_trace.py recorded that for a table of small builds — the three training nets, their
-forward-only builds, the f32 precision, and the two big nets with each of seven switches off — as the address-free list
-of one eager step's calls under `_lib.Recorder`, plus the loss bits of two training steps and a CRC-32 of the parameters
-after them.  Every build is recorded again here, in a fresh interpreter (the switches are read at import), and must give
+tensorflow_ocr_amd/layers.py, resnet_layers.py and head_layers.py decide which C-ABI entries a step calls, in which order
+and on which tensors.  tests/golden/make_layer_trace.py recorded that for a table of small builds — the three training
+nets, their forward-only builds, the f32 precision, the two big nets with each of seven switches off, and four builds
+for the head paths those do not reach — as the address-free list of one eager step's calls under `_lib.Recorder`, plus
+the loss bits of two training steps and a CRC-32 of the parameters after them.  Every build is recorded again here, in a fresh interpreter (the switches are read at import), and must give
 the SAME list (the golden keeps its SHA-256, and a CRC-32 per entry to name the first one that moved) and the SAME
 bits: no tolerance.  A replayed step issues the recorded list, so an equal list is an equal step.  When a change is
 MEANT to alter the launches: record the lists as text on both commits (`make_layer_trace.py --text DIR`), read their

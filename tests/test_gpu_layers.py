@@ -138,7 +138,7 @@ def test_maxpool3x3s1(device):
 
 def test_heads_and_dice(device):
     """fuse heads (1x1 small convs + BN + ReLU + unpool/add pyramid + predication convs) and dice."""
-    from tensorflow_ocr_amd import checkpoint, layers
+    from tensorflow_ocr_amd import checkpoint, head_layers
     from tensorflow_ocr_amd.graph import Act, Graph
     from tensorflow_ocr_amd.nets import model_vgg_16 as M
     rng = np.random.default_rng(4)
@@ -168,11 +168,11 @@ def test_heads_and_dice(device):
         with g.variable_scope('feature_fusion'):
             srcs = [('fc7', ('Conv', 'Conv_5')), ('conv5_3', ('Conv_1', 'Conv_6')),
                     ('conv4_3', ('Conv_2', 'Conv_7')), ('conv3_3', ('Conv_3', 'Conv_8'))]
-            hd = {k: layers.head_conv_bn(g, acts[k], nm, (2, 16)) for k, nm in srcs}
-            s1 = layers.fuse(g, (n, h, h, 18), a=hd['fc7'], b=hd['conv5_3'])
-            s2 = layers.fuse(g, (n, 2 * h, 2 * h, 18), a=hd['conv4_3'], prev=s1)
-            s3 = layers.fuse(g, (n, 4 * h, 4 * h, 18), a=hd['conv3_3'], prev=s2)
-            return layers.pointwise_bn(g, s3, 0, 2, 'Conv_4'), layers.pointwise_bn(g, s3, 2, 16, 'Conv_9')
+            hd = {k: head_layers.head_conv_bn(g, acts[k], nm, (2, 16)) for k, nm in srcs}
+            s1 = head_layers.fuse(g, (n, h, h, 18), a=hd['fc7'], b=hd['conv5_3'])
+            s2 = head_layers.fuse(g, (n, 2 * h, 2 * h, 18), a=hd['conv4_3'], prev=s1)
+            s3 = head_layers.fuse(g, (n, 4 * h, 4 * h, 18), a=hd['conv3_3'], prev=s2)
+            return head_layers.pointwise_bn(g, s3, 0, 2, 'Conv_4'), head_layers.pointwise_bn(g, s3, 2, 16, 'Conv_9')
 
     g = Graph(device, loss_scale=64.0)
     acts = {k: Act(torch.from_numpy(v).to(O.STORAGE).to(device)) for k, v in feats.items()}

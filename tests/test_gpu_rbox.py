@@ -405,7 +405,7 @@ def test_per_head_convolutions_give_the_same_gradients_bar(device, graph_case, m
     """OCR_RESNET_MERGE_HEADS=0: three convolutions (variables Conv_7, Conv_8, Conv_9), the activation kernel on their
     concatenation, the backward scattered into the three — against the same float64 reference and the same bar; the
     path refuses a recorded step."""
-    from tensorflow_ocr_amd import resnet_layers as R
+    from tensorflow_ocr_amd import head_layers as R
     from tensorflow_ocr_amd.graph import Graph
     from tensorflow_ocr_amd.nets import model_vgg_16 as M
     from tensorflow_ocr_amd.train import AdamOptimizer, TrainStep

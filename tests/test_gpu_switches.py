@@ -135,7 +135,8 @@ RESNET_FLAGS = ["USE_S2D", "FUSE_TAIL", "FUSE_SUB", "FUSE_FWD", "FUSE_BWD", "FUS
 
 @pytest.mark.parametrize("flag", RESNET_FLAGS)
 def test_resnet_east_step_with_one_switch_flipped(device, monkeypatch, flag):
-    from tensorflow_ocr_amd import resnet_layers as R
+    from tensorflow_ocr_amd import head_layers, resnet_layers
+    R = head_layers if flag == "MERGE_HEADS" else resnet_layers
     ref = _baseline(device, "east", _run_east)
     monkeypatch.setattr(R, flag, not getattr(R, flag))
     _agree(_run_east(device), ref, flag)

@@ -27,10 +27,10 @@ def _make(device, replay):
 
 @pytest.mark.parametrize("batch_heads", [True, False])
 def test_replay_equals_eager_bitwise(device, batch_heads, monkeypatch):
-    from tensorflow_ocr_amd import layers
-    # both head forms: one launch per kernel kind over the sources (layers.head_group, the default) and the per-source
-    # convolutions (layers.head_conv_bn)
-    monkeypatch.setattr(layers, "BATCH_HEADS", batch_heads)
+    from tensorflow_ocr_amd import head_layers
+    # both head forms: one launch per kernel kind over the sources (head_layers.head_group, the default) and the per-source
+    # convolutions (head_layers.head_conv_bn)
+    monkeypatch.setattr(head_layers, "BATCH_HEADS", batch_heads)
     ge, be, se = _make(device, False)
     gr, br, sr = _make(device, True)
     le, lr = [], []
