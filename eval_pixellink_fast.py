@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Held-out evaluation of the decode test_pixellink_fast.py runs (not in the reference, which writes boxes and never
+scores them): the images of --test_data_path go through PixelLinkNet at --eval_image_height x --eval_image_width, link-gated
+connected components at 1/4 resolution, one box per component with the component's mean pixel score, and the reference's
+raster-IoU matching (tool/bboxes.py:171-240; not the official ICDAR-2015 protocol) against the `gt_<name>.txt` files of
+--gt_path (ICDAR layout, `###` = ignored) — per batch one chain on the device, one read of the counters at its end
+(tensorflow_ocr_amd.evaluate.LinkEvaluator).  One line is printed:
+
+    precision .. recall .. hmean .. (gt .. det ..)
+
+    python eval_pixellink_fast.py --checkpoint_path /tmp/pixellink/ --test_data_path ./images --gt_path ./gt
+    python eval_pixellink_fast.py --synthetic 2 --gt_path ./gt         (random images named synthetic_<i>)
+
+Flag names and defaults are test_pixellink_fast.py's where the two scripts share them; that script itself is unchanged and
+writes the same `res_<name>.txt` files as before.  Unlike it, images of any size are taken: each is resized on the device
+and the boxes are matched in original-image pixels.  --min_side / --min_area drop small boxes (0: nothing, as the
+reference)."""
+import argparse
+import os
+import tempfile
+
+import numpy as np
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--checkpoint_path', type=str, default=None)
+    ap.add_argument('--test_data_path', type=str, default='/tmp/images/')
+    ap.add_argument('--gt_path', type=str, default=None, metavar='DIR', help="a directory of gt_<name>.txt files (ICDAR "
+                    "layout, ### = ignored); default: beside the images")
+    ap.add_argument('--pixel_conf_threshold', type=float, default=0.8)
+    ap.add_argument('--link_conf_threshold', type=float, default=0.9)
+    ap.add_argument('--eval_image_width', type=int, default=1280)
+    ap.add_argument('--eval_image_height', type=int, default=768)
+    ap.add_argument('--min_side', type=float, default=0.0, help="drop boxes whose shorter side is below this (image pixels).  "
+                    "Default 0: nothing is dropped, as in the reference")
+    ap.add_argument('--min_area', type=float, default=0.0, help="drop boxes whose area is below this")
+    ap.add_argument('--batch_size', type=int, default=8)
+    ap.add_argument('--synthetic', type=int, default=0, help='evaluate N synthetic images instead of files')
+    ap.add_argument('--precision', choices=['f16', 'f32'], default='f16', help="as test_pixellink_fast.py's flag")
+    FLAGS = ap.parse_args(argv)
+    if FLAGS.min_side < 0 or FLAGS.min_area < 0:
+        ap.error('--min_side and --min_area must not be negative')
+    if FLAGS.batch_size < 1:
+        ap.error('--batch_size must be positive')
+    if FLAGS.synthetic and FLAGS.gt_path is None:
+        ap.error('--synthetic needs --gt_path (there is no image directory to look beside)')
+    return FLAGS
+
+
+def main(argv=None):
+    FLAGS = parse(argv)
+    import torch
+    from tensorflow_ocr_amd import checkpoint, evaluate
+    from tensorflow_ocr_amd.graph import Graph
+    from tensorflow_ocr_amd.infer import GraphedForward
+    from tensorflow_ocr_amd.nets import pixellink
+    g = Graph('cuda:0', precision=FLAGS.precision)
+    H, W = FLAGS.eval_image_height, FLAGS.eval_image_width
+
+    def logits(gr, im):       # test_pixellink_fast.py's normalisation, (im - 120) / 60 in f32 ahead of the net, on the device
+        net = pixellink.PixelLinkNet((im - 120.0) / 60.0, graph=gr)
+        return net.pixel_cls, net.link_cls
+    tmp = None
+    if FLAGS.synthetic:       # random images, written where the evaluator reads images from
+        tmp = tempfile.TemporaryDirectory()
+        rng = np.random.default_rng(0)
+        for i in range(FLAGS.synthetic):
+            np.save(os.path.join(tmp.name, 'synthetic_%d.npy' % i), rng.integers(0, 256, (H, W, 3)).astype(np.uint8))
+        data = tmp.name
+    else:
+        data = FLAGS.test_data_path
+    forward = GraphedForward(g, logits)
+    if FLAGS.checkpoint_path:
+        forward(torch.zeros((1, H, W, 3), dtype=torch.float32, device=g.device))       # the variables exist after one forward
+        if FLAGS.checkpoint_path.endswith('.npz'):
+            sd = dict(np.load(FLAGS.checkpoint_path))
+        else:       # a TF checkpoint directory / prefix; EMA shadows restored like test.py:149-150
+            sd, _ = checkpoint.load_tf_checkpoint(FLAGS.checkpoint_path, use_moving_averages=True)
+        g.store.load_state_dict(checkpoint.tf_to_internal(g.store.order, sd), strict=False)
+    ev = evaluate.LinkEvaluator(g, forward, data, batch_size=FLAGS.batch_size, gt_path=FLAGS.gt_path,
+                                pixel_conf_threshold=FLAGS.pixel_conf_threshold,
+                                link_conf_threshold=FLAGS.link_conf_threshold, min_side=FLAGS.min_side,
+                                min_area=FLAGS.min_area, eval_image_height=H, eval_image_width=W)
+    try:
+        print(evaluate.format_line(ev.run()), flush=True)
+    finally:
+        if tmp is not None:
+            tmp.cleanup()
+
+
+if __name__ == '__main__':
+    main()

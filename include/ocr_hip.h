@@ -1112,6 +1112,40 @@ int ocr_eval_match_batch(const void* dets_i32, const void* nd_i32, const void* g
                          void* tp_u8, void* fp_u8, void* record_i64, void* workspace, size_t ws_bytes, void* stream);
 int ocr_eval_record_init(void* record_i64, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Link-geometry detections on the device (csrc/link_boxes.hip): what lies between ocr_min_area_rects and
+ * ocr_eval_collect, so that the PixelLink decode feeds the matcher without a host step.  Status (all entries):
+ * OCR_ERR_INVALID_ARG for a null pointer or a non-positive extent, OCR_ERR_UNSUPPORTED for n or max_comps beyond 65535 or
+ * a map side beyond 32768, OCR_ERR_WORKSPACE for ws_bytes below ocr_component_scores_workspace; nothing is written on
+ * error.
+ *
+ * ocr_component_scores: one detection score per component.  BUILD-DEFINED: the reference gives a link box no score
+ * (test_pixellink_fast.py writes corners only), the matcher needs one for its walk order.  labels int32 [n][h][w] (ids
+ * 1..ncomp[i], 0 = background, ocr_link_cc's output; an id outside 1..max_comps is ignored), pixel_score f32 [n][h][w],
+ * ncomp int32 [n] -> comp_score f32 [n][max_comps]: row c < min(ncomp[i], max_comps) is the mean pixel score of id c + 1,
+ * rows at or beyond that are written 0.  The mean is exact integer arithmetic, independent of scheduling: per pixel
+ * q = (uint32)rintf(clamp(s, 0, 1) * 2^24) with NaN -> 0, the q and the pixel count summed in 64 bits (integer atomics,
+ * one pair per run of equal labels inside a wave), mean = f32(f64(sum) / f64(count) / 16777216.0); an id without pixels
+ * scores 0.  Workspace: the sums, ocr_component_scores_workspace(n, max_comps) bytes (0 for a non-positive extent).
+ *
+ * ocr_link_boxes: cv2.minAreaRect's tail, cv2.boxPoints and np.int0 for every component, one thread each.  hull_n int32
+ * [n][max_comps], hull_head int32 [n][max_comps][4], calipers f32 [n][max_comps][6] as ocr_min_area_rects writes them;
+ * comp_score f32 [n][max_comps]; ncomp int32 [n].  RotatedRect: hull_n > 2: centre = corner + (e1 + e2) / 2, w = |e1|,
+ * h = |e2|, angle = atan2(e1.y, e1.x); hull_n = 2: the segment (h = 0); hull_n = 1: the point; else zeros.  f32 adds and
+ * multiplies (no contraction); sqrt, atan2, cos, sin and the radian / degree conversions in double, rounded to f32 where
+ * OpenCV rounds them.  Outputs in the layout ocr_eval_collect reads: merged f32 [n][max_comps][9] = the four corners of
+ * RotatedRect::points truncated toward zero (stored as f32), then comp_score; keep_idx int32 [n][max_comps] = the
+ * identity; n_keep int32 [n] = min(ncomp, max_comps); passed u8 [n][max_comps] = hull_n > 0 and min(w, h) >= min_side and
+ * w * h >= min_area (f32; both 0: nothing is filtered, the reference scripts' behaviour); total int32 [n] = ncomp, so the
+ * host sees an overflow of max_comps.  Rows at or beyond n_keep[i]: merged 0, passed 0.
+ * ------------------------------------------------------------------------- */
+size_t ocr_component_scores_workspace(int n, int max_comps);
+int ocr_component_scores(const void* labels_i32, const void* pixel_score_f32, const void* ncomp_i32, int n, int h, int w,
+                         int max_comps, void* comp_score_f32, void* workspace, size_t ws_bytes, void* stream);
+int ocr_link_boxes(const void* hull_n_i32, const void* hull_head_i32, const void* calipers_f32, const void* comp_score_f32,
+                   const void* ncomp_i32, int n, int max_comps, float min_side, float min_area, void* merged_f32,
+                   void* keep_idx_i32, void* n_keep_i32, void* passed_u8, void* total_i32, void* stream);
+
 /* Strided 3x3 convolutions of ResNet-v1 (nets/resnet_utils.py:85-122 conv2d_same with stride 2) as one
  * stride-1 2x2 convolution over a space-to-depth copy: xs[n][Y][X][(a*2+b)*c + ch] = x[n][2Y+a][2X+b][ch]
  * (h, w even; c a multiple of 8), weights w22 f32 [2][2][4c][k] from w33 f32 [3][3][c][k] (zero where a tap

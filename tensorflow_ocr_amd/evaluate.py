@@ -6,8 +6,15 @@
 with the counters of tool/metrics.py on the device (`metrics.DeviceTpFp`): the host reads them once per pass.  The
 matching rule is the reference's (tool/bboxes.py:171-240, rasterised IoU), NOT the official ICDAR-2015 polygon-IoU
 protocol; ground truths are matched in ORIGINAL image coordinates, detections are divided by the resize ratios as test.py
-divides them; `###` (or `*`) marks an ignored ground truth (icdar.load_annoataion).  RBOX geometry only: the link
-geometry's contour path ends on the host (pixellink_fn.find_contour_boxes)."""
+divides them; `###` (or `*`) marks an ignored ground truth (icdar.load_annoataion).
+
+`Evaluator` is the EAST RBOX geometry.  `LinkEvaluator` is the PixelLink (link) geometry of test_pixellink_fast.py, the same
+pass with another middle:
+
+    forward -> softmaxes -> pixellink_fn.detect_device (link_cc, min-area rectangles, component scores, boxes) -> ...
+
+(test.py's own link path, the contour decode of pixellink_fn.find_contour_boxes, still ends on the host and is not
+evaluated here)."""
 import os
 
 import numpy as np
@@ -99,11 +106,19 @@ class Evaluator:
         self.last = None          # the device tensors of the last chain (tests and the cost script look at them)
 
     # -- one chain -------------------------------------------------------------------------------
+    def _resized(self, h, w):
+        """the size an h x w image enters the network at"""
+        return resize_rule(h, w, self.max_side_len)
+
+    def _ratio(self, h, w, rh, rw):
+        """what ocr_eval_collect divides the detections by: (ratio_w, ratio_h) of test.py:127"""
+        return rw / float(w), rh / float(h)
+
     def _upload(self, batch):
         """batch: [(image uint8 [h,w,3], polys, ignored)] of one resized shape -> x, inv_ratio, gts, ng, gignored, mask_hw"""
         dev = self.g.device
         n = len(batch)
-        rh, rw = resize_rule(batch[0][0].shape[0], batch[0][0].shape[1], self.max_side_len)
+        rh, rw = self._resized(batch[0][0].shape[0], batch[0][0].shape[1])
         x = torch.empty((n, rh, rw, 3), dtype=torch.float32, device=dev)
         max_g = max([len(p) for _, p, _ in batch] + [1])
         gts = np.zeros((n, max_g, 4, 2), np.int32)
@@ -114,7 +129,7 @@ class Evaluator:
         for i, (im, polys, ignored) in enumerate(batch):
             h, w, _ = im.shape
             ops.resize_linear_u8(torch.from_numpy(np.ascontiguousarray(im, dtype=np.uint8)).to(dev), x[i])
-            ratio[i] = (rw / float(w), rh / float(h))                       # (ratio_w, ratio_h) of test.py:127
+            ratio[i] = self._ratio(h, w, rh, rw)
             k = len(polys)
             gts[i, :k], ng[i], gign[i, :k] = polys, k, ignored
             extent = max(extent, h, w, int(polys.max()) + 1 if k else 1)
@@ -125,12 +140,17 @@ class Evaluator:
         return x, up(ratio), up(gts), up(ng), up(gign), (side, side)
 
     def _chain(self, batch):
-        from .tool import bboxes, rbox
-        g = self.g
+        from .tool import rbox
         x, inv_ratio, gts, ng, gign, mask_hw = self._upload(batch)
         f_score, f_geometry = self.forward(x)
         merged, keep, n_keep, passed, total = rbox.detect_device(f_score, f_geometry, self.score_map_thresh, self.nms_thres,
-                                                                 self.max_k, graph=g, box_thresh=self.box_thresh)
+                                                                 self.max_k, graph=self.g, box_thresh=self.box_thresh)
+        return self._match(merged, keep, n_keep, passed, total, inv_ratio, gts, ng, gign, mask_hw)
+
+    def _match(self, merged, keep, n_keep, passed, total, inv_ratio, gts, ng, gign, mask_hw):
+        """detection rows -> ordered detection list -> matching, the counters added to the record"""
+        from .tool import bboxes
+        g = self.g
         n, max_k = merged.shape[:2]
         dets = torch.empty((n, self.max_d, 4, 2), dtype=torch.int32, device=g.device)
         det_score = torch.empty((n, self.max_d), dtype=torch.float32, device=g.device)
@@ -142,6 +162,9 @@ class Evaluator:
                                                  graph=g, mask_hw=mask_hw)
         self.last = dict(dets=dets, det_score=det_score, nd=nd, nd_total=nd_total, tp=tp, fp=fp, gts=gts, ng=ng)
         return total - max_k, nd_total - self.max_d          # > 0: overflow (device tensors, read at the end of the pass)
+
+    def _overflow(self, worst):
+        return 'an image selected %d pixels more than max_k: raise max_k or the score threshold' % worst
 
     # -- one pass --------------------------------------------------------------------------------
     def run(self):
@@ -163,16 +186,74 @@ class Evaluator:
                 flush(buckets.pop(key))
         for key in sorted(buckets):
             flush(buckets[key])
-        num_gt, tp, fp, n_det = self.acc.value()                            # the single read of the record
-        worst_k, worst_d = torch.stack([torch.cat(over_k).max(), torch.cat(over_d).max()]).cpu().tolist()
+        # the single read of the pass: the record and the two overflow maxima in one device-to-host copy
+        (num_gt, tp, fp, n_det), (worst_k, worst_d) = self.acc.value_with(
+            torch.stack([torch.cat(over_k).max(), torch.cat(over_d).max()]))
         if worst_k > 0:
-            raise ValueError('an image selected %d pixels more than max_k: raise max_k or the score threshold' % worst_k)
+            raise ValueError(self._overflow(worst_k))
         if worst_d > 0:
             raise ValueError('an image kept %d detections more than max_d = %d' % (worst_d, self.max_d))
         precision, recall = metrics.precision_recall(num_gt, tp, fp)
         hmean = metrics.fmean(precision, recall) if precision + recall > 0 else 0.0
         return {'precision': precision, 'recall': recall, 'hmean': hmean, 'num_gt': num_gt, 'tp': tp, 'fp': fp,
                 'num_det': n_det, 'images': len(self.samples)}
+
+
+class LinkEvaluator(Evaluator):
+    """The link geometry: `forward(x)` returns the (pixel_cls [n,H/4,W/4,2], link_cls [n,H/4,W/4,16]) LOGITS of
+    `PixelLinkNet` (tensors or head handles) as a pure launch sequence.  Every image is resized on the device to the
+    fixed eval_image_height x eval_image_width (test_pixellink_fast.py's flags) and batched by its ORIGINAL shape, because
+    ocr_min_area_rects takes one scale per call: a component pixel (x, y) of the 1/4-resolution maps becomes the point
+    (int(x * scale_x), int(y * scale_y)) with scale_x = orig_w / (eval_w / 4), scale_y = orig_h / (eval_h / 4), so the
+    boxes land in original-image pixels and ocr_eval_collect runs with ratios (1, 1).  An original side below a quarter
+    of the eval side (a scale below 1) is refused.  A detection's score is its component's mean pixel score
+    (ocr_component_scores; build-defined).  min_side / min_area filter the boxes (0: nothing, as the reference scripts).
+    `run()` reads the device once at its end: the record, and the two overflow counts (components over max_comps,
+    detections over max_d), either of which raises ValueError."""
+
+    def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, pixel_conf_threshold=0.8,
+                 link_conf_threshold=0.9, min_size=10, max_comps=4096, min_side=0.0, min_area=0.0, max_d=ops.EVAL_MAX_D,
+                 eval_image_height=768, eval_image_width=1280, gt_path=None):
+        super().__init__(graph, forward, data, batch_size=batch_size, max_images=max_images,
+                         matching_threshold=matching_threshold, max_d=max_d, gt_path=gt_path)
+        self.eval_hw = (int(eval_image_height), int(eval_image_width))
+        if min(self.eval_hw) < 4 or self.eval_hw[0] % 4 or self.eval_hw[1] % 4:
+            raise ValueError('the eval size must be positive multiples of 4, got %dx%d' % self.eval_hw)
+        if int(max_comps) < 1:
+            raise ValueError('max_comps must be positive')
+        self.pixel_conf_threshold, self.link_conf_threshold = float(pixel_conf_threshold), float(link_conf_threshold)
+        self.min_size, self.max_comps = int(min_size), int(max_comps)
+        self.min_side, self.min_area = float(min_side), float(min_area)
+
+    def _resized(self, h, w):
+        return self.eval_hw
+
+    def _ratio(self, h, w, rh, rw):
+        return 1.0, 1.0
+
+    def scales(self, h, w):
+        """(scale_x, scale_y) of an h x w original: 1/4-resolution map cell -> original-image pixels"""
+        sx, sy = w / float(self.eval_hw[1] // 4), h / float(self.eval_hw[0] // 4)
+        if sx < 1.0 or sy < 1.0:
+            raise ValueError('a %dx%d image is smaller than the %dx%d score maps: lower the eval size'
+                             % (h, w, self.eval_hw[0] // 4, self.eval_hw[1] // 4))
+        return sx, sy
+
+    def _chain(self, batch):
+        from .tool import pixellink_fn
+        g = self.g
+        scale_x, scale_y = self.scales(*batch[0][0].shape[:2])
+        x, inv_ratio, gts, ng, gign, mask_hw = self._upload(batch)
+        pixel_cls, link_cls = self.forward(x)
+        pixel_score = pixellink_fn.pixel_scores(pixel_cls, graph=g)[..., 1].contiguous()
+        link_score = pixellink_fn.link_scores(link_cls, graph=g)
+        merged, keep, n_keep, passed, total = pixellink_fn.detect_device(
+            pixel_score, link_score, self.pixel_conf_threshold, self.link_conf_threshold, self.min_size, scale_x, scale_y,
+            max_comps=self.max_comps, min_side=self.min_side, min_area=self.min_area, graph=g)
+        return self._match(merged, keep, n_keep, passed, total, inv_ratio, gts, ng, gign, mask_hw)
+
+    def _overflow(self, worst):
+        return 'an image holds %d components more than max_comps = %d' % (worst, self.max_comps)
 
 
 class EmaWeights:
@@ -204,17 +285,19 @@ class TrainEval:
     one `Evaluator` pass BETWEEN steps — nothing of it is part of the recorded step plan, whose call list is the same with
     and without it.  The network runs in inference mode on the training graph (batch norm on the moving statistics, eager
     launches) with the EMA shadows (`weights='ema'`, what test.py restores) or the raw weights; the raw weights are back
-    bit for bit before the next step.  `network(graph, images)` -> (score, geometry); `opt` is read when a pass runs
-    (the optimiser exists only after the step was built).  `last` holds the latest result."""
+    bit for bit before the next step.  `network(graph, images)` -> (score, geometry), or with `evaluator=LinkEvaluator`
+    (train_pixellink.py) -> (pixel_cls, link_cls); `opt` is read when a pass runs (the optimiser exists only after the
+    step was built).  `last` holds the latest result."""
 
-    def __init__(self, graph, step, network, data, every, max_images=None, weights='ema', batch_size=8, **evaluator_kw):
+    def __init__(self, graph, step, network, data, every, max_images=None, weights='ema', batch_size=8, evaluator=Evaluator,
+                 **evaluator_kw):
         if weights not in ('ema', 'raw'):
             raise ValueError("weights must be 'ema' or 'raw'")
         if int(every) < 1:
             raise ValueError('every must be positive')
         self.g, self.step, self.network = graph, step, network
         self.every, self.weights = int(every), weights
-        self.evaluator = Evaluator(graph, self._forward, data, batch_size=batch_size, max_images=max_images, **evaluator_kw)
+        self.evaluator = evaluator(graph, self._forward, data, batch_size=batch_size, max_images=max_images, **evaluator_kw)
         self.last = None
         self.passes = 0
 

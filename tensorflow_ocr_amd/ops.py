@@ -1297,6 +1297,49 @@ def eval_record_init(record):
     L.call("ocr_eval_record_init", ptr(record), _st())
 
 
+# ------------------------------------------------------------------ link-geometry detections (csrc/link_boxes.hip)
+def component_scores(labels, pixel_score, ncomp, comp_score, ws):
+    """labels int32 [n,h,w] (ocr_link_cc), pixel_score f32 [n,h,w], ncomp int32 [n] -> comp_score f32 [n,max_comps]: the
+    mean pixel score of every component, summed as exact integers (include/ocr_hip.h: ocr_component_scores)."""
+    n, h, w = labels.shape
+    max_comps = comp_score.shape[1]
+    if tuple(pixel_score.shape) != (n, h, w) or ncomp.numel() != n or tuple(comp_score.shape) != (n, max_comps):
+        raise ValueError("component_scores: tensors do not match n, h, w, max_comps")
+    if labels.dtype != torch.int32 or pixel_score.dtype != torch.float32 or ncomp.dtype != torch.int32 or \
+            comp_score.dtype != torch.float32:
+        raise ValueError("component_scores: labels / ncomp int32, pixel_score / comp_score f32")
+    for t in (labels, pixel_score, ncomp, comp_score):
+        if not t.is_contiguous():
+            raise ValueError("component_scores: contiguous tensors only")
+    nbytes = L.call_size("ocr_component_scores_workspace", c_int(n), c_int(max_comps))
+    buf = ws.get(nbytes)
+    L.call("ocr_component_scores", ptr(labels), ptr(pixel_score), ptr(ncomp), c_int(n), c_int(h), c_int(w), c_int(max_comps),
+           ptr(comp_score), ptr(buf), c_size_t(nbytes), _st())
+
+
+def link_boxes(hull_n, hull_head, calipers, comp_score, ncomp, min_side, min_area, merged, keep_idx, n_keep, passed, total):
+    """ocr_min_area_rects' outputs + comp_score f32 [n,max_comps] + ncomp int32 [n] -> the rows ocr_eval_collect reads:
+    merged f32 [n,max_comps,9] (truncated corners, score), keep_idx int32 [n,max_comps] (identity), n_keep int32 [n],
+    passed uint8 [n,max_comps], total int32 [n] (include/ocr_hip.h: ocr_link_boxes)."""
+    n, max_comps = hull_n.shape
+    if tuple(hull_head.shape) != (n, max_comps, 4) or tuple(calipers.shape) != (n, max_comps, 6) or \
+            tuple(comp_score.shape) != (n, max_comps) or ncomp.numel() != n or tuple(merged.shape) != (n, max_comps, 9) or \
+            tuple(keep_idx.shape) != (n, max_comps) or n_keep.numel() != n or tuple(passed.shape) != (n, max_comps) or \
+            total.numel() != n:
+        raise ValueError("link_boxes: tensors do not match n, max_comps")
+    if hull_n.dtype != torch.int32 or hull_head.dtype != torch.int32 or calipers.dtype != torch.float32 or \
+            comp_score.dtype != torch.float32 or ncomp.dtype != torch.int32 or merged.dtype != torch.float32 or \
+            keep_idx.dtype != torch.int32 or n_keep.dtype != torch.int32 or passed.dtype != torch.uint8 or \
+            total.dtype != torch.int32:
+        raise ValueError("link_boxes: calipers / comp_score / merged f32, passed uint8, everything else int32")
+    for t in (hull_n, hull_head, calipers, comp_score, ncomp, merged, keep_idx, n_keep, passed, total):
+        if not t.is_contiguous():
+            raise ValueError("link_boxes: contiguous tensors only")
+    L.call("ocr_link_boxes", ptr(hull_n), ptr(hull_head), ptr(calipers), ptr(comp_score), ptr(ncomp), c_int(n),
+           c_int(max_comps), c_float(min_side), c_float(min_area), ptr(merged), ptr(keep_idx), ptr(n_keep), ptr(passed),
+           ptr(total), _st())
+
+
 # -------------------------------------------------------------------------- optimiser
 def adam_step(w, g, m, v, ema, n_reg, lr_t, beta1, beta2, eps, wd, inv_scale, ema_decay):
     L.call("ocr_adam_step", ptr(w), ptr(g), ptr(m), ptr(v), ptr(ema), c_int64(w.numel()),

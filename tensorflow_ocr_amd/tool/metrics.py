@@ -34,7 +34,7 @@ class DeviceTpFp:
     ignored, tp, fp, detections} that `bboxes.bboxes_matching_batch(..., record=acc.record)` adds to, batch after batch,
     without a synchronisation.  `value()` is the single host read of a pass: (num_gbboxes, tp, fp, n_det) as Python
     ints — `precision_recall(num_gbboxes, tp, fp)` and `fmean` apply to them unchanged (they only sum tp and fp).
-    `reads` counts the calls of `value()`."""
+    `reads` counts the calls of `value()` / `value_with()`."""
 
     def __init__(self, graph=None):
         import torch
@@ -53,6 +53,14 @@ class DeviceTpFp:
         self.reads += 1
         num_gt, tp, fp, n_det = (int(v) for v in self.record.cpu().tolist())
         return num_gt, tp, fp, n_det
+
+    def value_with(self, extra):
+        """`value()` and the integers of the device tensor `extra` in ONE device-to-host copy: ((num_gbboxes, tp, fp,
+        n_det), [extra values]).  Counts as one read."""
+        import torch
+        self.reads += 1
+        host = [int(v) for v in torch.cat([self.record, extra.reshape(-1).to(torch.int64)]).cpu().tolist()]
+        return tuple(host[:4]), host[4:]
 
 
 def precision_recall(num_gbboxes, tp, fp, scope=None):

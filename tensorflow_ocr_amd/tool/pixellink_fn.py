@@ -207,6 +207,52 @@ def min_area_rect_boxes(labels, ncomp, scale_x=4.0, scale_y=4.0, max_comps=4096,
     return out
 
 
+def link_boxes_device(labels, ncomp, pixel_score, scale_x, scale_y, max_comps=4096, min_side=0.0, min_area=0.0, graph=None):
+    """`min_area_rect_boxes` without its host half, plus a score per box: hull + calipers (ocr_min_area_rects), the mean
+    pixel score of every component (ocr_component_scores; build-defined, the reference gives a link box none) and
+    RotatedRect + boxPoints + np.int0 (ocr_link_boxes) as a pure launch sequence — nothing is read from the device.
+    labels int32 [N,h,w], ncomp int32 [N] (link_cc_decode's outputs), pixel_score f32 [N,h,w].  Returns device tensors in
+    the layout `ops.eval_collect` reads: (merged f32 [N,max_comps,9] = truncated corners + score, keep int32
+    [N,max_comps] = the identity, n_keep int32 [N] = min(ncomp, max_comps), passed uint8 [N,max_comps] = the box has
+    pixels, min(w, h) >= min_side and w * h >= min_area, total int32 [N] = ncomp: total > max_comps means components
+    were dropped, which the caller must turn into an error once it reads it)."""
+    g = graph or get_default_graph()
+    if labels.dim() != 3:
+        raise ValueError("labels must be [N,h,w]")
+    n = labels.shape[0]
+    dev = g.device
+    labels = labels.to(device=dev, dtype=torch.int32).contiguous()
+    ncomp = ncomp.to(device=dev, dtype=torch.int32).contiguous()
+    ps = _dev(g, pixel_score)
+    if tuple(ps.shape) != tuple(labels.shape):
+        raise ValueError("pixel_score must have the shape of labels")
+    hull_n = torch.zeros((n, max_comps), dtype=torch.int32, device=dev)
+    head = torch.zeros((n, max_comps, 4), dtype=torch.int32, device=dev)
+    cal = torch.zeros((n, max_comps, 6), dtype=F32, device=dev)
+    ops.min_area_rects(labels, ncomp, max_comps, float(scale_x), float(scale_y), hull_n, head, cal, g.workspace())
+    comp_score = torch.empty((n, max_comps), dtype=F32, device=dev)
+    ops.component_scores(labels, ps, ncomp, comp_score, g.workspace())
+    merged = torch.empty((n, max_comps, 9), dtype=F32, device=dev)
+    keep = torch.empty((n, max_comps), dtype=torch.int32, device=dev)
+    n_keep = torch.empty((n,), dtype=torch.int32, device=dev)
+    passed = torch.empty((n, max_comps), dtype=torch.uint8, device=dev)
+    total = torch.empty((n,), dtype=torch.int32, device=dev)
+    ops.link_boxes(hull_n, head, cal, comp_score, ncomp, float(min_side), float(min_area), merged, keep, n_keep, passed, total)
+    return merged, keep, n_keep, passed, total
+
+
+def detect_device(pixel_score, link_score, pixel_conf_threshold=0.8, link_conf_threshold=0.9, min_size=10, scale_x=4.0,
+                  scale_y=4.0, max_comps=4096, min_side=0.0, min_area=0.0, graph=None):
+    """The link geometry's detections of a batch on the device, NO synchronisation: link_cc_decode (union mode) ->
+    link_boxes_device.  pixel_score [N,h,w] = softmax(pixel_cls)[...,1]; link_score [8,N,h,w,2] or [8,N,h,w]; a box
+    corner is in (x * scale_x, y * scale_y) pixels.  Returns link_boxes_device's five device tensors."""
+    g = graph or get_default_graph()
+    ps = _dev(g, pixel_score)
+    labels, ncomp, _ = link_cc_decode(ps, link_score, pixel_conf_threshold, link_conf_threshold, min_size=min_size,
+                                      max_comps=max_comps, graph=g)
+    return link_boxes_device(labels, ncomp, ps, scale_x, scale_y, max_comps, min_side, min_area, graph=g)
+
+
 def generate_rbox(h, w, xs, ys, bboxes, ignored, graph=None):
     """tool/pixellink_fn.py:53-110 for one image.  xs, ys normalised corner coordinates [k,4], bboxes
     [k,4], ignored [k] -> (res_score_map float32 [h/4,w/4], res_link_map float32 [h/4,w/4,8],

@@ -16,7 +16,11 @@ Data: the reference reads TFRecords through `datasets.dataset_factory` / `ssd_vg
 neither of which is in its tree (not runnable as shipped).  Here --dataset_dir is an
 ICDAR directory (images + gt_*.txt); every image is resized to the train size on the GPU and its
 quads go, normalised, through `pixellink_fn.generate_rbox` (tool/pixellink_fn.py:53-110) — the label
-generator this script's `tf_pixellink_get_rbox` wraps.  Without --dataset_dir: synthetic batches."""
+generator this script's `tf_pixellink_get_rbox` wraps.  Without --dataset_dir: synthetic batches.
+
+Not in the reference: `--eval_data_path DIR --eval_steps N` evaluates a held-out directory (images + gt_*.txt) between steps
+every N optimiser steps, on the device and outside the recorded step (tensorflow_ocr_amd/evaluate.py: LinkEvaluator), and
+reports precision / recall / hmean."""
 import argparse
 import os
 import time
@@ -69,7 +73,25 @@ def parse(argv=None):
     ap.add_argument('--pixel_loss', choices=('mean', 'instance_balanced'), default='mean')
     # config.max_neg_pos_ratio (nets/pixellink.py:116); read by --pixel_loss instance_balanced only
     ap.add_argument('--max_neg_pos_ratio', type=_neg_ratio_arg, default=3.0)
-    return ap.parse_args(argv)
+    # not reference flags: held-out evaluation between steps (tensorflow_ocr_amd.evaluate.TrainEval on a LinkEvaluator).
+    # Every --eval_steps optimiser steps (0 = off) rank 0 runs the images of --eval_data_path (images + gt_*.txt, at most
+    # --eval_max_images of them), resized to --eval_image_height x --eval_image_width, through forward -> link components ->
+    # boxes -> matching on the device and reports precision / recall / hmean; --eval_weights: ema = the moving averages
+    # (needs --using_moving_average), raw = the weights being trained
+    ap.add_argument('--eval_data_path', type=str, default=None, metavar='DIR')
+    ap.add_argument('--eval_steps', type=int, default=0, metavar='N')
+    ap.add_argument('--eval_max_images', type=int, default=None, metavar='M')
+    ap.add_argument('--eval_weights', choices=['ema', 'raw'], default='ema')
+    ap.add_argument('--eval_image_width', type=int, default=1280)
+    ap.add_argument('--eval_image_height', type=int, default=768)
+    FLAGS = ap.parse_args(argv)
+    if FLAGS.eval_steps < 0 or (FLAGS.eval_max_images is not None and FLAGS.eval_max_images < 1):
+        ap.error('--eval_steps must not be negative and --eval_max_images must be positive')
+    if FLAGS.eval_steps > 0 and not FLAGS.eval_data_path:
+        ap.error('--eval_steps needs --eval_data_path')
+    if FLAGS.eval_weights == 'ema' and FLAGS.eval_steps > 0 and not FLAGS.using_moving_average:
+        ap.error('--eval_weights ema needs --using_moving_average')
+    return FLAGS
 
 
 def _neg_ratio_arg(text):
@@ -182,6 +204,34 @@ def _window(step, K, next_batch):
     return loss if K == 1 else total / K
 
 
+def make_train_eval(FLAGS, g, step):
+    """The between-steps evaluation of --eval_data_path / --eval_steps (None when off): PixelLinkNet on the training graph
+    (it has no batch norm: the inference forward is the training forward without a loss) with the weights --eval_weights
+    names, its logits decoded by evaluate.LinkEvaluator."""
+    if not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
+        return None
+    from tensorflow_ocr_amd import evaluate
+    from tensorflow_ocr_amd.nets import pixellink
+
+    def network(gr, im):
+        net = pixellink.PixelLinkNet(im, graph=gr, input_norm=INPUT_NORM)
+        return net.pixel_cls, net.link_cls
+    return evaluate.TrainEval(g, step, network, FLAGS.eval_data_path, FLAGS.eval_steps, max_images=FLAGS.eval_max_images,
+                              weights=FLAGS.eval_weights, batch_size=max(1, int(FLAGS.batch_size / FLAGS.num_gpus)),
+                              evaluator=evaluate.LinkEvaluator, eval_image_height=FLAGS.eval_image_height,
+                              eval_image_width=FLAGS.eval_image_width)
+
+
+def _evaluate(train_eval, summaries, opt):
+    """One pass between two steps (rank 0; the other ranks meet it at the next exchange): the line eval_pixellink_fast.py
+    prints, and eval/precision, eval/recall, eval/hmean in the event file where one is open."""
+    from tensorflow_ocr_amd import evaluate
+    res = train_eval.run()
+    print('global step %d: ' % opt.global_step + evaluate.format_line(res), flush=True)
+    if summaries is not None:
+        train_eval.write(summaries.writer, opt.global_step)
+
+
 def main():
     FLAGS = parse()
     from tensorflow_ocr_amd import launch
@@ -243,6 +293,7 @@ def main():
                 last[0].append(synthetic_weights(ids, device))
         return last[0]
     summaries = None
+    train_eval = make_train_eval(FLAGS, g, step) if rank == 0 else None
     for it in range(FLAGS.max_number_of_steps):
         loss = _window(step, FLAGS.accumulate_steps, next_batch)
         if rank == 0 and FLAGS.save_summary_steps > 0 and it % FLAGS.save_summary_steps == 0:
@@ -255,6 +306,8 @@ def main():
             if step.opt.clip is not None:
                 scalars['grad_norm'] = step.opt.grad_norm()
             summaries.write(step.opt.global_step, scalars, [('input', last[0][0][0])])
+        if train_eval is not None and train_eval.due(it + 1):
+            _evaluate(train_eval, summaries, step.opt)
         if it % FLAGS.log_every_n_steps == 0:
             v = loss.item()
             dt = (time.time() - start) / FLAGS.log_every_n_steps
