@@ -7,6 +7,7 @@ device memory only.
 """
 import contextlib
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -149,6 +150,70 @@ class VariableStore:
         self.version += 1
 
 
+class BnCtx(NamedTuple):
+    """Act.bn_ctx / Act.bias_ctx: what a consumer's input-gradient epilogue needs to sum the producer's BN-backward terms."""
+    y: object
+    scale: object
+    shift: object
+    mean: object
+    invstd: object
+    relu: bool
+
+    @classmethod
+    def of_bias(cls, g, y, cout):
+        """A bias + ReLU producer in the same form: `y` is the activation, scale 1, shift 0, mean 0, 1/std 1."""
+        one, zero = g.const_vec(cout, 1.0), g.const_vec(cout, 0.0)
+        return cls(y, one, zero, zero, one, True)
+
+    def first(self):
+        """conv1_1 whose `y` is an ops.LazyFirstY: (x4, w_first, scale, shift, mean, invstd, relu), the order in which
+        ocr_conv2d_bnred_first_f16 takes them (y is evaluated again from the image, not read)."""
+        return (self.y.x4, self.y.w_first) + self[1:]
+
+
+class TailCtx(NamedTuple):
+    """Act.tail_ctx: the unit's last conv (y, mean, invstd), the unit's output and its ReLU-mask bits (None: read `out`)."""
+    y: object
+    mean: object
+    invstd: object
+    out: object
+    bits: object = None
+
+
+class TailFwd(NamedTuple):
+    """Act.tail_fwd: the deferred relu(bn(y) + bn?(shortcut)) of a bottleneck output."""
+    y: object
+    scale: object
+    shift: object
+    shortcut: object
+    sc_scale: object
+    sc_shift: object
+    bits: object
+
+
+class BnFwd(NamedTuple):
+    """Act.bn_fwd: a deferred relu?(bn(y))."""
+    y: object
+    scale: object
+    shift: object
+    relu: bool
+
+
+class PoolGrad(NamedTuple):
+    """Act.pool_grad: a max-pool's backward left to the producer; pad = (top, left)."""
+    grad: object
+    argmax: object
+    k: int
+    stride: int
+    pad: tuple
+
+
+class Partial(NamedTuple):
+    """Act.bn_partial / bias_partial / tail_partial: [T, 2, channels] f32 rows of a fused input-gradient epilogue."""
+    rows: object
+    T: int
+
+
 class Act:
     """Activation handle: device tensor + (lazily created) gradient.
 
@@ -157,38 +222,66 @@ class Act:
     (resnet_layers.conv_bn_raw, ocr_conv2d_pw_bnaddrelu_f16).  Any other access to `.data` runs the plain
     element-wise pass first, so consumers that know nothing about this stay correct."""
 
-    __slots__ = ("_data", "grad", "requires_grad", "name", "bn_ctx", "bn_partial", "tail_ctx", "tail_partial",
-                 "pending", "sub_grad", "deferred", "tail_fwd", "pending_owner", "consumed", "bn_fwd", "bias_ctx",
-                 "bias_partial", "sole_consumer", "bias_done", "pool_grad", "takes_pool_grad", "first_s1")
+    __slots__ = ("_data", "grad", "requires_grad", "name", "deferred", "consumed", "sole_consumer",
+                 # the handshake between the layer that produced this activation and the layers that read it (below)
+                 "bn_fwd", "tail_fwd", "bn_ctx", "bias_ctx", "tail_ctx", "takes_pool_grad", "pending", "pending_owner",
+                 "bn_partial", "bias_partial", "tail_partial", "first_s1", "sub_grad", "pool_grad", "bias_done")
 
     def __init__(self, data, requires_grad=True, name=""):
         self._data = data
         self.grad = None
         self.requires_grad = requires_grad
         self.name = name
-        self.bn_ctx = None        # (y, scale, shift, mean, invstd, relu) of the conv+BN that made it
-        self.bn_partial = None    # (partial, T): BN-backward sums already reduced by the dgrad conv
-        # ResNet bottleneck outputs (resnet_layers.bottleneck): (y, mean, invstd of the unit's last conv, own data, mask
-        # bits); the next unit's LAST gradient contribution (counted down in `pending`, by the consumers that carry
-        # `pending_owner`) then stores the gradient past this output's ReLU and leaves the BN-backward sums in
-        # tail_partial = (partial, T)
-        self.tail_ctx = None
-        self.tail_partial = None
+        self.deferred = None      # callable that fills _data (the plain pass), while nobody has computed it yet
+        self.consumed = False     # a convolution has read it already (tail fusion must then stay off: build order)
+        self.sole_consumer = False  # set by the NET for activations read by exactly one convolution (nets/vgg.py)
+        # --- The fusion handshake.  Three groups of slots, all None / False until somebody speaks:
+        # OFFERS, set once by the PRODUCER when it is built and never cleared.  Forward: a deferred activation that a
+        # fusing reader (a 1x1 convolution, a max-pool) evaluates itself.  Backward: what the reader's input-gradient
+        # launch needs to do part of the producer's backward in its epilogue (layers.select_input_grad picks the route).
+        self.bn_fwd = None        # BnFwd: relu?(bn(y))                                  (conv_bn_act(defer), root_block)
+        self.tail_fwd = None      # TailFwd: relu(bn(y3) + shortcut)                     (bottleneck)
+        self.bn_ctx = None        # BnCtx of the conv + BN that made it                  (conv2d, conv_bn_act)
+        self.bias_ctx = None      # BnCtx.of_bias of the conv + bias + ReLU that made it (conv2d); honoured for a sole_consumer
+        self.tail_ctx = None      # TailCtx of the bottleneck that made it
+        self.takes_pool_grad = False   # the producer's backward can gather its gradient from a max-pool's operands
+        # COUNTDOWN, set by the bottleneck that READS a bottleneck output twice (conv1 + shortcut): its `pending`
+        # contributions are counted down by count_contribution (only those made for `pending_owner`) and by the
+        # shortcut's backward; the one that reaches 0 is the LAST contribution and takes the tail route.  The producer's
+        # backward sets `pending` back to None.
         self.pending = None
         self.pending_owner = None
-        self.consumed = False     # a convolution has read it already (tail fusion must then stay off: build order)
-        self.sub_grad = None      # gradient of this output's stride-2 subsample, waiting for the fused tail conv
-        self.deferred = None      # callable that fills _data (the plain pass), while nobody has computed it yet
-        self.bias_ctx = None      # bias + ReLU producers: bn_ctx-shaped tuple (activation, 1, 0, 0, 1, relu) for the consumer's epilogue
-        self.bias_partial = None  # (partial, T): the consumer stored dz and left the bias-gradient partial sums
+        # ANSWERS, left by a READER's backward and cleared by the PRODUCER's backward when it has used them:
+        self.bn_partial = None    # Partial: the BN-backward sums over the gradient the reader stored ...
+        self.bias_partial = None  # Partial: ... or the bias-gradient sums; `grad` is then dz, past the ReLU
+        self.tail_partial = None  # Partial: `grad` is complete and past the output's ReLU, conv3's BN-backward sums
+        self.first_s1 = None      # conv1_1's activation: the sums its weight gradient is finished from, left INSTEAD of
+                                  # the gradient (`grad` stays None) together with bn_partial
+        self.sub_grad = None      # gradient of this output's stride-2 subsample, waiting for the tail launch to add it
+        self.pool_grad = None     # PoolGrad: the pool wrote nothing, the producer gathers (takes_pool_grad)
         self.bias_done = False    # the layer's own pool already produced dz and the bias gradient (layers.max_pool2d)
-        self.sole_consumer = False  # set by the NET for activations read by exactly one convolution (nets/vgg.py)
-        self.takes_pool_grad = False   # the producer's backward can gather its gradient from a max-pool's operands ...
-        self.pool_grad = None     # ... which that pool's backward then leaves here: (pooled grad, argmax, k, stride, (pt, pl))
-        self.first_s1 = None      # conv1_1's activation: the sums its weight gradient is finished from, left by the sole consumer's
-                                  # input-gradient launch INSTEAD of the gradient (layers._conv_dgrad; `grad` then stays None)
-        self.bn_fwd = None        # (y, scale, shift, relu): a deferred relu(bn(y)) a fusing consumer (max-pool) can evaluate itself
-        self.tail_fwd = None      # (y3, scale, shift, shortcut tensor, sc_scale, sc_shift, bits): what a fusing consumer needs
+        # bn_partial and bias_partial describe the FIRST contribution only: a contribution that accumulates into `grad`
+        # drops them (open_grad), and the producer then reduces (masks: idempotent) the whole sum itself.  tail_partial
+        # and first_s1 need no such rule: the countdown / the net's sole_consumer say that nothing follows them.
+
+    def open_grad(self, g):
+        """-> (grad, accumulating): the buffer the next gradient contribution goes into — allocated here by the first
+        one; a later one adds to it, and what the first one's fused epilogue left no longer covers the whole gradient."""
+        accumulating = self.grad is not None
+        if accumulating:
+            self.bn_partial = self.bias_partial = None
+        else:
+            self.grad = g.empty(self.shape)
+        return self.grad, accumulating
+
+    def count_contribution(self, owner):
+        """-> whether this is the LAST gradient contribution to a bottleneck output.  Only the owning unit's two are
+        counted (any other consumer was built later, runs earlier in the backward pass and has added its share)."""
+        if self.pending is None or owner is None or owner is not self.pending_owner:
+            return False
+        self.pending -= 1
+        assert self.pending >= 0, "more gradient contributions than the owning unit has consumers"
+        return self.pending == 0
 
     @property
     def data(self):
@@ -390,6 +483,7 @@ class Graph:
         self.ws_split = None
         self.collections = {"losses": [], "update_ops": []}
         self.keepalive = None        # list while a step is being recorded (train.TrainStep)
+        self._const_vecs = {}
 
     # --- scopes / variables (tf.variable_scope, tf.get_variable) ---
     @contextlib.contextmanager
@@ -439,6 +533,13 @@ class Graph:
         t = torch.zeros(shape, dtype=dtype, device=self.device)
         if self.keepalive is not None:
             self.keepalive.append(t)
+        return t
+
+    def const_vec(self, n, value):
+        """A cached constant f32 vector (filled once, outside any recorded step)."""
+        t = self._const_vecs.get((n, value))
+        if t is None:
+            t = self._const_vecs[(n, value)] = torch.full((n,), float(value), dtype=F32, device=self.device)
         return t
 
     def ensure_materialised(self):

@@ -12,7 +12,7 @@ import torch
 
 from . import layers_f32, ops
 from .graph import F32, constant, variance_scaling, xavier_uniform
-from .layers import BN_DECAY, BN_EPS, _bn_buffers, _bn_params, _bn_vars, _grad_buffer, _switch
+from .layers import BN_DECAY, BN_EPS, _bn_buffers, _bn_params, _bn_vars, _switch
 
 BATCH_HEADS = _switch("OCR_BATCH_HEADS")    # one launch per kernel kind over the head sources
 MERGE_HEADS = _switch("OCR_RESNET_MERGE_HEADS")   # F_score + geo_map: one pass over the feature
@@ -173,7 +173,7 @@ def _head_conv(g, feat, names, couts, mode, is_training=True, relu=True, initial
             ops.sc_colsum(dz, C, bias.grad, ws)
         ops.conv1x1_small_wgrad(feat.data, dz, C, wv.grad, ws)
         if feat.requires_grad:
-            ops.conv1x1_small_dgrad(dz, w_ck32, C, *_grad_buffer(g, feat))
+            ops.conv1x1_small_dgrad(dz, w_ck32, C, *feat.open_grad(g))
         out.grad = None
     g.record(backward, (wv, gamma, beta) if mode == "bn" else (wv, bias))
     return out, scale, shift
@@ -241,7 +241,7 @@ def head_group(g, feats, names_list, couts, *, mode="bn", is_training=True, relu
         for s in live:
             if not is_wide(s):
                 ops.conv1x1_small_wgrad(s.feat.data, s.dz, C, s.wv.grad, ws)
-        items = [(s.dz, s.w_ck32) + _grad_buffer(g, s.feat) for s in live if s.feat.requires_grad]
+        items = [(s.dz, s.w_ck32) + s.feat.open_grad(g) for s in live if s.feat.requires_grad]
         if items:
             ops.conv1x1_small_dgrad_batch(items)
         for s in live:

@@ -6,12 +6,14 @@ graph's tape.  Variable names follow tf.contrib.slim so checkpoints/state-dicts 
 the reference: `<scope>/weights`, `<scope>/biases`,
 `<scope>/BatchNorm/{gamma,beta,moving_mean,moving_variance}`.
 """
+import functools
 import os
+from typing import NamedTuple
 
 import torch
 
 from . import ops
-from .graph import Act, F16, F32, constant, variance_scaling
+from .graph import Act, BnCtx, F16, F32, Partial, PoolGrad, constant, variance_scaling
 from ._lib import CONV_ACCUM_F16, CONV_BIAS, CONV_RELU, CONV_STATS
 
 BN_DECAY = 0.997
@@ -108,15 +110,6 @@ def _packs(g, w, first):
     return g.packed(w, "kc_ck", mk)
 
 
-def _const_vec(g, n, value):
-    """A cached per-graph constant f32 vector (filled once, outside any recorded step)."""
-    cache = g.__dict__.setdefault("_const_vecs", {})
-    t = cache.get((n, value))
-    if t is None:
-        t = cache[(n, value)] = torch.full((n,), float(value), dtype=F32, device=g.device)
-    return t
-
-
 def conv2d(g, x, cout, k, scope, *, stride=1, rate=1, normalizer="bn", relu=True, pool=0,
            keep_full=True, is_training=True, bn_training=None, first=False, weight_decay=True,
            initializer=None):
@@ -176,7 +169,7 @@ def _conv2d_bn(g, x, scope, wv, bn_vars, packs, d, mt, y, shape, relu, pool, kee
     ws = g.workspace()
     drop_y = isinstance(y, ops.LazyFirstY)
     flags = CONV_STATS if train_stats else 0
-    part, stage = g.ws_small.two(mt * 2 * cout * 4, ops.bn_reduce_workspace(mt, cout))
+    part, stage = _stats_rows(g, mt, cout)
     mt_fin = mt
     if first and drop_y and train_stats and FIRST_MOMENTS:
         # the statistics from the image's second moments (csrc/conv_first.hip: first_moments_kernel): no pass over the
@@ -227,12 +220,12 @@ def _conv2d_bn(g, x, scope, wv, bn_vars, packs, d, mt, y, shape, relu, pool, kee
     a_pool = Act(pooled, name=scope + "/pool") if pooled is not None else None
     if not pool and train_stats:
         # lets the consumer conv's input-gradient kernel do this layer's BN-backward reduction
-        a_full.bn_ctx = (y, scale, shift, mean, invstd, relu)
+        a_full.bn_ctx = BnCtx(y, scale, shift, mean, invstd, relu)
     if pool and argmax is not None and y_pool is not None:
-        a_pool.bn_ctx = (y_pool, scale, shift, mean, invstd, relu)
+        a_pool.bn_ctx = BnCtx(y_pool, scale, shift, mean, invstd, relu)
 
     def first_from_sums():
-        # conv1_1 whose sole consumer left the sums instead of the gradient (_conv_dgrad): dgamma / dbeta and the
+        # conv1_1 whose sole consumer left the sums instead of the gradient (input_grad): dgamma / dbeta and the
         # apply coefficients from the partial rows, then dW = A .* S1 + B .* (M W) + C .* m — no pass over a
         # 64-channel tensor at all
         coef = _bn_bwd_coef(g, bn, *a_full.bn_partial, count)
@@ -373,11 +366,7 @@ def _conv2d_bias(g, x, scope, wv, bias, packs, d, y, shape, relu, pool, keep_ful
         ops.conv2d(d, x.data, w_fwd, y, bias.data, None)
     a_full = Act(y, name=scope)
     if relu and is_training:
-        # (activation, scale 1, shift 0, mean 0, 1/std 1, relu): lets the ONE convolution that consumes this activation
-        # store the gradient past the ReLU and sum the bias gradient in its input-gradient epilogue (_conv_backward);
-        # used only when the net marks the activation `sole_consumer` (nets/vgg.py)
-        a_full.bias_ctx = (y, _const_vec(g, cout, 1.0), _const_vec(g, cout, 0.0), _const_vec(g, cout, 0.0),
-                           _const_vec(g, cout, 1.0), True)
+        a_full.bias_ctx = BnCtx.of_bias(g, y, cout)
 
     def backward_bias():
         if a_full.grad is None:
@@ -420,34 +409,10 @@ def _partial_rows(g, dg):
     return g.empty((T, 2, dg.cout), F32), T
 
 
-def _open_input_grad(g, x):
-    """-> the input-gradient launch's flags: 0 for the first contribution (x.grad allocated here), CONV_ACCUM_F16 for
-    a later one, which also drops what an earlier consumer's fused epilogue left: its BN-backward sums no longer cover
-    the full gradient, nor does its masked store (backward_bias then masks the whole sum again: idempotent)."""
-    if x.grad is None:
-        x.grad = g.empty(x.shape)
-        return 0
-    x.bn_partial = None
-    x.bias_partial = None
-    return CONV_ACCUM_F16
-
-
-def _grad_buffer(g, x):
-    """-> (x.grad, whether the caller accumulates into it): allocated here when this is the first contribution."""
-    acc = x.grad is not None
-    if not acc:
-        x.grad = g.empty(x.shape)
-    return x.grad, acc
-
-
-def _count_contribution(x, owner):
-    """-> whether this is the LAST gradient contribution to a bottleneck output.  Only the owning unit's two are counted
-    (any other consumer of x was built later, runs earlier in the backward pass and has added its share)."""
-    if x.pending is None or owner is None or owner is not x.pending_owner:
-        return False
-    x.pending -= 1
-    assert x.pending >= 0, "more gradient contributions than the owning unit has consumers"
-    return x.pending == 0
+def _stats_rows(g, T, c):
+    """(part, stage) in the small arena: the [T, 2, c] f32 rows a forward launch leaves its statistics in, and the
+    staging ops.bn_finalize folds them through."""
+    return g.ws_small.two(T * 2 * c * 4, ops.bn_reduce_workspace(T, c))
 
 
 def _conv_backward(g, x, wv, w_dg, d, dy, first):
@@ -460,54 +425,122 @@ def _conv_backward(g, x, wv, w_dg, d, dy, first):
     if ops.GUEST_BN and x.requires_grad:
         # input gradient FIRST: the layer below can then start its backward while this layer's weight gradient runs —
         # its batch-norm apply pass is a guest beside it (csrc/guest_bn.hip; the recorded step pairs the two)
-        _conv_dgrad(g, x, wv, w_dg, d, dy)
+        input_grad(g, x, d, w_dg, dy, conv2d_routes=True)
         ops.conv2d_wgrad(dd, x.data, dy, wv.grad, g.ws_wgrad, alloc=lambda nb: g.empty((nb,), torch.uint8))
         return
     ops.conv2d_wgrad(dd, x.data, dy, wv.grad, g.ws_wgrad)
-    if not x.requires_grad:
-        return
-    _conv_dgrad(g, x, wv, w_dg, d, dy)
+    if x.requires_grad:
+        input_grad(g, x, d, w_dg, dy, conv2d_routes=True)
 
 
-def _conv_dgrad(g, x, wv, w_dg, d, dy):
+class PwxOperand(NamedTuple):
+    """input_grad's `fused`: dy is still EMPTY — it is the batch-norm backward apply A*dz + B*y + C (coef = (A, B, C)), masked
+    by the ReLU of that batch norm when relu_shift (its shift) is given, which the 1x1 input-gradient convolution computes
+    while loading its operand (conv_pwx_kernel) and writes into dy for the weight gradient."""
+    dz: object
+    y: object
+    coef: tuple
+    relu_shift: object
+
+
+def select_input_grad(x, d, *, fused, last, variant, plain_only=False, conv2d_routes=False, tail=False,
+                      tail_1x1_only=False, bnred_unpended_only=False, first_sums=True):
+    """Which launch the backward of convolution `d` (its FORWARD descriptor, stride 1) issues for the gradient of its input
+    x: the epilogue, behind "pwx_" when `fused` (a PwxOperand) asks for the operand-transforming loader.  Pure: it reads x,
+    the switches and — through variant(), the kernel the library runs for this launch — nothing else.
+
+      first_sums   x is conv1_1's activation and nobody stored conv1_1's y: the launch leaves the sums conv1_1's weight
+                   gradient is finished from INSTEAD of the gradient (that gradient has no other reader)
+      bias_masked  x = relu(conv + bias): the gradient is stored past the ReLU, beside the bias gradient's sums
+      tail         the LAST contribution (`last`) to a bottleneck output: the gradient is stored past the output's ReLU,
+                   beside the BN-backward sums of the unit's last conv
+      bnred_first  x = relu?(bn(y)): the BN-backward sums of that layer, conv1_1's y recomputed in the epilogue ...
+      bnred        ... or read
+      plain        the gradient and nothing else
+    Every fused epilogue but `tail` describes the whole gradient only while it is the FIRST contribution.
+
+    The callers differ, and each difference has a name here:
+      plain_only           the merge convolutions (_cat_backward) never fuse
+      conv2d_routes        layers.conv2d alone knows first_sums, bias_masked, bnred_first — all for an x the net marked
+                           sole_consumer or that is conv1_1's — and the FUSE_BN_W4_MAXHW cut-off
+      tail                 the caller's FUSE_TAIL: resnet_layers alone builds bottlenecks
+      tail_1x1_only        its unfused launch takes the tail route for a 1x1 convolution only (a fused one is 1x1 anyway)
+      bnred_unpended_only  its fused launch leaves an x that counts contributions (x.pending) to the tail route
+      first_sums           False: the library has answered that it does not take this shape (input_grad)"""
+    pwx = "pwx_" if fused is not None else ""
+    if plain_only:
+        return pwx + "plain"
+    first = x.grad is None
+    by = x.bn_ctx.y if x.bn_ctx is not None else None
+    lazy_first = isinstance(by, ops.LazyFirstY) and by.t is None and d.cin == 64      # conv1_1's y, stored by nobody
+    if conv2d_routes and first and x.sole_consumer:
+        if first_sums and FIRST_WGRAD_SUMS and FUSE_BN_REDUCE and lazy_first and by.moments is not None:
+            return pwx + "first_sums"
+        if x.bias_ctx is not None and FUSE_BIAS_RELU:
+            return pwx + "bias_masked"
+    if tail and last and x.tail_ctx is not None and (d.kh == 1 or not tail_1x1_only):
+        return pwx + "tail"
+    if not (x.bn_ctx is not None and first and FUSE_BN_REDUCE):
+        return pwx + "plain"
+    if fused is not None and fused.relu_shift is not None:
+        return pwx + "plain"        # (ocr_conv2d_pw_bnbwd_bnred_f16 has no ReLU mask on load)
+    if bnred_unpended_only and x.pending is not None:
+        return pwx + "plain"
+    if conv2d_routes and d.h >= FUSE_BN_W4_MAXHW and variant() == "conv3x3_w4_kernel":
+        return pwx + "plain"        # (measurement switch: the one-wave-per-SIMD kernel cannot overlap its epilogue with anything)
+    if conv2d_routes and lazy_first and variant() == "conv_c64_persist_kernel<64>":
+        return pwx + "bnred_first"
+    return pwx + "bnred"
+
+
+# the Act slot in which each fused epilogue leaves its Partial for the producer's backward
+_PARTIAL_SLOT = {"first_sums": "bn_partial", "bnred_first": "bn_partial", "bnred": "bn_partial",
+                 "bias_masked": "bias_partial", "tail": "tail_partial"}
+
+
+def input_grad(g, x, d, w_dg, dy, *, owner=None, fused=None, **guards):
+    """The input-gradient launch of the convolution with forward descriptor `d` and input-gradient pack w_dg, into x's
+    gradient: the route select_input_grad names (guards: its named parameters), its partial rows and what it leaves
+    on x.  owner: the bottleneck on whose behalf x's contributions are counted; fused: a PwxOperand."""
     if d.stride != 1:
         raise NotImplementedError("strided dgrad")
-    by = x.bn_ctx[0] if x.bn_ctx is not None else None
-    lazy_first = isinstance(by, ops.LazyFirstY) and by.t is None and d.cin == 64      # conv1_1's y, stored by nobody
-    if x.grad is None and x.sole_consumer and FIRST_WGRAD_SUMS and FUSE_BN_REDUCE and lazy_first and by.moments is not None:
-        # conv1_1's activation, read by this convolution only: its gradient has one more reader — conv1_1's weight
-        # gradient — which needs sums of it, not the tensor; the launch leaves those (epilogue mode 7) and nothing else
-        dg = _dgrad_desc(d, 0)
+    dg = _dgrad_desc(d, 0)
+    select = functools.partial(select_input_grad, x, d, fused=fused, last=x.count_contribution(owner),
+                               variant=lambda: ops.conv2d_variant(dg), **guards)
+    route = select()
+    if route == "first_sums":
         blocks = ops.conv2d_bnred_first_wgrad_blocks(dg)
-        if blocks > 0:
-            partial, T = _partial_rows(g, dg)
-            s1 = g.empty((blocks, 32, 64), F32)
-            ops.conv2d_bnred_first_wgrad(dg, dy, w_dg, partial, (by.x4, by.w_first) + tuple(x.bn_ctx[1:]), s1)
-            x.bn_partial = (partial, T)
-            x.first_s1 = s1
-            return
-    flags = _open_input_grad(g, x)
-    dg = _dgrad_desc(d, flags)
-    if x.bias_ctx is not None and x.sole_consumer and not flags and FUSE_BIAS_RELU:
-        # bias + ReLU producer whose only reader is this convolution: dz and the bias-gradient partial sums come out of
-        # this kernel's epilogue, the producer's bias_relu_bwd pass (read a, read da, write dz) disappears
-        partial, T = _partial_rows(g, dg)
-        ops.conv2d_bnred(dg, dy, w_dg, x.grad, partial, x.bias_ctx, store_masked=True)
-        x.bias_partial = (partial, T)
-        return
-    fuse = x.bn_ctx is not None and not flags and FUSE_BN_REDUCE
-    if fuse and d.h >= FUSE_BN_W4_MAXHW and ops.conv2d_variant(dg) == "conv3x3_w4_kernel":
-        fuse = False        # (measurement switch: the one-wave-per-SIMD kernel cannot overlap its epilogue with anything)
-    if fuse:
-        partial, T = _partial_rows(g, dg)
-        if lazy_first and ops.conv2d_variant(dg) == "conv_c64_persist_kernel<64>":
-            # the consumer of conv1_1's activation (conv1_2): conv1_1's y is recomputed in the epilogue, not read
-            ops.conv2d_bnred_first(dg, dy, w_dg, x.grad, partial, (by.x4, by.w_first) + tuple(x.bn_ctx[1:]))
-        else:
-            ops.conv2d_bnred(dg, dy, w_dg, x.grad, partial, x.bn_ctx)
-        x.bn_partial = (partial, T)
+        if blocks <= 0:
+            route = select(first_sums=False)
+    if route != "first_sums":
+        dx, accumulating = x.open_grad(g)
+        dg.flags = CONV_ACCUM_F16 if accumulating else 0
+    epilogue = route[4:] if fused is not None else route
+    rows = None
+    if epilogue != "plain":
+        part = Partial(*_partial_rows(g, dg))
+        setattr(x, _PARTIAL_SLOT[epilogue], part)
+        rows = part.rows
+    is_tail = epilogue == "tail"
+    if fused is not None and epilogue == "bnred":
+        ops.conv2d_pw_bnbwd_bnred(dg, fused.dz, fused.y, fused.coef, dy, w_dg, dx, rows, x.bn_ctx)
+    elif fused is not None:
+        ops.conv2d_pw_bnbwd_tail(dg, fused.dz, fused.y, fused.coef, fused.relu_shift, dy, w_dg, dx, rows,
+                                 x.tail_ctx if is_tail else None, x.sub_grad if is_tail else None)
+    elif epilogue == "first_sums":
+        x.first_s1 = g.empty((blocks, 32, 64), F32)
+        ops.conv2d_bnred_first_wgrad(dg, dy, w_dg, rows, x.bn_ctx.first(), x.first_s1)
+    elif epilogue == "bnred_first":
+        ops.conv2d_bnred_first(dg, dy, w_dg, dx, rows, x.bn_ctx.first())
+    elif epilogue in ("bnred", "bias_masked"):
+        masked = epilogue == "bias_masked"
+        ops.conv2d_bnred(dg, dy, w_dg, dx, rows, x.bias_ctx if masked else x.bn_ctx, store_masked=masked)
+    elif is_tail:
+        ops.conv2d_bnred_tail(dg, dy, w_dg, dx, rows, x.tail_ctx, x.sub_grad)
     else:
-        ops.conv2d(dg, dy, w_dg, x.grad, None, None)
+        ops.conv2d(dg, dy, w_dg, dx, None, None)
+    if is_tail:
+        x.sub_grad = None
 
 
 def max_pool2d(g, x, k, stride, scope="pool", bias_relu=None):
@@ -525,12 +558,11 @@ def max_pool2d(g, x, k, stride, scope="pool", bias_relu=None):
     y = g.empty((n, oh, ow, c))
     # index of the first maximum per window (TF gradient routing), kept for the backward pass
     argmax = g.empty((n, oh, ow, c), torch.uint8) if x.requires_grad else None
-    fwd = getattr(x, "bn_fwd", None)
+    fwd = x.bn_fwd
     if x.deferred is not None and fwd is not None:
         # x = relu(bn(y)) that nobody has computed yet (resnet_layers.root_block): the pool evaluates it per window
         # element from the raw conv output and x stays unwritten unless somebody else asks for x.data
-        by, bsc, bsh, brelu = fwd
-        ops.bn_relu_maxpool(by, bsc, bsh, brelu, k, stride, (pt, pl), y, argmax)
+        ops.bn_relu_maxpool(fwd.y, fwd.scale, fwd.shift, fwd.relu, k, stride, (pt, pl), y, argmax)
     else:
         ops.maxpool(x.data, k, stride, (pt, pl), y, argmax)
     out = Act(y, name=scope)
@@ -548,10 +580,10 @@ def max_pool2d(g, x, k, stride, scope="pool", bias_relu=None):
             return
         if x.takes_pool_grad and x.grad is None and x.pool_grad is None and argmax is not None:
             # the producer gathers this gradient while it loads (resnet_layers.root_block): nothing is written here
-            x.pool_grad = (out.grad, argmax, k, stride, (pt, pl))
+            x.pool_grad = PoolGrad(out.grad, argmax, k, stride, (pt, pl))
             out.grad = None
             return
-        dx, acc = _grad_buffer(g, x)
+        dx, acc = x.open_grad(g)
         # (with the forward's index tensor the backward never reads x: do not force a deferred x into existence)
         ops.maxpool_bwd(x._data if argmax is not None else x.data, out.grad, k, stride, (pt, pl), dx, acc,
                         argmax=argmax, in_shape=x.shape)

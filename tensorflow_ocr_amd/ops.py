@@ -11,6 +11,7 @@ from ctypes import byref, c_double, c_float, c_int, c_int64, c_size_t
 import torch
 
 from . import _lib as L, step_plan
+from . import graph as G      # (the handshake records only, at call time: graph imports this module)
 from ._lib import ConvDesc, CONV_ACCUM_F16, CONV_BIAS, CONV_RELU, CONV_STATS, ptr
 
 F16, F32 = (torch.bfloat16 if L.STORAGE == "bf16" else torch.float16), torch.float32
@@ -123,12 +124,12 @@ def conv2d_relu_pool(d, x, w_kc, bias, pooled, argmax=None):
 
 def conv2d_bnred(d, x, w_kc, y, partial, bn_ctx, store_masked=False):
     """Input-gradient conv fused with the BN-backward reduction of the layer below.  store_masked: y receives the
-    gradient PAST that layer's ReLU (bias nets: bn_ctx = (activation, ones, zeros, zeros, ones, True))."""
-    by, sc, sh, mu, istd, relu = bn_ctx
-    if isinstance(by, LazyFirstY):
-        by = by.tensor()                 # a consumer that cannot recompute conv1_1's y: evaluate and store it now
-    _conv_call("ocr_conv2d_bnred_f16", d, ptr(x), ptr(w_kc), ptr(y), ptr(partial), ptr(by), ptr(sc), ptr(sh), ptr(mu),
-               ptr(istd), c_int(int(relu)), c_int(int(store_masked)), phase="dgrad")
+    gradient PAST that layer's ReLU (bias nets: graph.BnCtx.of_bias).  bn_ctx: a graph.BnCtx, or its six fields."""
+    c = G.BnCtx(*bn_ctx)
+    # (a consumer that cannot recompute conv1_1's y evaluates and stores it now)
+    by = c.y.tensor() if isinstance(c.y, LazyFirstY) else c.y
+    _conv_call("ocr_conv2d_bnred_f16", d, ptr(x), ptr(w_kc), ptr(y), ptr(partial), ptr(by), ptr(c.scale), ptr(c.shift),
+               ptr(c.mean), ptr(c.invstd), c_int(int(c.relu)), c_int(int(store_masked)), phase="dgrad")
 
 
 class LazyFirstY:
@@ -150,7 +151,7 @@ class LazyFirstY:
 
 def conv2d_bnred_first(d, x, w_kc, y, partial, first_ctx):
     """conv2d_bnred for the consumer of conv1_1's activation with conv1_1's y recomputed from the image instead of read:
-    first_ctx = (x4, w_first, scale, shift, mean, invstd, relu)."""
+    first_ctx = graph.BnCtx.first(): (x4, w_first, scale, shift, mean, invstd, relu)."""
     x4, wf, sc, sh, mu, istd, relu = first_ctx
     _conv_call("ocr_conv2d_bnred_first_f16", d, ptr(x), ptr(w_kc), ptr(y), ptr(partial), ptr(x4), ptr(wf), ptr(sc), ptr(sh),
                ptr(mu), ptr(istd), c_int(int(relu)), phase="dgrad")
@@ -179,12 +180,11 @@ def conv2d_first_wgrad_sums(s1, moments, w_first, coef, dw):
 def conv2d_bnred_tail(d, x, w_kc, y, partial, tail_ctx, sub_grad=None):
     """Input-gradient conv that completes the gradient of a bottleneck output: stores the gradient past the
     output ReLU and emits the BN-backward sums of the unit's last conv; `sub_grad`: gradient of the output's
-    stride-2 subsample, added at the even positions (include/ocr_hip.h).  tail_ctx = (y, mean, invstd, out[, bits]):
+    stride-2 subsample, added at the even positions (include/ocr_hip.h).  tail_ctx: a graph.TailCtx, or its fields;
     with `bits` (the output's ReLU mask, one byte per 8 channels) the kernel reads them instead of `out`."""
-    by, mu, istd, out = tail_ctx[:4]
-    bits = tail_ctx[4] if len(tail_ctx) > 4 else None
-    _conv_call("ocr_conv2d_bnred_tail_f16", d, ptr(x), ptr(w_kc), ptr(y), ptr(partial), ptr(by), ptr(mu), ptr(istd),
-               ptr(out), ptr(bits), ptr(sub_grad), phase="dgrad")
+    t = G.TailCtx(*tail_ctx)
+    _conv_call("ocr_conv2d_bnred_tail_f16", d, ptr(x), ptr(w_kc), ptr(y), ptr(partial), ptr(t.y), ptr(t.mean), ptr(t.invstd),
+               ptr(t.out), ptr(t.bits), ptr(sub_grad), phase="dgrad")
 
 
 def conv2d_pw_bnaddrelu(d, prev_y, prev_scale, prev_shift, shortcut, sc_scale, sc_shift, x_out, bits, w_kc, y, stats):
@@ -202,24 +202,21 @@ def conv2d_pw_bnrelu(d, prev_y, prev_scale, prev_shift, x_out, w_kc, y, stats):
 def conv2d_pw_bnbwd_bnred(d, dz, y_above, coef, dy_out, w_kc, dx, partial, bn_ctx):
     """1x1 input-gradient conv whose operand dy = A*dz + B*y_above + C is computed while it is loaded and written to
     dy_out; fused BN-backward reduction of the layer below as in conv2d_bnred."""
-    by, sc, sh, mu, istd, relu = bn_ctx
-    if isinstance(by, LazyFirstY):
-        by = by.tensor()
+    bn = G.BnCtx(*bn_ctx)
+    by = bn.y.tensor() if isinstance(bn.y, LazyFirstY) else bn.y
     a, b, c = coef
     _conv_call("ocr_conv2d_pw_bnbwd_bnred_f16", d, ptr(dz), ptr(y_above), ptr(a), ptr(b), ptr(c), ptr(dy_out), ptr(w_kc),
-               ptr(dx), ptr(partial), ptr(by), ptr(sc), ptr(sh), ptr(mu), ptr(istd), c_int(int(relu)), phase="dgrad", pwx=True)
+               ptr(dx), ptr(partial), ptr(by), ptr(bn.scale), ptr(bn.shift), ptr(bn.mean), ptr(bn.invstd),
+               c_int(int(bn.relu)), phase="dgrad", pwx=True)
 
 
 def conv2d_pw_bnbwd_tail(d, dz, y_above, coef, relu_shift, dy_out, w_kc, dx, partial=None, tail_ctx=None, sub_grad=None):
     """conv2d_pw_bnbwd_bnred's loader (+ the ReLU mask of the BN above when relu_shift is given) in front of the plain /
     accumulating (d.flags) / bottleneck-tail epilogue (tail_ctx, sub_grad as conv2d_bnred_tail)."""
     a, b, c = coef
-    by = mu = istd = out = bits = None
-    if tail_ctx is not None:
-        by, mu, istd, out = tail_ctx[:4]
-        bits = tail_ctx[4] if len(tail_ctx) > 4 else None
+    t = G.TailCtx(*tail_ctx) if tail_ctx is not None else G.TailCtx(None, None, None, None)
     _conv_call("ocr_conv2d_pw_bnbwd_tail_f16", d, ptr(dz), ptr(y_above), ptr(a), ptr(b), ptr(c), ptr(relu_shift), ptr(dy_out),
-               ptr(w_kc), ptr(dx), ptr(partial), ptr(by), ptr(mu), ptr(istd), ptr(out), ptr(bits), ptr(sub_grad),
+               ptr(w_kc), ptr(dx), ptr(partial), ptr(t.y), ptr(t.mean), ptr(t.invstd), ptr(t.out), ptr(t.bits), ptr(sub_grad),
                phase="dgrad", pwx=True)
 
 
@@ -463,7 +460,8 @@ def bn_relu_poolfull_bwd_apply_affine(y, da_full, da_pool, argmax, scale, shift,
 
 def bn_relu_bwd_reduce_pooled(y, scale, shift, save_mean, save_invstd, pooled, relu, da_out, dgamma, dbeta, coef, ws):
     """bn_relu_bwd_reduce with the max-pool backward that produces the activation gradient folded in.
-    pooled = (da_pooled [n,oh,ow,c], argmax u8, k, stride, (pad_top, pad_left)); da_out (nullable): the gathered gradient."""
+    pooled: a graph.PoolGrad (grad [n,oh,ow,c], argmax u8, k, stride, (pad_top, pad_left)); da_out (nullable): the gathered
+    gradient."""
     n, h, w, c = y.shape
     dap, argmax, k, stride, (pt, pl) = pooled
     T = bn_bwd_num_partials(y.shape, 0)

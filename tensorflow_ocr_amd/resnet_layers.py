@@ -12,9 +12,9 @@ sums).  Other strides fall back on the identity the reference's own docstring st
 import torch
 
 from . import ops
-from .graph import Act, F32, constant, variance_scaling
-from .layers import (FUSE_BN_REDUCE, _bn_bwd_coef, _bn_params, _bn_vars, _coef, _count_contribution, _dgrad_desc,
-                     _grad_buffer, _open_input_grad, _packs, _partial_rows, _switch, _wgrad_desc, max_pool2d)
+from .graph import Act, BnCtx, BnFwd, F32, TailCtx, TailFwd, variance_scaling
+from .layers import (FUSE_BN_REDUCE, PwxOperand, _bn_bwd_coef, _bn_params, _bn_vars, _coef, _dgrad_desc, _packs,
+                     _stats_rows, _switch, _wgrad_desc, input_grad, max_pool2d)
 from ._lib import CONV_ACCUM_F16, CONV_STATS
 
 USE_S2D = _switch("OCR_RESNET_S2D")     # measurement switch (A/B against the subsample form)
@@ -84,7 +84,7 @@ def conv_bn_raw(g, x, cout, k, scope, *, stride=1, rate=1, is_training=True, wei
         y_full = None
         y = g.empty((n, oh, ow, cout))
         T = ops.conv2d_num_mtiles(d)
-        part, stage = g.ws_small.two(T * 2 * cout * 4, ops.bn_reduce_workspace(T, cout))
+        part, stage = _stats_rows(g, T, cout)
         d.flags = CONV_STATS if is_training else 0
         ops.conv2d(d, xs, w_fwd, y, None, part if is_training else None)
         x_in = xs
@@ -94,110 +94,69 @@ def conv_bn_raw(g, x, cout, k, scope, *, stride=1, rate=1, is_training=True, wei
         x_in = x._data            # (the buffer: a deferred x is filled by the convolution below or by x.data)
         y_full = g.empty((n, d.oh, d.ow, cout))
         mt = ops.conv2d_num_mtiles(d)
-    if s2d:
-        pass
-    elif strided:
-        d.flags = 0
-        ops.conv2d(d, x.data, w_fwd, y_full, None, None)
-        oh, ow = -(-h // stride), -(-w // stride)
-        y = g.empty((n, oh, ow, cout))
-        ops.maxpool(y_full, 1, stride, (0, 0), y)                   # subsample (resnet_utils.py:74)
-        T = ops.channel_stats_num_partials(n * oh * ow, cout)
-        part, stage = g.ws_small.two(T * 2 * cout * 4, ops.bn_reduce_workspace(T, cout))
-        if is_training:
-            ops.channel_stats(y, part)
-    else:
-        oh, ow = d.oh, d.ow
-        y = y_full
-        T = mt
-        part, stage = g.ws_small.two(T * 2 * cout * 4, ops.bn_reduce_workspace(T, cout))
-        d.flags = CONV_STATS if is_training else 0
-        if (x.deferred is not None and x.tail_fwd is not None and is_training and FUSE_FWD and cout <= 512
-                and _pw_fusable(d)):
-            # x is the previous unit's output and nobody has computed it yet: this convolution does, while loading
-            # its pixel operand, and writes it (and its ReLU-mask bits) for the consumers that follow
-            x.deferred = None
-            py, psc, psh, short, ssc, ssh, bits = x.tail_fwd
-            ops.conv2d_pw_bnaddrelu(d, py, psc, psh, short, ssc, ssh, x._data, bits, w_fwd, y, part)
-        elif (x.deferred is not None and x.bn_fwd is not None and x.bn_fwd[3] and is_training and FUSE_FWD_ACT
-                and _pw_fusable(d)):
-            # x = relu(bn(conv2)) that nobody has computed yet (conv_bn_act(defer=True)): applied to the operand rows
-            x.deferred = None
-            by, bsc, bsh, _ = x.bn_fwd
-            ops.conv2d_pw_bnrelu(d, by, bsc, bsh, x._data, w_fwd, y, part)
+        if strided:
+            d.flags = 0
+            ops.conv2d(d, x.data, w_fwd, y_full, None, None)
+            oh, ow = -(-h // stride), -(-w // stride)
+            y = g.empty((n, oh, ow, cout))
+            ops.maxpool(y_full, 1, stride, (0, 0), y)                   # subsample (resnet_utils.py:74)
+            T = ops.channel_stats_num_partials(n * oh * ow, cout)
+            part, stage = _stats_rows(g, T, cout)
+            if is_training:
+                ops.channel_stats(y, part)
         else:
-            ops.conv2d(d, x.data, w_fwd, y, None, part if is_training else None)
+            oh, ow = d.oh, d.ow
+            y = y_full
+            T = mt
+            part, stage = _stats_rows(g, T, cout)
+            d.flags = CONV_STATS if is_training else 0
+            if (x.deferred is not None and x.tail_fwd is not None and is_training and FUSE_FWD and cout <= 512
+                    and _pw_fusable(d)):
+                # x is the previous unit's output and nobody has computed it yet: this convolution does, while loading
+                # its pixel operand, and writes it (and its ReLU-mask bits) for the consumers that follow
+                x.deferred = None
+                t = x.tail_fwd
+                ops.conv2d_pw_bnaddrelu(d, t.y, t.scale, t.shift, t.shortcut, t.sc_scale, t.sc_shift, x._data, t.bits,
+                                        w_fwd, y, part)
+            elif (x.deferred is not None and x.bn_fwd is not None and x.bn_fwd.relu and is_training and FUSE_FWD_ACT
+                    and _pw_fusable(d)):
+                # x = relu(bn(conv2)) that nobody has computed yet (conv_bn_act(defer=True)): applied to the operand rows
+                x.deferred = None
+                ops.conv2d_pw_bnrelu(d, x.bn_fwd.y, x.bn_fwd.scale, x.bn_fwd.shift, x._data, w_fwd, y, part)
+            else:
+                ops.conv2d(d, x.data, w_fwd, y, None, part if is_training else None)
     c = ConvBN()
     c.y, c.gamma, c.beta, c.wv = y, gamma, beta, wv
     c.scale, c.shift, c.mean, c.invstd = _bn_params(g, cout, (gamma, beta, mm, mv),
                                                     (part, T, float(n) * oh * ow, stage) if is_training else None)
 
     def backward_from(dy, fused=None):
-        """dy: gradient of the conv output.  fused = (dz, y_bn, (A, B, C)): dy is still EMPTY — it is the batch-norm
-        backward apply A*dz + B*y_bn + C, which the input-gradient convolution computes while loading its operand and
-        writes into `dy` for the weight gradient (see `can_fuse_bwd`)."""
+        """dy: gradient of the conv output.  fused: a PwxOperand — dy is still EMPTY, the input-gradient convolution computes
+        it while loading its operand and writes it for the weight gradient (see `can_fuse_bwd`)."""
         dd = _wgrad_desc(d)
         if fused is not None:
-            dz_f, ybn_f, coef_f, relu_shift = fused
-            flags = _open_input_grad(g, x)
-            last = _count_contribution(x, owner)
-            dg = _dgrad_desc(d, flags)
-            if last and x.tail_ctx is not None and FUSE_TAIL:
-                # (as the unfused path below: the last contribution to a bottleneck output's gradient)
-                partial, Tm = _partial_rows(g, dg)
-                ops.conv2d_pw_bnbwd_tail(dg, dz_f, ybn_f, coef_f, relu_shift, dy, w_dg, x.grad, partial, x.tail_ctx, x.sub_grad)
-                x.sub_grad = None
-                x.tail_partial = (partial, Tm)
-            elif x.bn_ctx is not None and not flags and FUSE_BN_REDUCE and relu_shift is None and x.pending is None:
-                partial, Tm = _partial_rows(g, dg)
-                ops.conv2d_pw_bnbwd_bnred(dg, dz_f, ybn_f, coef_f, dy, w_dg, x.grad, partial, x.bn_ctx)
-                x.bn_partial = (partial, Tm)
-            else:
-                ops.conv2d_pw_bnbwd_tail(dg, dz_f, ybn_f, coef_f, relu_shift, dy, w_dg, x.grad)
+            input_grad(g, x, d, w_dg, dy, owner=owner, fused=fused, tail=FUSE_TAIL, bnred_unpended_only=True)
             ops.conv2d_wgrad(dd, x_in, dy, wv.grad, g.ws_wgrad)
             return
         if strided and not s2d:
             dy_full = g.empty(y_full.shape)
             ops.maxpool_bwd(y_full, dy, 1, stride, (0, 0), dy_full, False)   # zero insertion
             dy = dy_full
-
-        def weight_gradient():
-            if s2d:
-                dw22 = g.empty((2, 2, 4 * cin, cout), F32)
-                ops.conv2d_wgrad(dd, x_in, dy, dw22, g.ws_wgrad)
-                ops.weights_s2d_grad(dw22, wv.grad)
-            else:
-                ops.conv2d_wgrad(dd, x_in, dy, wv.grad, g.ws_wgrad)
-
-        def input_gradient():
-            if s2d:
-                # input gradient in the shuffled layout, then back to full resolution (added to what is there)
-                dxs = g.empty(x_in.shape)
-                ops.conv2d(_dgrad_desc(d, 0), dy, w_dg, dxs, None, None)
-                ops.depth_to_space(dxs, *_grad_buffer(g, x))
-                x.bn_partial = None
-                return
-            flags = _open_input_grad(g, x)
-            dg = _dgrad_desc(d, flags)
-            last = _count_contribution(x, owner)
-            if last and x.tail_ctx is not None and k == 1 and FUSE_TAIL:
-                # x is the previous bottleneck's output and this is the last contribution to its gradient: store
-                # the gradient past its ReLU and emit the BN-backward sums of its last conv (ops.conv2d_bnred_tail)
-                partial, Tm = _partial_rows(g, dg)
-                ops.conv2d_bnred_tail(dg, dy, w_dg, x.grad, partial, x.tail_ctx, x.sub_grad)
-                x.sub_grad = None
-                x.tail_partial = (partial, Tm)
-            elif x.bn_ctx is not None and not flags and FUSE_BN_REDUCE:
-                # sole consumer of a conv+BN(+ReLU) output: this input-gradient kernel also emits that
-                # layer's BN-backward sums, so its backward skips the reduction pass (layers.py does the same)
-                partial, Tm = _partial_rows(g, dg)
-                ops.conv2d_bnred(dg, dy, w_dg, x.grad, partial, x.bn_ctx)
-                x.bn_partial = (partial, Tm)
-            else:
-                ops.conv2d(dg, dy, w_dg, x.grad, None, None)
-        weight_gradient()
-        if x.requires_grad:
-            input_gradient()
+        if s2d:
+            dw22 = g.empty((2, 2, 4 * cin, cout), F32)
+            ops.conv2d_wgrad(dd, x_in, dy, dw22, g.ws_wgrad)
+            ops.weights_s2d_grad(dw22, wv.grad)
+        else:
+            ops.conv2d_wgrad(dd, x_in, dy, wv.grad, g.ws_wgrad)
+        if not x.requires_grad:
+            return
+        if s2d:
+            # input gradient in the shuffled layout, then back to full resolution (added to what is there)
+            dxs = g.empty(x_in.shape)
+            ops.conv2d(_dgrad_desc(d, 0), dy, w_dg, dxs, None, None)
+            ops.depth_to_space(dxs, *x.open_grad(g))
+        else:
+            input_grad(g, x, d, w_dg, dy, owner=owner, tail=FUSE_TAIL, tail_1x1_only=True)
 
     def can_fuse_bwd(wide=False):
         """The fused form of `backward_from`: this is a stride-1 1x1 convolution the pointwise kernel takes.  Default: its
@@ -236,12 +195,12 @@ def conv_bn_act(g, x, cout, k, scope, *, stride=1, rate=1, relu=True, is_trainin
         ops.bn_relu(c.y, c.scale, c.shift, relu, 0, a._data, None)
     if defer and is_training and FUSE_FWD_ACT:
         a.deferred = fill
-        a.bn_fwd = (c.y, c.scale, c.shift, relu)
+        a.bn_fwd = BnFwd(c.y, c.scale, c.shift, relu)
     else:
         fill()
     ws = g.workspace()
     if is_training:
-        a.bn_ctx = (c.y, c.scale, c.shift, c.mean, c.invstd, relu)
+        a.bn_ctx = BnCtx(c.y, c.scale, c.shift, c.mean, c.invstd, relu)
 
     def backward():
         if a.grad is None:
@@ -252,7 +211,7 @@ def conv_bn_act(g, x, cout, k, scope, *, stride=1, rate=1, relu=True, is_trainin
             # coefficients and let this layer's own input-gradient convolution apply them (and the ReLU mask) on load
             coef = _bn_bwd_coef(g, (c.scale, c.mean, c.invstd, c.gamma, c.beta), *a.bn_partial, float(c.y.numel() // cout))
             a.bn_partial = None
-            c.backward_from(dy, fused=(a.grad, c.y, coef, c.shift if relu else None))
+            c.backward_from(dy, fused=PwxOperand(a.grad, c.y, coef, c.shift if relu else None))
             a.grad = None
             return
         if a.bn_partial is not None:
@@ -288,7 +247,7 @@ def root_block(g, x4, scope="conv1", cout=64, is_training=True):
     oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     y = g.empty((n, oh, ow, cout))
     mt = ops.conv2d_stem_num_mtiles(n, h, w)
-    part, stage = g.ws_small.two(mt * 2 * cout * 4, ops.bn_reduce_workspace(mt, cout))
+    part, stage = _stats_rows(g, mt, cout)
     ops.conv2d_stem(x4.data, w_stem, y, CONV_STATS if is_training else 0, None, part if is_training else None)
     scale, shift, mean, invstd = _bn_params(g, cout, (gamma, beta, mm, mv),
                                             (part, mt, float(n) * oh * ow, stage) if is_training else None)
@@ -300,7 +259,7 @@ def root_block(g, x4, scope="conv1", cout=64, is_training=True):
         # the 3x3/2 max-pool that follows (nets/resnet_v1.py:194) is the activation's only reader: it evaluates
         # relu(bn(y)) per window element (layers.max_pool2d) and the 64-channel half-resolution activation is never written
         a.deferred = fill
-        a.bn_fwd = (y, scale, shift, True)
+        a.bn_fwd = BnFwd(y, scale, shift, True)
         a.takes_pool_grad = FUSE_ROOT_WGRAD and FUSE_ROOT_GATHER
     else:
         fill()
@@ -316,8 +275,8 @@ def root_block(g, x4, scope="conv1", cout=64, is_training=True):
             a.pool_grad = None
             return
         if a.pool_grad is not None:              # somebody else contributed as well: materialise the pool's share
-            dap, argmax, pk, ps, pads = a.pool_grad
-            ops.maxpool_bwd(a._data, dap, pk, ps, pads, a.grad, True, argmax=argmax, in_shape=a.shape)
+            pg = a.pool_grad
+            ops.maxpool_bwd(a._data, pg.grad, pg.k, pg.stride, pg.pad, a.grad, True, argmax=pg.argmax, in_shape=a.shape)
             a.pool_grad = None
         if a.grad is None:
             return
@@ -388,7 +347,7 @@ def bottleneck(g, x, depth, depth_bottleneck, stride, scope, is_training=True):
                 coef = _coef(g, depth)
                 ops.bn_relu_bwd_reduce(sc.y, sc.scale, sc.shift, sc.mean, sc.invstd, dz, False, sc.gamma.grad,
                                        sc.beta.grad, coef, ws)
-                sc.backward_from(dy, fused=(dz, sc.y, coef, None))
+                sc.backward_from(dy, fused=PwxOperand(dz, sc.y, coef, None))
             else:
                 ops.bn_relu_bwd(sc.y, sc.scale, sc.shift, sc.mean, sc.invstd, dz, None, False, 0, sc.gamma.grad,
                                 sc.beta.grad, dy, ws)
@@ -421,7 +380,7 @@ def bottleneck(g, x, depth, depth_bottleneck, stride, scope, is_training=True):
                     if x.grad is None and x.pending == 2 and stride == 2:
                         x.sub_grad = shortcut.grad
                     else:                            # someone else contributed already: materialise
-                        dx, acc = _grad_buffer(g, x)
+                        dx, acc = x.open_grad(g)
                         ops.maxpool_bwd(x.data, shortcut.grad, 1, stride, (0, 0), dx, acc, in_shape=x.shape)
                     x.pending -= 1
                     shortcut.grad = None
@@ -442,11 +401,11 @@ def bottleneck(g, x, depth, depth_bottleneck, stride, scope, is_training=True):
         ops.bn_add_relu(c3.y, c3.scale, c3.shift, short_t, out._data, sc_scale, sc_shift, bits)
     if is_training and FUSE_FWD:
         out.deferred = fill
-        out.tail_fwd = (c3.y, c3.scale, c3.shift, short_t, sc_scale, sc_shift, bits)
+        out.tail_fwd = TailFwd(c3.y, c3.scale, c3.shift, short_t, sc_scale, sc_shift, bits)
     else:
         fill()
     if is_training and FUSE_TAIL:
-        out.tail_ctx = (c3.y, c3.mean, c3.invstd, out._data, bits)
+        out.tail_ctx = TailCtx(c3.y, c3.mean, c3.invstd, out._data, bits)
 
     def backward():
         if out.grad is None:
@@ -459,7 +418,7 @@ def bottleneck(g, x, depth, depth_bottleneck, stride, scope, is_training=True):
             if c3.can_fuse_bwd():
                 coef = _bn_bwd_coef(g, (c3.scale, c3.mean, c3.invstd, c3.gamma, c3.beta), part_f, T_f,
                                     float(c3.y.numel() // depth))
-                c3.backward_from(dy, fused=(dz, c3.y, coef, None))
+                c3.backward_from(dy, fused=PwxOperand(dz, c3.y, coef, None))
             else:
                 ops.bn_relu_bwd_apply(c3.y, c3.scale, c3.shift, c3.mean, c3.invstd, dz, False, part_f, T_f,
                                       c3.gamma.grad, c3.beta.grad, dy, ws)
@@ -499,7 +458,7 @@ def unpool(g, x):
     def backward():
         if out.grad is None or not x.requires_grad:
             return
-        ops.unpool_bwd_f16(out.grad, *_grad_buffer(g, x))
+        ops.unpool_bwd_f16(out.grad, *x.open_grad(g))
         out.grad = None
     g.record(backward)
     return out
@@ -531,7 +490,7 @@ def _cat_backward(g, wv, branches):
         dd = ops.conv_desc(x.shape, cout, 1, 1)
         ops.conv2d_wgrad(dd, x.data, dy, wv.grad[:, :, lo:lo + c, :], g.ws_wgrad)
         if x.requires_grad:
-            ops.conv2d(_dgrad_desc(dd, _open_input_grad(g, x)), dy, w_ck, x.grad, None, None)
+            input_grad(g, x, dd, w_ck, dy, plain_only=True)
         lo += c
 
 
@@ -551,7 +510,7 @@ def concat_conv_bn_relu(g, xa, xb, cout, scope, is_training=True):
     db = ops.conv_desc((n, h, w, cb), cout, 1, 1)
     y = g.empty((n, h, w, cout))
     mt = ops.conv2d_num_mtiles(da)
-    part, stage = g.ws_small.two(mt * 2 * cout * 4, ops.bn_reduce_workspace(mt, cout))
+    part, stage = _stats_rows(g, mt, cout)
     da.flags = 0
     ops.conv2d(da, xa.data, wa_kc, y, None, None)
     db.flags = CONV_ACCUM_F16 | (CONV_STATS if is_training else 0)
@@ -595,7 +554,7 @@ def unpool_concat_conv_bn_relu(g, lo, xb, cout, scope, is_training=True):
     db.flags = 0
     ops.conv2d(db, xb.data, wb_kc, y, None, None)
     T = ops.channel_stats_num_partials(n * h * w, cout)
-    part, stage = g.ws_small.two(T * 2 * cout * 4, ops.bn_reduce_workspace(T, cout))
+    part, stage = _stats_rows(g, T, cout)
     ops.unpool_add_stats(t, y, part if is_training else None)
     scale, shift, mean, invstd = _bn_params(g, cout, bn_vars, (part, T, float(n) * h * w, stage) if is_training else None)
     a = Act(g.empty(y.shape), name=scope)
