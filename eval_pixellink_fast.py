@@ -38,6 +38,9 @@ def parse(argv=None):
     ap.add_argument('--batch_size', type=int, default=8)
     ap.add_argument('--synthetic', type=int, default=0, help='evaluate N synthetic images instead of files')
     ap.add_argument('--precision', choices=['f16', 'f32'], default='f16', help="as test_pixellink_fast.py's flag")
+    ap.add_argument('--eval_protocol', choices=['raster', 'icdar15'], default='raster', help="raster = the reference's "
+                    "matching rule; icdar15 = the official ICDAR-2015 protocol (polygon IoU, ### as don't-care regions), the "
+                    "line then ends in [icdar15]")
     FLAGS = ap.parse_args(argv)
     if FLAGS.min_side < 0 or FLAGS.min_area < 0:
         ap.error('--min_side and --min_area must not be negative')
@@ -81,7 +84,8 @@ def main(argv=None):
     ev = evaluate.LinkEvaluator(g, forward, data, batch_size=FLAGS.batch_size, gt_path=FLAGS.gt_path,
                                 pixel_conf_threshold=FLAGS.pixel_conf_threshold,
                                 link_conf_threshold=FLAGS.link_conf_threshold, min_side=FLAGS.min_side,
-                                min_area=FLAGS.min_area, eval_image_height=H, eval_image_width=W)
+                                min_area=FLAGS.min_area, eval_image_height=H, eval_image_width=W,
+                                protocol=FLAGS.eval_protocol)
     try:
         print(evaluate.format_line(ev.run()), flush=True)
     finally:

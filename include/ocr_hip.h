@@ -1111,6 +1111,9 @@ int ocr_eval_match_batch(const void* dets_i32, const void* nd_i32, const void* g
                          const void* gignored_u8, int n, int max_d, int max_g, float threshold, int mask_h, int mask_w,
                          void* tp_u8, void* fp_u8, void* record_i64, void* workspace, size_t ws_bytes, void* stream);
 int ocr_eval_record_init(void* record_i64, void* stream);
+/* The official ICDAR-2015 protocol (polygon IoU, don't-care regions) on the same operands and the same record: its two
+ * entries and their comment block are in a header of their own, part of this ABI. */
+#include "ocr_eval_ic15.h"
 
 /* ------------------------------------------------------------------------- *
  * Link-geometry detections on the device (csrc/link_boxes.hip): what lies between ocr_min_area_rects and

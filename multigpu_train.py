@@ -76,7 +76,11 @@ def parse(argv=None):
     ap.add_argument('--eval_steps', type=int, default=0, metavar='N')
     ap.add_argument('--eval_max_images', type=int, default=None, metavar='M')
     ap.add_argument('--eval_weights', choices=['ema', 'raw'], default='ema')
+    # --eval_protocol: raster = the reference's matching rule, icdar15 = the official ICDAR-2015 protocol (polygon IoU)
+    ap.add_argument('--eval_protocol', choices=['raster', 'icdar15'], default='raster')
     FLAGS = ap.parse_args(argv)
+    if FLAGS.eval_protocol != 'raster' and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
+        ap.error('--eval_protocol needs --eval_data_path and --eval_steps')
     if FLAGS.geometry == 'RBOX' and FLAGS.net != 'east':
         ap.error('--geometry RBOX needs --net east (the RBOX heads sit on the EAST merge branch)')
     if FLAGS.eval_steps < 0 or (FLAGS.eval_max_images is not None and FLAGS.eval_max_images < 1):
@@ -291,7 +295,8 @@ def make_train_eval(FLAGS, g, step, blocks=None):
     def network(gr, im):
         return model_vgg_16.model_rbox(im, is_training=False, text_scale=FLAGS.text_scale, graph=gr, blocks=blocks)
     return evaluate.TrainEval(g, step, network, FLAGS.eval_data_path, FLAGS.eval_steps, max_images=FLAGS.eval_max_images,
-                              weights=FLAGS.eval_weights, batch_size=FLAGS.batch_size_per_gpu)
+                              weights=FLAGS.eval_weights, batch_size=FLAGS.batch_size_per_gpu,
+                              protocol=FLAGS.eval_protocol)
 
 
 def _evaluate(train_eval, summaries, opt):

@@ -3,10 +3,14 @@
 
     forward -> rbox.detect_device (decode, LANMS, mean-score mask) -> ocr_eval_collect -> bboxes.bboxes_matching_batch
 
-with the counters of tool/metrics.py on the device (`metrics.DeviceTpFp`): the host reads them once per pass.  The
-matching rule is the reference's (tool/bboxes.py:171-240, rasterised IoU), NOT the official ICDAR-2015 polygon-IoU
-protocol; ground truths are matched in ORIGINAL image coordinates, detections are divided by the resize ratios as test.py
-divides them; `###` (or `*`) marks an ignored ground truth (icdar.load_annoataion).
+with the counters of tool/metrics.py on the device (`metrics.DeviceTpFp`): the host reads them once per pass.  Two
+matching rules: `protocol='raster'` (the default) is the reference's (tool/bboxes.py:171-240, rasterised IoU);
+`protocol='icdar15'` is the official ICDAR-2015 Task-1 localisation protocol (polygon IoU, `###` ground truths as
+don't-care regions, ground-truth-major greedy matching: bboxes.ic15_matching_batch), the figure
+that papers and the leaderboard report — up to three build-defined points stated there (detection order, orientation,
+self-intersecting quads), since no run of the official script pins it.  Ground truths are matched in ORIGINAL image
+coordinates, detections are divided by the resize ratios as test.py divides them; `###` (or `*`) marks an ignored
+(don't-care) ground truth (icdar.load_annoataion).
 
 `Evaluator` is the EAST RBOX geometry.  `LinkEvaluator` is the PixelLink (link) geometry of test_pixellink_fast.py, the same
 pass with another middle:
@@ -67,9 +71,24 @@ def load_ground_truth(im_fn, gt_path=None):
     return polys.astype(np.int32), np.asarray(tags, bool).reshape(-1)
 
 
+PROTOCOLS = ('raster', 'icdar15')
+
+
+def quad_is_bow_tie(poly):
+    """ocr_eval_ic15_match_batch's classification of one int quad [4,2]: counter-clockwise by the sign of the integer
+    shoelace sum, then two or more negative turns = self-intersecting."""
+    p = [(int(x), int(y)) for x, y in np.asarray(poly).reshape(4, 2)]
+    if sum(p[i][0] * p[(i + 1) % 4][1] - p[(i + 1) % 4][0] * p[i][1] for i in range(4)) < 0:
+        p[1], p[3] = p[3], p[1]
+    turns = [(p[i][0] - p[i - 1][0]) * (p[(i + 1) % 4][1] - p[i][1]) - (p[i][1] - p[i - 1][1]) * (p[(i + 1) % 4][0] - p[i][0])
+             for i in range(4)]
+    return sum(t < 0 for t in turns) >= 2
+
+
 def format_line(result):
-    return 'precision %.4f recall %.4f hmean %.4f (gt %d det %d)' % (
+    line = 'precision %.4f recall %.4f hmean %.4f (gt %d det %d)' % (
         result['precision'], result['recall'], result['hmean'], result['num_gt'], result['num_det'])
+    return line + ' [icdar15]' if result.get('protocol') == 'icdar15' else line
 
 
 class Evaluator:
@@ -78,11 +97,19 @@ class Evaluator:
     `data` is a directory of images with gt_<stem>.txt beside them, or under `gt_path` (an image without one is skipped).
     Images are resized by test.py's rule and batched by resized shape, at most `batch_size` per chain.  `run()` makes one pass and returns
     {'precision', 'recall', 'hmean', 'num_gt', 'tp', 'fp', 'num_det', 'images'}; it reads the device once at its end: the
-    record, and the two overflow counts (pixels over max_k, detections over max_d), either of which raises ValueError."""
+    record, and the two overflow counts (pixels over max_k, detections over max_d), either of which raises ValueError.
+    protocol='icdar15' swaps the matcher for the official ICDAR-2015 one (matching_threshold is its IoU threshold, the
+    area-precision threshold is 0.5): self-intersecting ground truths are dropped when the files are read and counted in
+    the result as 'invalid_gt', 'tp' / 'fp' / 'num_gt' / 'num_det' are matched / care detections - matched / care ground
+    truths / detections before the don't-care filter, and the result names its 'protocol'."""
 
     def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, score_map_thresh=0.8,
-                 nms_thres=0.2, box_thresh=None, max_k=None, max_d=ops.EVAL_MAX_D, max_side_len=3000, gt_path=None):
+                 nms_thres=0.2, box_thresh=None, max_k=None, max_d=ops.EVAL_MAX_D, max_side_len=3000, gt_path=None,
+                 protocol='raster'):
         from .tool import metrics
+        if protocol not in PROTOCOLS:
+            raise ValueError("protocol must be 'raster' or 'icdar15', got %r" % (protocol,))
+        self.protocol, self.area_prec_thr, self.invalid_gt = protocol, 0.5, 0
         self.g = graph or get_default_graph()
         self.forward = forward
         if not os.path.isdir(data):
@@ -93,6 +120,13 @@ class Evaluator:
             self.samples = self.samples[:int(max_images)]
         if not self.samples:
             raise FileNotFoundError('no image with a gt_*.txt under %r' % (data,))
+        if protocol == 'icdar15':
+            kept = []
+            for f, (polys, ignored) in self.samples:
+                ok = np.array([not quad_is_bow_tie(q) for q in polys], bool).reshape(-1)
+                self.invalid_gt += int((~ok).sum())
+                kept.append((f, (polys[ok], ignored[ok])))
+            self.samples = kept
         too_many = [f for f, (polys, _) in self.samples if len(polys) > ops.EVAL_MAX_G]
         if too_many:
             raise ValueError('more than %d ground truths in %s' % (ops.EVAL_MAX_G, too_many[0]))
@@ -158,6 +192,12 @@ class Evaluator:
         nd_total = torch.empty_like(nd)
         ops.eval_collect(merged, keep, n_keep, None if passed is None else passed.to(torch.uint8), inv_ratio, dets,
                          det_score, nd, nd_total)
+        if self.protocol == 'icdar15':
+            det_match, gt_match, _ = bboxes.ic15_matching_batch(dets, nd, gts, ng, gign, self.matching_threshold,
+                                                                self.area_prec_thr, record=self.acc.record, graph=g)
+            self.last = dict(dets=dets, det_score=det_score, nd=nd, nd_total=nd_total, det_match=det_match,
+                             gt_match=gt_match, gts=gts, ng=ng, gdontcare=gign)
+            return total - max_k, nd_total - self.max_d
         tp, fp, _ = bboxes.bboxes_matching_batch(dets, nd, gts, ng, gign, self.matching_threshold, record=self.acc.record,
                                                  graph=g, mask_hw=mask_hw)
         self.last = dict(dets=dets, det_score=det_score, nd=nd, nd_total=nd_total, tp=tp, fp=fp, gts=gts, ng=ng)
@@ -195,8 +235,11 @@ class Evaluator:
             raise ValueError('an image kept %d detections more than max_d = %d' % (worst_d, self.max_d))
         precision, recall = metrics.precision_recall(num_gt, tp, fp)
         hmean = metrics.fmean(precision, recall) if precision + recall > 0 else 0.0
-        return {'precision': precision, 'recall': recall, 'hmean': hmean, 'num_gt': num_gt, 'tp': tp, 'fp': fp,
-                'num_det': n_det, 'images': len(self.samples)}
+        result = {'precision': precision, 'recall': recall, 'hmean': hmean, 'num_gt': num_gt, 'tp': tp, 'fp': fp,
+                  'num_det': n_det, 'images': len(self.samples)}
+        if self.protocol == 'icdar15':
+            result.update(invalid_gt=self.invalid_gt, protocol=self.protocol)
+        return result
 
 
 class LinkEvaluator(Evaluator):
@@ -213,9 +256,9 @@ class LinkEvaluator(Evaluator):
 
     def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, pixel_conf_threshold=0.8,
                  link_conf_threshold=0.9, min_size=10, max_comps=4096, min_side=0.0, min_area=0.0, max_d=ops.EVAL_MAX_D,
-                 eval_image_height=768, eval_image_width=1280, gt_path=None):
+                 eval_image_height=768, eval_image_width=1280, gt_path=None, protocol='raster'):
         super().__init__(graph, forward, data, batch_size=batch_size, max_images=max_images,
-                         matching_threshold=matching_threshold, max_d=max_d, gt_path=gt_path)
+                         matching_threshold=matching_threshold, max_d=max_d, gt_path=gt_path, protocol=protocol)
         self.eval_hw = (int(eval_image_height), int(eval_image_width))
         if min(self.eval_hw) < 4 or self.eval_hw[0] % 4 or self.eval_hw[1] % 4:
             raise ValueError('the eval size must be positive multiples of 4, got %dx%d' % self.eval_hw)

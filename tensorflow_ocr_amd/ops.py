@@ -1289,6 +1289,32 @@ def eval_match_batch(dets, nd, gts, ng, gignored, threshold, mask_h, mask_w, tp,
            c_float(threshold), c_int(mask_h), c_int(mask_w), ptr(tp), ptr(fp), ptr(record), ptr(buf), c_size_t(nbytes), _st())
 
 
+def eval_ic15_match_batch(dets, nd, gts, ng, gdontcare, iou_thr, area_prec_thr, det_match, gt_match, record, ws, inter=None):
+    """The ICDAR-2015 matching of n images in one call (include/ocr_eval_ic15.h): dets int32 [n,max_d,4,2] / nd int32 [n] in
+    ocr_eval_collect's order, gts int32 [n,max_g,4,2] / ng int32 [n], gdontcare uint8 [n,max_g] -> det_match int32 [n,max_d]
+    (gt index, -1 unmatched, -2 don't-care), gt_match int32 [n,max_g] (det index, -1, -2); record int64 [4] is added to;
+    inter: optional float64 [n,max_g,max_d], the pair intersection areas."""
+    n, max_d = dets.shape[:2]
+    max_g = gts.shape[1]
+    if tuple(dets.shape) != (n, max_d, 4, 2) or tuple(gts.shape) != (n, max_g, 4, 2) or nd.numel() != n or ng.numel() != n or \
+            tuple(gdontcare.shape) != (n, max_g) or tuple(det_match.shape) != (n, max_d) or \
+            tuple(gt_match.shape) != (n, max_g) or record.numel() != 4 or \
+            (inter is not None and tuple(inter.shape) != (n, max_g, max_d)):
+        raise ValueError("eval_ic15_match_batch: tensors do not match n, max_d, max_g")
+    if dets.dtype != torch.int32 or gts.dtype != torch.int32 or nd.dtype != torch.int32 or ng.dtype != torch.int32 or \
+            gdontcare.dtype != torch.uint8 or det_match.dtype != torch.int32 or gt_match.dtype != torch.int32 or \
+            record.dtype != torch.int64 or (inter is not None and inter.dtype != torch.float64):
+        raise ValueError("eval_ic15_match_batch: quads, counts and matches int32, flags uint8, record int64, inter float64")
+    for t in (dets, nd, gts, ng, gdontcare, det_match, gt_match, record) + (() if inter is None else (inter,)):
+        if not t.is_contiguous():
+            raise ValueError("eval_ic15_match_batch: contiguous tensors only")
+    nbytes = L.call_size("ocr_eval_ic15_workspace", c_int(n), c_int(max_d), c_int(max_g))
+    buf = ws.get(nbytes)
+    L.call("ocr_eval_ic15_match_batch", ptr(dets), ptr(nd), ptr(gts), ptr(ng), ptr(gdontcare), c_int(n), c_int(max_d),
+           c_int(max_g), c_double(iou_thr), c_double(area_prec_thr), ptr(det_match), ptr(gt_match), ptr(inter), ptr(record),
+           ptr(buf), c_size_t(nbytes), _st())
+
+
 def eval_record_init(record):
     if record.numel() != 4 or record.dtype != torch.int64 or not record.is_contiguous():
         raise ValueError("eval_record_init: record is int64 [4]")

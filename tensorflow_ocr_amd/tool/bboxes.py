@@ -65,6 +65,30 @@ def bboxes_matching_batch(dets, nd, gts, ng, gignored, matching_threshold=0.5, r
     return tp, fp, record
 
 
+def ic15_matching_batch(dets, nd, gts, ng, gdontcare, iou_thr=0.5, area_prec_thr=0.5, record=None, graph=None, inter=None):
+    """The official ICDAR-2015 Task-1 matching for a batch, on the device and without a synchronisation
+    (ocr_eval_ic15_match_batch, include/ocr_eval_ic15.h): polygon IoU instead of rasters, `###` ground truths as don't-care
+    regions (a detection more than area_prec_thr inside one is left out of the count), ground-truth-major greedy
+    matching with a strict iou > iou_thr.  Operands as `bboxes_matching_batch`; no mask extent is needed.  record: int64
+    [4] device tensor that {care ground truths, matched, care detections - matched, detections} are ADDED to
+    (`metrics.DeviceTpFp.record`, the same slots: precision_recall / fmean apply unchanged); None: a fresh zeroed one.
+    inter: optional float64 [n,max_g,max_d] that receives the pair intersection areas.
+    Returns (det_match, gt_match, record): int32 [n,max_d] (gt index, -1 unmatched, -2 don't-care; -1 beyond nd), int32
+    [n,max_g] (det index, -1 unmatched, -2 don't-care or bow-tie; -1 beyond ng) and the record."""
+    g = graph or get_default_graph()
+    n, max_d = dets.shape[:2]
+    if gdontcare.dtype == torch.bool:
+        gdontcare = gdontcare.to(torch.uint8)
+    if record is None:
+        record = torch.empty((4,), dtype=torch.int64, device=g.device)
+        ops.eval_record_init(record)
+    det_match = torch.empty((n, max_d), dtype=torch.int32, device=g.device)
+    gt_match = torch.empty((n, gts.shape[1]), dtype=torch.int32, device=g.device)
+    ops.eval_ic15_match_batch(dets, nd, gts, ng, gdontcare, float(iou_thr), float(area_prec_thr), det_match, gt_match, record,
+                              g.workspace(), inter=inter)
+    return det_match, gt_match, record
+
+
 def bboxes_matching(bboxes, gxs, gys, gignored, matching_threshold=0.5, scope=None, graph=None):
     """tool/bboxes.py:171-240.  bboxes [N,8] detections sorted by score, gxs/gys [G,4], gignored [G].
     Returns (n_gbboxes, tp_match bool [N], fp_match bool [N]): a detection is a TP when its best

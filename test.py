@@ -50,9 +50,14 @@ def parse(argv=None):
                     "(ICDAR layout, ### = ignored).  After the run the detections are matched against them on the device "
                     "(tensorflow_ocr_amd.evaluate: the reference's raster-IoU rule, not the official ICDAR protocol) and one "
                     "line `precision .. recall .. hmean .. (gt .. det ..)` is printed")
+    ap.add_argument('--eval_protocol', choices=['raster', 'icdar15'], default='raster', help="with --gt_path: raster = the "
+                    "reference's rule above; icdar15 = the official ICDAR-2015 protocol (polygon IoU, ### as don't-care "
+                    "regions), the line then ends in [icdar15]")
     FLAGS = ap.parse_args(argv)
     if FLAGS.gt_path is not None and FLAGS.geometry != 'RBOX':
         ap.error('--gt_path needs --geometry RBOX (the link geometry\'s contour decode ends on the host)')
+    if FLAGS.eval_protocol != 'raster' and FLAGS.gt_path is None:
+        ap.error('--eval_protocol needs --gt_path')
     return FLAGS
 
 
@@ -197,7 +202,8 @@ def main_rbox(FLAGS):
         # a second pass over the same images with the restored weights: forward -> decode -> LANMS -> filter -> match
         # per batch on the device, one read of the counters at its end
         from tensorflow_ocr_amd import evaluate
-        ev = evaluate.Evaluator(g, forward, FLAGS.test_data_path, gt_path=FLAGS.gt_path, box_thresh=FLAGS.box_thresh)
+        ev = evaluate.Evaluator(g, forward, FLAGS.test_data_path, gt_path=FLAGS.gt_path, box_thresh=FLAGS.box_thresh,
+                                protocol=FLAGS.eval_protocol)
         print(evaluate.format_line(ev.run()), flush=True)
 
 

@@ -84,6 +84,8 @@ def parse(argv=None):
     ap.add_argument('--eval_weights', choices=['ema', 'raw'], default='ema')
     ap.add_argument('--eval_image_width', type=int, default=1280)
     ap.add_argument('--eval_image_height', type=int, default=768)
+    # --eval_protocol: raster = the reference's matching rule, icdar15 = the official ICDAR-2015 protocol (polygon IoU)
+    ap.add_argument('--eval_protocol', choices=['raster', 'icdar15'], default='raster')
     FLAGS = ap.parse_args(argv)
     if FLAGS.eval_steps < 0 or (FLAGS.eval_max_images is not None and FLAGS.eval_max_images < 1):
         ap.error('--eval_steps must not be negative and --eval_max_images must be positive')
@@ -219,7 +221,7 @@ def make_train_eval(FLAGS, g, step):
     return evaluate.TrainEval(g, step, network, FLAGS.eval_data_path, FLAGS.eval_steps, max_images=FLAGS.eval_max_images,
                               weights=FLAGS.eval_weights, batch_size=max(1, int(FLAGS.batch_size / FLAGS.num_gpus)),
                               evaluator=evaluate.LinkEvaluator, eval_image_height=FLAGS.eval_image_height,
-                              eval_image_width=FLAGS.eval_image_width)
+                              eval_image_width=FLAGS.eval_image_width, protocol=FLAGS.eval_protocol)
 
 
 def _evaluate(train_eval, summaries, opt):
