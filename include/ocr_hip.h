@@ -870,14 +870,15 @@ int ocr_softmax_pairs(const void* logits, int64_t pairs, void* probs, void* stre
 /* link_logits [m][16] -> [8][m][2]: tf.stack of the eight per-direction softmaxes */
 int ocr_link_softmax_stack(const void* link_logits, int64_t m, void* out, void* stream);
 /* pixel_detect: score_map [n,h,w,1], link_scores [8,n,h,w,2] -> uint8 [h,w] for batch element 0:
- * score > score_map_thresh and every link[i,0,y,x,1] >= link_thresh */
+ * score > score_map_thresh and every link[i,0,y,x,1] >= link_thresh.  h*w > INT32_MAX: OCR_ERR_UNSUPPORTED. */
 int ocr_pixel_detect(const void* score_map, const void* link_scores, int n, int h, int w,
                      float score_map_thresh, float link_thresh, void* mask_u8, void* stream);
 /* Link-gated connected components, batched.  pixel_score [n,h,w]; link_score element
  * (d, img, y, x) at ((d*n+img)*h*w + y*w+x)*link_elem_stride + link_elem_offset.  Outputs: labels
  * int32 [n,h,w] (0 = background, dense ids 1..K in ascending order of each component's smallest
  * pixel index, only components with more than min_size pixels), ncomp [n], comps
- * [n][max_comps][2] = (smallest pixel index, size). */
+ * [n][max_comps][2] = (smallest pixel index, size): ncomp is the true count, rows at or beyond
+ * min(ncomp, max_comps) are not written.  h, w >= 3.  n > 65535 or h*w > INT32_MAX: OCR_ERR_UNSUPPORTED. */
 size_t ocr_link_cc_workspace(int n, int h, int w);
 int ocr_link_cc(const void* pixel_score, const void* link_score, int link_elem_stride,
                 int link_elem_offset, int n, int h, int w, float pixel_thresh, float link_thresh,
@@ -894,7 +895,8 @@ int ocr_link_cc(const void* pixel_score, const void* link_score, int link_elem_s
  * pixel index (the order rounds 1-3 of this build used).  Bit-exact against
  * oracle.ocr_oracle.link_cc_reference_dfs(key_order="py27" | "ascending").
  * Cost: ONE 1024-thread workgroup per image, rounds x sweeps of full-image scans: ~1 ms per 256 x 256 map, but
- * seconds per image at 720 x 1280 with many failing seeds — an exactness mode, opt-in, never the throughput path. */
+ * seconds per image at 720 x 1280 with many failing seeds — an exactness mode, opt-in, never the throughput path.
+ * h*w > INT32_MAX: OCR_ERR_UNSUPPORTED. */
 size_t ocr_link_cc_directed_workspace(int n, int h, int w);
 int ocr_link_cc_directed(const void* pixel_score, const void* link_score, int link_elem_stride,
                          int link_elem_offset, int n, int h, int w, float pixel_thresh, float link_thresh,
@@ -982,7 +984,9 @@ int ocr_rbox_decode(const void* score, const void* geo, int n, int h, int w, flo
  * (image, id-1) in [n][max_comps]: hull_n = number of convex-hull vertices (0: id without pixels),
  * hull_head [4] = the first two hull vertices (x0,y0,x1,y1) in OpenCV's clockwise order,
  * calipers [6] = (corner x, corner y, edge-1 vector, edge-2 vector) of the minimum-area rectangle
- * (zeros when hull_n <= 2).  RotatedRect / boxPoints are O(1) per box on the host.
+ * (zeros when hull_n <= 2; hull_head and calipers are not written when hull_n = 0, nothing for ids beyond
+ * min(ncomp, max_comps)).  RotatedRect / boxPoints are O(1) per box on the host.  scale < 1, h > 1024, n or
+ * max_comps > 65535, w*scale_x or h*scale_y >= 2^24, h*w > INT32_MAX: OCR_ERR_UNSUPPORTED.
  * ------------------------------------------------------------------------- */
 size_t ocr_min_area_rects_workspace(int n, int h, int w, int max_comps);
 int ocr_min_area_rects(const void* labels_i32, const void* ncomp_i32, int n, int h, int w, int max_comps,
@@ -995,27 +999,31 @@ int ocr_min_area_rects(const void* labels_i32, const void* ncomp_i32, int n, int
  * ------------------------------------------------------------------------- */
 /* mask = score > score_thresh (score f32 [h][w]); first_second int32 [2][8] (pre-filled with INT_MAX)
  * receives, per link channel c, the raster indices of the first and the second pixel with
- * link16[.., 2c+1] < link_thresh — the only two `argwhere` rows test.py:70-72 uses. */
+ * link16[.., 2c+1] < link_thresh — the only two `argwhere` rows test.py:70-72 uses.  h*w > INT32_MAX:
+ * OCR_ERR_UNSUPPORTED. */
 int ocr_east_pixel_detect(const void* score_f32, const void* link16_f32, int h, int w, float score_thresh,
                           float link_thresh, void* mask_u8, void* first_second_i32, void* stream);
+/* mask[idx[k]] = 0 for k < count; one 256-thread block: 0 <= count <= 256 (0: nothing launched), else
+ * OCR_ERR_INVALID_ARG. */
 int ocr_zero_pixels_u8(void* mask_u8, const void* idx_i32, int count, void* stream);
 /* Parent links of cv2.findContours(mask, RETR_TREE, ...) (test.py:182), from the two ocr_mask_cc
  * labellings of one mask (labels/comps: 8-connected components of the 1-pixels; zlabels/zcomps:
  * 4-connected regions of the 0-pixels): parent_c[i] = 0-region left of component i's first pixel,
  * parent_z[j] = component left of region j's first pixel; 0 = column 0 (the frame).  The host derives
- * OpenCV's list order from them (newest sibling first, pre-order). */
+ * OpenCV's list order from them (newest sibling first, pre-order).  ncomp + nregions > INT32_MAX:
+ * OCR_ERR_UNSUPPORTED. */
 int ocr_contour_parents(const void* labels_i32, const void* zlabels_i32, const void* comps_i32, int ncomp,
                         const void* zcomps_i32, int nregions, int h, int w, void* parent_c_i32,
                         void* parent_z_i32, void* stream);
 /* Connected components of the pixels with (mask != 0) == (value != 0), connectivity 4 or 8; outputs as
  * ocr_link_cc (dense ids in ascending order of the smallest pixel index).  Workspace:
- * ocr_link_cc_workspace(n, h, w). */
+ * ocr_link_cc_workspace(n, h, w).  h, w >= 1.  n > 65535 or h*w > INT32_MAX: OCR_ERR_UNSUPPORTED. */
 int ocr_mask_cc(const void* mask_u8, int value, int connectivity, int n, int h, int w, void* labels_i32,
                 void* ncomp_i32, void* comps_i32, int max_comps, void* workspace, size_t ws_bytes, void* stream);
 /* Inner contours: zlabels = 4-connected components of the 0-pixels (ocr_mask_cc value 0).  A region
  * touching the image edge is background; any other is a hole whose contour is the set of 1-pixels
  * with a 4-neighbour in it.  Per region id: hull_n (0 for background regions), hull_head, calipers as
- * ocr_min_area_rects. */
+ * ocr_min_area_rects; the same limits, with 3*h*w <= INT32_MAX (the row table holds three entries per pixel). */
 size_t ocr_hole_border_rects_workspace(int n, int h, int w, int max_regions);
 int ocr_hole_border_rects(const void* mask_u8, const void* zlabels_i32, const void* nregions_i32, int n, int h,
                           int w, int max_regions, double scale_x, double scale_y, void* hull_n_i32,

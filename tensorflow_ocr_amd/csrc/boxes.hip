@@ -380,6 +380,7 @@ extern "C" int ocr_min_area_rects(const void* labels_i32, const void* ncomp_i32,
   // strictly increasing integer maps (rows stay distinct) and LDS staging of one component's rows
   OCR_CHECK_SHAPE(scale_x >= 1.0 && scale_y >= 1.0 && h <= kMaxRows && max_comps <= 65535 && n <= 65535);
   OCR_CHECK_SHAPE((double)w * scale_x < 16777216.0 && (double)h * scale_y < 16777216.0);   // exact in f32
+  OCR_CHECK_SHAPE((int64_t)h * w <= INT32_MAX);                                            // row-table entries per image are int
   if (ws_bytes < ocr_min_area_rects_workspace(n, h, w, max_comps)) return OCR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   MarP p{n, h, w, max_comps, scale_x, scale_y, h * w};
@@ -417,6 +418,7 @@ extern "C" int ocr_hole_border_rects(const void* mask_u8, const void* zlabels_i3
   OCR_CHECK_ARG(n > 0 && h > 0 && w > 0 && max_regions > 0);
   OCR_CHECK_SHAPE(scale_x >= 1.0 && scale_y >= 1.0 && h <= kMaxRows && max_regions <= 65535 && n <= 65535);
   OCR_CHECK_SHAPE((double)w * scale_x < 16777216.0 && (double)h * scale_y < 16777216.0);
+  OCR_CHECK_SHAPE((int64_t)3 * h * w <= INT32_MAX);
   if (ws_bytes < ocr_hole_border_rects_workspace(n, h, w, max_regions)) return OCR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   MarP p{n, h, w, max_regions, scale_x, scale_y, 3 * h * w};

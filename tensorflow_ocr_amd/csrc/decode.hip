@@ -506,6 +506,7 @@ extern "C" int ocr_pixel_detect(const void* score_map, const void* link_scores, 
                                 float score_map_thresh, float link_thresh, void* mask_u8,
                                 void* stream) {
   OCR_CHECK_ARG(score_map && link_scores && mask_u8 && n > 0 && h > 0 && w > 0);
+  OCR_CHECK_SHAPE((int64_t)h * w <= INT32_MAX);                  // the kernel indexes a map with int
   hipLaunchKernelGGL(pixel_detect_kernel, dim3(ocr_cdiv(h * w, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const float*>(score_map),
                      static_cast<const float*>(link_scores), n, h, w, score_map_thresh, link_thresh,
@@ -533,6 +534,7 @@ extern "C" int ocr_link_cc(const void* pixel_score, const void* link_score, int 
                            size_t ws_bytes, void* stream) {
   OCR_CHECK_ARG(pixel_score && link_score && labels_i32 && ncomp_i32 && comps_i32 && workspace);
   OCR_CHECK_ARG(n > 0 && h > 2 && w > 2 && max_comps > 0);
+  OCR_CHECK_SHAPE(n <= 65535 && (int64_t)h * w <= INT32_MAX);    // images are gridDim.y; pixel indices of a map are int
   if (ws_bytes < ocr_link_cc_workspace(n, h, w)) return OCR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t total = (size_t)n * h * w;
@@ -622,6 +624,7 @@ extern "C" int ocr_link_cc_directed(const void* pixel_score, const void* link_sc
                 workspace);
   OCR_CHECK_ARG(n > 0 && h > 2 && w > 2 && max_comps > 0 && labels_i32 != union_labels_i32);
   OCR_CHECK_ARG(link_elem_stride >= 1 && link_elem_offset >= 0 && link_elem_offset < link_elem_stride);
+  OCR_CHECK_SHAPE((int64_t)h * w <= INT32_MAX);
   if (ws_bytes < ocr_link_cc_directed_workspace(n, h, w)) return OCR_ERR_WORKSPACE;
   CcP p{n, h, w, min_size, pixel_thresh, link_thresh, link_elem_stride, link_elem_offset};
   const size_t total = (size_t)n * h * w;
@@ -640,6 +643,7 @@ extern "C" int ocr_mask_cc(const void* mask_u8, int value, int connectivity, int
                            void* stream) {
   OCR_CHECK_ARG(mask_u8 && labels_i32 && ncomp_i32 && comps_i32 && workspace);
   OCR_CHECK_ARG(n > 0 && h > 0 && w > 0 && max_comps > 0 && (connectivity == 4 || connectivity == 8));
+  OCR_CHECK_SHAPE(n <= 65535 && (int64_t)h * w <= INT32_MAX);    // as ocr_link_cc
   if (ws_bytes < ocr_link_cc_workspace(n, h, w)) return OCR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t total = (size_t)n * h * w;
@@ -668,6 +672,7 @@ extern "C" int ocr_mask_cc(const void* mask_u8, int value, int connectivity, int
 extern "C" int ocr_east_pixel_detect(const void* score_f32, const void* link16_f32, int h, int w, float score_thresh,
                                      float link_thresh, void* mask_u8, void* first_second_i32, void* stream) {
   OCR_CHECK_ARG(score_f32 && link16_f32 && mask_u8 && first_second_i32 && h > 0 && w > 0);
+  OCR_CHECK_SHAPE((int64_t)h * w <= INT32_MAX);
   hipStream_t st = static_cast<hipStream_t>(stream);
   int* fs = static_cast<int*>(first_second_i32);      // [2][8], pre-filled with INT_MAX by the caller
   const int hw = h * w;
@@ -702,6 +707,7 @@ extern "C" int ocr_contour_parents(const void* labels_i32, const void* zlabels_i
                                    void* parent_c_i32, void* parent_z_i32, void* stream) {
   OCR_CHECK_ARG(labels_i32 && zlabels_i32 && comps_i32 && zcomps_i32 && parent_c_i32 && parent_z_i32);
   OCR_CHECK_ARG(ncomp >= 0 && nregions >= 0 && h > 0 && w > 0);
+  OCR_CHECK_SHAPE((int64_t)ncomp + nregions <= INT32_MAX);
   if (ncomp + nregions == 0) return OCR_OK;
   hipLaunchKernelGGL(contour_parents_kernel, dim3((ncomp + nregions + 255) / 256), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const int*>(labels_i32),
