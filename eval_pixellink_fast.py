@@ -22,6 +22,16 @@ import tempfile
 import numpy as np
 
 
+def _sweep_arg(text):
+    from tensorflow_ocr_amd.evaluate import sweep_arg
+    return sweep_arg(text)
+
+
+def _sweep_help():
+    from tensorflow_ocr_amd.evaluate import SWEEP_HELP
+    return SWEEP_HELP % "the component's mean pixel score, in [0, 1]"
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--checkpoint_path', type=str, default=None)
@@ -41,6 +51,7 @@ def parse(argv=None):
     ap.add_argument('--eval_protocol', choices=['raster', 'icdar15'], default='raster', help="raster = the reference's "
                     "matching rule; icdar15 = the official ICDAR-2015 protocol (polygon IoU, ### as don't-care regions), the "
                     "line then ends in [icdar15]")
+    ap.add_argument('--eval_sweep', type=_sweep_arg, default=None, metavar='LO:HI:N', help=_sweep_help())
     FLAGS = ap.parse_args(argv)
     if FLAGS.min_side < 0 or FLAGS.min_area < 0:
         ap.error('--min_side and --min_area must not be negative')
@@ -85,9 +96,12 @@ def main(argv=None):
                                 pixel_conf_threshold=FLAGS.pixel_conf_threshold,
                                 link_conf_threshold=FLAGS.link_conf_threshold, min_side=FLAGS.min_side,
                                 min_area=FLAGS.min_area, eval_image_height=H, eval_image_width=W,
-                                protocol=FLAGS.eval_protocol)
+                                protocol=FLAGS.eval_protocol, sweep=FLAGS.eval_sweep)
     try:
-        print(evaluate.format_line(ev.run()), flush=True)
+        res = ev.run()
+        print(evaluate.format_line(res), flush=True)
+        if FLAGS.eval_sweep is not None:
+            print(evaluate.format_sweep(res), flush=True)
     finally:
         if tmp is not None:
             tmp.cleanup()

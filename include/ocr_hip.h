@@ -1122,6 +1122,9 @@ int ocr_eval_record_init(void* record_i64, void* stream);
 /* The official ICDAR-2015 protocol (polygon IoU, don't-care regions) on the same operands and the same record: its two
  * entries and their comment block are in a header of their own, part of this ABI. */
 #include "ocr_eval_ic15.h"
+/* The score-threshold sweep and average precision counted from either matcher's outputs: its entries and their comment
+ * block are in a header of their own, part of this ABI. */
+#include "ocr_eval_curve.h"
 
 /* ------------------------------------------------------------------------- *
  * Link-geometry detections on the device (csrc/link_boxes.hip): what lies between ocr_min_area_rects and

@@ -30,6 +30,11 @@ import numpy as np
 import torch
 
 
+def _sweep_arg(text):
+    from tensorflow_ocr_amd.evaluate import sweep_arg
+    return sweep_arg(text)
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--input_size', type=int, default=512)
@@ -78,7 +83,12 @@ def parse(argv=None):
     ap.add_argument('--eval_weights', choices=['ema', 'raw'], default='ema')
     # --eval_protocol: raster = the reference's matching rule, icdar15 = the official ICDAR-2015 protocol (polygon IoU)
     ap.add_argument('--eval_protocol', choices=['raster', 'icdar15'], default='raster')
+    # --eval_sweep LO:HI:N (or a comma list): every pass also reports the precision / recall curve over LANMS's merged score (a
+    # sum of pixel scores, not a probability), its best row and AP, from the one matching pass (evaluate.Evaluator's sweep)
+    ap.add_argument('--eval_sweep', type=_sweep_arg, default=None, metavar='LO:HI:N')
     FLAGS = ap.parse_args(argv)
+    if FLAGS.eval_sweep is not None and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
+        ap.error('--eval_sweep needs --eval_data_path and --eval_steps')
     if FLAGS.eval_protocol != 'raster' and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
         ap.error('--eval_protocol needs --eval_data_path and --eval_steps')
     if FLAGS.geometry == 'RBOX' and FLAGS.net != 'east':
@@ -296,15 +306,18 @@ def make_train_eval(FLAGS, g, step, blocks=None):
         return model_vgg_16.model_rbox(im, is_training=False, text_scale=FLAGS.text_scale, graph=gr, blocks=blocks)
     return evaluate.TrainEval(g, step, network, FLAGS.eval_data_path, FLAGS.eval_steps, max_images=FLAGS.eval_max_images,
                               weights=FLAGS.eval_weights, batch_size=FLAGS.batch_size_per_gpu,
-                              protocol=FLAGS.eval_protocol)
+                              protocol=FLAGS.eval_protocol, sweep=FLAGS.eval_sweep)
 
 
 def _evaluate(train_eval, summaries, opt):
     """One pass between two steps (rank 0; the other ranks meet it at the next exchange): the line test.py prints, and
-    eval/precision, eval/recall, eval/hmean in the event file where one is open."""
+    eval/precision, eval/recall, eval/hmean (with --eval_sweep also eval/ap, eval/best_hmean, eval/best_threshold) in the
+    event file where one is open."""
     from tensorflow_ocr_amd import evaluate
     res = train_eval.run()
     print('Step {:06d}, '.format(opt.global_step) + evaluate.format_line(res), flush=True)
+    if 'sweep' in res:
+        print(evaluate.format_sweep(res), flush=True)
     if summaries is not None:
         train_eval.write(summaries.writer, opt.global_step)
 

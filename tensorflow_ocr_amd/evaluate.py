@@ -18,7 +18,10 @@ pass with another middle:
     forward -> softmaxes -> pixellink_fn.detect_device (link_cc, min-area rectangles, component scores, boxes) -> ...
 
 (test.py's own link path, the contour decode of pixellink_fn.find_contour_boxes, still ends on the host and is not
-evaluated here)."""
+evaluated here).
+
+`sweep=[...]` (`--eval_sweep`) adds the precision / recall curve over detection scores, its best row and average
+precision, counted on the device from the same matching pass (include/ocr_eval_curve.h)."""
 import os
 
 import numpy as np
@@ -91,6 +94,72 @@ def format_line(result):
     return line + ' [icdar15]' if result.get('protocol') == 'icdar15' else line
 
 
+def parse_sweep(text):
+    """--eval_sweep: 'LO:HI:N' = N evenly spaced thresholds from LO to HI (both included), or a comma list of numbers ->
+    a list of 1..64 floats; ValueError otherwise."""
+    text = str(text).strip()
+    if ':' in text:
+        parts = text.split(':')
+        if len(parts) != 3:
+            raise ValueError('a sweep range is LO:HI:N, got %r' % (text,))
+        lo, hi, n = float(parts[0]), float(parts[1]), int(parts[2])
+        if n < 1 or (n == 1 and lo != hi):
+            raise ValueError('a sweep range needs N >= 2 thresholds (or LO = HI), got %r' % (text,))
+        values = [lo] if n == 1 else [lo + (hi - lo) * k / (n - 1) for k in range(n)]
+    else:
+        values = [float(v) for v in text.split(',') if v.strip()]
+    return check_sweep(values)
+
+
+SWEEP_HELP = ("also report precision / recall / hmean with only the detections of score >= each threshold kept, the best "
+              "of them and AP, counted from the one matching pass: LO:HI:N = N evenly spaced thresholds, or a comma list "
+              "(at most 64).  The threshold is on the matcher's order key: %s")
+
+
+def sweep_arg(text):
+    """`parse_sweep` as an argparse type"""
+    import argparse
+    try:
+        return parse_sweep(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def check_sweep(sweep):
+    values = [float(v) for v in sweep]
+    if not 1 <= len(values) <= ops.EVAL_MAX_T:
+        raise ValueError('a sweep takes 1 to %d thresholds, got %d' % (ops.EVAL_MAX_T, len(values)))
+    return values
+
+
+def sweep_rows(thresholds, rows):
+    """curve rows [T][4] -> the 'sweep' list of a result, and its 'best' row (highest hmean, ties to the lowest index)"""
+    from .tool import metrics
+    out = []
+    for thr, (num_gt, tp, fp, n_det) in zip(thresholds, rows):
+        precision, recall = metrics.precision_recall(num_gt, tp, fp)
+        hmean = metrics.fmean(precision, recall) if precision + recall > 0 else 0.0
+        out.append({'threshold': thr, 'precision': precision, 'recall': recall, 'hmean': hmean, 'tp': tp, 'fp': fp,
+                    'num_det': n_det})
+    best = out[0]
+    for row in out[1:]:
+        if row['hmean'] > best['hmean']:
+            best = row
+    return out, best
+
+
+def format_sweep(result):
+    """the lines of a result's sweep: one per threshold, the best one marked, and AP"""
+    lines = []
+    for row in result['sweep']:
+        lines.append('  score >= %-10.6g precision %.4f recall %.4f hmean %.4f (tp %d fp %d det %d)%s' % (
+            row['threshold'], row['precision'], row['recall'], row['hmean'], row['tp'], row['fp'], row['num_det'],
+            ' *' if row is result['best'] else ''))
+    lines.append('  AP %.4f, best hmean %.4f at score >= %.6g' % (result['ap'], result['best']['hmean'],
+                                                                result['best']['threshold']))
+    return '\n'.join(lines)
+
+
 class Evaluator:
     """Evaluator(graph, forward, data): `forward(x)` takes a device f32 [n,H,W,3] batch (0..255, RGB) and returns the
     (score [n,H/4,W/4,1], geometry [n,H/4,W/4,5]) maps of model_rbox (tensors or head handles) as a pure launch sequence;
@@ -101,15 +170,25 @@ class Evaluator:
     protocol='icdar15' swaps the matcher for the official ICDAR-2015 one (matching_threshold is its IoU threshold, the
     area-precision threshold is 0.5): self-intersecting ground truths are dropped when the files are read and counted in
     the result as 'invalid_gt', 'tp' / 'fp' / 'num_gt' / 'num_det' are matched / care detections - matched / care ground
-    truths / detections before the don't-care filter, and the result names its 'protocol'."""
+    truths / detections before the don't-care filter, and the result names its 'protocol'.
+
+    sweep: None, or a sequence of 1..64 score thresholds.  Then the pass also counts, from the SAME matching (no walk is
+    repeated: DESIGN.md §3.3.18), what the matcher gives with only the detections of score >= threshold kept, and the
+    result gains 'sweep' (a list of {'threshold', 'precision', 'recall', 'hmean', 'tp', 'fp', 'num_det'}), 'best' (its
+    row of highest hmean, ties to the lowest index) and 'ap' (average precision over the pooled detection scores of the
+    pass); still one device read.  The threshold is on the MATCHER'S ORDER KEY, ocr_eval_collect's det_score: for this
+    geometry that is LANMS's merged score, a SUM of the merged pixels' scores — not a probability and not EAST's
+    box_thresh mean; for `LinkEvaluator` it is the component's mean pixel score, in [0, 1].  Sweeping box_thresh,
+    score_map_thresh or the link threshold would change the detection set or its order and is not what this does."""
 
     def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, score_map_thresh=0.8,
                  nms_thres=0.2, box_thresh=None, max_k=None, max_d=ops.EVAL_MAX_D, max_side_len=3000, gt_path=None,
-                 protocol='raster'):
+                 protocol='raster', sweep=None):
         from .tool import metrics
         if protocol not in PROTOCOLS:
             raise ValueError("protocol must be 'raster' or 'icdar15', got %r" % (protocol,))
         self.protocol, self.area_prec_thr, self.invalid_gt = protocol, 0.5, 0
+        self.sweep = None if sweep is None else check_sweep(sweep)
         self.g = graph or get_default_graph()
         self.forward = forward
         if not os.path.isdir(data):
@@ -137,6 +216,7 @@ class Evaluator:
         self.score_map_thresh, self.nms_thres, self.box_thresh = float(score_map_thresh), float(nms_thres), box_thresh
         self.max_k, self.max_d, self.max_side_len = max_k, int(max_d), max_side_len
         self.acc = metrics.DeviceTpFp(self.g)
+        self.curve = None if self.sweep is None else metrics.DeviceCurve(self.sweep, len(self.samples), self.max_d, self.g)
         self.last = None          # the device tensors of the last chain (tests and the cost script look at them)
 
     # -- one chain -------------------------------------------------------------------------------
@@ -197,10 +277,15 @@ class Evaluator:
                                                                 self.area_prec_thr, record=self.acc.record, graph=g)
             self.last = dict(dets=dets, det_score=det_score, nd=nd, nd_total=nd_total, det_match=det_match,
                              gt_match=gt_match, gts=gts, ng=ng, gdontcare=gign)
+            if self.curve is not None:
+                self.curve.add_ic15(det_match, gt_match, det_score, nd, ng)
             return total - max_k, nd_total - self.max_d
         tp, fp, _ = bboxes.bboxes_matching_batch(dets, nd, gts, ng, gign, self.matching_threshold, record=self.acc.record,
                                                  graph=g, mask_hw=mask_hw)
         self.last = dict(dets=dets, det_score=det_score, nd=nd, nd_total=nd_total, tp=tp, fp=fp, gts=gts, ng=ng)
+        if self.curve is not None:
+            self.last['gignored'] = gign
+            self.curve.add_raster(tp, fp, det_score, nd, ng, gign if gign.dtype == torch.uint8 else gign.to(torch.uint8))
         return total - max_k, nd_total - self.max_d          # > 0: overflow (device tensors, read at the end of the pass)
 
     def _overflow(self, worst):
@@ -211,6 +296,8 @@ class Evaluator:
         from .datasets import icdar
         from .tool import metrics
         self.acc.reset()
+        if self.curve is not None:
+            self.curve.reset()
         over_k, over_d, buckets = [], [], {}
 
         def flush(items):
@@ -227,8 +314,12 @@ class Evaluator:
         for key in sorted(buckets):
             flush(buckets[key])
         # the single read of the pass: the record and the two overflow maxima in one device-to-host copy
-        (num_gt, tp, fp, n_det), (worst_k, worst_d) = self.acc.value_with(
-            torch.stack([torch.cat(over_k).max(), torch.cat(over_d).max()]))
+        worst = torch.stack([torch.cat(over_k).max(), torch.cat(over_d).max()])
+        if self.curve is None:
+            (num_gt, tp, fp, n_det), (worst_k, worst_d) = self.acc.value_with(worst)
+        else:       # ... and the curve, the order flag and AP in the same copy
+            self.curve.finish(self.acc.record)
+            (num_gt, tp, fp, n_det), (worst_k, worst_d), rows, unsorted, ap = self.curve.value_with(self.acc, worst)
         if worst_k > 0:
             raise ValueError(self._overflow(worst_k))
         if worst_d > 0:
@@ -239,6 +330,12 @@ class Evaluator:
                   'num_det': n_det, 'images': len(self.samples)}
         if self.protocol == 'icdar15':
             result.update(invalid_gt=self.invalid_gt, protocol=self.protocol)
+        if self.curve is not None:
+            if unsorted:
+                raise ValueError('the detection scores of an image are not in descending order (NaNs last): the sweep '
+                                 'and AP count score prefixes of the matching order')
+            sweep, best = sweep_rows(self.curve.thresholds_host, rows)
+            result.update(sweep=sweep, best=best, ap=ap)
         return result
 
 
@@ -252,13 +349,14 @@ class LinkEvaluator(Evaluator):
     of the eval side (a scale below 1) is refused.  A detection's score is its component's mean pixel score
     (ocr_component_scores; build-defined).  min_side / min_area filter the boxes (0: nothing, as the reference scripts).
     `run()` reads the device once at its end: the record, and the two overflow counts (components over max_comps,
-    detections over max_d), either of which raises ValueError."""
+    detections over max_d), either of which raises ValueError.  `sweep` as for `Evaluator`: its thresholds are on the
+    component's mean pixel score, in [0, 1]."""
 
     def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, pixel_conf_threshold=0.8,
                  link_conf_threshold=0.9, min_size=10, max_comps=4096, min_side=0.0, min_area=0.0, max_d=ops.EVAL_MAX_D,
-                 eval_image_height=768, eval_image_width=1280, gt_path=None, protocol='raster'):
+                 eval_image_height=768, eval_image_width=1280, gt_path=None, protocol='raster', sweep=None):
         super().__init__(graph, forward, data, batch_size=batch_size, max_images=max_images,
-                         matching_threshold=matching_threshold, max_d=max_d, gt_path=gt_path, protocol=protocol)
+                         matching_threshold=matching_threshold, max_d=max_d, gt_path=gt_path, protocol=protocol, sweep=sweep)
         self.eval_hw = (int(eval_image_height), int(eval_image_width))
         if min(self.eval_hw) < 4 or self.eval_hw[0] % 4 or self.eval_hw[1] % 4:
             raise ValueError('the eval size must be positive multiples of 4, got %dx%d' % self.eval_hw)
@@ -330,16 +428,19 @@ class TrainEval:
     launches) with the EMA shadows (`weights='ema'`, what test.py restores) or the raw weights; the raw weights are back
     bit for bit before the next step.  `network(graph, images)` -> (score, geometry), or with `evaluator=LinkEvaluator`
     (train_pixellink.py) -> (pixel_cls, link_cls); `opt` is read when a pass runs (the optimiser exists only after the
-    step was built).  `last` holds the latest result."""
+    step was built).  `last` holds the latest result.  sweep: None, or the score thresholds of the evaluator's `sweep`
+    (the pass still reads the device once; `write` then adds eval/ap, eval/best_hmean, eval/best_threshold)."""
 
     def __init__(self, graph, step, network, data, every, max_images=None, weights='ema', batch_size=8, evaluator=Evaluator,
-                 **evaluator_kw):
+                 sweep=None, **evaluator_kw):
         if weights not in ('ema', 'raw'):
             raise ValueError("weights must be 'ema' or 'raw'")
         if int(every) < 1:
             raise ValueError('every must be positive')
         self.g, self.step, self.network = graph, step, network
         self.every, self.weights = int(every), weights
+        if sweep is not None:
+            evaluator_kw['sweep'] = sweep
         self.evaluator = evaluator(graph, self._forward, data, batch_size=batch_size, max_images=max_images, **evaluator_kw)
         self.last = None
         self.passes = 0
@@ -370,7 +471,12 @@ class TrainEval:
         return self.last
 
     def write(self, writer, global_step):
-        """eval/precision, eval/recall, eval/hmean of the latest pass as one event of a summary.FileWriter."""
+        """eval/precision, eval/recall, eval/hmean of the latest pass as one event of a summary.FileWriter; with a sweep
+        also eval/ap, eval/best_hmean, eval/best_threshold."""
         for k in ('precision', 'recall', 'hmean'):
             writer.add_scalar('eval/' + k, self.last[k])
+        if 'sweep' in self.last:
+            writer.add_scalar('eval/ap', self.last['ap'])
+            writer.add_scalar('eval/best_hmean', self.last['best']['hmean'])
+            writer.add_scalar('eval/best_threshold', self.last['best']['threshold'])
         writer.flush_step(global_step)

@@ -1321,6 +1321,96 @@ def eval_record_init(record):
     L.call("ocr_eval_record_init", ptr(record), _st())
 
 
+# ------------------------------------------------------------------ score-threshold sweep and AP (csrc/eval_curve.hip)
+EVAL_MAX_T = 64                         # the most thresholds one sweep takes
+
+
+def _curve_operands(what, det_score, nd, ng, thresholds, curve, unsorted, pool, n, max_d):
+    """the checks the two curve entries share -> (T, pool pointers)"""
+    T = thresholds.numel()
+    if tuple(det_score.shape) != (n, max_d) or nd.numel() != n or ng.numel() != n or thresholds.dim() != 1 or \
+            tuple(curve.shape) != (T, 4) or unsorted.numel() != 1:
+        raise ValueError("%s: tensors do not match n, max_d, max_g, T" % what)
+    if det_score.dtype != torch.float32 or nd.dtype != torch.int32 or ng.dtype != torch.int32 or \
+            thresholds.dtype != torch.float32 or curve.dtype != torch.int64 or unsorted.dtype != torch.int32:
+        raise ValueError("%s: scores and thresholds f32, counts and the flag int32, curve int64" % what)
+    ts = [det_score, nd, ng, thresholds, curve, unsorted]
+    if pool is not None:
+        pool_score, pool_cum, pool_nd = pool
+        if tuple(pool_score.shape) != (n, max_d) or tuple(pool_cum.shape) != (n, max_d, 2) or pool_nd.numel() != n:
+            raise ValueError("%s: tensors do not match n, max_d, max_g, T" % what)
+        if pool_score.dtype != torch.float32 or pool_cum.dtype != torch.int32 or pool_nd.dtype != torch.int32:
+            raise ValueError("%s: pool scores f32, pool counts int32" % what)
+        ts += [pool_score, pool_cum, pool_nd]
+    for t in ts:
+        if not t.is_contiguous():
+            raise ValueError("%s: contiguous tensors only" % what)
+    return T, [ptr(t) for t in (pool if pool is not None else (None, None, None))]
+
+
+def eval_curve_init(curve, unsorted, ap=None):
+    """zeroes curve int64 [T,4], the order flag int32 [1] and, when given, ap float64 [1] (include/ocr_eval_curve.h)"""
+    if curve.dim() != 2 or curve.shape[1] != 4 or curve.dtype != torch.int64 or unsorted.numel() != 1 or \
+            unsorted.dtype != torch.int32 or (ap is not None and (ap.numel() != 1 or ap.dtype != torch.float64)) or \
+            not curve.is_contiguous():
+        raise ValueError("eval_curve_init: curve int64 [T,4], unsorted int32 [1], ap float64 [1]")
+    L.call("ocr_eval_curve_init", ptr(curve), c_int(curve.shape[0]), ptr(unsorted), ptr(ap), _st())
+
+
+def eval_curve_batch(tp, fp, det_score, nd, ng, gignored, thresholds, curve, unsorted, pool=None):
+    """The counters of T score thresholds from the raster matcher's outputs (include/ocr_eval_curve.h): tp, fp uint8
+    [n,max_d], det_score f32 [n,max_d], nd, ng int32 [n], gignored uint8 [n,max_g], thresholds f32 [T] -> curve int64 [T,4]
+    is added to, unsorted int32 [1] OR-ed into; pool: None or (pool_score f32 [n,max_d], pool_cum int32 [n,max_d,2],
+    pool_nd int32 [n]), these images' rows of the AP pool."""
+    n, max_d = tp.shape
+    max_g = gignored.shape[1]
+    if tuple(fp.shape) != (n, max_d) or tuple(gignored.shape) != (n, max_g):
+        raise ValueError("eval_curve_batch: tensors do not match n, max_d, max_g, T")
+    if tp.dtype != torch.uint8 or fp.dtype != torch.uint8 or gignored.dtype != torch.uint8:
+        raise ValueError("eval_curve_batch: flags uint8")
+    T, pp = _curve_operands("eval_curve_batch", det_score, nd, ng, thresholds, curve, unsorted, pool, n, max_d)
+    for t in (tp, fp, gignored):
+        if not t.is_contiguous():
+            raise ValueError("eval_curve_batch: contiguous tensors only")
+    L.call("ocr_eval_curve_batch", ptr(tp), ptr(fp), ptr(det_score), ptr(nd), ptr(ng), ptr(gignored), ptr(thresholds), c_int(n),
+           c_int(max_d), c_int(max_g), c_int(T), ptr(curve), ptr(unsorted), pp[0], pp[1], pp[2], _st())
+
+
+def eval_ic15_curve_batch(det_match, gt_match, det_score, nd, ng, thresholds, curve, unsorted, pool=None):
+    """`eval_curve_batch` from the ICDAR-2015 matcher's outputs: det_match int32 [n,max_d], gt_match int32 [n,max_g]."""
+    n, max_d = det_match.shape
+    max_g = gt_match.shape[1]
+    if gt_match.shape[0] != n:
+        raise ValueError("eval_ic15_curve_batch: tensors do not match n, max_d, max_g, T")
+    if det_match.dtype != torch.int32 or gt_match.dtype != torch.int32:
+        raise ValueError("eval_ic15_curve_batch: matches int32")
+    T, pp = _curve_operands("eval_ic15_curve_batch", det_score, nd, ng, thresholds, curve, unsorted, pool, n, max_d)
+    for t in (det_match, gt_match):
+        if not t.is_contiguous():
+            raise ValueError("eval_ic15_curve_batch: contiguous tensors only")
+    L.call("ocr_eval_ic15_curve_batch", ptr(det_match), ptr(gt_match), ptr(det_score), ptr(nd), ptr(ng), ptr(thresholds),
+           c_int(n), c_int(max_d), c_int(max_g), c_int(T), ptr(curve), ptr(unsorted), pp[0], pp[1], pp[2], _st())
+
+
+def eval_ap(pool_score, pool_cum, pool_nd, record, ap, ws):
+    """Average precision over the pool of a pass (include/ocr_eval_curve.h: ocr_eval_ap): pool_score f32 [n_img,max_d],
+    pool_cum int32 [n_img,max_d,2], pool_nd int32 [n_img], record int64 [4] (slot 0 = G, read on the device) -> ap
+    float64 [1]."""
+    n_img, max_d = pool_score.shape
+    if tuple(pool_cum.shape) != (n_img, max_d, 2) or pool_nd.numel() != n_img or record.numel() != 4 or ap.numel() != 1:
+        raise ValueError("eval_ap: tensors do not match n_img, max_d")
+    if pool_score.dtype != torch.float32 or pool_cum.dtype != torch.int32 or pool_nd.dtype != torch.int32 or \
+            record.dtype != torch.int64 or ap.dtype != torch.float64:
+        raise ValueError("eval_ap: pool scores f32, pool counts int32, record int64, ap float64")
+    for t in (pool_score, pool_cum, pool_nd, record, ap):
+        if not t.is_contiguous():
+            raise ValueError("eval_ap: contiguous tensors only")
+    nbytes = L.call_size("ocr_eval_ap_workspace", c_int(n_img), c_int(max_d))
+    buf = ws.get(nbytes)
+    L.call("ocr_eval_ap", ptr(pool_score), ptr(pool_cum), ptr(pool_nd), c_int(n_img), c_int(max_d), ptr(record), ptr(ap),
+           ptr(buf), c_size_t(nbytes), _st())
+
+
 # ------------------------------------------------------------------ link-geometry detections (csrc/link_boxes.hip)
 def component_scores(labels, pixel_score, ncomp, comp_score, ws):
     """labels int32 [n,h,w] (ocr_link_cc), pixel_score f32 [n,h,w], ncomp int32 [n] -> comp_score f32 [n,max_comps]: the

@@ -63,6 +63,79 @@ class DeviceTpFp:
         return tuple(host[:4]), host[4:]
 
 
+class DeviceCurve:
+    """The score-threshold sweep of a pass beside `DeviceTpFp` (include/ocr_eval_curve.h): owns, on the device, the int64
+    [T,4] curve (row t = the record's four slots with only the detections of score >= thresholds[t] kept, so
+    `precision_recall` / `fmean` apply per row), the `unsorted` flag, the AP pool of `n_images` x `max_d` slots and the
+    AP scalar.  `add_raster` / `add_ic15` count one batch from the matcher's outputs, in the order the batches come
+    (the image sequence of the pool); `finish(record)` computes AP once; `value_with(acc, extra)` is the single host
+    read of a pass."""
+
+    def __init__(self, thresholds, n_images, max_d, graph=None):
+        import torch
+        from .. import ops
+        from ..graph import get_default_graph
+        self.g = graph or get_default_graph()
+        self.thresholds_host = [float(t) for t in thresholds]
+        T = len(self.thresholds_host)
+        if not 1 <= T <= ops.EVAL_MAX_T:
+            raise ValueError('a sweep takes 1 to %d thresholds, got %d' % (ops.EVAL_MAX_T, T))
+        if int(n_images) < 1 or not 1 <= int(max_d) <= ops.EVAL_MAX_D:
+            raise ValueError('the AP pool needs n_images >= 1 and max_d in [1, %d]' % ops.EVAL_MAX_D)
+        dev = self.g.device
+        self.T, self.n_images, self.max_d = T, int(n_images), int(max_d)
+        self.thresholds = torch.tensor(self.thresholds_host, dtype=torch.float32, device=dev)
+        # one int64 buffer, so that the read is one slice: curve [T][4] | AP (f64 bit pattern) | unsorted (low int32)
+        self.state = torch.empty((4 * T + 2,), dtype=torch.int64, device=dev)
+        self.curve = self.state[:4 * T].view(T, 4)
+        self.ap = self.state[4 * T:4 * T + 1].view(torch.float64)
+        self.unsorted = self.state[4 * T + 1:].view(torch.int32)[:1]
+        self.pool_score = torch.empty((self.n_images, self.max_d), dtype=torch.float32, device=dev)
+        self.pool_cum = torch.empty((self.n_images, self.max_d, 2), dtype=torch.int32, device=dev)
+        self.pool_nd = torch.empty((self.n_images,), dtype=torch.int32, device=dev)
+        self._ops = ops
+        self.reset()
+
+    def reset(self):
+        self.state[4 * self.T + 1:].zero_()         # (the flag's upper half; the entry zeroes the rest)
+        self._ops.eval_curve_init(self.curve, self.unsorted, self.ap)
+        self.pool_nd.zero_()
+        self.seq = 0
+
+    def _rows(self, n):
+        if self.seq + n > self.n_images:
+            raise ValueError('the AP pool holds %d images, batch rows %d..%d do not fit' % (self.n_images, self.seq, self.seq + n))
+        s = slice(self.seq, self.seq + n)
+        self.seq += n
+        return self.pool_score[s], self.pool_cum[s], self.pool_nd[s]
+
+    def add_raster(self, tp, fp, det_score, nd, ng, gignored):
+        self._ops.eval_curve_batch(tp, fp, det_score, nd, ng, gignored, self.thresholds, self.curve, self.unsorted,
+                                   pool=self._rows(tp.shape[0]))
+
+    def add_ic15(self, det_match, gt_match, det_score, nd, ng):
+        self._ops.eval_ic15_curve_batch(det_match, gt_match, det_score, nd, ng, self.thresholds, self.curve, self.unsorted,
+                                        pool=self._rows(det_match.shape[0]))
+
+    def finish(self, record):
+        """AP over the pooled detections of the pass; G = record[0], read on the device"""
+        self._ops.eval_ap(self.pool_score, self.pool_cum, self.pool_nd, record, self.ap, self.g.workspace())
+
+    def value_with(self, acc, extra):
+        """`acc.value_with(extra)` and the curve, the flag and AP in ONE device-to-host copy (the f64 travels as its int64
+        bit pattern): ((num_gbboxes, tp, fp, n_det), [extra values], curve rows [T][4], unsorted, ap).  Counts as one
+        read of `acc`."""
+        import struct
+        import torch
+        acc.reads += 1
+        n_extra = extra.numel()
+        host = [int(v) for v in torch.cat([acc.record, extra.reshape(-1).to(torch.int64), self.state]).cpu().tolist()]
+        rest = host[4 + n_extra:]
+        rows = [rest[4 * t:4 * t + 4] for t in range(self.T)]
+        ap = struct.unpack('<d', struct.pack('<q', rest[4 * self.T]))[0]
+        return tuple(host[:4]), host[4:4 + n_extra], rows, rest[4 * self.T + 1] & 0xffffffff, ap
+
+
 def precision_recall(num_gbboxes, tp, fp, scope=None):
     """tool/metrics.py:67-79 -> (precision, recall)."""
     tp = float(np.sum(np.asarray(tp, np.float32)))

@@ -25,6 +25,16 @@ import numpy as np
 import torch
 
 
+def _sweep_arg(text):
+    from tensorflow_ocr_amd.evaluate import sweep_arg
+    return sweep_arg(text)
+
+
+def _sweep_help():
+    from tensorflow_ocr_amd.evaluate import SWEEP_HELP
+    return SWEEP_HELP % "LANMS's merged score, a sum of pixel scores (not a probability, not --box_thresh's mean)"
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--input_size', type=int, default=512)
@@ -53,7 +63,10 @@ def parse(argv=None):
     ap.add_argument('--eval_protocol', choices=['raster', 'icdar15'], default='raster', help="with --gt_path: raster = the "
                     "reference's rule above; icdar15 = the official ICDAR-2015 protocol (polygon IoU, ### as don't-care "
                     "regions), the line then ends in [icdar15]")
+    ap.add_argument('--eval_sweep', type=_sweep_arg, default=None, metavar='LO:HI:N', help="with --gt_path: " + _sweep_help())
     FLAGS = ap.parse_args(argv)
+    if FLAGS.eval_sweep is not None and FLAGS.gt_path is None:
+        ap.error('--eval_sweep needs --gt_path')
     if FLAGS.gt_path is not None and FLAGS.geometry != 'RBOX':
         ap.error('--gt_path needs --geometry RBOX (the link geometry\'s contour decode ends on the host)')
     if FLAGS.eval_protocol != 'raster' and FLAGS.gt_path is None:
@@ -203,8 +216,11 @@ def main_rbox(FLAGS):
         # per batch on the device, one read of the counters at its end
         from tensorflow_ocr_amd import evaluate
         ev = evaluate.Evaluator(g, forward, FLAGS.test_data_path, gt_path=FLAGS.gt_path, box_thresh=FLAGS.box_thresh,
-                                protocol=FLAGS.eval_protocol)
-        print(evaluate.format_line(ev.run()), flush=True)
+                                protocol=FLAGS.eval_protocol, sweep=FLAGS.eval_sweep)
+        res = ev.run()
+        print(evaluate.format_line(res), flush=True)
+        if FLAGS.eval_sweep is not None:
+            print(evaluate.format_sweep(res), flush=True)
 
 
 def main():

@@ -29,6 +29,11 @@ import numpy as np
 import torch
 
 
+def _sweep_arg(text):
+    from tensorflow_ocr_amd.evaluate import sweep_arg
+    return sweep_arg(text)
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--train_with_ignored', action='store_true')
@@ -86,7 +91,12 @@ def parse(argv=None):
     ap.add_argument('--eval_image_height', type=int, default=768)
     # --eval_protocol: raster = the reference's matching rule, icdar15 = the official ICDAR-2015 protocol (polygon IoU)
     ap.add_argument('--eval_protocol', choices=['raster', 'icdar15'], default='raster')
+    # --eval_sweep LO:HI:N (or a comma list): every pass also reports the precision / recall curve over the component's mean
+    # pixel score (in [0, 1]), its best row and AP, from the one matching pass (evaluate.LinkEvaluator's sweep)
+    ap.add_argument('--eval_sweep', type=_sweep_arg, default=None, metavar='LO:HI:N')
     FLAGS = ap.parse_args(argv)
+    if FLAGS.eval_sweep is not None and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
+        ap.error('--eval_sweep needs --eval_data_path and --eval_steps')
     if FLAGS.eval_steps < 0 or (FLAGS.eval_max_images is not None and FLAGS.eval_max_images < 1):
         ap.error('--eval_steps must not be negative and --eval_max_images must be positive')
     if FLAGS.eval_steps > 0 and not FLAGS.eval_data_path:
@@ -221,15 +231,19 @@ def make_train_eval(FLAGS, g, step):
     return evaluate.TrainEval(g, step, network, FLAGS.eval_data_path, FLAGS.eval_steps, max_images=FLAGS.eval_max_images,
                               weights=FLAGS.eval_weights, batch_size=max(1, int(FLAGS.batch_size / FLAGS.num_gpus)),
                               evaluator=evaluate.LinkEvaluator, eval_image_height=FLAGS.eval_image_height,
-                              eval_image_width=FLAGS.eval_image_width, protocol=FLAGS.eval_protocol)
+                              eval_image_width=FLAGS.eval_image_width, protocol=FLAGS.eval_protocol,
+                              sweep=FLAGS.eval_sweep)
 
 
 def _evaluate(train_eval, summaries, opt):
     """One pass between two steps (rank 0; the other ranks meet it at the next exchange): the line eval_pixellink_fast.py
-    prints, and eval/precision, eval/recall, eval/hmean in the event file where one is open."""
+    prints, and eval/precision, eval/recall, eval/hmean (with --eval_sweep also eval/ap, eval/best_hmean,
+    eval/best_threshold) in the event file where one is open."""
     from tensorflow_ocr_amd import evaluate
     res = train_eval.run()
     print('global step %d: ' % opt.global_step + evaluate.format_line(res), flush=True)
+    if 'sweep' in res:
+        print(evaluate.format_sweep(res), flush=True)
     if summaries is not None:
         train_eval.write(summaries.writer, opt.global_step)
 
