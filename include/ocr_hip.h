@@ -1125,6 +1125,9 @@ int ocr_eval_record_init(void* record_i64, void* stream);
 /* The score-threshold sweep and average precision counted from either matcher's outputs: its entries and their comment
  * block are in a header of their own, part of this ABI. */
 #include "ocr_eval_curve.h"
+/* Multi-scale RBOX inference: pooling the per-scale LANMS results of an image and fusing them across scales, in the layout
+ * ocr_eval_collect reads: its entries and their comment block are in a header of their own, part of this ABI. */
+#include "ocr_multiscale.h"
 
 /* ------------------------------------------------------------------------- *
  * Link-geometry detections on the device (csrc/link_boxes.hip): what lies between ocr_min_area_rects and

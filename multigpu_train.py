@@ -35,6 +35,11 @@ def _sweep_arg(text):
     return sweep_arg(text)
 
 
+def _scales_arg(text):
+    from tensorflow_ocr_amd.tool.rbox import scales_arg
+    return scales_arg(text)
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--input_size', type=int, default=512)
@@ -86,7 +91,16 @@ def parse(argv=None):
     # --eval_sweep LO:HI:N (or a comma list): every pass also reports the precision / recall curve over LANMS's merged score (a
     # sum of pixel scores, not a probability), its best row and AP, from the one matching pass (evaluate.Evaluator's sweep)
     ap.add_argument('--eval_sweep', type=_sweep_arg, default=None, metavar='LO:HI:N')
+    # --eval_scales 0.5,1,2: multi-scale testing in every pass — one forward per scale, the per-scale detections pooled and
+    # fused on the device (evaluate.Evaluator's scales); --eval_fuse: nms = score-ordered suppression, vote = score-weighted
+    # coordinates.  The detection score (and --eval_sweep's threshold) is then the mean pixel score, in [0, 1]
+    ap.add_argument('--eval_scales', type=_scales_arg, default=None, metavar='S1,S2,..')
+    ap.add_argument('--eval_fuse', choices=['nms', 'vote'], default='nms')
     FLAGS = ap.parse_args(argv)
+    if FLAGS.eval_scales is not None and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
+        ap.error('--eval_scales needs --eval_data_path and --eval_steps')
+    if FLAGS.eval_fuse != 'nms' and FLAGS.eval_scales is None:
+        ap.error('--eval_fuse needs --eval_scales')
     if FLAGS.eval_sweep is not None and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
         ap.error('--eval_sweep needs --eval_data_path and --eval_steps')
     if FLAGS.eval_protocol != 'raster' and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
@@ -306,7 +320,8 @@ def make_train_eval(FLAGS, g, step, blocks=None):
         return model_vgg_16.model_rbox(im, is_training=False, text_scale=FLAGS.text_scale, graph=gr, blocks=blocks)
     return evaluate.TrainEval(g, step, network, FLAGS.eval_data_path, FLAGS.eval_steps, max_images=FLAGS.eval_max_images,
                               weights=FLAGS.eval_weights, batch_size=FLAGS.batch_size_per_gpu,
-                              protocol=FLAGS.eval_protocol, sweep=FLAGS.eval_sweep)
+                              protocol=FLAGS.eval_protocol, sweep=FLAGS.eval_sweep, scales=FLAGS.eval_scales,
+                              fuse=FLAGS.eval_fuse)
 
 
 def _evaluate(train_eval, summaries, opt):

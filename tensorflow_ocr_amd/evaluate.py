@@ -21,7 +21,11 @@ pass with another middle:
 evaluated here).
 
 `sweep=[...]` (`--eval_sweep`) adds the precision / recall curve over detection scores, its best row and average
-precision, counted on the device from the same matching pass (include/ocr_eval_curve.h)."""
+precision, counted on the device from the same matching pass (include/ocr_eval_curve.h).
+
+`Evaluator(scales=[...])` (`--scales`, `--eval_scales`) is multi-scale testing: one forward per scale, the per-scale LANMS
+results pooled in original-image pixels and fused on the device (rbox.detect_multiscale_device, include/ocr_multiscale.h,
+DESIGN.md §3.3.19), then the same matcher."""
 import os
 
 import numpy as np
@@ -179,14 +183,24 @@ class Evaluator:
     pass); still one device read.  The threshold is on the MATCHER'S ORDER KEY, ocr_eval_collect's det_score: for this
     geometry that is LANMS's merged score, a SUM of the merged pixels' scores — not a probability and not EAST's
     box_thresh mean; for `LinkEvaluator` it is the component's mean pixel score, in [0, 1].  Sweeping box_thresh,
-    score_map_thresh or the link threshold would change the detection set or its order and is not what this does."""
+    score_map_thresh or the link threshold would change the detection set or its order and is not what this does.
+    With `scales` (below) the order key, and so the sweep's threshold, is instead the fused quad's MEAN pixel score, in
+    [0, 1].
+
+    scales: None = the single-scale pass above, bit for bit.  A sequence of 1..8 scales = multi-scale testing (DESIGN.md
+    §3.3.19): every image is resized from the ORIGINAL to rbox.scale_sizes' size at each scale, `forward` runs once per
+    scale, and rbox.detect_multiscale_device pools the per-scale LANMS results in original-image pixels and fuses them
+    (fuse = 'nms' or 'vote', at most max_pool <= 4096 pooled quads per image); the fused list goes to the same matcher.
+    The pass still reads the device once; a pool overflow or a non-finite pooled quad raises ValueError there too."""
 
     def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, score_map_thresh=0.8,
                  nms_thres=0.2, box_thresh=None, max_k=None, max_d=ops.EVAL_MAX_D, max_side_len=3000, gt_path=None,
-                 protocol='raster', sweep=None):
+                 protocol='raster', sweep=None, scales=None, fuse='nms', max_pool=1024):
         from .tool import metrics
         if protocol not in PROTOCOLS:
             raise ValueError("protocol must be 'raster' or 'icdar15', got %r" % (protocol,))
+        self.ms_scales = self._check_scales(scales, fuse, max_pool)
+        self.fuse, self.max_pool = fuse, int(max_pool)
         self.protocol, self.area_prec_thr, self.invalid_gt = protocol, 0.5, 0
         self.sweep = None if sweep is None else check_sweep(sweep)
         self.g = graph or get_default_graph()
@@ -230,20 +244,38 @@ class Evaluator:
 
     def _upload(self, batch):
         """batch: [(image uint8 [h,w,3], polys, ignored)] of one resized shape -> x, inv_ratio, gts, ng, gignored, mask_hw"""
+        rh, rw = self._resized(batch[0][0].shape[0], batch[0][0].shape[1])
+        srcs = self._sources(batch)
+        x, ratio = self._resize_batch(batch, srcs, rh, rw)
+        return (x, ratio) + self._ground_truths(batch)
+
+    def _sources(self, batch):
+        """the original images of a batch on the device (uint8 [h,w,3] each)"""
+        return [torch.from_numpy(np.ascontiguousarray(im, dtype=np.uint8)).to(self.g.device) for im, _, _ in batch]
+
+    def _resize_batch(self, batch, srcs, rh, rw):
+        """-> x f32 [n,rh,rw,3] (every original resized to rh x rw on the device), ratio f32 [n,2] = (ratio_w, ratio_h)"""
         dev = self.g.device
         n = len(batch)
-        rh, rw = self._resized(batch[0][0].shape[0], batch[0][0].shape[1])
         x = torch.empty((n, rh, rw, 3), dtype=torch.float32, device=dev)
+        ratio = np.zeros((n, 2), np.float32)
+        for i, (im, _, _) in enumerate(batch):
+            h, w, _ = im.shape
+            ops.resize_linear_u8(srcs[i], x[i])
+            ratio[i] = self._ratio(h, w, rh, rw)
+        return x, torch.from_numpy(ratio).to(dev)
+
+    def _ground_truths(self, batch):
+        """-> gts int32 [n,max_g,4,2], ng int32 [n], gignored uint8 [n,max_g] on the device, and the matcher's mask size"""
+        dev = self.g.device
+        n = len(batch)
         max_g = max([len(p) for _, p, _ in batch] + [1])
         gts = np.zeros((n, max_g, 4, 2), np.int32)
         ng = np.zeros((n,), np.int32)
         gign = np.zeros((n, max_g), np.uint8)
-        ratio = np.zeros((n, 2), np.float32)
         extent = 1
         for i, (im, polys, ignored) in enumerate(batch):
             h, w, _ = im.shape
-            ops.resize_linear_u8(torch.from_numpy(np.ascontiguousarray(im, dtype=np.uint8)).to(dev), x[i])
-            ratio[i] = self._ratio(h, w, rh, rw)
             k = len(polys)
             gts[i, :k], ng[i], gign[i, :k] = polys, k, ignored
             extent = max(extent, h, w, int(polys.max()) + 1 if k else 1)
@@ -251,7 +283,45 @@ class Evaluator:
         # overhang the image, and bounds what a wild quad can cost
         side = int(min(32768, 2 * extent + 10))
         up = lambda a: torch.from_numpy(a).to(dev)
-        return x, up(ratio), up(gts), up(ng), up(gign), (side, side)
+        return up(gts), up(ng), up(gign), (side, side)
+
+    # -- the multi-scale chain (scales=...): beside the single-scale one, which it leaves as it is ----------------
+    @staticmethod
+    def _check_scales(scales, fuse, max_pool):
+        from .tool import rbox
+        if fuse not in rbox.FUSE_MODES:
+            raise ValueError("fuse must be 'nms' or 'vote', got %r" % (fuse,))
+        if not 1 <= int(max_pool) <= ops.FUSE_MAX_POOL:
+            raise ValueError('max_pool must be in [1, %d]' % ops.FUSE_MAX_POOL)
+        if scales is None:
+            return None
+        return rbox.check_scales(scales)              # count, sign and finiteness; the sizes are checked per image shape
+
+    def _upload_multiscale(self, batch):
+        """batch of one ORIGINAL shape -> xs (one resized batch per scale, each made from the original images), ratios (one f32
+        [n,2] per scale), gts, ng, gignored, mask_hw"""
+        from .tool import rbox
+        h, w = batch[0][0].shape[:2]
+        srcs = self._sources(batch)
+        xs, ratios = [], []
+        for rh, rw in rbox.scale_sizes(h, w, self.ms_scales, self.max_side_len):
+            x, ratio = self._resize_batch(batch, srcs, rh, rw)
+            xs.append(x)
+            ratios.append(ratio)
+        return (xs, ratios) + self._ground_truths(batch)
+
+    def _chain_multiscale(self, batch):
+        from .tool import rbox
+        xs, ratios, gts, ng, gign, mask_hw = self._upload_multiscale(batch)
+        maps = (self.forward(x) for x in xs)          # a scale's forward runs when detect_multiscale_device asks for it
+        fused, keep, n_keep, overflow = rbox.detect_multiscale_device(
+            maps, ratios, self.score_map_thresh, self.nms_thres, self.box_thresh, fuse=self.fuse, max_pool=self.max_pool,
+            max_k=self.max_k, graph=self.g)
+        self._over_pool.append(overflow[:, 1:])
+        # the fused quads are in original-image pixels already: the collect pass divides by 1.  `total` is given so that
+        # _match's `total - rows` is the worst per-scale overflow over max_k
+        ones = torch.ones((len(batch), 2), dtype=torch.float32, device=self.g.device)
+        return self._match(fused, keep, n_keep, None, overflow[:, 0] + fused.shape[1], ones, gts, ng, gign, mask_hw)
 
     def _chain(self, batch):
         from .tool import rbox
@@ -299,9 +369,11 @@ class Evaluator:
         if self.curve is not None:
             self.curve.reset()
         over_k, over_d, buckets = [], [], {}
+        self._over_pool = []      # multi-scale only: per chain, int32 [n,2] = (pool_total - max_pool, non-finite rows)
+        chain = self._chain if self.ms_scales is None else self._chain_multiscale
 
         def flush(items):
-            a, b = self._chain(items)
+            a, b = chain(items)
             over_k.append(a)
             over_d.append(b)
         for im_fn, (polys, ignored) in self.samples:
@@ -315,11 +387,18 @@ class Evaluator:
             flush(buckets[key])
         # the single read of the pass: the record and the two overflow maxima in one device-to-host copy
         worst = torch.stack([torch.cat(over_k).max(), torch.cat(over_d).max()])
+        if self.ms_scales is not None:     # ... and the pool's two counts
+            worst = torch.cat([worst, torch.cat(self._over_pool).max(dim=0).values.to(worst.dtype)])
         if self.curve is None:
-            (num_gt, tp, fp, n_det), (worst_k, worst_d) = self.acc.value_with(worst)
+            (num_gt, tp, fp, n_det), (worst_k, worst_d, *worst_pool) = self.acc.value_with(worst)
         else:       # ... and the curve, the order flag and AP in the same copy
             self.curve.finish(self.acc.record)
-            (num_gt, tp, fp, n_det), (worst_k, worst_d), rows, unsorted, ap = self.curve.value_with(self.acc, worst)
+            (num_gt, tp, fp, n_det), (worst_k, worst_d, *worst_pool), rows, unsorted, ap = self.curve.value_with(self.acc, worst)
+        if worst_pool:
+            from .tool import rbox
+            msg = rbox.overflow_error(worst_k, worst_pool[0], worst_pool[1], self.max_pool)
+            if msg:
+                raise ValueError(msg)
         if worst_k > 0:
             raise ValueError(self._overflow(worst_k))
         if worst_d > 0:
@@ -354,7 +433,10 @@ class LinkEvaluator(Evaluator):
 
     def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, pixel_conf_threshold=0.8,
                  link_conf_threshold=0.9, min_size=10, max_comps=4096, min_side=0.0, min_area=0.0, max_d=ops.EVAL_MAX_D,
-                 eval_image_height=768, eval_image_width=1280, gt_path=None, protocol='raster', sweep=None):
+                 eval_image_height=768, eval_image_width=1280, gt_path=None, protocol='raster', sweep=None, scales=None):
+        if scales is not None:
+            # the min-area-rectangle vertices of a component have no fixed correspondence across scales for the vote
+            raise ValueError('multi-scale evaluation (scales=...) is built for the RBOX geometry only')
         super().__init__(graph, forward, data, batch_size=batch_size, max_images=max_images,
                          matching_threshold=matching_threshold, max_d=max_d, gt_path=gt_path, protocol=protocol, sweep=sweep)
         self.eval_hw = (int(eval_image_height), int(eval_image_width))
@@ -429,10 +511,11 @@ class TrainEval:
     bit for bit before the next step.  `network(graph, images)` -> (score, geometry), or with `evaluator=LinkEvaluator`
     (train_pixellink.py) -> (pixel_cls, link_cls); `opt` is read when a pass runs (the optimiser exists only after the
     step was built).  `last` holds the latest result.  sweep: None, or the score thresholds of the evaluator's `sweep`
-    (the pass still reads the device once; `write` then adds eval/ap, eval/best_hmean, eval/best_threshold)."""
+    (the pass still reads the device once; `write` then adds eval/ap, eval/best_hmean, eval/best_threshold).
+    scales / fuse / max_pool: the evaluator's multi-scale options (None = single scale; the RBOX `Evaluator` only)."""
 
     def __init__(self, graph, step, network, data, every, max_images=None, weights='ema', batch_size=8, evaluator=Evaluator,
-                 sweep=None, **evaluator_kw):
+                 sweep=None, scales=None, fuse='nms', max_pool=1024, **evaluator_kw):
         if weights not in ('ema', 'raw'):
             raise ValueError("weights must be 'ema' or 'raw'")
         if int(every) < 1:
@@ -441,6 +524,8 @@ class TrainEval:
         self.every, self.weights = int(every), weights
         if sweep is not None:
             evaluator_kw['sweep'] = sweep
+        if scales is not None:
+            evaluator_kw.update(scales=scales, fuse=fuse, max_pool=max_pool)
         self.evaluator = evaluator(graph, self._forward, data, batch_size=batch_size, max_images=max_images, **evaluator_kw)
         self.last = None
         self.passes = 0

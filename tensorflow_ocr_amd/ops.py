@@ -1411,6 +1411,65 @@ def eval_ap(pool_score, pool_cum, pool_nd, record, ap, ws):
            ptr(buf), c_size_t(nbytes), _st())
 
 
+# ------------------------------------------------------------------ multi-scale pooling and fusion (csrc/multiscale.hip)
+FUSE_MAX_POOL = 4096                    # the most pooled quads per image ocr_quad_fuse takes
+FUSE_MODES = {'nms': 0, 'vote': 1}
+
+
+def ms_pool_append(merged, keep_idx, n_keep, passed, mean, ratio, scale_id, pool, pool_scale, pool_count, pool_total,
+                   pool_nonfinite):
+    """One scale's LANMS output (merged f32 [n,max_k,9], keep_idx int32 [n,max_k], n_keep int32 [n]; passed uint8 [n,max_k] or
+    None, per keep slot; mean f32 [n,max_k], the pooled score of each keep slot; ratio f32 [n,2] = (ratio_w, ratio_h)) is
+    appended in keep order to pool f32 [n,max_pool,9] / pool_scale int32 [n,max_pool] after pool_count int32 [n]; pool_total
+    keeps the true count, pool_nonfinite the dropped non-finite rows (include/ocr_multiscale.h: ocr_ms_pool_append)."""
+    n, max_k, _ = merged.shape
+    max_pool = pool.shape[1]
+    if tuple(merged.shape) != (n, max_k, 9) or tuple(keep_idx.shape) != (n, max_k) or n_keep.numel() != n or \
+            tuple(mean.shape) != (n, max_k) or tuple(ratio.shape) != (n, 2) or tuple(pool.shape) != (n, max_pool, 9) or \
+            tuple(pool_scale.shape) != (n, max_pool) or pool_count.numel() != n or pool_total.numel() != n or \
+            pool_nonfinite.numel() != n or (passed is not None and tuple(passed.shape) != (n, max_k)):
+        raise ValueError("ms_pool_append: tensors do not match n, max_k, max_pool")
+    if merged.dtype != torch.float32 or keep_idx.dtype != torch.int32 or n_keep.dtype != torch.int32 or \
+            mean.dtype != torch.float32 or ratio.dtype != torch.float32 or pool.dtype != torch.float32 or \
+            pool_scale.dtype != torch.int32 or pool_count.dtype != torch.int32 or pool_total.dtype != torch.int32 or \
+            pool_nonfinite.dtype != torch.int32 or (passed is not None and passed.dtype != torch.uint8):
+        raise ValueError("ms_pool_append: merged / mean / ratio / pool f32, passed uint8, the index and count tensors int32")
+    for t in (merged, keep_idx, n_keep, mean, ratio, pool, pool_scale, pool_count, pool_total, pool_nonfinite) + \
+            (() if passed is None else (passed,)):
+        if not t.is_contiguous():
+            raise ValueError("ms_pool_append: contiguous tensors only")
+    L.call("ocr_ms_pool_append", ptr(merged), ptr(keep_idx), ptr(n_keep), ptr(passed), ptr(mean), ptr(ratio), c_int(scale_id),
+           c_int(n), c_int(max_k), c_int(max_pool), ptr(pool), ptr(pool_scale), ptr(pool_count), ptr(pool_total),
+           ptr(pool_nonfinite), _st())
+
+
+def quad_fuse(pool, pool_count, iou_thresh, mode, fused, keep_idx, n_keep, owner, ws):
+    """Score-ordered NMS over each image's pooled list (include/ocr_multiscale.h: ocr_quad_fuse): pool f32 [n,max_pool,9],
+    pool_count int32 [n], mode 'nms' / 'vote' (or 0 / 1) -> fused f32 [n,max_pool,9], keep_idx int32 [n,max_pool], n_keep int32
+    [n] (ocr_lanms's layout: ocr_eval_collect takes them as they are), owner int32 [n,max_pool]."""
+    n, max_pool, _ = pool.shape
+    mode = FUSE_MODES.get(mode, mode)
+    if mode not in (0, 1):
+        raise ValueError("quad_fuse: mode is 'nms' (0) or 'vote' (1), got %r" % (mode,))
+    if tuple(pool.shape) != (n, max_pool, 9) or pool_count.numel() != n or tuple(fused.shape) != (n, max_pool, 9) or \
+            tuple(keep_idx.shape) != (n, max_pool) or n_keep.numel() != n or tuple(owner.shape) != (n, max_pool):
+        raise ValueError("quad_fuse: tensors do not match n, max_pool")
+    if max_pool > FUSE_MAX_POOL:
+        raise ValueError("quad_fuse: max_pool %d is beyond the %d pooled quads per image it takes" % (max_pool, FUSE_MAX_POOL))
+    if pool.dtype != torch.float32 or pool_count.dtype != torch.int32 or fused.dtype != torch.float32 or \
+            keep_idx.dtype != torch.int32 or n_keep.dtype != torch.int32 or owner.dtype != torch.int32:
+        raise ValueError("quad_fuse: pool / fused f32, the index and count tensors int32")
+    for t in (pool, pool_count, fused, keep_idx, n_keep, owner):
+        if not t.is_contiguous():
+            raise ValueError("quad_fuse: contiguous tensors only")
+    if fused.data_ptr() == pool.data_ptr():
+        raise ValueError("quad_fuse: fused must not be the pool")
+    nbytes = L.call_size("ocr_quad_fuse_workspace", c_int(n), c_int(max_pool))
+    buf = ws.get(nbytes)
+    L.call("ocr_quad_fuse", ptr(pool), ptr(pool_count), c_int(n), c_int(max_pool), c_float(iou_thresh), c_int(mode), ptr(fused),
+           ptr(keep_idx), ptr(n_keep), ptr(owner), ptr(buf), c_size_t(nbytes), _st())
+
+
 # ------------------------------------------------------------------ link-geometry detections (csrc/link_boxes.hip)
 def component_scores(labels, pixel_score, ncomp, comp_score, ws):
     """labels int32 [n,h,w] (ocr_link_cc), pixel_score f32 [n,h,w], ncomp int32 [n] -> comp_score f32 [n,max_comps]: the

@@ -8,7 +8,9 @@ heads), softmax scores, the script's own `pixel_detect`, one `cv2.minAreaRect` b
 (score, four distances x `--text_scale`, angle), per-pixel quads in raster order, locality-aware NMS, all on the device
 (`main_rbox`); the default `--geometry link` is the path described above, unchanged.  With `--gt_path DIR` (RBOX only) the
 detections are then matched against the `gt_<name>.txt` files there on the device (tensorflow_ocr_amd/evaluate.py) and one
-line `precision .. recall .. hmean .. (gt .. det ..)` is printed.
+line `precision .. recall .. hmean .. (gt .. det ..)` is printed.  `--scales 0.5,1,2 [--fuse nms|vote]` (RBOX only) is
+multi-scale testing: one forward per scale, the per-scale detections pooled and fused on the device
+(tool/rbox.detect_multiscale); without it the script is what it was.
 
     python test.py --test_data_path ./exhibition --checkpoint_path /tmp/east_icdar2015_resnet_v1_50_rbox/ --output_dir /tmp/res/
 
@@ -28,6 +30,11 @@ import torch
 def _sweep_arg(text):
     from tensorflow_ocr_amd.evaluate import sweep_arg
     return sweep_arg(text)
+
+
+def _scales_arg(text):
+    from tensorflow_ocr_amd.tool.rbox import scales_arg
+    return scales_arg(text)
 
 
 def _sweep_help():
@@ -64,7 +71,18 @@ def parse(argv=None):
                     "reference's rule above; icdar15 = the official ICDAR-2015 protocol (polygon IoU, ### as don't-care "
                     "regions), the line then ends in [icdar15]")
     ap.add_argument('--eval_sweep', type=_sweep_arg, default=None, metavar='LO:HI:N', help="with --gt_path: " + _sweep_help())
+    ap.add_argument('--scales', type=_scales_arg, default=None, metavar='S1,S2,..', help="RBOX only: multi-scale testing, e.g. "
+                    "0.5,1,2 — the image is resized from the original to each scale (then by the sizing rule), one forward per "
+                    "scale, the per-scale detections are pooled in original-image pixels and fused on the device "
+                    "(tool/rbox.detect_multiscale).  The fused quads carry the mean pixel score, in [0, 1]; with --gt_path "
+                    "the evaluator runs the same way.  Default: one scale, the script as it was")
+    ap.add_argument('--fuse', choices=['nms', 'vote'], default='nms', help="with --scales: nms = score-ordered suppression "
+                    "across the scales; vote = a kept quad's corners become the score-weighted mean of the quads it claimed")
     FLAGS = ap.parse_args(argv)
+    if FLAGS.scales is not None and FLAGS.geometry != 'RBOX':
+        ap.error('--scales needs --geometry RBOX (multi-scale fusion is built for the RBOX quads only)')
+    if FLAGS.fuse != 'nms' and FLAGS.scales is None:
+        ap.error('--fuse needs --scales')
     if FLAGS.eval_sweep is not None and FLAGS.gt_path is None:
         ap.error('--eval_sweep needs --gt_path')
     if FLAGS.gt_path is not None and FLAGS.geometry != 'RBOX':
@@ -145,6 +163,24 @@ def resize_image(im, max_side_len=3000, graph=None):
     return out, (resize_h / float(h), resize_w / float(w))
 
 
+def multiscale_inputs(im, scales, graph=None, max_side_len=3000):
+    """--scales: the image resized from the ORIGINAL to tool/rbox.scale_sizes' size at each scale -> (xs, ratios): one device
+    f32 [1,H_s,W_s,3] batch and one f32 [1,2] (ratio_w, ratio_h) tensor per scale."""
+    from tensorflow_ocr_amd import ops
+    from tensorflow_ocr_amd.graph import get_default_graph
+    from tensorflow_ocr_amd.tool import rbox
+    g = graph or get_default_graph()
+    h, w, _ = im.shape
+    src = torch.from_numpy(np.ascontiguousarray(im, dtype=np.uint8)).to(g.device)
+    xs, ratios = [], []
+    for rh, rw in rbox.scale_sizes(h, w, scales, max_side_len):
+        x = torch.empty((1, rh, rw, 3), dtype=torch.float32, device=g.device)
+        ops.resize_linear_u8(src, x[0])
+        xs.append(x)
+        ratios.append(torch.tensor([[rw / float(w), rh / float(h)]], dtype=torch.float32, device=g.device))
+    return xs, ratios
+
+
 def boxes_from_mask(score_map_res, ratio_h, ratio_w, graph=None):
     """test.py:182-199: contours -> minAreaRect -> boxPoints -> np.int0 -> x4 -> / ratio (integer
     array: the division result is truncated on assignment)."""
@@ -192,22 +228,36 @@ def main_rbox(FLAGS):
     for im_fn in get_images(FLAGS.test_data_path):
         im = icdar.read_image_rgb(im_fn)
         start_time = time.time()
-        im_resized, (ratio_h, ratio_w) = resize_image(im, graph=g)
-        x = im_resized[None]
-        f_score, f_geometry = forward(x)
-        if not restored:
-            _restore(FLAGS, g)
+        if FLAGS.scales is not None:
+            # one resize (from the original) and one forward per scale, pooled and fused on the device: the quads come
+            # back in original-image pixels, so nothing is divided below
+            xs, ratios = multiscale_inputs(im, FLAGS.scales, g)
+            if not restored:
+                forward(xs[0])
+                _restore(FLAGS, g)
+                restored = True
+            quads = rbox.detect_multiscale((forward(x) for x in xs), ratios, box_thresh=FLAGS.box_thresh, fuse=FLAGS.fuse,
+                                           graph=g)[0]
+            print('net + fusion time:' + str((time.time() - start_time) * 1000) + 'ms')
+            ratio_h = ratio_w = 1.0
+        else:
+            im_resized, (ratio_h, ratio_w) = resize_image(im, graph=g)
+            x = im_resized[None]
             f_score, f_geometry = forward(x)
-            restored = True
-        torch.cuda.synchronize()
-        print('net time:' + str((time.time() - start_time) * 1000) + 'ms')
-        quads = rbox.detect(f_score, f_geometry, graph=g, box_thresh=FLAGS.box_thresh)[0]
+            if not restored:
+                _restore(FLAGS, g)
+                f_score, f_geometry = forward(x)
+                restored = True
+            torch.cuda.synchronize()
+            print('net time:' + str((time.time() - start_time) * 1000) + 'ms')
+            quads = rbox.detect(f_score, f_geometry, graph=g, box_thresh=FLAGS.box_thresh)[0]
         res_file = os.path.join(FLAGS.output_dir, 'res_{}.txt'.format(os.path.basename(im_fn).split('.')[0]))
         with open(res_file, 'w') as f:
             for q in quads:
                 box = q[:8].reshape(4, 2).astype(np.float64)
-                box[:, 0] /= ratio_w
-                box[:, 1] /= ratio_h
+                if FLAGS.scales is None:
+                    box[:, 0] /= ratio_w
+                    box[:, 1] /= ratio_h
                 box = box.astype(np.int32)
                 f.write('{},{},{},{},{},{},{},{}\r\n'.format(box[0, 0], box[0, 1], box[1, 0], box[1, 1],
                                                             box[2, 0], box[2, 1], box[3, 0], box[3, 1]))
@@ -216,7 +266,7 @@ def main_rbox(FLAGS):
         # per batch on the device, one read of the counters at its end
         from tensorflow_ocr_amd import evaluate
         ev = evaluate.Evaluator(g, forward, FLAGS.test_data_path, gt_path=FLAGS.gt_path, box_thresh=FLAGS.box_thresh,
-                                protocol=FLAGS.eval_protocol, sweep=FLAGS.eval_sweep)
+                                protocol=FLAGS.eval_protocol, sweep=FLAGS.eval_sweep, scales=FLAGS.scales, fuse=FLAGS.fuse)
         res = ev.run()
         print(evaluate.format_line(res), flush=True)
         if FLAGS.eval_sweep is not None:
