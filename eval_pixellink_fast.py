@@ -10,6 +10,9 @@ raster-IoU matching (tool/bboxes.py:171-240; not the official ICDAR-2015 protoco
 
     python eval_pixellink_fast.py --checkpoint_path /tmp/pixellink/ --test_data_path ./images --gt_path ./gt
     python eval_pixellink_fast.py --synthetic 2 --gt_path ./gt         (random images named synthetic_<i>)
+    python eval_pixellink_fast.py ... --map_scales 0.5,1,2 --flip      (multi-scale and flip testing: the passes' score maps
+                                                                        are fused on the device and decoded once; build-defined,
+                                                                        its effect on the F-measure is unmeasured)
 
 Flag names and defaults are test_pixellink_fast.py's where the two scripts share them; that script itself is unchanged and
 writes the same `res_<name>.txt` files as before.  Unlike it, images of any size are taken: each is resized on the device
@@ -32,6 +35,20 @@ def _sweep_help():
     return SWEEP_HELP % "the component's mean pixel score, in [0, 1]"
 
 
+def _map_scales_arg(text):
+    from tensorflow_ocr_amd.tool.pixellink_fn import map_scales_arg
+    return map_scales_arg(text)
+
+
+MAP_SCALES_HELP = ("multi-scale testing by score-map fusion: the network runs at each of these scales of the eval size (sides "
+                   "rounded to multiples of 32), the pixel and link probabilities of all passes are resampled onto the 1/4 "
+                   "eval-size grid and averaged on the device, and the link decode runs once (1 to 8 numbers, e.g. 0.5,1,2; "
+                   "1 need not be among them).  Build-defined; whether it raises the F-measure is unmeasured.  Activation "
+                   "memory grows with the square of the largest scale")
+FLIP_HELP = ("also run every scale on the images mirrored left to right and fuse those maps too (alone: scale 1 plus its "
+             "mirror)")
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--checkpoint_path', type=str, default=None)
@@ -52,6 +69,8 @@ def parse(argv=None):
                     "matching rule; icdar15 = the official ICDAR-2015 protocol (polygon IoU, ### as don't-care regions), the "
                     "line then ends in [icdar15]")
     ap.add_argument('--eval_sweep', type=_sweep_arg, default=None, metavar='LO:HI:N', help=_sweep_help())
+    ap.add_argument('--map_scales', type=_map_scales_arg, default=None, metavar='S1,S2,...', help=MAP_SCALES_HELP)
+    ap.add_argument('--flip', action='store_true', help=FLIP_HELP)
     FLAGS = ap.parse_args(argv)
     if FLAGS.min_side < 0 or FLAGS.min_area < 0:
         ap.error('--min_side and --min_area must not be negative')
@@ -96,7 +115,8 @@ def main(argv=None):
                                 pixel_conf_threshold=FLAGS.pixel_conf_threshold,
                                 link_conf_threshold=FLAGS.link_conf_threshold, min_side=FLAGS.min_side,
                                 min_area=FLAGS.min_area, eval_image_height=H, eval_image_width=W,
-                                protocol=FLAGS.eval_protocol, sweep=FLAGS.eval_sweep)
+                                protocol=FLAGS.eval_protocol, sweep=FLAGS.eval_sweep, map_scales=FLAGS.map_scales,
+                                flip=FLAGS.flip)
     try:
         res = ev.run()
         print(evaluate.format_line(res), flush=True)

@@ -1128,6 +1128,10 @@ int ocr_eval_record_init(void* record_i64, void* stream);
 /* Multi-scale RBOX inference: pooling the per-scale LANMS results of an image and fusing them across scales, in the layout
  * ocr_eval_collect reads: its entries and their comment block are in a header of their own, part of this ABI. */
 #include "ocr_multiscale.h"
+/* Multi-scale and flip testing for the link geometry: one pass that turns a forward's logits into probabilities on a
+ * fusion grid and adds them to an accumulator ocr_link_cc reads as it is: its entry and comment block are in a header of
+ * their own, part of this ABI. */
+#include "ocr_map_fuse.h"
 
 /* ------------------------------------------------------------------------- *
  * Link-geometry detections on the device (csrc/link_boxes.hip): what lies between ocr_min_area_rects and

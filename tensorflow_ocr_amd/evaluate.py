@@ -25,7 +25,9 @@ precision, counted on the device from the same matching pass (include/ocr_eval_c
 
 `Evaluator(scales=[...])` (`--scales`, `--eval_scales`) is multi-scale testing: one forward per scale, the per-scale LANMS
 results pooled in original-image pixels and fused on the device (rbox.detect_multiscale_device, include/ocr_multiscale.h,
-DESIGN.md §3.3.19), then the same matcher."""
+DESIGN.md §3.3.19), then the same matcher.  `LinkEvaluator(map_scales=[...], flip=...)` (`--map_scales`, `--flip`,
+`--eval_map_scales`, `--eval_flip`) is multi-scale and flip testing for the link geometry: the passes' score maps are
+fused on the device (pixellink_fn.fuse_score_maps, include/ocr_map_fuse.h) and decoded once."""
 import os
 
 import numpy as np
@@ -358,6 +360,10 @@ class Evaluator:
             self.curve.add_raster(tp, fp, det_score, nd, ng, gign if gign.dtype == torch.uint8 else gign.to(torch.uint8))
         return total - max_k, nd_total - self.max_d          # > 0: overflow (device tensors, read at the end of the pass)
 
+    def _pick_chain(self):
+        """the chain a pass runs per batch"""
+        return self._chain if self.ms_scales is None else self._chain_multiscale
+
     def _overflow(self, worst):
         return 'an image selected %d pixels more than max_k: raise max_k or the score threshold' % worst
 
@@ -370,7 +376,7 @@ class Evaluator:
             self.curve.reset()
         over_k, over_d, buckets = [], [], {}
         self._over_pool = []      # multi-scale only: per chain, int32 [n,2] = (pool_total - max_pool, non-finite rows)
-        chain = self._chain if self.ms_scales is None else self._chain_multiscale
+        chain = self._pick_chain()
 
         def flush(items):
             a, b = chain(items)
@@ -429,14 +435,34 @@ class LinkEvaluator(Evaluator):
     (ocr_component_scores; build-defined).  min_side / min_area filter the boxes (0: nothing, as the reference scripts).
     `run()` reads the device once at its end: the record, and the two overflow counts (components over max_comps,
     detections over max_d), either of which raises ValueError.  `sweep` as for `Evaluator`: its thresholds are on the
-    component's mean pixel score, in [0, 1]."""
+    component's mean pixel score, in [0, 1].
+
+    map_scales / flip / scale_weights: None / False / None = the single-scale pass above, bit for bit.  `scales=` (box-level
+    fusion) stays refused for this geometry; multi-scale and flip testing fuse the SCORE MAPS instead (DESIGN.md §3.3.20,
+    include/ocr_map_fuse.h).  map_scales: 1 to 8 positive finite scales (1 need not be among them): every batch is resized
+    from the ORIGINALS to each pixellink_fn.map_scale_sizes entry of the eval size and forwarded once, with flip=True a
+    second time mirrored left to right; each pass's pixel and link probabilities are resampled onto the eval_hw / 4 grid
+    and averaged with scale_weights (default: equal; a scale's two passes share its weight), and the link decode runs
+    once on the fused maps.  The fusion grid is the single-scale one, so the box scales, the matcher, `protocol`, `sweep`
+    and the single device read per pass are what they were.  flip without map_scales is scale 1 plus its mirror.
+    Activation memory grows with the square of the largest scale.  Whether any of this raises the F-measure is
+    unmeasured: no dataset or trained checkpoint is on any machine that built it."""
 
     def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, pixel_conf_threshold=0.8,
                  link_conf_threshold=0.9, min_size=10, max_comps=4096, min_side=0.0, min_area=0.0, max_d=ops.EVAL_MAX_D,
-                 eval_image_height=768, eval_image_width=1280, gt_path=None, protocol='raster', sweep=None, scales=None):
+                 eval_image_height=768, eval_image_width=1280, gt_path=None, protocol='raster', sweep=None, scales=None,
+                 map_scales=None, flip=False, scale_weights=None):
         if scales is not None:
             # the min-area-rectangle vertices of a component have no fixed correspondence across scales for the vote
             raise ValueError('multi-scale evaluation (scales=...) is built for the RBOX geometry only')
+        from .tool import pixellink_fn
+        self.flip = bool(flip)
+        if map_scales is None and scale_weights is not None:
+            raise ValueError('scale_weights come with map_scales')
+        if map_scales is None and self.flip:
+            map_scales = [1.0]                       # flip alone: scale 1 and its mirror
+        self.map_scales, self.scale_weights = (None, None) if map_scales is None else \
+            pixellink_fn.check_map_scales(map_scales, scale_weights)
         super().__init__(graph, forward, data, batch_size=batch_size, max_images=max_images,
                          matching_threshold=matching_threshold, max_d=max_d, gt_path=gt_path, protocol=protocol, sweep=sweep)
         self.eval_hw = (int(eval_image_height), int(eval_image_width))
@@ -475,6 +501,37 @@ class LinkEvaluator(Evaluator):
             max_comps=self.max_comps, min_side=self.min_side, min_area=self.min_area, graph=g)
         return self._match(merged, keep, n_keep, passed, total, inv_ratio, gts, ng, gign, mask_hw)
 
+    # -- score-map fusion (map_scales=..., flip=...): beside the single-scale chain, which it leaves as it is ---------
+    def _passes(self, batch, srcs):
+        """the forward passes of a batch, one at a time: every original resized to each map_scale_sizes entry, forwarded,
+        and with `flip` forwarded again mirrored left to right.  A generator: fuse_score_maps uses a pass's logits up
+        before it asks for the next forward, which may return the same buffers."""
+        from .tool import pixellink_fn
+        for rh, rw in pixellink_fn.map_scale_sizes(self.eval_hw[0], self.eval_hw[1], self.map_scales):
+            x, _ = self._resize_batch(batch, srcs, rh, rw)
+            pixel_cls, link_cls = self.forward(x)
+            yield pixel_cls, link_cls, False
+            if self.flip:
+                pixel_cls, link_cls = self.forward(torch.flip(x, dims=[2]))
+                yield pixel_cls, link_cls, True
+
+    def _chain_fused(self, batch):
+        from .tool import pixellink_fn
+        g = self.g
+        scale_x, scale_y = self.scales(*batch[0][0].shape[:2])
+        gts, ng, gign, mask_hw = self._ground_truths(batch)
+        weights = np.repeat(np.asarray(self.scale_weights, np.float64), 2 if self.flip else 1)
+        # the fusion grid is the single-scale pass's: eval_hw / 4, so the box scales and everything behind them stay
+        merged, keep, n_keep, passed, total = pixellink_fn.detect_device_multiscale(
+            self._passes(batch, self._sources(batch)), weights, (self.eval_hw[0] // 4, self.eval_hw[1] // 4),
+            self.pixel_conf_threshold, self.link_conf_threshold, self.min_size, scale_x, scale_y, max_comps=self.max_comps,
+            min_side=self.min_side, min_area=self.min_area, graph=g)
+        ones = torch.ones((len(batch), 2), dtype=torch.float32, device=g.device)
+        return self._match(merged, keep, n_keep, passed, total, ones, gts, ng, gign, mask_hw)
+
+    def _pick_chain(self):
+        return self._chain if self.map_scales is None else self._chain_fused
+
     def _overflow(self, worst):
         return 'an image holds %d components more than max_comps = %d' % (worst, self.max_comps)
 
@@ -512,7 +569,8 @@ class TrainEval:
     (train_pixellink.py) -> (pixel_cls, link_cls); `opt` is read when a pass runs (the optimiser exists only after the
     step was built).  `last` holds the latest result.  sweep: None, or the score thresholds of the evaluator's `sweep`
     (the pass still reads the device once; `write` then adds eval/ap, eval/best_hmean, eval/best_threshold).
-    scales / fuse / max_pool: the evaluator's multi-scale options (None = single scale; the RBOX `Evaluator` only)."""
+    scales / fuse / max_pool: the evaluator's multi-scale options (None = single scale; the RBOX `Evaluator` only).
+    `LinkEvaluator`'s map_scales / flip / scale_weights travel in **evaluator_kw."""
 
     def __init__(self, graph, step, network, data, every, max_images=None, weights='ema', batch_size=8, evaluator=Evaluator,
                  sweep=None, scales=None, fuse='nms', max_pool=1024, **evaluator_kw):

@@ -1470,6 +1470,31 @@ def quad_fuse(pool, pool_count, iou_thresh, mode, fused, keep_idx, n_keep, owner
            ptr(keep_idx), ptr(n_keep), ptr(owner), ptr(buf), c_size_t(nbytes), _st())
 
 
+# ------------------------------------------------------------------ score-map fusion of the link geometry (csrc/map_fuse.hip)
+def link_map_accumulate(pixel_logits, link_logits, flip, weight, first, acc):
+    """One forward pass's LOGITS (pixel_logits f32 [n,hs,ws,2], link_logits f32 [n,hs,ws,16]) -> softmax index 1, sampled
+    on the fusion grid, times `weight` (a normalised weight, finite and > 0), stored in (`first`) or added to acc f32
+    [9,n,hf,wf]: plane 0 = P(text), 1 + d = P(link d); `flip`: the pass saw the images mirrored left to right
+    (include/ocr_map_fuse.h: ocr_link_map_accumulate)."""
+    if pixel_logits.dim() != 4 or link_logits.dim() != 4 or acc.dim() != 4:
+        raise ValueError("link_map_accumulate: pixel_logits [n,hs,ws,2], link_logits [n,hs,ws,16], acc [9,n,hf,wf]")
+    n, hs, ws, _ = pixel_logits.shape
+    hf, wf = acc.shape[2:]
+    if tuple(pixel_logits.shape) != (n, hs, ws, 2) or tuple(link_logits.shape) != (n, hs, ws, 16) or \
+            tuple(acc.shape) != (9, n, hf, wf):
+        raise ValueError("link_map_accumulate: tensors do not match n, hs, ws (logits [..,2] and [..,16]) or acc is not [9,n,hf,wf]")
+    if pixel_logits.dtype != torch.float32 or link_logits.dtype != torch.float32 or acc.dtype != torch.float32:
+        raise ValueError("link_map_accumulate: logits and acc f32")
+    for t in (pixel_logits, link_logits, acc):
+        if not t.is_contiguous():
+            raise ValueError("link_map_accumulate: contiguous tensors only")
+    weight = float(weight)
+    if not (weight > 0.0 and weight != float("inf")):
+        raise ValueError("link_map_accumulate: weight must be finite and positive, got %r" % (weight,))
+    L.call("ocr_link_map_accumulate", ptr(pixel_logits), ptr(link_logits), c_int(n), c_int(hs), c_int(ws), c_int(int(bool(flip))),
+           c_float(weight), c_int(int(bool(first))), ptr(acc), c_int(hf), c_int(wf), _st())
+
+
 # ------------------------------------------------------------------ link-geometry detections (csrc/link_boxes.hip)
 def component_scores(labels, pixel_score, ncomp, comp_score, ws):
     """labels int32 [n,h,w] (ocr_link_cc), pixel_score f32 [n,h,w], ncomp int32 [n] -> comp_score f32 [n,max_comps]: the

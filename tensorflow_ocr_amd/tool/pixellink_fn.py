@@ -253,6 +253,101 @@ def detect_device(pixel_score, link_score, pixel_conf_threshold=0.8, link_conf_t
     return link_boxes_device(labels, ncomp, ps, scale_x, scale_y, max_comps, min_side, min_area, graph=g)
 
 
+# ------------------------------------------------------------------ multi-scale / flip testing: score-map fusion
+MAX_MAP_SCALES = 8
+
+
+def check_map_scales(scales, weights=None):
+    """1 to 8 positive finite scales and, if given, as many positive finite weights -> (scales, weights) as lists of
+    floats (weights default to 1 each); ValueError otherwise.  A scale list need not contain 1."""
+    import math
+    try:
+        values = [float(s) for s in scales]
+        wts = [1.0] * len(values) if weights is None else [float(v) for v in weights]
+    except TypeError:
+        raise ValueError('map scales and their weights are sequences of numbers, got %r, %r' % (scales, weights))
+    if not 1 <= len(values) <= MAX_MAP_SCALES:
+        raise ValueError('score-map fusion takes 1 to %d scales, got %d' % (MAX_MAP_SCALES, len(values)))
+    if len(wts) != len(values):
+        raise ValueError('%d scale weights for %d scales' % (len(wts), len(values)))
+    for v in values + wts:
+        if not (math.isfinite(v) and v > 0):
+            raise ValueError('a map scale and its weight must be positive and finite, got %r' % (v,))
+    return values, wts
+
+
+def parse_map_scales(text):
+    """--map_scales / --eval_map_scales: a comma list of numbers -> a list of floats; ValueError otherwise."""
+    return check_map_scales([float(v) for v in str(text).split(',') if v.strip()])[0]
+
+
+def map_scales_arg(text):
+    """`parse_map_scales` as an argparse type"""
+    import argparse
+    try:
+        return parse_map_scales(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def map_scale_sizes(eval_h, eval_w, scales):
+    """The network input sizes of score-map fusion: [(H_s, W_s)] with side_s = max(32, floor(side * s / 32 + 0.5) * 32)
+    (build-defined rounding).  PixelLinkNet itself needs multiples of 16 — four 2x2/2 pools down to fc7, then the two x2
+    unpools back to the 1/4-resolution heads — which every multiple of 32 is; 32 is kept as the step because it is the
+    step of the reference's own sizing rule (test.py:92-121)."""
+    import math
+    values, _ = check_map_scales(scales)
+    side = lambda v, s: max(32, int(math.floor(v * s / 32.0 + 0.5)) * 32)
+    return [(side(int(eval_h), s), side(int(eval_w), s)) for s in values]
+
+
+def pass_weights(weights, flip=False):
+    """The normalised f32 weight of every forward pass, in the order the passes run (per scale: un-flipped, then flipped):
+    float32(w_s / sum over all passes), the quotient formed in float64."""
+    import numpy as np
+    w = np.repeat(np.asarray(weights, np.float64), 2 if flip else 1)
+    return [float(np.float32(v / w.sum())) for v in w]
+
+
+def fuse_score_maps(passes, weights, out_hw, graph=None):
+    """Score-map fusion (include/ocr_map_fuse.h): `passes` is an iterable of (pixel_cls [N,hs,ws,2], link_cls [N,hs,ws,16],
+    flip) LOGITS, one item per forward pass; `weights` the passes' weights (any positive scale: they are normalised here,
+    in float64).  Every item is used up — its accumulate launched — BEFORE the next one is asked for, because a graphed
+    forward returns the same output buffers for the same shape: the flipped pass of a scale overwrites the un-flipped
+    logits.  Returns (pixel_score [N,h,w], link_score [8,N,h,w]), views of ONE accumulator [9,N,h,w] in the layout
+    `link_cc_decode` reads, h, w = out_hw.  The mean is of probabilities, not of logits.  A pure launch sequence: no
+    synchronisation."""
+    g = graph or get_default_graph()
+    h, w = int(out_hw[0]), int(out_hw[1])
+    import math
+    raw = [float(v) for v in weights]
+    if not raw or not all(math.isfinite(v) and v > 0 for v in raw):
+        raise ValueError('the pass weights must be positive and finite, got %r' % (weights,))
+    norm = pass_weights(raw)
+    acc, used = None, 0
+    for pixel_cls, link_cls, flip in passes:
+        if used == len(norm):
+            raise ValueError('more forward passes than the %d weights' % len(norm))
+        px, lk = _dev(g, pixel_cls), _dev(g, link_cls)
+        if acc is None:
+            acc = torch.empty((9, px.shape[0], h, w), dtype=F32, device=g.device)
+        ops.link_map_accumulate(px, lk, flip, norm[used], used == 0, acc)
+        used += 1
+    if used != len(norm):
+        raise ValueError('%d forward passes for %d weights' % (used, len(norm)))
+    return acc[0], acc[1:]
+
+
+def detect_device_multiscale(passes, weights, out_hw, pixel_conf_threshold=0.8, link_conf_threshold=0.9, min_size=10,
+                             scale_x=4.0, scale_y=4.0, max_comps=4096, min_side=0.0, min_area=0.0, graph=None):
+    """`fuse_score_maps` followed by `detect_device` on the fused maps: the link decode runs ONCE.  Returns
+    link_boxes_device's five device tensors; no synchronisation."""
+    g = graph or get_default_graph()
+    pixel_score, link_score = fuse_score_maps(passes, weights, out_hw, graph=g)
+    return detect_device(pixel_score, link_score, pixel_conf_threshold, link_conf_threshold, min_size, scale_x, scale_y,
+                         max_comps=max_comps, min_side=min_side, min_area=min_area, graph=g)
+
+
 def generate_rbox(h, w, xs, ys, bboxes, ignored, graph=None):
     """tool/pixellink_fn.py:53-110 for one image.  xs, ys normalised corner coordinates [k,4], bboxes
     [k,4], ignored [k] -> (res_score_map float32 [h/4,w/4], res_link_map float32 [h/4,w/4,8],

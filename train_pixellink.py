@@ -20,7 +20,8 @@ generator this script's `tf_pixellink_get_rbox` wraps.  Without --dataset_dir: s
 
 Not in the reference: `--eval_data_path DIR --eval_steps N` evaluates a held-out directory (images + gt_*.txt) between steps
 every N optimiser steps, on the device and outside the recorded step (tensorflow_ocr_amd/evaluate.py: LinkEvaluator), and
-reports precision / recall / hmean."""
+reports precision / recall / hmean; `--eval_map_scales 0.5,1,2 [--eval_flip]` makes every such pass a multi-scale / flip
+test by score-map fusion."""
 import argparse
 import os
 import time
@@ -32,6 +33,11 @@ import torch
 def _sweep_arg(text):
     from tensorflow_ocr_amd.evaluate import sweep_arg
     return sweep_arg(text)
+
+
+def _map_scales_arg(text):
+    from tensorflow_ocr_amd.tool.pixellink_fn import map_scales_arg
+    return map_scales_arg(text)
 
 
 def parse(argv=None):
@@ -94,7 +100,14 @@ def parse(argv=None):
     # --eval_sweep LO:HI:N (or a comma list): every pass also reports the precision / recall curve over the component's mean
     # pixel score (in [0, 1]), its best row and AP, from the one matching pass (evaluate.LinkEvaluator's sweep)
     ap.add_argument('--eval_sweep', type=_sweep_arg, default=None, metavar='LO:HI:N')
+    # --eval_map_scales S1,S2,... [--eval_flip]: multi-scale / flip testing of every pass by score-map fusion (the flags
+    # --map_scales / --flip of eval_pixellink_fast.py: evaluate.LinkEvaluator's map_scales / flip; build-defined, its effect
+    # on the F-measure unmeasured; activation memory grows with the square of the largest scale)
+    ap.add_argument('--eval_map_scales', type=_map_scales_arg, default=None, metavar='S1,S2,...')
+    ap.add_argument('--eval_flip', action='store_true')
     FLAGS = ap.parse_args(argv)
+    if (FLAGS.eval_map_scales is not None or FLAGS.eval_flip) and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
+        ap.error('--eval_map_scales and --eval_flip need --eval_data_path and --eval_steps')
     if FLAGS.eval_sweep is not None and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
         ap.error('--eval_sweep needs --eval_data_path and --eval_steps')
     if FLAGS.eval_steps < 0 or (FLAGS.eval_max_images is not None and FLAGS.eval_max_images < 1):
@@ -232,7 +245,7 @@ def make_train_eval(FLAGS, g, step):
                               weights=FLAGS.eval_weights, batch_size=max(1, int(FLAGS.batch_size / FLAGS.num_gpus)),
                               evaluator=evaluate.LinkEvaluator, eval_image_height=FLAGS.eval_image_height,
                               eval_image_width=FLAGS.eval_image_width, protocol=FLAGS.eval_protocol,
-                              sweep=FLAGS.eval_sweep)
+                              sweep=FLAGS.eval_sweep, map_scales=FLAGS.eval_map_scales, flip=FLAGS.eval_flip)
 
 
 def _evaluate(train_eval, summaries, opt):
