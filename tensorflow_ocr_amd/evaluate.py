@@ -1,33 +1,13 @@
 """Held-out evaluation on the device: precision / recall / F-measure of a detector over a directory of images and
-`gt_*.txt` files (the ICDAR layout datasets/icdar.py reads), one chain per batch
+`gt_*.txt` files (the ICDAR layout datasets/icdar.py reads).  One pass driver, `Evaluator`, runs per batch
 
-    forward -> rbox.detect_device (decode, LANMS, mean-score mask) -> ocr_eval_collect -> bboxes.bboxes_matching_batch
+    upload -> detector.detect (resize, forward, decode) -> ocr_eval_collect -> matcher (-> curve)
 
-with the counters of tool/metrics.py on the device (`metrics.DeviceTpFp`): the host reads them once per pass.  Two
-matching rules: `protocol='raster'` (the default) is the reference's (tool/bboxes.py:171-240, rasterised IoU);
-`protocol='icdar15'` is the official ICDAR-2015 Task-1 localisation protocol (polygon IoU, `###` ground truths as
-don't-care regions, ground-truth-major greedy matching: bboxes.ic15_matching_batch), the figure
-that papers and the leaderboard report — up to three build-defined points stated there (detection order, orientation,
-self-intersecting quads), since no run of the official script pins it.  Ground truths are matched in ORIGINAL image
-coordinates, detections are divided by the resize ratios as test.py divides them; `###` (or `*`) marks an ignored
-(don't-care) ground truth (icdar.load_annoataion).
-
-`Evaluator` is the EAST RBOX geometry.  `LinkEvaluator` is the PixelLink (link) geometry of test_pixellink_fast.py, the same
-pass with another middle:
-
-    forward -> softmaxes -> pixellink_fn.detect_device (link_cc, min-area rectangles, component scores, boxes) -> ...
-
-(test.py's own link path, the contour decode of pixellink_fn.find_contour_boxes, still ends on the host and is not
-evaluated here).
-
-`sweep=[...]` (`--eval_sweep`) adds the precision / recall curve over detection scores, its best row and average
-precision, counted on the device from the same matching pass (include/ocr_eval_curve.h).
-
-`Evaluator(scales=[...])` (`--scales`, `--eval_scales`) is multi-scale testing: one forward per scale, the per-scale LANMS
-results pooled in original-image pixels and fused on the device (rbox.detect_multiscale_device, include/ocr_multiscale.h,
-DESIGN.md §3.3.19), then the same matcher.  `LinkEvaluator(map_scales=[...], flip=...)` (`--map_scales`, `--flip`,
-`--eval_map_scales`, `--eval_flip`) is multi-scale and flip testing for the link geometry: the passes' score maps are
-fused on the device (pixellink_fn.fuse_score_maps, include/ocr_map_fuse.h) and decoded once."""
+with the counters of tool/metrics.py on the device, and reads the device once at its end.  What lies between the upload
+and the collect step is one of four detectors: `RboxSingleScale` / `RboxMultiScale` (`Evaluator`, the EAST RBOX
+geometry) and `LinkSingleScale` / `LinkFused` (`LinkEvaluator`, the PixelLink geometry of test_pixellink_fast.py; test.py's
+own link path, the contour decode, still ends on the host and is not evaluated here).  Ground truths are matched in
+ORIGINAL image coordinates; `###` (or `*`) marks an ignored (don't-care) ground truth (icdar.load_annoataion)."""
 import os
 
 import numpy as np
@@ -81,6 +61,11 @@ def load_ground_truth(im_fn, gt_path=None):
 
 
 PROTOCOLS = ('raster', 'icdar15')
+
+
+def _check_protocol(protocol):
+    if protocol not in PROTOCOLS:
+        raise ValueError("protocol must be 'raster' or 'icdar15', got %r" % (protocol,))
 
 
 def quad_is_bow_tie(poly):
@@ -166,47 +151,248 @@ def format_sweep(result):
     return '\n'.join(lines)
 
 
+# -- resizing on the device: the evaluator's detectors and test.py ---------------------------------------------
+def to_device(im, device):
+    """an image uint8 [h,w,3] on the device"""
+    return torch.from_numpy(np.ascontiguousarray(im, dtype=np.uint8)).to(device)
+
+
+def resize_batch(srcs, rh, rw):
+    """device originals (uint8 [h,w,3] each) -> x f32 [n,rh,rw,3], every one resized to rh x rw on the device"""
+    x = torch.empty((len(srcs), rh, rw, 3), dtype=torch.float32, device=srcs[0].device)
+    for i, src in enumerate(srcs):
+        ops.resize_linear_u8(src, x[i])
+    return x
+
+
+def ratio_rows(n, ratio_w=1.0, ratio_h=1.0, device=None):
+    """f32 [n,2] rows (ratio_w, ratio_h): what ocr_eval_collect divides the detections by (test.py:127).  The default,
+    (1, 1), is for detections that are in original-image pixels already."""
+    return torch.from_numpy(np.tile(np.array([ratio_w, ratio_h], np.float32), (n, 1))).to(device)
+
+
+def multiscale_inputs(srcs, scales, max_side_len=3000):
+    """device originals of ONE shape -> (xs, ratios): per scale one f32 [n,H_s,W_s,3] batch, every image resized from the
+    ORIGINAL to rbox.scale_sizes' size, and one f32 [n,2] (ratio_w, ratio_h) tensor"""
+    from .tool import rbox
+    h, w = srcs[0].shape[:2]
+    xs, ratios = [], []
+    for rh, rw in rbox.scale_sizes(h, w, scales, max_side_len):
+        xs.append(resize_batch(srcs, rh, rw))
+        ratios.append(ratio_rows(len(srcs), rw / float(w), rh / float(h), srcs[0].device))
+    return xs, ratios
+
+
+# -- the detectors ---------------------------------------------------------------------------------------------
+# detect(batch, srcs): batch = [(image uint8 [h,w,3], polys, ignored)] of one ORIGINAL shape, srcs = its images on the
+# device -> the rows ops.eval_collect reads (merged, keep, n_keep, passed or None, inv_ratio f32 [n,2]) and `overflow`
+# int32 [n,m], one column per limit the detector can exceed (> 0: candidates were lost).  A pure launch sequence.
+# `overflow_messages`: m formatters, one per column, in the order the columns are reported.
+class RboxSingleScale:
+    """EAST RBOX at one scale: `forward(x)` takes a device f32 [n,H,W,3] batch (0..255, RGB) and returns the (score
+    [n,H/4,W/4,1], geometry [n,H/4,W/4,5]) maps of model_rbox (tensors or head handles) as a pure launch sequence.  Images
+    are resized by test.py's rule, then forward -> rbox.detect_device (decode, LANMS, the mean-score mask of box_thresh);
+    the quads are in resized pixels, which the collect step divides by the resize ratios as test.py divides them.  A
+    detection's score, the matcher's order key, is LANMS's merged score: a SUM of the merged pixels' scores."""
+
+    def __init__(self, graph, forward, score_map_thresh, nms_thres, box_thresh, max_k, max_side_len):
+        self.g, self.forward = graph, forward
+        self.score_map_thresh, self.nms_thres, self.box_thresh = float(score_map_thresh), float(nms_thres), box_thresh
+        self.max_k, self.max_side_len = max_k, max_side_len
+        self.overflow_messages = (
+            lambda worst: 'an image selected %d pixels more than max_k: raise max_k or the score threshold' % worst,)
+
+    def resized(self, h, w):
+        """the size an h x w image enters the network at"""
+        return resize_rule(h, w, self.max_side_len)
+
+    def ratio(self, h, w, rh, rw):
+        """(ratio_w, ratio_h) of test.py:127"""
+        return rw / float(w), rh / float(h)
+
+    def detect(self, batch, srcs):
+        from .tool import rbox
+        h, w = batch[0][0].shape[:2]
+        rh, rw = self.resized(h, w)
+        x = resize_batch(srcs, rh, rw)
+        inv_ratio = ratio_rows(len(srcs), *self.ratio(h, w, rh, rw), self.g.device)
+        f_score, f_geometry = self.forward(x)
+        merged, keep, n_keep, passed, total = rbox.detect_device(f_score, f_geometry, self.score_map_thresh, self.nms_thres,
+                                                                 self.max_k, graph=self.g, box_thresh=self.box_thresh)
+        return merged, keep, n_keep, passed, inv_ratio, (total - merged.shape[1])[:, None]
+
+
+class RboxMultiScale(RboxSingleScale):
+    """EAST RBOX, multi-scale testing: every image is resized from the ORIGINAL to rbox.scale_sizes' size
+    at each of 1..8 scales, `forward` runs once per scale, and rbox.detect_multiscale_device pools the per-scale LANMS results
+    in original-image pixels and fuses them (fuse = 'nms' or 'vote', at most max_pool <= 4096 pooled quads per image:
+    include/ocr_multiscale.h).  The fused quads are in original pixels already, so the collect step divides by 1; their
+    score, the matcher's order key, is the MEAN pixel score, in [0, 1].  Overflow columns: the worst total - max_k over
+    the scales, pool_total - max_pool, the non-finite pooled rows."""
+
+    def __init__(self, *single_scale, scales, fuse, max_pool):
+        from .tool import rbox
+        super().__init__(*single_scale)
+        self.scales, self.fuse, self.max_pool = scales, fuse, int(max_pool)
+        # rbox.overflow_error's three messages, each for its own column
+        self.overflow_messages = tuple(
+            (lambda worst, c=c: rbox.overflow_error(*[worst if k == c else 0 for k in range(3)], max_pool=self.max_pool))
+            for c in range(3))
+
+    @staticmethod
+    def check(scales, fuse, max_pool):
+        """the options as the constructor is given them -> the scale list, or None for one scale"""
+        from .tool import rbox
+        if fuse not in rbox.FUSE_MODES:
+            raise ValueError("fuse must be 'nms' or 'vote', got %r" % (fuse,))
+        if not 1 <= int(max_pool) <= ops.FUSE_MAX_POOL:
+            raise ValueError('max_pool must be in [1, %d]' % ops.FUSE_MAX_POOL)
+        if scales is None:
+            return None
+        return rbox.check_scales(scales)              # count, sign and finiteness; the sizes are checked per image shape
+
+    def detect(self, batch, srcs):
+        from .tool import rbox
+        xs, ratios = multiscale_inputs(srcs, self.scales, self.max_side_len)
+        maps = (self.forward(x) for x in xs)          # a scale's forward runs when detect_multiscale_device asks for it
+        fused, keep, n_keep, overflow = rbox.detect_multiscale_device(
+            maps, ratios, self.score_map_thresh, self.nms_thres, self.box_thresh, fuse=self.fuse, max_pool=self.max_pool,
+            max_k=self.max_k, graph=self.g)
+        return fused, keep, n_keep, None, ratio_rows(len(srcs), device=self.g.device), overflow
+
+
+class LinkSingleScale:
+    """The link geometry at one scale: `forward(x)` returns the (pixel_cls [n,H/4,W/4,2], link_cls [n,H/4,W/4,16]) LOGITS of
+    `PixelLinkNet` (tensors or head handles) as a pure launch sequence.  Every image is resized on the device to the fixed
+    eval_image_height x eval_image_width (test_pixellink_fast.py's flags), then forward -> softmaxes ->
+    pixellink_fn.detect_device (link_cc, min-area rectangles, component scores, boxes).  ocr_min_area_rects takes one scale
+    per call (hence the batches of one ORIGINAL shape): a component pixel (x, y) of the 1/4-resolution maps becomes the point
+    (int(x * scale_x), int(y * scale_y)), so the boxes land in original-image pixels and the collect step divides by 1.
+    A detection's score is its component's mean pixel score, in [0, 1] (ocr_component_scores; build-defined).  min_side /
+    min_area filter the boxes (0: nothing, as the reference scripts).  Overflow column: ncomp - max_comps."""
+    map_scales = scale_weights = None                 # (what `LinkFused` holds: one pass at the eval size, not mirrored)
+    flip = False
+
+    def __init__(self, graph, forward, eval_hw, pixel_conf_threshold, link_conf_threshold, min_size, max_comps, min_side,
+                 min_area):
+        self.g, self.forward = graph, forward
+        self.eval_hw = (int(eval_hw[0]), int(eval_hw[1]))
+        if min(self.eval_hw) < 4 or self.eval_hw[0] % 4 or self.eval_hw[1] % 4:
+            raise ValueError('the eval size must be positive multiples of 4, got %dx%d' % self.eval_hw)
+        if int(max_comps) < 1:
+            raise ValueError('max_comps must be positive')
+        self.pixel_conf_threshold, self.link_conf_threshold = float(pixel_conf_threshold), float(link_conf_threshold)
+        self.min_size, self.max_comps = int(min_size), int(max_comps)
+        self.min_side, self.min_area = float(min_side), float(min_area)
+        self.overflow_messages = (
+            lambda worst: 'an image holds %d components more than max_comps = %d' % (worst, self.max_comps),)
+
+    def scales(self, h, w):
+        """(scale_x, scale_y) of an h x w original: 1/4-resolution map cell -> original-image pixels.  An original side
+        below a quarter of the eval side (a scale below 1) is refused."""
+        sx, sy = w / float(self.eval_hw[1] // 4), h / float(self.eval_hw[0] // 4)
+        if sx < 1.0 or sy < 1.0:
+            raise ValueError('a %dx%d image is smaller than the %dx%d score maps: lower the eval size'
+                             % (h, w, self.eval_hw[0] // 4, self.eval_hw[1] // 4))
+        return sx, sy
+
+    def _decode(self, decode, maps, box_scales):
+        """`decode` = pixellink_fn.detect_device or detect_device_multiscale, on its leading arguments `maps`"""
+        merged, keep, n_keep, passed, total = decode(
+            *maps, self.pixel_conf_threshold, self.link_conf_threshold, self.min_size, *box_scales,
+            max_comps=self.max_comps, min_side=self.min_side, min_area=self.min_area, graph=self.g)
+        inv_ratio = ratio_rows(merged.shape[0], device=self.g.device)
+        return merged, keep, n_keep, passed, inv_ratio, (total - merged.shape[1])[:, None]
+
+    def detect(self, batch, srcs):
+        from .tool import pixellink_fn
+        box_scales = self.scales(*batch[0][0].shape[:2])
+        pixel_cls, link_cls = self.forward(resize_batch(srcs, *self.eval_hw))
+        pixel_score = pixellink_fn.pixel_scores(pixel_cls, graph=self.g)[..., 1].contiguous()
+        link_score = pixellink_fn.link_scores(link_cls, graph=self.g)
+        return self._decode(pixellink_fn.detect_device, (pixel_score, link_score), box_scales)
+
+
+class LinkFused(LinkSingleScale):
+    """The link geometry, multi-scale and flip testing by SCORE-MAP fusion (include/ocr_map_fuse.h; the
+    min-area-rectangle vertices of a component have no fixed correspondence across scales for a box-level vote).
+    map_scales: 1 to 8 positive finite scales (1 need not be among them): every batch is resized from the ORIGINALS to each
+    pixellink_fn.map_scale_sizes entry of the eval size and forwarded once, with flip=True a second time mirrored left to
+    right; each pass's pixel and link probabilities are resampled onto the eval_hw / 4 grid and averaged with scale_weights
+    (a scale's two passes share its weight), and the link decode runs once on the fused maps.  The fusion grid is the
+    single-scale one, so the box scales and everything behind them are what they were.  Activation memory grows with the
+    square of the largest scale.  Whether any of this raises the F-measure is unmeasured: no dataset or trained checkpoint
+    is on any machine that built it."""
+
+    def __init__(self, *single_scale, map_scales, scale_weights, flip):
+        super().__init__(*single_scale)
+        self.map_scales, self.scale_weights, self.flip = map_scales, scale_weights, flip
+
+    def _passes(self, srcs):
+        """the forward passes of a batch, one at a time.  A generator: fuse_score_maps uses a pass's logits up before it
+        asks for the next forward, which may return the same buffers."""
+        from .tool import pixellink_fn
+        for rh, rw in pixellink_fn.map_scale_sizes(self.eval_hw[0], self.eval_hw[1], self.map_scales):
+            x = resize_batch(srcs, rh, rw)
+            pixel_cls, link_cls = self.forward(x)
+            yield pixel_cls, link_cls, False
+            if self.flip:
+                pixel_cls, link_cls = self.forward(torch.flip(x, dims=[2]))
+                yield pixel_cls, link_cls, True
+
+    def detect(self, batch, srcs):
+        from .tool import pixellink_fn
+        weights = np.repeat(np.asarray(self.scale_weights, np.float64), 2 if self.flip else 1)
+        grid = (self.eval_hw[0] // 4, self.eval_hw[1] // 4)
+        return self._decode(pixellink_fn.detect_device_multiscale, (self._passes(srcs), weights, grid),
+                            self.scales(*batch[0][0].shape[:2]))
+
+
+# -- the pass driver -------------------------------------------------------------------------------------------
 class Evaluator:
-    """Evaluator(graph, forward, data): `forward(x)` takes a device f32 [n,H,W,3] batch (0..255, RGB) and returns the
-    (score [n,H/4,W/4,1], geometry [n,H/4,W/4,5]) maps of model_rbox (tensors or head handles) as a pure launch sequence;
-    `data` is a directory of images with gt_<stem>.txt beside them, or under `gt_path` (an image without one is skipped).
-    Images are resized by test.py's rule and batched by resized shape, at most `batch_size` per chain.  `run()` makes one pass and returns
-    {'precision', 'recall', 'hmean', 'num_gt', 'tp', 'fp', 'num_det', 'images'}; it reads the device once at its end: the
-    record, and the two overflow counts (pixels over max_k, detections over max_d), either of which raises ValueError.
-    protocol='icdar15' swaps the matcher for the official ICDAR-2015 one (matching_threshold is its IoU threshold, the
-    area-precision threshold is 0.5): self-intersecting ground truths are dropped when the files are read and counted in
+    """Evaluator(graph, forward, data): the pass driver, and the EAST RBOX geometry's options.  `data` is a directory of
+    images with gt_<stem>.txt beside them, or under `gt_path` (an image without one is skipped).  Images are batched by
+    ORIGINAL shape, at most `batch_size` per chain; per chain `self.detector.detect` is all that knows the geometry
+    (`RboxSingleScale`, or with scales=[...] `RboxMultiScale`; fuse / max_pool are the latter's).  `run()` makes one
+    pass and returns {'precision', 'recall', 'hmean', 'num_gt', 'tp', 'fp', 'num_det', 'images'}; it reads the device once
+    at its end: the record, and the column maxima of the chains' overflow counts — the detector's columns, then the
+    detections over max_d — the first positive of which raises ValueError.
+
+    protocol: 'raster' (the default) is the reference's matching rule (tool/bboxes.py:171-240, rasterised IoU).
+    'icdar15' is the official ICDAR-2015 Task-1 localisation protocol (polygon IoU, `###` ground truths as don't-care
+    regions, ground-truth-major greedy matching: bboxes.ic15_matching_batch), the figure that papers and the leaderboard
+    report, up to the three build-defined points of DESIGN.md §3.3.17.  matching_threshold is its IoU threshold, the
+    area-precision threshold is 0.5; self-intersecting ground truths are dropped when the files are read and counted in
     the result as 'invalid_gt', 'tp' / 'fp' / 'num_gt' / 'num_det' are matched / care detections - matched / care ground
     truths / detections before the don't-care filter, and the result names its 'protocol'.
 
     sweep: None, or a sequence of 1..64 score thresholds.  Then the pass also counts, from the SAME matching (no walk is
-    repeated: DESIGN.md §3.3.18), what the matcher gives with only the detections of score >= threshold kept, and the
-    result gains 'sweep' (a list of {'threshold', 'precision', 'recall', 'hmean', 'tp', 'fp', 'num_det'}), 'best' (its
-    row of highest hmean, ties to the lowest index) and 'ap' (average precision over the pooled detection scores of the
-    pass); still one device read.  The threshold is on the MATCHER'S ORDER KEY, ocr_eval_collect's det_score: for this
-    geometry that is LANMS's merged score, a SUM of the merged pixels' scores — not a probability and not EAST's
-    box_thresh mean; for `LinkEvaluator` it is the component's mean pixel score, in [0, 1].  Sweeping box_thresh,
-    score_map_thresh or the link threshold would change the detection set or its order and is not what this does.
-    With `scales` (below) the order key, and so the sweep's threshold, is instead the fused quad's MEAN pixel score, in
-    [0, 1].
+    repeated: include/ocr_eval_curve.h), what the matcher gives with only the detections of score >=
+    threshold kept, and the result gains 'sweep' (a list of {'threshold', 'precision', 'recall', 'hmean', 'tp', 'fp',
+    'num_det'}), 'best' (its row of highest hmean, ties to the lowest index) and 'ap' (average precision over the pooled
+    detection scores of the pass); still one device read.  The threshold is on the MATCHER'S ORDER KEY, ocr_eval_collect's
+    det_score, which each detector's docstring names.  Sweeping box_thresh, score_map_thresh or the link threshold would
+    change the detection set or its order and is not what this does.
 
-    scales: None = the single-scale pass above, bit for bit.  A sequence of 1..8 scales = multi-scale testing (DESIGN.md
-    §3.3.19): every image is resized from the ORIGINAL to rbox.scale_sizes' size at each scale, `forward` runs once per
-    scale, and rbox.detect_multiscale_device pools the per-scale LANMS results in original-image pixels and fuses them
-    (fuse = 'nms' or 'vote', at most max_pool <= 4096 pooled quads per image); the fused list goes to the same matcher.
-    The pass still reads the device once; a pool overflow or a non-finite pooled quad raises ValueError there too."""
+    A detector's options read as attributes of the evaluator (`ev.max_k`, `ev.eval_hw`, `ev.scales(h, w)`)."""
 
     def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, score_map_thresh=0.8,
                  nms_thres=0.2, box_thresh=None, max_k=None, max_d=ops.EVAL_MAX_D, max_side_len=3000, gt_path=None,
                  protocol='raster', sweep=None, scales=None, fuse='nms', max_pool=1024):
+        _check_protocol(protocol)                     # (its error comes before the scale options', as it always did)
+        scales = RboxMultiScale.check(scales, fuse, max_pool)
+        self._init_pass(graph, data, batch_size, max_images, matching_threshold, max_d, gt_path, protocol, sweep)
+        options = (self.g, forward, score_map_thresh, nms_thres, box_thresh, max_k, max_side_len)
+        self.detector = RboxSingleScale(*options) if scales is None else \
+            RboxMultiScale(*options, scales=scales, fuse=fuse, max_pool=max_pool)
+
+    def _init_pass(self, graph, data, batch_size, max_images, matching_threshold, max_d, gt_path, protocol, sweep):
+        """the driver's own state: the samples, the matcher's options, the record and the curve"""
         from .tool import metrics
-        if protocol not in PROTOCOLS:
-            raise ValueError("protocol must be 'raster' or 'icdar15', got %r" % (protocol,))
-        self.ms_scales = self._check_scales(scales, fuse, max_pool)
-        self.fuse, self.max_pool = fuse, int(max_pool)
+        _check_protocol(protocol)
         self.protocol, self.area_prec_thr, self.invalid_gt = protocol, 0.5, 0
         self.sweep = None if sweep is None else check_sweep(sweep)
         self.g = graph or get_default_graph()
-        self.forward = forward
         if not os.path.isdir(data):
             raise FileNotFoundError('no evaluation directory %r' % (data,))
         files = [(f, load_ground_truth(f, gt_path)) for f in list_images(data)]
@@ -228,44 +414,20 @@ class Evaluator:
         if not 1 <= int(max_d) <= ops.EVAL_MAX_D:
             raise ValueError('max_d must be in [1, %d]' % ops.EVAL_MAX_D)
         self.batch_size = max(1, int(batch_size))
-        self.matching_threshold = float(matching_threshold)
-        self.score_map_thresh, self.nms_thres, self.box_thresh = float(score_map_thresh), float(nms_thres), box_thresh
-        self.max_k, self.max_d, self.max_side_len = max_k, int(max_d), max_side_len
+        self.matching_threshold, self.max_d = float(matching_threshold), int(max_d)
         self.acc = metrics.DeviceTpFp(self.g)
         self.curve = None if self.sweep is None else metrics.DeviceCurve(self.sweep, len(self.samples), self.max_d, self.g)
         self.last = None          # the device tensors of the last chain (tests and the cost script look at them)
 
+    def __getattr__(self, name):
+        if name == 'detector':    # (asked for before the constructor made it)
+            raise AttributeError(name)
+        return getattr(self.detector, name)
+
     # -- one chain -------------------------------------------------------------------------------
-    def _resized(self, h, w):
-        """the size an h x w image enters the network at"""
-        return resize_rule(h, w, self.max_side_len)
-
-    def _ratio(self, h, w, rh, rw):
-        """what ocr_eval_collect divides the detections by: (ratio_w, ratio_h) of test.py:127"""
-        return rw / float(w), rh / float(h)
-
-    def _upload(self, batch):
-        """batch: [(image uint8 [h,w,3], polys, ignored)] of one resized shape -> x, inv_ratio, gts, ng, gignored, mask_hw"""
-        rh, rw = self._resized(batch[0][0].shape[0], batch[0][0].shape[1])
-        srcs = self._sources(batch)
-        x, ratio = self._resize_batch(batch, srcs, rh, rw)
-        return (x, ratio) + self._ground_truths(batch)
-
     def _sources(self, batch):
         """the original images of a batch on the device (uint8 [h,w,3] each)"""
-        return [torch.from_numpy(np.ascontiguousarray(im, dtype=np.uint8)).to(self.g.device) for im, _, _ in batch]
-
-    def _resize_batch(self, batch, srcs, rh, rw):
-        """-> x f32 [n,rh,rw,3] (every original resized to rh x rw on the device), ratio f32 [n,2] = (ratio_w, ratio_h)"""
-        dev = self.g.device
-        n = len(batch)
-        x = torch.empty((n, rh, rw, 3), dtype=torch.float32, device=dev)
-        ratio = np.zeros((n, 2), np.float32)
-        for i, (im, _, _) in enumerate(batch):
-            h, w, _ = im.shape
-            ops.resize_linear_u8(srcs[i], x[i])
-            ratio[i] = self._ratio(h, w, rh, rw)
-        return x, torch.from_numpy(ratio).to(dev)
+        return [to_device(im, self.g.device) for im, _, _ in batch]
 
     def _ground_truths(self, batch):
         """-> gts int32 [n,max_g,4,2], ng int32 [n], gignored uint8 [n,max_g] on the device, and the matcher's mask size"""
@@ -287,57 +449,19 @@ class Evaluator:
         up = lambda a: torch.from_numpy(a).to(dev)
         return up(gts), up(ng), up(gign), (side, side)
 
-    # -- the multi-scale chain (scales=...): beside the single-scale one, which it leaves as it is ----------------
-    @staticmethod
-    def _check_scales(scales, fuse, max_pool):
-        from .tool import rbox
-        if fuse not in rbox.FUSE_MODES:
-            raise ValueError("fuse must be 'nms' or 'vote', got %r" % (fuse,))
-        if not 1 <= int(max_pool) <= ops.FUSE_MAX_POOL:
-            raise ValueError('max_pool must be in [1, %d]' % ops.FUSE_MAX_POOL)
-        if scales is None:
-            return None
-        return rbox.check_scales(scales)              # count, sign and finiteness; the sizes are checked per image shape
-
-    def _upload_multiscale(self, batch):
-        """batch of one ORIGINAL shape -> xs (one resized batch per scale, each made from the original images), ratios (one f32
-        [n,2] per scale), gts, ng, gignored, mask_hw"""
-        from .tool import rbox
-        h, w = batch[0][0].shape[:2]
-        srcs = self._sources(batch)
-        xs, ratios = [], []
-        for rh, rw in rbox.scale_sizes(h, w, self.ms_scales, self.max_side_len):
-            x, ratio = self._resize_batch(batch, srcs, rh, rw)
-            xs.append(x)
-            ratios.append(ratio)
-        return (xs, ratios) + self._ground_truths(batch)
-
-    def _chain_multiscale(self, batch):
-        from .tool import rbox
-        xs, ratios, gts, ng, gign, mask_hw = self._upload_multiscale(batch)
-        maps = (self.forward(x) for x in xs)          # a scale's forward runs when detect_multiscale_device asks for it
-        fused, keep, n_keep, overflow = rbox.detect_multiscale_device(
-            maps, ratios, self.score_map_thresh, self.nms_thres, self.box_thresh, fuse=self.fuse, max_pool=self.max_pool,
-            max_k=self.max_k, graph=self.g)
-        self._over_pool.append(overflow[:, 1:])
-        # the fused quads are in original-image pixels already: the collect pass divides by 1.  `total` is given so that
-        # _match's `total - rows` is the worst per-scale overflow over max_k
-        ones = torch.ones((len(batch), 2), dtype=torch.float32, device=self.g.device)
-        return self._match(fused, keep, n_keep, None, overflow[:, 0] + fused.shape[1], ones, gts, ng, gign, mask_hw)
-
     def _chain(self, batch):
-        from .tool import rbox
-        x, inv_ratio, gts, ng, gign, mask_hw = self._upload(batch)
-        f_score, f_geometry = self.forward(x)
-        merged, keep, n_keep, passed, total = rbox.detect_device(f_score, f_geometry, self.score_map_thresh, self.nms_thres,
-                                                                 self.max_k, graph=self.g, box_thresh=self.box_thresh)
-        return self._match(merged, keep, n_keep, passed, total, inv_ratio, gts, ng, gign, mask_hw)
+        """one batch -> its overflow counts int32 [n,m+1]: the detector's columns, then nd_total - max_d"""
+        srcs = self._sources(batch)
+        ground_truths = self._ground_truths(batch)
+        *rows, overflow = self.detector.detect(batch, srcs)
+        return torch.cat([overflow, self._match(*rows, *ground_truths)[:, None]], dim=1)
 
-    def _match(self, merged, keep, n_keep, passed, total, inv_ratio, gts, ng, gign, mask_hw):
-        """detection rows -> ordered detection list -> matching, the counters added to the record"""
+    def _match(self, merged, keep, n_keep, passed, inv_ratio, gts, ng, gign, mask_hw):
+        """detection rows -> ordered detection list -> matching, the counters added to the record (-> the curve).  Returns
+        nd_total - max_d (> 0: detections were lost), a device tensor like everything here."""
         from .tool import bboxes
         g = self.g
-        n, max_k = merged.shape[:2]
+        n = merged.shape[0]
         dets = torch.empty((n, self.max_d, 4, 2), dtype=torch.int32, device=g.device)
         det_score = torch.empty((n, self.max_d), dtype=torch.float32, device=g.device)
         nd = torch.empty((n,), dtype=torch.int32, device=g.device)
@@ -351,21 +475,14 @@ class Evaluator:
                              gt_match=gt_match, gts=gts, ng=ng, gdontcare=gign)
             if self.curve is not None:
                 self.curve.add_ic15(det_match, gt_match, det_score, nd, ng)
-            return total - max_k, nd_total - self.max_d
+            return nd_total - self.max_d
         tp, fp, _ = bboxes.bboxes_matching_batch(dets, nd, gts, ng, gign, self.matching_threshold, record=self.acc.record,
                                                  graph=g, mask_hw=mask_hw)
         self.last = dict(dets=dets, det_score=det_score, nd=nd, nd_total=nd_total, tp=tp, fp=fp, gts=gts, ng=ng)
         if self.curve is not None:
             self.last['gignored'] = gign
             self.curve.add_raster(tp, fp, det_score, nd, ng, gign if gign.dtype == torch.uint8 else gign.to(torch.uint8))
-        return total - max_k, nd_total - self.max_d          # > 0: overflow (device tensors, read at the end of the pass)
-
-    def _pick_chain(self):
-        """the chain a pass runs per batch"""
-        return self._chain if self.ms_scales is None else self._chain_multiscale
-
-    def _overflow(self, worst):
-        return 'an image selected %d pixels more than max_k: raise max_k or the score threshold' % worst
+        return nd_total - self.max_d
 
     # -- one pass --------------------------------------------------------------------------------
     def run(self):
@@ -374,41 +491,28 @@ class Evaluator:
         self.acc.reset()
         if self.curve is not None:
             self.curve.reset()
-        over_k, over_d, buckets = [], [], {}
-        self._over_pool = []      # multi-scale only: per chain, int32 [n,2] = (pool_total - max_pool, non-finite rows)
-        chain = self._pick_chain()
-
-        def flush(items):
-            a, b = chain(items)
-            over_k.append(a)
-            over_d.append(b)
+        overflow, buckets = [], {}
         for im_fn, (polys, ignored) in self.samples:
             im = icdar.read_image_rgb(im_fn)
             key = tuple(im.shape[:2])
             items = buckets.setdefault(key, [])
             items.append((im, polys, ignored))
             if len(items) == self.batch_size:
-                flush(buckets.pop(key))
+                overflow.append(self._chain(buckets.pop(key)))
         for key in sorted(buckets):
-            flush(buckets[key])
-        # the single read of the pass: the record and the two overflow maxima in one device-to-host copy
-        worst = torch.stack([torch.cat(over_k).max(), torch.cat(over_d).max()])
-        if self.ms_scales is not None:     # ... and the pool's two counts
-            worst = torch.cat([worst, torch.cat(self._over_pool).max(dim=0).values.to(worst.dtype)])
+            overflow.append(self._chain(buckets[key]))
+        # the single read of the pass: the record and the overflow columns' maxima in one device-to-host copy
+        worst = torch.cat(overflow).max(dim=0).values
         if self.curve is None:
-            (num_gt, tp, fp, n_det), (worst_k, worst_d, *worst_pool) = self.acc.value_with(worst)
+            (num_gt, tp, fp, n_det), worst = self.acc.value_with(worst)
         else:       # ... and the curve, the order flag and AP in the same copy
             self.curve.finish(self.acc.record)
-            (num_gt, tp, fp, n_det), (worst_k, worst_d, *worst_pool), rows, unsorted, ap = self.curve.value_with(self.acc, worst)
-        if worst_pool:
-            from .tool import rbox
-            msg = rbox.overflow_error(worst_k, worst_pool[0], worst_pool[1], self.max_pool)
-            if msg:
-                raise ValueError(msg)
-        if worst_k > 0:
-            raise ValueError(self._overflow(worst_k))
-        if worst_d > 0:
-            raise ValueError('an image kept %d detections more than max_d = %d' % (worst_d, self.max_d))
+            (num_gt, tp, fp, n_det), worst, rows, unsorted, ap = self.curve.value_with(self.acc, worst)
+        messages = self.detector.overflow_messages + (
+            lambda over: 'an image kept %d detections more than max_d = %d' % (over, self.max_d),)
+        for over, message in zip(worst, messages):
+            if over > 0:
+                raise ValueError(message(over))
         precision, recall = metrics.precision_recall(num_gt, tp, fp)
         hmean = metrics.fmean(precision, recall) if precision + recall > 0 else 0.0
         result = {'precision': precision, 'recall': recall, 'hmean': hmean, 'num_gt': num_gt, 'tp': tp, 'fp': fp,
@@ -425,115 +529,30 @@ class Evaluator:
 
 
 class LinkEvaluator(Evaluator):
-    """The link geometry: `forward(x)` returns the (pixel_cls [n,H/4,W/4,2], link_cls [n,H/4,W/4,16]) LOGITS of
-    `PixelLinkNet` (tensors or head handles) as a pure launch sequence.  Every image is resized on the device to the
-    fixed eval_image_height x eval_image_width (test_pixellink_fast.py's flags) and batched by its ORIGINAL shape, because
-    ocr_min_area_rects takes one scale per call: a component pixel (x, y) of the 1/4-resolution maps becomes the point
-    (int(x * scale_x), int(y * scale_y)) with scale_x = orig_w / (eval_w / 4), scale_y = orig_h / (eval_h / 4), so the
-    boxes land in original-image pixels and ocr_eval_collect runs with ratios (1, 1).  An original side below a quarter
-    of the eval side (a scale below 1) is refused.  A detection's score is its component's mean pixel score
-    (ocr_component_scores; build-defined).  min_side / min_area filter the boxes (0: nothing, as the reference scripts).
-    `run()` reads the device once at its end: the record, and the two overflow counts (components over max_comps,
-    detections over max_d), either of which raises ValueError.  `sweep` as for `Evaluator`: its thresholds are on the
-    component's mean pixel score, in [0, 1].
-
-    map_scales / flip / scale_weights: None / False / None = the single-scale pass above, bit for bit.  `scales=` (box-level
-    fusion) stays refused for this geometry; multi-scale and flip testing fuse the SCORE MAPS instead (DESIGN.md §3.3.20,
-    include/ocr_map_fuse.h).  map_scales: 1 to 8 positive finite scales (1 need not be among them): every batch is resized
-    from the ORIGINALS to each pixellink_fn.map_scale_sizes entry of the eval size and forwarded once, with flip=True a
-    second time mirrored left to right; each pass's pixel and link probabilities are resampled onto the eval_hw / 4 grid
-    and averaged with scale_weights (default: equal; a scale's two passes share its weight), and the link decode runs
-    once on the fused maps.  The fusion grid is the single-scale one, so the box scales, the matcher, `protocol`, `sweep`
-    and the single device read per pass are what they were.  flip without map_scales is scale 1 plus its mirror.
-    Activation memory grows with the square of the largest scale.  Whether any of this raises the F-measure is
-    unmeasured: no dataset or trained checkpoint is on any machine that built it."""
+    """The pass driver with the link geometry's detectors: `LinkSingleScale`, or with map_scales / flip `LinkFused` (flip
+    without map_scales is scale 1 plus its mirror; scale_weights default to equal).  The options are
+    test_pixellink_fast.py's flags and the detectors' docstrings describe them; `scales=` (box-level fusion) is refused
+    for this geometry.  `protocol`, `sweep`, max_d and the single device read per pass are `Evaluator`'s."""
 
     def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, pixel_conf_threshold=0.8,
                  link_conf_threshold=0.9, min_size=10, max_comps=4096, min_side=0.0, min_area=0.0, max_d=ops.EVAL_MAX_D,
                  eval_image_height=768, eval_image_width=1280, gt_path=None, protocol='raster', sweep=None, scales=None,
                  map_scales=None, flip=False, scale_weights=None):
         if scales is not None:
-            # the min-area-rectangle vertices of a component have no fixed correspondence across scales for the vote
             raise ValueError('multi-scale evaluation (scales=...) is built for the RBOX geometry only')
         from .tool import pixellink_fn
-        self.flip = bool(flip)
+        flip = bool(flip)
         if map_scales is None and scale_weights is not None:
             raise ValueError('scale_weights come with map_scales')
-        if map_scales is None and self.flip:
+        if map_scales is None and flip:
             map_scales = [1.0]                       # flip alone: scale 1 and its mirror
-        self.map_scales, self.scale_weights = (None, None) if map_scales is None else \
-            pixellink_fn.check_map_scales(map_scales, scale_weights)
-        super().__init__(graph, forward, data, batch_size=batch_size, max_images=max_images,
-                         matching_threshold=matching_threshold, max_d=max_d, gt_path=gt_path, protocol=protocol, sweep=sweep)
-        self.eval_hw = (int(eval_image_height), int(eval_image_width))
-        if min(self.eval_hw) < 4 or self.eval_hw[0] % 4 or self.eval_hw[1] % 4:
-            raise ValueError('the eval size must be positive multiples of 4, got %dx%d' % self.eval_hw)
-        if int(max_comps) < 1:
-            raise ValueError('max_comps must be positive')
-        self.pixel_conf_threshold, self.link_conf_threshold = float(pixel_conf_threshold), float(link_conf_threshold)
-        self.min_size, self.max_comps = int(min_size), int(max_comps)
-        self.min_side, self.min_area = float(min_side), float(min_area)
-
-    def _resized(self, h, w):
-        return self.eval_hw
-
-    def _ratio(self, h, w, rh, rw):
-        return 1.0, 1.0
-
-    def scales(self, h, w):
-        """(scale_x, scale_y) of an h x w original: 1/4-resolution map cell -> original-image pixels"""
-        sx, sy = w / float(self.eval_hw[1] // 4), h / float(self.eval_hw[0] // 4)
-        if sx < 1.0 or sy < 1.0:
-            raise ValueError('a %dx%d image is smaller than the %dx%d score maps: lower the eval size'
-                             % (h, w, self.eval_hw[0] // 4, self.eval_hw[1] // 4))
-        return sx, sy
-
-    def _chain(self, batch):
-        from .tool import pixellink_fn
-        g = self.g
-        scale_x, scale_y = self.scales(*batch[0][0].shape[:2])
-        x, inv_ratio, gts, ng, gign, mask_hw = self._upload(batch)
-        pixel_cls, link_cls = self.forward(x)
-        pixel_score = pixellink_fn.pixel_scores(pixel_cls, graph=g)[..., 1].contiguous()
-        link_score = pixellink_fn.link_scores(link_cls, graph=g)
-        merged, keep, n_keep, passed, total = pixellink_fn.detect_device(
-            pixel_score, link_score, self.pixel_conf_threshold, self.link_conf_threshold, self.min_size, scale_x, scale_y,
-            max_comps=self.max_comps, min_side=self.min_side, min_area=self.min_area, graph=g)
-        return self._match(merged, keep, n_keep, passed, total, inv_ratio, gts, ng, gign, mask_hw)
-
-    # -- score-map fusion (map_scales=..., flip=...): beside the single-scale chain, which it leaves as it is ---------
-    def _passes(self, batch, srcs):
-        """the forward passes of a batch, one at a time: every original resized to each map_scale_sizes entry, forwarded,
-        and with `flip` forwarded again mirrored left to right.  A generator: fuse_score_maps uses a pass's logits up
-        before it asks for the next forward, which may return the same buffers."""
-        from .tool import pixellink_fn
-        for rh, rw in pixellink_fn.map_scale_sizes(self.eval_hw[0], self.eval_hw[1], self.map_scales):
-            x, _ = self._resize_batch(batch, srcs, rh, rw)
-            pixel_cls, link_cls = self.forward(x)
-            yield pixel_cls, link_cls, False
-            if self.flip:
-                pixel_cls, link_cls = self.forward(torch.flip(x, dims=[2]))
-                yield pixel_cls, link_cls, True
-
-    def _chain_fused(self, batch):
-        from .tool import pixellink_fn
-        g = self.g
-        scale_x, scale_y = self.scales(*batch[0][0].shape[:2])
-        gts, ng, gign, mask_hw = self._ground_truths(batch)
-        weights = np.repeat(np.asarray(self.scale_weights, np.float64), 2 if self.flip else 1)
-        # the fusion grid is the single-scale pass's: eval_hw / 4, so the box scales and everything behind them stay
-        merged, keep, n_keep, passed, total = pixellink_fn.detect_device_multiscale(
-            self._passes(batch, self._sources(batch)), weights, (self.eval_hw[0] // 4, self.eval_hw[1] // 4),
-            self.pixel_conf_threshold, self.link_conf_threshold, self.min_size, scale_x, scale_y, max_comps=self.max_comps,
-            min_side=self.min_side, min_area=self.min_area, graph=g)
-        ones = torch.ones((len(batch), 2), dtype=torch.float32, device=g.device)
-        return self._match(merged, keep, n_keep, passed, total, ones, gts, ng, gign, mask_hw)
-
-    def _pick_chain(self):
-        return self._chain if self.map_scales is None else self._chain_fused
-
-    def _overflow(self, worst):
-        return 'an image holds %d components more than max_comps = %d' % (worst, self.max_comps)
+        if map_scales is not None:
+            map_scales, scale_weights = pixellink_fn.check_map_scales(map_scales, scale_weights)
+        self._init_pass(graph, data, batch_size, max_images, matching_threshold, max_d, gt_path, protocol, sweep)
+        options = (self.g, forward, (eval_image_height, eval_image_width), pixel_conf_threshold, link_conf_threshold,
+                   min_size, max_comps, min_side, min_area)
+        self.detector = LinkSingleScale(*options) if map_scales is None else \
+            LinkFused(*options, map_scales=map_scales, scale_weights=scale_weights, flip=flip)
 
 
 class EmaWeights:

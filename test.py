@@ -151,34 +151,13 @@ def resize_image(im, max_side_len=3000, graph=None):
     """test.py:92-121: limit the longer side, round both sides to multiples of 32 (the reference's
     rule: already-multiples stay, others become (x // 32 - 1) * 32), cv2.resize.  Returns the resized
     image as a DEVICE float32 [H,W,3] tensor and (ratio_h, ratio_w)."""
-    from tensorflow_ocr_amd import ops
+    from tensorflow_ocr_amd import evaluate
     from tensorflow_ocr_amd.graph import get_default_graph
-    from tensorflow_ocr_amd.evaluate import resize_rule
     g = graph or get_default_graph()
     h, w, _ = im.shape
-    resize_h, resize_w = resize_rule(h, w, max_side_len)          # the sizing rule, shared with the evaluator
-    src = torch.from_numpy(np.ascontiguousarray(im, dtype=np.uint8)).to(g.device)
-    out = torch.empty((int(resize_h), int(resize_w), 3), dtype=torch.float32, device=g.device)
-    ops.resize_linear_u8(src, out)
+    resize_h, resize_w = evaluate.resize_rule(h, w, max_side_len)          # the sizing rule and the resize are the evaluator's
+    out = evaluate.resize_batch([evaluate.to_device(im, g.device)], resize_h, resize_w)[0]
     return out, (resize_h / float(h), resize_w / float(w))
-
-
-def multiscale_inputs(im, scales, graph=None, max_side_len=3000):
-    """--scales: the image resized from the ORIGINAL to tool/rbox.scale_sizes' size at each scale -> (xs, ratios): one device
-    f32 [1,H_s,W_s,3] batch and one f32 [1,2] (ratio_w, ratio_h) tensor per scale."""
-    from tensorflow_ocr_amd import ops
-    from tensorflow_ocr_amd.graph import get_default_graph
-    from tensorflow_ocr_amd.tool import rbox
-    g = graph or get_default_graph()
-    h, w, _ = im.shape
-    src = torch.from_numpy(np.ascontiguousarray(im, dtype=np.uint8)).to(g.device)
-    xs, ratios = [], []
-    for rh, rw in rbox.scale_sizes(h, w, scales, max_side_len):
-        x = torch.empty((1, rh, rw, 3), dtype=torch.float32, device=g.device)
-        ops.resize_linear_u8(src, x[0])
-        xs.append(x)
-        ratios.append(torch.tensor([[rw / float(w), rh / float(h)]], dtype=torch.float32, device=g.device))
-    return xs, ratios
 
 
 def boxes_from_mask(score_map_res, ratio_h, ratio_w, graph=None):
@@ -213,6 +192,7 @@ def main_rbox(FLAGS):
     """--geometry RBOX: model_rbox -> per-pixel quads -> locality-aware NMS, all on the device; the kept quads, divided
     by the resize ratios and truncated to integers, in the res_<name>.txt format of the link path.  --box_thresh adds the
     mean-score filter over each quad's raster that EAST's eval script applies after the NMS."""
+    from tensorflow_ocr_amd import evaluate
     from tensorflow_ocr_amd.datasets import icdar
     from tensorflow_ocr_amd.graph import Graph
     from tensorflow_ocr_amd.infer import GraphedForward
@@ -231,7 +211,7 @@ def main_rbox(FLAGS):
         if FLAGS.scales is not None:
             # one resize (from the original) and one forward per scale, pooled and fused on the device: the quads come
             # back in original-image pixels, so nothing is divided below
-            xs, ratios = multiscale_inputs(im, FLAGS.scales, g)
+            xs, ratios = evaluate.multiscale_inputs([evaluate.to_device(im, g.device)], FLAGS.scales)
             if not restored:
                 forward(xs[0])
                 _restore(FLAGS, g)
@@ -264,7 +244,6 @@ def main_rbox(FLAGS):
     if FLAGS.gt_path is not None:
         # a second pass over the same images with the restored weights: forward -> decode -> LANMS -> filter -> match
         # per batch on the device, one read of the counters at its end
-        from tensorflow_ocr_amd import evaluate
         ev = evaluate.Evaluator(g, forward, FLAGS.test_data_path, gt_path=FLAGS.gt_path, box_thresh=FLAGS.box_thresh,
                                 protocol=FLAGS.eval_protocol, sweep=FLAGS.eval_sweep, scales=FLAGS.scales, fuse=FLAGS.fuse)
         res = ev.run()

@@ -3,23 +3,19 @@ tests/test_eval_match_host.collect_ref (integers and copied scores: bit for bit)
 against rbox.detect -> divide -> oracle/evalboxes.py per image (counter for counter, one read of the record per pass),
 and the evaluation inside a training run: the recorded step's call list and the weights are the same with it and
 without it."""
-import importlib
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import eval_support as E
 import test_eval_match_host as H
 from oracle import evalboxes as OE
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32, i32 = np.float32, np.int32
 SENT_I, SENT_F = -123456, f32(-12345.5)
-SMALL = [("block1", [(128, 64, 1), (128, 64, 2)]), ("block2", [(256, 64, 1), (256, 64, 2)]),
-         ("block3", [(256, 128, 1), (256, 128, 2)]), ("block4", [(512, 128, 1)])]
 
 
 @pytest.fixture(scope="module")
@@ -102,50 +98,16 @@ def test_collect_status_codes_leave_the_outputs_alone(device):
 
 
 # ------------------------------------------------------------------------------------------------ Evaluator
-def _write_gt(path, quads, tags):
-    with open(path, "w") as f:
-        for q, t in zip(quads, tags):
-            f.write(",".join(str(int(v)) for v in np.asarray(q).reshape(-1)) + "," + t + "\r\n")
-
-
 @pytest.fixture(scope="module")
-def eval_dir(device, graph, tmp_path_factory):
-    """3 images (two 64 x 64, one 96 wide x 64 high) with label maps from synthetic.rbox_labels and ground truths made from
-    what the detector finds on them: the best detection exactly, an ignored quad, and one nothing matches."""
-    from tensorflow_ocr_amd import synthetic
-    from tensorflow_ocr_amd.tool import rbox
-    d = str(tmp_path_factory.mktemp("eval"))
-    rng = np.random.default_rng(77)
-    s64, g64, _ = synthetic.rbox_labels(2, 64, rng, rects=2)
-    s96, g96, _ = synthetic.rbox_labels(1, 96, rng, rects=3)
-    maps = {"img_a": (s64[0], g64[0]), "img_b": (s64[1], g64[1]), "img_c": (s96[0, :16], g96[0, :16])}      # [16,24] for 64 x 96
-    shapes = {"img_a": (64, 64), "img_b": (64, 64), "img_c": (64, 96)}
-    for name, (h, w) in shapes.items():
-        np.save(os.path.join(d, name + ".npy"), rng.integers(0, 256, (h, w, 3)).astype(np.uint8))
-        quads = rbox.detect(maps[name][0][None], maps[name][1][None], graph=graph)[0]
-        assert len(quads) >= 1, name
-        best = quads[np.argsort(-quads[:, 8], kind="stable")[0], :8].astype(i32)
-        _write_gt(os.path.join(d, "gt_%s.txt" % name), [best, H.rect(1, 1, 9, 6), H.rect(50, 2, 62, 9)], ["text", "###", "far"])
-    return d, maps, shapes
-
-
-def _stub_forward(device, maps):
-    """the maps of the images a batch holds, by its shape: (2, 64, 64) = img_a, img_b in name order; (1, 64, 96) = img_c"""
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    calls = []
-
-    def forward(x):
-        calls.append(tuple(x.shape))
-        names = {(2, 64, 64, 3): ["img_a", "img_b"], (1, 64, 96, 3): ["img_c"]}[tuple(x.shape)]
-        return up(np.stack([maps[k][0] for k in names])), up(np.stack([maps[k][1] for k in names]))
-    return forward, calls
+def eval_dir(graph, tmp_path_factory):
+    return E.rbox_eval_dir(graph, str(tmp_path_factory.mktemp("eval")))
 
 
 def test_evaluator_counts_equal_detect_divide_oracle(device, graph, eval_dir):
     from tensorflow_ocr_amd import evaluate
     from tensorflow_ocr_amd.tool import metrics, rbox
     d, maps, shapes = eval_dir
-    forward, calls = _stub_forward(device, maps)
+    forward, calls = E.rbox_stub_forward(device, maps)
     ev = evaluate.Evaluator(graph, forward, d, batch_size=2)
     res = ev.run()
     assert sorted(calls) == [(1, 64, 96, 3), (2, 64, 64, 3)] and ev.acc.reads == 1         # one read of the record per pass
@@ -175,49 +137,11 @@ def test_evaluator_counts_equal_detect_divide_oracle(device, graph, eval_dir):
 
 
 # ------------------------------------------------------------------------------------------------ training
-def _train(device, eval_dir_path, with_eval, steps=5):
-    from tensorflow_ocr_amd import synthetic
-    from tensorflow_ocr_amd.graph import Graph
-    from tensorflow_ocr_amd.nets import model_vgg_16 as M
-    from tensorflow_ocr_amd.train import AdamOptimizer, TrainStep
-    sys.path.insert(0, ROOT)
-    T = importlib.import_module("multigpu_train")
-    argv = ["--net", "east", "--geometry", "RBOX", "--input_size", "64", "--batch_size_per_gpu", "2"]
-    if with_eval:
-        argv += ["--eval_steps", "1", "--eval_data_path", eval_dir_path]
-    FLAGS = T.parse(argv)
-    rng = np.random.default_rng(51)
-    images = rng.uniform(0, 255, (2, 64, 64, 3)).astype(f32)
-    batch = [torch.from_numpy(a).to(device) for a in (images,) + tuple(synthetic.rbox_labels(2, 64, rng))]
-
-    def fl(gr, im, yy, gg, mm):
-        a, b = M.model_rbox(im, text_scale=FLAGS.text_scale, graph=gr, blocks=SMALL)
-        return M.loss_rbox(yy, a, gg, b, mm, graph=gr)
-    g = Graph(device, loss_scale=1024.0, seed=6)
-    step = TrainStep(g, fl, lambda gr: AdamOptimizer(gr, learning_rate=1e-3))
-    te = T.make_train_eval(FLAGS, g, step, blocks=SMALL)
-    assert (te is not None) == with_eval
-    results = []
-    for it in range(steps):
-        step(*batch)
-        if te is not None and te.due(it + 1):
-            T._evaluate(te, None, step.opt)
-            results.append(te.last)
-    torch.cuda.synchronize()
-    assert step.plan is not None
-    calls = [(e[0], e[3] if e[0] == "c" else (e[2] if len(e) > 2 else None)) for e in step.recorded]      # C entry names, host entry tags
-    state = [t.clone() for t in (g.store.flat, g.store.flat_aux, step.opt.ema, step.opt.m, step.opt.v)]
-    return calls, list(step.plan_kinds), state, results, te
-
-
 def test_training_with_evaluation_records_the_same_step_and_trains_the_same_weights(device, tmp_path):
     d = str(tmp_path)
-    rng = np.random.default_rng(5)
-    for name in ("img_1", "img_2"):
-        np.save(os.path.join(d, name + ".npy"), rng.integers(0, 256, (64, 64, 3)).astype(np.uint8))
-        _write_gt(os.path.join(d, "gt_%s.txt" % name), [H.rect(8, 8, 40, 24), H.rect(30, 40, 60, 56)], ["text", "###"])
-    calls0, kinds0, state0, _, _ = _train(device, d, False)
-    calls1, kinds1, state1, results, te = _train(device, d, True)
+    E.write_training_eval_dir(d)
+    calls0, kinds0, state0, _, _ = E.train_east_rbox(device, d, False)
+    calls1, kinds1, state1, results, te = E.train_east_rbox(device, d, True)
     assert calls1 == calls0 and kinds1 == kinds0 and len(calls0) > 50       # the recorded call list is identical
     for a, b in zip(state0, state1):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))        # weights, moving statistics, EMA, Adam slots: bit for bit

@@ -11,12 +11,9 @@ import numpy as np
 import pytest
 import torch
 
+import eval_support as E
 import ic15_ref as R
-from test_gpu_eval_chain import _stub_forward as rbox_stub_forward
-from test_gpu_eval_chain import eval_dir as rbox_eval_dir            # noqa: F401  (fixtures, used by name)
-from test_gpu_link_eval_chain import EVAL
-from test_gpu_link_eval_chain import _stub_forward as link_stub_forward
-from test_gpu_link_eval_chain import eval_dir as link_eval_dir       # noqa: F401
+from eval_support import EVAL
 
 pytestmark = pytest.mark.gpu
 MAX_D, MAX_G, N = R.MAX_D, R.MAX_G, R.N
@@ -30,6 +27,16 @@ TOL = Fr(1, 2 ** 40)
 def graph(device):
     from tensorflow_ocr_amd.graph import Graph
     return Graph(device)
+
+
+@pytest.fixture(scope="module")
+def rbox_eval_dir(graph, tmp_path_factory):
+    return E.rbox_eval_dir(graph, str(tmp_path_factory.mktemp("eval")))
+
+
+@pytest.fixture(scope="module")
+def link_eval_dir(device, graph, tmp_path_factory):
+    return E.link_eval_dir(str(tmp_path_factory.mktemp("link_eval")), E.host_best_box(graph, device))
 
 
 @pytest.fixture(scope="module")
@@ -195,29 +202,10 @@ def test_every_status_code_leaves_the_outputs_alone(device, expected):
 
 
 # ------------------------------------------------------------------------------------------------ the chain
-def _spy_reads(monkeypatch, calls):
-    reads = []
-    for name in ("cpu", "item", "tolist", "numpy"):
-        orig = getattr(torch.Tensor, name)
-
-        def spy(self, *a, _orig=orig, _name=name, **kw):
-            if self.is_cuda:
-                reads.append((_name, len(calls)))
-            return _orig(self, *a, **kw)
-        monkeypatch.setattr(torch.Tensor, name, spy)
-    return reads
-
-
 def _chain_case(ev, calls, monkeypatch):
     """one icdar15 pass with every chain's `last` kept (device tensors, no read) -> (result, reads, reference record)"""
-    chains, match = [], ev._match
-
-    def keeping(*a, **kw):
-        out = match(*a, **kw)
-        chains.append(dict(ev.last))
-        return out
-    ev._match = keeping
-    reads = _spy_reads(monkeypatch, calls)
+    chains = E.keep_lasts(ev)
+    reads = E.spy_reads(monkeypatch, calls)
     res = ev.run()
     monkeypatch.undo()
     want = np.zeros(4, np.int64)
@@ -256,7 +244,7 @@ def _same_last(a, b):
 def test_evaluator_icdar15_equals_the_reference_and_raster_is_untouched(device, graph, rbox_eval_dir, monkeypatch):
     from tensorflow_ocr_amd import evaluate
     d, maps, _ = rbox_eval_dir
-    forward, calls = rbox_stub_forward(device, maps)
+    forward, calls = E.rbox_stub_forward(device, maps)
     ev = evaluate.Evaluator(graph, forward, d, batch_size=2, protocol="icdar15")
     res, reads, want = _chain_case(ev, calls, monkeypatch)
     assert ev.acc.reads == 1
@@ -270,7 +258,7 @@ def test_evaluator_icdar15_equals_the_reference_and_raster_is_untouched(device, 
 def test_link_evaluator_icdar15_equals_the_reference_and_raster_is_untouched(device, graph, link_eval_dir, monkeypatch):
     from tensorflow_ocr_amd import evaluate
     d, maps = link_eval_dir
-    forward, calls = link_stub_forward(device, maps)
+    forward, calls = E.link_stub_forward(device, maps)
     kw = dict(batch_size=2, eval_image_height=EVAL, eval_image_width=EVAL)
     ev = evaluate.LinkEvaluator(graph, forward, d, protocol="icdar15", **kw)
     res, reads, want = _chain_case(ev, calls, monkeypatch)

@@ -13,14 +13,9 @@ import numpy as np
 import pytest
 import torch
 
+import eval_support as E
 import sweep_ref as S
-import test_gpu_eval_chain as RC
-from test_gpu_eval_chain import _stub_forward as rbox_stub_forward
-from test_gpu_eval_chain import eval_dir as rbox_eval_dir            # noqa: F401  (fixtures, used by name)
-from test_gpu_eval_ic15 import _spy_reads
-from test_gpu_link_eval_chain import EVAL
-from test_gpu_link_eval_chain import _stub_forward as link_stub_forward
-from test_gpu_link_eval_chain import eval_dir as link_eval_dir       # noqa: F401
+from eval_support import EVAL
 
 pytestmark = pytest.mark.gpu
 N, MAX_D, MAX_G, T = S.N, S.MAX_D, S.MAX_G, S.T
@@ -33,6 +28,16 @@ f32 = np.float32
 def graph(device):
     from tensorflow_ocr_amd.graph import Graph
     return Graph(device)
+
+
+@pytest.fixture(scope="module")
+def rbox_eval_dir(graph, tmp_path_factory):
+    return E.rbox_eval_dir(graph, str(tmp_path_factory.mktemp("eval")))
+
+
+@pytest.fixture(scope="module")
+def link_eval_dir(device, graph, tmp_path_factory):
+    return E.link_eval_dir(str(tmp_path_factory.mktemp("link_eval")), E.host_best_box(graph, device))
 
 
 @pytest.fixture(scope="module")
@@ -252,14 +257,8 @@ CHAIN_SWEEP = [-1.0, 0.9, 0.97, 1e9, 2.5]      # below every score of both geome
 
 def _sweep_case(ev, calls, monkeypatch):
     """one pass with every chain's `last` kept (device tensors, no read) -> (result, reads, the reference's rows, exact AP, K)"""
-    chains, match = [], ev._match
-
-    def keeping(*a, **kw):
-        out = match(*a, **kw)
-        chains.append(dict(ev.last))
-        return out
-    ev._match = keeping
-    reads = _spy_reads(monkeypatch, calls)
+    chains = E.keep_lasts(ev)
+    reads = E.spy_reads(monkeypatch, calls)
     res = ev.run()
     monkeypatch.undo()
     rule = "icdar15" if ev.protocol == "icdar15" else "raster"
@@ -302,7 +301,7 @@ def _check_sweep_result(evaluate, res, plain, reads, want, exact, k_matched, n_c
 def test_evaluator_with_a_sweep_reads_once_and_keeps_the_operating_point(device, graph, rbox_eval_dir, monkeypatch, protocol):
     from tensorflow_ocr_amd import evaluate
     d, maps, _ = rbox_eval_dir
-    forward, calls = rbox_stub_forward(device, maps)
+    forward, calls = E.rbox_stub_forward(device, maps)
     plain = evaluate.Evaluator(graph, forward, d, batch_size=2, protocol=protocol).run()
     del calls[:]
     ev = evaluate.Evaluator(graph, forward, d, batch_size=2, protocol=protocol, sweep=CHAIN_SWEEP)
@@ -316,7 +315,7 @@ def test_evaluator_with_a_sweep_reads_once_and_keeps_the_operating_point(device,
 def test_link_evaluator_with_a_sweep_reads_once_and_keeps_the_operating_point(device, graph, link_eval_dir, monkeypatch, protocol):
     from tensorflow_ocr_amd import evaluate
     d, maps = link_eval_dir
-    forward, calls = link_stub_forward(device, maps)
+    forward, calls = E.link_stub_forward(device, maps)
     kw = dict(batch_size=2, eval_image_height=EVAL, eval_image_width=EVAL, protocol=protocol)
     plain = evaluate.LinkEvaluator(graph, forward, d, **kw).run()
     del calls[:]
@@ -330,7 +329,7 @@ def test_link_evaluator_with_a_sweep_reads_once_and_keeps_the_operating_point(de
 def test_an_unsorted_score_list_is_an_error_of_the_pass(device, graph, rbox_eval_dir, monkeypatch):
     from tensorflow_ocr_amd import evaluate, ops
     d, maps, _ = rbox_eval_dir
-    forward, _ = rbox_stub_forward(device, maps)
+    forward, _ = E.rbox_stub_forward(device, maps)
     ev = evaluate.Evaluator(graph, forward, d, batch_size=2, sweep=[0.5])
     collect = ops.eval_collect
 
@@ -345,19 +344,15 @@ def test_an_unsorted_score_list_is_an_error_of_the_pass(device, graph, rbox_eval
 
 
 def test_training_with_a_sweep_records_the_same_step_and_trains_the_same_weights(device, tmp_path, monkeypatch):
-    import os
     d = str(tmp_path)
-    rng = np.random.default_rng(5)
-    for name in ("img_1", "img_2"):
-        np.save(os.path.join(d, name + ".npy"), rng.integers(0, 256, (64, 64, 3)).astype(np.uint8))
-        RC._write_gt(os.path.join(d, "gt_%s.txt" % name), [RC.H.rect(8, 8, 40, 24), RC.H.rect(30, 40, 60, 56)], ["text", "###"])
-    calls0, kinds0, state0, _, _ = RC._train(device, d, False)
+    E.write_training_eval_dir(d)
+    calls0, kinds0, state0, _, _ = E.train_east_rbox(device, d, False)
     import sys
-    sys.path.insert(0, RC.ROOT)
+    sys.path.insert(0, E.ROOT)
     T_ = importlib.import_module("multigpu_train")
     parse = T_.parse
     monkeypatch.setattr(T_, "parse", lambda argv: parse(argv + ["--eval_sweep", "0:40:5"]))
-    calls1, kinds1, state1, results, te = RC._train(device, d, True)
+    calls1, kinds1, state1, results, te = E.train_east_rbox(device, d, True)
     assert te.evaluator.sweep == [0.0, 10.0, 20.0, 30.0, 40.0] and te.evaluator.curve is not None
     assert calls1 == calls0 and kinds1 == kinds0 and len(calls0) > 50       # the recorded call list is identical
     for a, b in zip(state0, state1):

@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-import test_link_eval_host as H
+import eval_support as E
+from eval_support import EVAL, SHAPES            # the link directory: the eval size, the originals' (h, w)
 from oracle import evalboxes as OE
 
 pytestmark = pytest.mark.gpu
@@ -25,36 +26,12 @@ def graph(device):
     return Graph(device)
 
 
-def _rot(h, w, cx, cy, a, b, deg):
-    ys, xs = np.mgrid[0:h, 0:w]
-    th = np.deg2rad(deg)
-    u = (xs - cx) * np.cos(th) + (ys - cy) * np.sin(th)
-    v = -(xs - cx) * np.sin(th) + (ys - cy) * np.cos(th)
-    return (np.abs(u) <= a) & (np.abs(v) <= b)
-
-
 def _painted(rng, regions, h=32, w=32):
     """pixel scores in (0.82, 0.99) inside the regions and below 0.5 outside: every region is one component"""
     inside = np.zeros((h, w), bool)
     for m in regions:
         inside |= m
     return np.where(inside, rng.uniform(0.82, 0.99, (h, w)), rng.uniform(0.0, 0.5, (h, w))).astype(f32)
-
-
-def _host_detections(graph, pixel_score, link_score, scale_x, scale_y, min_size, max_comps=64):
-    """The parent path, per image: link_cc_decode -> min_area_rect_boxes (host formatting), the NumPy mean score of every
-    component, ordered by a stable descending sort -> [(boxes int32 [k,4,2], scores f32 [k])]"""
-    from tensorflow_ocr_amd.tool import pixellink_fn as P
-    labels, ncomp, _ = P.link_cc_decode(pixel_score, link_score, 0.8, 0.9, min_size=min_size, max_comps=max_comps, graph=graph)
-    boxes = P.min_area_rect_boxes(labels, ncomp, scale_x, scale_y, max_comps=max_comps, graph=graph)
-    ps = pixel_score.cpu().numpy() if isinstance(pixel_score, torch.Tensor) else pixel_score
-    scores = H.component_scores_ref(labels.cpu().numpy(), ps, ncomp.cpu().numpy(), max_comps)
-    out = []
-    for b, (_, bx) in enumerate(boxes):
-        sc = scores[b, :len(bx)]
-        order = np.argsort(-sc.astype(np.float64), kind="stable")
-        out.append((bx[order].astype(i32), sc[order]))
-    return out
 
 
 # ------------------------------------------------------------------------------------------------ detect -> collect
@@ -64,13 +41,13 @@ def test_detect_device_and_collect_equal_the_host_path(device, graph):
     rng = np.random.default_rng(11)
     tiny = np.zeros((32, 32), bool)
     tiny[29:31, 1:3] = True                                                 # 4 pixels: dropped by min_size
-    ps = np.stack([_painted(rng, [_rot(32, 32, 8, 6, 6, 2, 0), _rot(32, 32, 22, 12, 7, 2, 30), _rot(32, 32, 10, 24, 4, 3, 0), tiny]),
-                   _painted(rng, [_rot(32, 32, 16, 16, 9, 3, -40)]),
+    ps = np.stack([_painted(rng, [E.rot(32, 32, 8, 6, 6, 2, 0), E.rot(32, 32, 22, 12, 7, 2, 30), E.rot(32, 32, 10, 24, 4, 3, 0), tiny]),
+                   _painted(rng, [E.rot(32, 32, 16, 16, 9, 3, -40)]),
                    _painted(rng, [])])
     link = np.full((8, 3, 32, 32), 0.95, f32)
     max_comps, max_d, min_size = 16, 8, 5
     for scale in ((4.0, 4.0), (5.0, 3.0)):
-        want = _host_detections(graph, torch.from_numpy(ps).to(device), torch.from_numpy(link).to(device), scale[0], scale[1],
+        want = E.host_detections(graph, torch.from_numpy(ps).to(device), torch.from_numpy(link).to(device), scale[0], scale[1],
                                 min_size, max_comps)
         assert [len(b) for b, _ in want] == [3, 1, 0]
         merged, keep, n_keep, passed, total = P.detect_device(torch.from_numpy(ps).to(device), torch.from_numpy(link).to(device),
@@ -92,67 +69,9 @@ def test_detect_device_and_collect_equal_the_host_path(device, graph):
 
 
 # ------------------------------------------------------------------------------------------------ LinkEvaluator
-EVAL = 128                                       # the eval size of the tests: maps of 32 x 32
-SHAPES = {"img_a": (96, 128), "img_b": (96, 128), "img_c": (96, 160)}      # (h, w) of the originals
-
-
-def _logits(rng, regions):
-    """(pixel_cls [32,32,2], link_cls [32,32,16]) whose softmaxes paint the regions: P(text) in (0.88, 0.99) inside, below
-    0.12 outside; every link 0.993"""
-    inside = np.zeros((32, 32), bool)
-    for m in regions:
-        inside |= m
-    px = np.zeros((32, 32, 2), f32)
-    px[..., 1] = np.where(inside, rng.uniform(2.0, 4.5, (32, 32)), rng.uniform(-4.5, -2.0, (32, 32)))
-    lk = np.zeros((32, 32, 16), f32)
-    lk[..., 1::2] = 5.0
-    return px, lk
-
-
-def _write_gt(path, quads, tags):
-    with open(path, "w") as f:
-        for q, t in zip(quads, tags):
-            f.write(",".join(str(int(v)) for v in np.asarray(q).reshape(-1)) + "," + t + "\r\n")
-
-
-def _host_image(graph, device, px, lk, h, w):
-    """the host path for ONE image of original size h x w: boxes in original pixels and scores, in matching order"""
-    from tensorflow_ocr_amd.tool import pixellink_fn as P
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    pixel_score = P.pixel_scores(up(px[None]), graph=graph)[..., 1].contiguous()
-    link_score = P.link_scores(up(lk[None]), graph=graph)
-    return _host_detections(graph, pixel_score, link_score, w / 32.0, h / 32.0, 10)[0]
-
-
 @pytest.fixture(scope="module")
 def eval_dir(device, graph, tmp_path_factory):
-    """3 images of two original shapes with the logits the stub forward returns for them, and ground truths made from what
-    the host path finds: its best detection exactly, an ignored quad, and one nothing matches."""
-    d = str(tmp_path_factory.mktemp("link_eval"))
-    rng = np.random.default_rng(78)
-    regions = {"img_a": [_rot(32, 32, 9, 8, 6, 2, 0), _rot(32, 32, 20, 22, 8, 2, 35)],
-               "img_b": [_rot(32, 32, 16, 10, 9, 3, -20), _rot(32, 32, 8, 25, 5, 2, 0), _rot(32, 32, 25, 25, 3, 3, 0)],
-               "img_c": [_rot(32, 32, 16, 16, 10, 3, 60), _rot(32, 32, 5, 5, 3, 2, 0)]}
-    maps = {k: _logits(rng, r) for k, r in regions.items()}
-    for name, (h, w) in SHAPES.items():
-        np.save(os.path.join(d, name + ".npy"), rng.integers(0, 256, (h, w, 3)).astype(np.uint8))
-        boxes, scores = _host_image(graph, device, maps[name][0], maps[name][1], h, w)
-        assert len(boxes) == len(regions[name]), name
-        _write_gt(os.path.join(d, "gt_%s.txt" % name), [boxes[0], [[1, 1], [9, 1], [9, 6], [1, 6]],
-                                                      [[w - 14, 2], [w - 2, 2], [w - 2, 9], [w - 14, 9]]], ["text", "###", "far"])
-    return d, maps
-
-
-def _stub_forward(device, maps):
-    """the logits of the images a batch holds, by its size: 2 = img_a, img_b (one original shape, name order); 1 = img_c"""
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    calls = []
-
-    def forward(x):
-        calls.append(tuple(x.shape))
-        names = {2: ["img_a", "img_b"], 1: ["img_c"]}[x.shape[0]]
-        return up(np.stack([maps[k][0] for k in names])), up(np.stack([maps[k][1] for k in names]))
-    return forward, calls
+    return E.link_eval_dir(str(tmp_path_factory.mktemp("link_eval")), E.host_best_box(graph, device))
 
 
 def test_link_evaluator_counts_equal_host_path_and_oracle(device, graph, eval_dir, monkeypatch):
@@ -162,22 +81,14 @@ def test_link_evaluator_counts_equal_host_path_and_oracle(device, graph, eval_di
     want = np.zeros(4, np.int64)
     for name in sorted(maps):
         h, w = SHAPES[name]
-        boxes, _ = _host_image(graph, device, maps[name][0], maps[name][1], h, w)
+        boxes, _ = E.host_image(graph, device, maps[name][0], maps[name][1], h, w)
         gts, ign = evaluate.load_ground_truth(os.path.join(d, name + ".npy"))
         n_g, tp, fp = OE.bboxes_matching(boxes.reshape(-1, 8), gts[:, :, 0], gts[:, :, 1], ign, 0.5)
         want += [n_g, int(tp.sum()), int(fp.sum()), len(boxes)]
-    forward, calls = _stub_forward(device, maps)
+    forward, calls = E.link_stub_forward(device, maps)
     ev = evaluate.LinkEvaluator(graph, forward, d, batch_size=2, eval_image_height=EVAL, eval_image_width=EVAL)
     # every read of the device during the pass, with the number of chains launched before it
-    reads = []
-    for name in ("cpu", "item", "tolist", "numpy"):
-        orig = getattr(torch.Tensor, name)
-
-        def spy(self, *a, _orig=orig, _name=name, **kw):
-            if self.is_cuda:
-                reads.append((_name, len(calls)))
-            return _orig(self, *a, **kw)
-        monkeypatch.setattr(torch.Tensor, name, spy)
+    reads = E.spy_reads(monkeypatch, calls)
     res = ev.run()
     monkeypatch.undo()
     assert sorted(calls) == [(1, EVAL, EVAL, 3), (2, EVAL, EVAL, 3)]       # both shapes enter at the eval size
@@ -207,58 +118,18 @@ def test_eval_pixellink_fast_prints_the_line_for_synthetic_images(device, tmp_pa
     S = importlib.import_module("eval_pixellink_fast")
     d = str(tmp_path)
     for i in range(2):
-        _write_gt(os.path.join(d, "gt_synthetic_%d.txt" % i), [[8, 8, 40, 8, 40, 24, 8, 24], [30, 40, 60, 40, 60, 56, 30, 56]], ["text", "###"])
+        E.write_gt(os.path.join(d, "gt_synthetic_%d.txt" % i), [[8, 8, 40, 8, 40, 24, 8, 24], [30, 40, 60, 40, 60, 56, 30, 56]], ["text", "###"])
     S.main(["--synthetic", "2", "--gt_path", d, "--eval_image_height", "64", "--eval_image_width", "64", "--batch_size", "2"])
     lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("precision ")]
     assert len(lines) == 1 and " recall " in lines[0] and " hmean " in lines[0] and "(gt 2 det " in lines[0], lines
 
 
 # ------------------------------------------------------------------------------------------------ training
-def _train(device, eval_dir_path, with_eval, steps=4):
-    from tensorflow_ocr_amd import synthetic
-    from tensorflow_ocr_amd.graph import Graph
-    from tensorflow_ocr_amd.nets import pixellink
-    from tensorflow_ocr_amd.train import MomentumOptimizer, TrainStep
-    sys.path.insert(0, ROOT)
-    T = importlib.import_module("train_pixellink")
-    argv = ["--batch_size", "2", "--train_image_height", "64", "--train_image_width", "64", "--using_moving_average",
-            "--eval_image_height", "64", "--eval_image_width", "64"]
-    if with_eval:
-        argv += ["--eval_steps", "1", "--eval_data_path", eval_dir_path]
-    FLAGS = T.parse(argv)
-    rng = np.random.default_rng(52)
-    im, px, lk, _ = synthetic.make_batch(rng, 2, 64)
-    batch = [torch.from_numpy(a).to(device) for a in (im, px[..., 0], lk)]
-
-    def fl(gr, images, pixel_labels, link_labels):
-        net = pixellink.PixelLinkNet(images, graph=gr, input_norm=T.INPUT_NORM)
-        return net.build_loss(pixel_labels, link_labels)
-    g = Graph(device, loss_scale=1024.0, seed=6)
-    step = TrainStep(g, fl, lambda gr: MomentumOptimizer(gr, base_lr=1e-3, momentum=0.9, weight_decay=5e-4,
-                                                         moving_average_decay=FLAGS.moving_average_decay))
-    te = T.make_train_eval(FLAGS, g, step)
-    assert (te is not None) == with_eval
-    results = []
-    for it in range(steps):
-        step(*batch)
-        if te is not None and te.due(it + 1):
-            T._evaluate(te, None, step.opt)
-            results.append(te.last)
-    torch.cuda.synchronize()
-    assert step.plan is not None
-    calls = [(e[0], e[3] if e[0] == "c" else (e[2] if len(e) > 2 else None)) for e in step.recorded]      # C entry names, host entry tags
-    state = [t.clone() for t in (g.store.flat, g.store.flat_aux, step.opt.ema)]
-    return calls, list(step.plan_kinds), state, results, te
-
-
 def test_training_with_link_evaluation_records_the_same_step_and_trains_the_same_weights(device, tmp_path):
     d = str(tmp_path)
-    rng = np.random.default_rng(5)
-    for name in ("img_1", "img_2"):
-        np.save(os.path.join(d, name + ".npy"), rng.integers(0, 256, (64, 64, 3)).astype(np.uint8))
-        _write_gt(os.path.join(d, "gt_%s.txt" % name), [[8, 8, 40, 8, 40, 24, 8, 24], [30, 40, 60, 40, 60, 56, 30, 56]], ["text", "###"])
-    calls0, kinds0, state0, _, _ = _train(device, d, False)
-    calls1, kinds1, state1, results, te = _train(device, d, True)
+    E.write_training_eval_dir(d)
+    calls0, kinds0, state0, _, _ = E.train_pixellink(device, d, None)
+    calls1, kinds1, state1, results, te = E.train_pixellink(device, d, [])
     assert calls1 == calls0 and kinds1 == kinds0 and len(calls0) > 50       # the recorded call list is identical
     for a, b in zip(state0, state1):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))        # weights, auxiliaries, EMA: bit for bit

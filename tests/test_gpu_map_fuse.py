@@ -13,7 +13,9 @@ import numpy as np
 import pytest
 import torch
 
+import eval_support as E
 import mapfuse_ref as R
+from eval_support import EVAL, SHAPES            # the link directory: the eval size (a fusion grid of 32 x 32), the originals' (h, w)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -182,30 +184,7 @@ def test_status_codes_and_nothing_written_on_error(device):
 
 
 # ------------------------------------------------------------------------------------------------ the planted words
-EVAL = 128                                       # the eval size of the tests: a fusion grid of 32 x 32
-SHAPES = {"img_a": (96, 128), "img_b": (96, 128), "img_c": (96, 160)}      # (h, w) of the originals
 BATCHES = [["img_a", "img_b"], ["img_c"]]        # the chains of a pass with batch_size 2, in order
-
-
-def _rot(h, w, cx, cy, a, b, deg):
-    ys, xs = np.mgrid[0:h, 0:w]
-    th = np.deg2rad(deg)
-    u = (xs - cx) * np.cos(th) + (ys - cy) * np.sin(th)
-    v = -(xs - cx) * np.sin(th) + (ys - cy) * np.cos(th)
-    return (np.abs(u) <= a) & (np.abs(v) <= b)
-
-
-def _planted(rng, regions):
-    """(pixel_cls [32,32,2], link_cls [32,32,16]) whose softmaxes paint the regions: P(text) in (0.95, 0.99) inside, below
-    0.12 outside; every link 0.993"""
-    inside = np.zeros((32, 32), bool)
-    for m in regions:
-        inside |= m
-    px = np.zeros((32, 32, 2), f32)
-    px[..., 1] = np.where(inside, rng.uniform(3.0, 4.5, (32, 32)), rng.uniform(-4.5, -2.0, (32, 32)))
-    lk = np.zeros((32, 32, 16), f32)
-    lk[..., 1::2] = 5.0
-    return px, lk
 
 
 def _at_scale(px, lk, side):
@@ -224,12 +203,6 @@ def _mirrored(px, lk, perm):
     return px[:, :, ::-1].copy(), lk.reshape(n, h, w, 8, 2)[:, :, ::-1][:, :, :, perm].reshape(n, h, w, 16).copy()
 
 
-def _write_gt(path, quads, tags):
-    with open(path, "w") as f:
-        for q, t in zip(quads, tags):
-            f.write(",".join(str(int(v)) for v in np.asarray(q).reshape(-1)) + "," + t + "\r\n")
-
-
 def _collect(device, five, max_d=None):
     """ocr_eval_collect on detect_device's five tensors with ratios (1, 1) -> (dets, det_score, nd) as NumPy"""
     from tensorflow_ocr_amd import ops
@@ -246,26 +219,18 @@ def _collect(device, five, max_d=None):
 
 @pytest.fixture(scope="module")
 def eval_dir(device, graph, tmp_path_factory):
-    """test_gpu_link_eval_chain.py's directory, rebuilt: 3 images of two original shapes with the logits the stub forward
-    returns for them, and per image three ground truths: the best single-scale detection exactly, an ignored quad, and one
-    nothing matches.  (The text logits are a little stronger than there, so that a word's border survives the blend with
-    the half-size map: see _at_scale.)"""
+    """eval_support's link directory with the text logits a little stronger (P(text) in (0.95, 0.99)), so that a word's
+    border survives the blend with the half-size map (see _at_scale); an image's first ground truth is its best
+    single-scale detection, exactly."""
     from tensorflow_ocr_amd.tool import pixellink_fn as P
-    d = str(tmp_path_factory.mktemp("map_fuse_eval"))
-    rng = np.random.default_rng(78)
-    regions = {"img_a": [_rot(32, 32, 9, 8, 6, 2, 0), _rot(32, 32, 20, 22, 8, 2, 35)],
-               "img_b": [_rot(32, 32, 16, 10, 9, 3, -20), _rot(32, 32, 8, 25, 5, 2, 0), _rot(32, 32, 25, 25, 3, 3, 0)],
-               "img_c": [_rot(32, 32, 16, 16, 10, 3, 60), _rot(32, 32, 5, 5, 3, 2, 0)]}
-    maps = {k: _planted(rng, r) for k, r in regions.items()}
-    for name, (h, w) in SHAPES.items():
-        np.save(os.path.join(d, name + ".npy"), rng.integers(0, 256, (h, w, 3)).astype(np.uint8))
-        ps = P.pixel_scores(_up(device, maps[name][0][None]), graph=graph)[..., 1].contiguous()
-        ls = P.link_scores(_up(device, maps[name][1][None]), graph=graph)
+
+    def best_box(name, px, lk, h, w, n_regions):
+        ps = P.pixel_scores(_up(device, px[None]), graph=graph)[..., 1].contiguous()
+        ls = P.link_scores(_up(device, lk[None]), graph=graph)
         dets, _, nd = _collect(device, P.detect_device(ps, ls, 0.8, 0.9, 10, w / 32.0, h / 32.0, graph=graph))
-        assert nd[0] == len(regions[name]), name
-        _write_gt(os.path.join(d, "gt_%s.txt" % name), [dets[0, 0], [[1, 1], [9, 1], [9, 6], [1, 6]],
-                                                      [[w - 14, 2], [w - 2, 2], [w - 2, 9], [w - 14, 9]]], ["text", "###", "far"])
-    return d, maps
+        assert nd[0] == n_regions, name
+        return dets[0, 0]
+    return E.link_eval_dir(str(tmp_path_factory.mktemp("map_fuse_eval")), best_box, text=(3.0, 4.5))
 
 
 def _stub_forward(device, maps, perm, flip=False):
@@ -336,21 +301,13 @@ def test_link_evaluator_at_the_identity_scale_returns_the_single_scale_record(de
     forward, _ = _stub_forward(device, maps, perm)
     kw = dict(batch_size=2, eval_image_height=EVAL, eval_image_width=EVAL)
     single = evaluate.LinkEvaluator(graph, forward, d, **kw)
-    assert single.map_scales is None and single.flip is False and single._pick_chain() == single._chain
+    assert single.map_scales is None and single.flip is False and type(single.detector) is evaluate.LinkSingleScale
     want = single.run()
     assert _record(want)[0] == 6 and want["tp"] >= 3 and want["num_det"] == 7 and want["images"] == 3
     forward, calls = _stub_forward(device, maps, perm)
     ev = evaluate.LinkEvaluator(graph, forward, d, map_scales=[1], **kw)
-    assert ev.map_scales == [1.0] and ev.scale_weights == [1.0] and ev._pick_chain() == ev._chain_fused
-    reads = []
-    for name in ("cpu", "item", "tolist", "numpy"):
-        orig = getattr(torch.Tensor, name)
-
-        def spy(self, *a, _orig=orig, _name=name, **k):
-            if self.is_cuda:
-                reads.append((_name, len(calls)))
-            return _orig(self, *a, **k)
-        monkeypatch.setattr(torch.Tensor, name, spy)
+    assert ev.map_scales == [1.0] and ev.scale_weights == [1.0] and type(ev.detector) is evaluate.LinkFused
+    reads = E.spy_reads(monkeypatch, calls)
     got = ev.run()
     monkeypatch.undo()
     assert got == want                                                        # weight 1 at the identity size: the softmaxes
@@ -372,12 +329,17 @@ def test_link_evaluator_three_scales_with_flip_equals_the_calls_composed_by_hand
     kw = dict(batch_size=2, eval_image_height=EVAL, eval_image_width=EVAL)
     forward, calls = _stub_forward(device, maps, perm, flip=True)
     ev = evaluate.LinkEvaluator(graph, forward, d, map_scales=[0.5, 1, 2], flip=True, scale_weights=[1, 2, 1], max_comps=64, **kw)
-    seen, match = [], ev._match
+    seen, match, detect = [], ev._match, ev.detector.detect
 
-    def spy(*a):
-        seen.append([t.clone() for t in a[:5]])
+    def spy(*a):                                  # the rows the collect-and-match step is given ...
+        seen[-1][:4] = [t.clone() for t in a[:4]]
         return match(*a)
-    ev._match = spy
+
+    def spy_detect(*a):                           # ... and the detector's total: its overflow column is total - max_comps
+        out = detect(*a)
+        seen.append([None] * 4 + [out[5][:, 0] + ev.max_comps])
+        return out
+    ev._match, ev.detector.detect = spy, spy_detect
     res = ev.run()
     sizes = P.map_scale_sizes(EVAL, EVAL, [0.5, 1, 2])
     assert sizes == [(64, 64), (128, 128), (256, 256)]
@@ -427,7 +389,7 @@ def test_eval_pixellink_fast_runs_multi_scale_with_flip_on_graphed_forwards(devi
     S = importlib.import_module("eval_pixellink_fast")
     d = str(tmp_path)
     for i in range(2):
-        _write_gt(os.path.join(d, "gt_synthetic_%d.txt" % i), [[8, 8, 40, 8, 40, 24, 8, 24], [30, 40, 60, 40, 60, 56, 30, 56]], ["text", "###"])
+        E.write_gt(os.path.join(d, "gt_synthetic_%d.txt" % i), [[8, 8, 40, 8, 40, 24, 8, 24], [30, 40, 60, 40, 60, 56, 30, 56]], ["text", "###"])
     S.main(["--synthetic", "2", "--gt_path", d, "--eval_image_height", "64", "--eval_image_width", "64", "--batch_size", "2",
             "--map_scales", "1,2", "--flip"])
     lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("precision ")]
@@ -435,51 +397,11 @@ def test_eval_pixellink_fast_runs_multi_scale_with_flip_on_graphed_forwards(devi
 
 
 # ------------------------------------------------------------------------------------------------ training
-def _train(device, eval_dir_path, extra, steps=4):
-    from tensorflow_ocr_amd import synthetic
-    from tensorflow_ocr_amd.graph import Graph
-    from tensorflow_ocr_amd.nets import pixellink
-    from tensorflow_ocr_amd.train import MomentumOptimizer, TrainStep
-    sys.path.insert(0, ROOT)
-    T = importlib.import_module("train_pixellink")
-    argv = ["--batch_size", "2", "--train_image_height", "64", "--train_image_width", "64", "--using_moving_average",
-            "--eval_image_height", "64", "--eval_image_width", "64"]
-    if extra is not None:
-        argv += ["--eval_steps", "1", "--eval_data_path", eval_dir_path] + extra
-    FLAGS = T.parse(argv)
-    rng = np.random.default_rng(52)
-    im, px, lk, _ = synthetic.make_batch(rng, 2, 64)
-    batch = [torch.from_numpy(a).to(device) for a in (im, px[..., 0], lk)]
-
-    def fl(gr, images, pixel_labels, link_labels):
-        net = pixellink.PixelLinkNet(images, graph=gr, input_norm=T.INPUT_NORM)
-        return net.build_loss(pixel_labels, link_labels)
-    g = Graph(device, loss_scale=1024.0, seed=6)
-    step = TrainStep(g, fl, lambda gr: MomentumOptimizer(gr, base_lr=1e-3, momentum=0.9, weight_decay=5e-4,
-                                                         moving_average_decay=FLAGS.moving_average_decay))
-    te = T.make_train_eval(FLAGS, g, step)
-    assert (te is not None) == (extra is not None)
-    results = []
-    for it in range(steps):
-        step(*batch)
-        if te is not None and te.due(it + 1):
-            T._evaluate(te, None, step.opt)
-            results.append(te.last)
-    torch.cuda.synchronize()
-    assert step.plan is not None
-    calls = [(e[0], e[3] if e[0] == "c" else (e[2] if len(e) > 2 else None)) for e in step.recorded]
-    state = [t.clone() for t in (g.store.flat, g.store.flat_aux, step.opt.ema)]
-    return calls, list(step.plan_kinds), state, results, te
-
-
 def test_training_with_a_fused_evaluation_records_the_same_step_and_trains_the_same_weights(device, tmp_path):
     d = str(tmp_path)
-    rng = np.random.default_rng(5)
-    for name in ("img_1", "img_2"):
-        np.save(os.path.join(d, name + ".npy"), rng.integers(0, 256, (64, 64, 3)).astype(np.uint8))
-        _write_gt(os.path.join(d, "gt_%s.txt" % name), [[8, 8, 40, 8, 40, 24, 8, 24], [30, 40, 60, 40, 60, 56, 30, 56]], ["text", "###"])
-    calls0, kinds0, state0, _, _ = _train(device, d, None)
-    calls1, kinds1, state1, results, te = _train(device, d, ["--eval_map_scales", "1,2", "--eval_flip"])
+    E.write_training_eval_dir(d)
+    calls0, kinds0, state0, _, _ = E.train_pixellink(device, d, None)
+    calls1, kinds1, state1, results, te = E.train_pixellink(device, d, ["--eval_map_scales", "1,2", "--eval_flip"])
     assert calls1 == calls0 and kinds1 == kinds0 and len(calls0) > 50       # the recorded call list is identical
     assert not [c for c in calls0 if c[1] == "ocr_link_map_accumulate"]     # ... and holds nothing of the evaluation
     for a, b in zip(state0, state1):

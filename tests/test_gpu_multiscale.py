@@ -11,7 +11,6 @@ import pytest
 import torch
 
 import ms_ref as M
-import test_eval_match_host as H
 from oracle import evalboxes as OE
 
 pytestmark = pytest.mark.gpu

@@ -344,4 +344,4 @@ def test_link_evaluator_buckets_by_original_shape_and_scales_to_original_pixels(
         evaluate.LinkEvaluator(g, forward, d, eval_image_height=130)
     # the RBOX evaluator's sizing is what it was
     rb = evaluate.Evaluator(g, forward, d)
-    assert rb._resized(720, 1280) == (672, 1280) and rb._ratio(720, 1280, 672, 1280) == (1.0, 672 / 720.0)
+    assert rb.detector.resized(720, 1280) == (672, 1280) and rb.detector.ratio(720, 1280, 672, 1280) == (1.0, 672 / 720.0)
