@@ -24,21 +24,7 @@ import tempfile
 
 import numpy as np
 
-
-def _sweep_arg(text):
-    from tensorflow_ocr_amd.evaluate import sweep_arg
-    return sweep_arg(text)
-
-
-def _sweep_help():
-    from tensorflow_ocr_amd.evaluate import SWEEP_HELP
-    return SWEEP_HELP % "the component's mean pixel score, in [0, 1]"
-
-
-def _map_scales_arg(text):
-    from tensorflow_ocr_amd.tool.pixellink_fn import map_scales_arg
-    return map_scales_arg(text)
-
+from tensorflow_ocr_amd import cli
 
 MAP_SCALES_HELP = ("multi-scale testing by score-map fusion: the network runs at each of these scales of the eval size (sides "
                    "rounded to multiples of 32), the pixel and link probabilities of all passes are resampled onto the 1/4 "
@@ -68,8 +54,9 @@ def parse(argv=None):
     ap.add_argument('--eval_protocol', choices=['raster', 'icdar15'], default='raster', help="raster = the reference's "
                     "matching rule; icdar15 = the official ICDAR-2015 protocol (polygon IoU, ### as don't-care regions), the "
                     "line then ends in [icdar15]")
-    ap.add_argument('--eval_sweep', type=_sweep_arg, default=None, metavar='LO:HI:N', help=_sweep_help())
-    ap.add_argument('--map_scales', type=_map_scales_arg, default=None, metavar='S1,S2,...', help=MAP_SCALES_HELP)
+    ap.add_argument('--eval_sweep', type=cli.sweep_arg, default=None, metavar='LO:HI:N',
+                    help=cli.sweep_help("the component's mean pixel score, in [0, 1]"))
+    ap.add_argument('--map_scales', type=cli.map_scales_arg, default=None, metavar='S1,S2,...', help=MAP_SCALES_HELP)
     ap.add_argument('--flip', action='store_true', help=FLIP_HELP)
     FLAGS = ap.parse_args(argv)
     if FLAGS.min_side < 0 or FLAGS.min_area < 0:

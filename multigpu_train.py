@@ -29,15 +29,8 @@ import time
 import numpy as np
 import torch
 
-
-def _sweep_arg(text):
-    from tensorflow_ocr_amd.evaluate import sweep_arg
-    return sweep_arg(text)
-
-
-def _scales_arg(text):
-    from tensorflow_ocr_amd.tool.rbox import scales_arg
-    return scales_arg(text)
+from tensorflow_ocr_amd import cli
+from tensorflow_ocr_amd.cli import window as _window
 
 
 def parse(argv=None):
@@ -56,65 +49,37 @@ def parse(argv=None):
     ap.add_argument('--pretrained_model_path', type=str, default=None)
     ap.add_argument('--training_data_path', type=str, default='/data/ocr/icdar2015/')
     ap.add_argument('--net', choices=['model', 'model_vgg', 'east', 'pixellink'], default='model')
-    # not a reference flag (TF-1.4 trains in f32): the f16 loss scale, a number or "dynamic" (graph.DynamicLossScale:
-    # a step whose gradients overflow is skipped and the scale backs off; it grows again after a run of clean steps)
-    ap.add_argument('--loss_scale', type=_loss_scale_arg, default=1024.0)
-    # not a reference flag: clip the un-scaled gradients to this global L2 norm on the device (train.GradClip); a step whose
-    # norm is not finite is skipped.  Off by default.
-    ap.add_argument('--clip_norm', type=_clip_norm_arg, default=None)
-    # not a reference flag: gradient accumulation (train.TrainStep(accumulate_steps=K)): one optimiser step on the mean gradient
-    # of K micro-batches of --batch_size_per_gpu, so one card reaches the effective batch of K.  The step counters
-    # below (--max_steps, --save_checkpoint_steps, --save_summary_steps, the staircase) count OPTIMISER steps.  1 = off.
-    ap.add_argument('--accumulate_steps', type=_accumulate_steps_arg, default=1)
+    cli.add_step_flags(ap, '--batch_size_per_gpu')
     # the augmentation the reference keeps disabled (datasets/icdar.py:576-615), on the device: none | east | pixellink |
     # key=value,... (datasets/augment.py: Augment.parse).  Only with --training_data_path; synthetic batches have none.
     ap.add_argument('--augment', type=_augment_arg, default=None, metavar='SPEC')
-    # not a reference flag: with the scalars and images that --save_summary_steps writes (0: no event file), the four
-    # per-variable summaries of train_pixellink.py:179-194 (histograms of every variable and gradient, their means) from
-    # one device pass over the flat buffers (summary.TensorStats)
-    ap.add_argument('--summary_variables', action='store_true')
     # not a flag of this reference script (EAST's own has the head built in): link = the PixelLink-style 8 link maps the
     # reference trains; RBOX = EAST's score + four distances + angle (--net east only), labels from the same polygons
     ap.add_argument('--geometry', choices=['link', 'RBOX'], default='link')
     ap.add_argument('--text_scale', type=int, default=512, help="RBOX only: the distance scale of the geometry head "
                     "(the reference's nets/model.py flag)")
-    # not reference flags: held-out evaluation between steps (tensorflow_ocr_amd.evaluate.TrainEval), --net east --geometry
-    # RBOX only.  Every --eval_steps optimiser steps (0 = off) rank 0 runs the images of --eval_data_path (images + gt_*.txt,
-    # at most --eval_max_images of them) through forward -> decode -> LANMS -> matching on the device and reports precision /
-    # recall / hmean; --eval_weights: ema = the moving averages test.py restores, raw = the weights being trained
-    ap.add_argument('--eval_data_path', type=str, default=None, metavar='DIR')
-    ap.add_argument('--eval_steps', type=int, default=0, metavar='N')
-    ap.add_argument('--eval_max_images', type=int, default=None, metavar='M')
-    ap.add_argument('--eval_weights', choices=['ema', 'raw'], default='ema')
-    # --eval_protocol: raster = the reference's matching rule, icdar15 = the official ICDAR-2015 protocol (polygon IoU)
-    ap.add_argument('--eval_protocol', choices=['raster', 'icdar15'], default='raster')
-    # --eval_sweep LO:HI:N (or a comma list): every pass also reports the precision / recall curve over LANMS's merged score (a
-    # sum of pixel scores, not a probability), its best row and AP, from the one matching pass (evaluate.Evaluator's sweep)
-    ap.add_argument('--eval_sweep', type=_sweep_arg, default=None, metavar='LO:HI:N')
+    # between-steps evaluation, --net east --geometry RBOX only; --eval_sweep's order key is LANMS's merged score (a sum of
+    # pixel scores, not a probability)
+    cli.add_train_eval_flags(ap)
     # --eval_scales 0.5,1,2: multi-scale testing in every pass — one forward per scale, the per-scale detections pooled and
     # fused on the device (evaluate.Evaluator's scales); --eval_fuse: nms = score-ordered suppression, vote = score-weighted
     # coordinates.  The detection score (and --eval_sweep's threshold) is then the mean pixel score, in [0, 1]
-    ap.add_argument('--eval_scales', type=_scales_arg, default=None, metavar='S1,S2,..')
+    ap.add_argument('--eval_scales', type=cli.scales_arg, default=None, metavar='S1,S2,..')
     ap.add_argument('--eval_fuse', choices=['nms', 'vote'], default='nms')
     FLAGS = ap.parse_args(argv)
-    if FLAGS.eval_scales is not None and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
+    if FLAGS.eval_scales is not None and not cli.eval_on(FLAGS):
         ap.error('--eval_scales needs --eval_data_path and --eval_steps')
     if FLAGS.eval_fuse != 'nms' and FLAGS.eval_scales is None:
         ap.error('--eval_fuse needs --eval_scales')
-    if FLAGS.eval_sweep is not None and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
-        ap.error('--eval_sweep needs --eval_data_path and --eval_steps')
-    if FLAGS.eval_protocol != 'raster' and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
-        ap.error('--eval_protocol needs --eval_data_path and --eval_steps')
-    if FLAGS.geometry == 'RBOX' and FLAGS.net != 'east':
-        ap.error('--geometry RBOX needs --net east (the RBOX heads sit on the EAST merge branch)')
-    if FLAGS.eval_steps < 0 or (FLAGS.eval_max_images is not None and FLAGS.eval_max_images < 1):
-        ap.error('--eval_steps must not be negative and --eval_max_images must be positive')
-    if FLAGS.eval_steps > 0 and not FLAGS.eval_data_path:
-        ap.error('--eval_steps needs --eval_data_path')
-    if (FLAGS.eval_steps > 0 or FLAGS.eval_data_path) and not (FLAGS.net == 'east' and FLAGS.geometry == 'RBOX'):
-        ap.error('--eval_data_path / --eval_steps need --net east --geometry RBOX (the evaluation decodes RBOX maps)')
-    if FLAGS.eval_weights == 'ema' and FLAGS.eval_steps > 0 and not FLAGS.moving_average_decay:
-        ap.error('--eval_weights ema needs a --moving_average_decay')
+    rbox = FLAGS.net == 'east' and FLAGS.geometry == 'RBOX'
+    cli.check_train_eval_flags(
+        ap, FLAGS, FLAGS.moving_average_decay, '--eval_weights ema needs a --moving_average_decay',
+        after_sweep=[(FLAGS.eval_protocol != 'raster' and not cli.eval_on(FLAGS),
+                      '--eval_protocol needs --eval_data_path and --eval_steps'),
+                     (FLAGS.geometry == 'RBOX' and FLAGS.net != 'east',
+                      '--geometry RBOX needs --net east (the RBOX heads sit on the EAST merge branch)')],
+        before_ema=[((FLAGS.eval_steps > 0 or FLAGS.eval_data_path) and not rbox,
+                     '--eval_data_path / --eval_steps need --net east --geometry RBOX (the evaluation decodes RBOX maps)')])
     return FLAGS
 
 
@@ -122,30 +87,6 @@ def _augment_arg(text):
     from tensorflow_ocr_amd.datasets.augment import Augment
     try:
         return Augment.parse(text)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-
-
-def _accumulate_steps_arg(text):
-    from tensorflow_ocr_amd.train import check_accumulate_steps
-    try:
-        return check_accumulate_steps(int(text))
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-
-
-def _clip_norm_arg(text):
-    from tensorflow_ocr_amd.train import check_clip_norm
-    try:
-        return check_clip_norm(float(text))
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-
-
-def _loss_scale_arg(text):
-    from tensorflow_ocr_amd.graph import parse_loss_scale
-    try:
-        return parse_loss_scale(text)
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e))
 
@@ -235,17 +176,6 @@ def _next_batch(FLAGS, feeder, rng, device):
     return [torch.from_numpy(a).to(device, non_blocking=True) for a in data]
 
 
-def _window(step, K, next_batch):
-    """One optimiser step: K calls of `step`, each on a batch of its own.  Returns the mean of the micro-step losses as a
-    device tensor (summed on the device: no read here)."""
-    total = None
-    for _ in range(K):
-        loss = step(*next_batch())
-        if K > 1:
-            total = loss.clone() if total is None else total + loss
-    return loss if K == 1 else total / K
-
-
 def _train_loop(FLAGS, g, step, feeder, rng, rank, world, device, start):
     from tensorflow_ocr_amd import checkpoint, dist
     batch = _next_batch(FLAGS, feeder, rng, device)
@@ -298,10 +228,7 @@ def _write_summaries(summaries, g, opt, loss, batch):
     :189-194): behind the window's closing call, so store.flat_grad holds that optimiser step's gradients."""
     ml = loss.item()
     scalars = {'model_loss': ml, 'total_loss': ml + opt.regularization_loss().item(), 'learning_rate': opt.learning_rate()}
-    if g.loss_scaler is not None:
-        scalars['loss_scale'] = g.loss_scaler.scale()
-    if opt.clip is not None:
-        scalars['grad_norm'] = opt.grad_norm()
+    scalars.update(cli.grad_factor_scalars(opt))
     images, score_maps, geo_maps = batch[0], batch[1], batch[2]
     summaries.write(opt.global_step, scalars, [('input', images[0]), ('score_map', score_maps[0]),
                                                ('geo_map_0', geo_maps[0][..., 0:1])])
@@ -325,16 +252,7 @@ def make_train_eval(FLAGS, g, step, blocks=None):
 
 
 def _evaluate(train_eval, summaries, opt):
-    """One pass between two steps (rank 0; the other ranks meet it at the next exchange): the line test.py prints, and
-    eval/precision, eval/recall, eval/hmean (with --eval_sweep also eval/ap, eval/best_hmean, eval/best_threshold) in the
-    event file where one is open."""
-    from tensorflow_ocr_amd import evaluate
-    res = train_eval.run()
-    print('Step {:06d}, '.format(opt.global_step) + evaluate.format_line(res), flush=True)
-    if 'sweep' in res:
-        print(evaluate.format_sweep(res), flush=True)
-    if summaries is not None:
-        train_eval.write(summaries.writer, opt.global_step)
+    cli.report_eval(train_eval, summaries, opt, 'Step {:06d}, ')       # ... and the line test.py prints
 
 
 def _steps(FLAGS, g, step, opt, K, next_batch, last, summaries, rank, world, start, train_eval=None):
@@ -361,11 +279,7 @@ def _steps(FLAGS, g, step, opt, K, next_batch, last, summaries, rank, world, sta
                 tl = ml + opt.regularization_loss().item()
                 print('Step {:06d}, model loss {:.4f}, total loss {:.4f}, {:.2f} seconds/step, {:.2f} examples/second'.format(
                     it, ml, tl, avg_time_per_step, avg_examples_per_second), flush=True)
-                if g.loss_scaler is not None:       # (the loss was just read: one more device read costs nothing here)
-                    print('loss scale {:g}, {:d} steps skipped'.format(g.loss_scaler.scale(), g.loss_scaler.skipped_steps()),
-                          flush=True)
-                if opt.clip is not None:
-                    print('grad norm {:.4g}, {:d} steps clipped'.format(opt.grad_norm(), opt.clipped_steps()), flush=True)
+                cli.log_grad_factor(opt)
         if rank == 0 and it % FLAGS.save_checkpoint_steps == 0:     # step 0 included (multigpu_train.py:185-186)
             # saver.save(sess, FLAGS.checkpoint_path + 'model.ckpt', global_step=global_step) (:186-187):
             # a TensorFlow V2 bundle of Saver(tf.global_variables()) — variables, EMA shadows, Adam slots

@@ -5,6 +5,7 @@ TF-slim variable names, activation handles, and a reverse-mode tape.
 Nothing here computes: every FLOP happens in libocr_hip.so via `ops`.  torch is used for
 device memory only.
 """
+import collections
 import contextlib
 import math
 from typing import NamedTuple
@@ -431,6 +432,9 @@ def parse_loss_scale(text):
     return v
 
 
+LossSeed = collections.namedtuple("LossSeed", "factor scale_ptr")
+
+
 class Graph:
     """One tower: variable store + tape + scratch.  `loss_scale` multiplies the loss gradient so
     that f16 activation gradients stay in range; the optimiser divides it out."""
@@ -506,6 +510,14 @@ class Graph:
         """d(loss)/d(loss) the loss kernels start the backward pass from: the f16 loss scale, over
         the clone count when the caller pre-divides its loss (grad_op="sum")."""
         return self.loss_scale / self.loss_div
+
+    def loss_seed(self):
+        """The same seed as a record, for either kind of loss scale: `factor` is the host's share of it (the whole seed
+        for a constant scale, 1 / loss_div for a dynamic one), `scale_ptr` the device's (the scaler's scale word, or None).
+        `losses.launch_seed` starts a loss family's backward entry from it."""
+        if self.loss_scaler is not None:
+            return LossSeed(1.0 / self.loss_div, self.loss_scaler.scale_ptr)
+        return LossSeed(self.seed_scale(), None)
 
     # --- device memory ---
     def workspace(self):

@@ -29,6 +29,17 @@ def to_device(g, arr, dtype=F32):
     return torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).to(g.device)
 
 
+def launch_seed(seed, entries, operands, grads):
+    """Start a loss family's backward pass from `seed` (Graph.loss_seed()): `entries` is the family's (bwd, bwd_dyn)
+    pair of ops, which take the operands, the host factor — the dynamic one also the device scale word — and the gradient
+    arguments, in this order."""
+    bwd, bwd_dyn = entries
+    if seed.scale_ptr is not None:      # dynamic loss scaling: the kernel reads the scale from the device state
+        bwd_dyn(*operands, seed.factor, seed.scale_ptr, *grads)
+    else:
+        bwd(*operands, seed.factor, *grads)
+
+
 def softmax_loss(g, pixel_logits, link_logits, pixel_labels, link_labels, *, pixel_rule, label_rule,
                  link_gate, focal=None, neg_ratio=3.0):
     """pixel_logits / link_logits: head handles (`.data` f32 [n,h,w,2] / [n,h,w,16], `.grad`).
@@ -47,12 +58,8 @@ def softmax_loss(g, pixel_logits, link_logits, pixel_labels, link_labels, *, pix
     def backward():
         pixel_logits.grad = g.empty(pixel_logits.data.shape, F32)
         link_logits.grad = g.empty(link_logits.data.shape, F32)
-        if g.loss_scaler is not None:       # dynamic loss scaling: the kernel reads the scale from the device state
-            ops.softmax_loss_bwd_dyn(d, pixel_logits.data, link_logits.data, pl, ll, thr, sums, 1.0 / g.loss_div,
-                                     g.loss_scaler.scale_ptr, pixel_logits.grad, link_logits.grad)
-        else:
-            ops.softmax_loss_bwd(d, pixel_logits.data, link_logits.data, pl, ll, thr, sums, g.seed_scale(),
-                                 pixel_logits.grad, link_logits.grad)
+        launch_seed(g.loss_seed(), (ops.softmax_loss_bwd, ops.softmax_loss_bwd_dyn),
+                    (d, pixel_logits.data, link_logits.data, pl, ll, thr, sums), (pixel_logits.grad, link_logits.grad))
     g.record(backward)
     res = Scalar(out)
     res.ohnm_threshold = thr
@@ -86,12 +93,8 @@ def balanced_loss(g, pixel_logits, link_logits, pixel_labels, link_labels, pixel
     def backward():
         pixel_logits.grad = g.empty(pixel_logits.data.shape, F32)
         link_logits.grad = g.empty(link_logits.data.shape, F32)
-        if g.loss_scaler is not None:       # dynamic loss scaling: the kernel reads the scale from the device state
-            ops.balanced_loss_bwd_dyn(d, pixel_logits.data, link_logits.data, pl, ll, pw, thr, sums, 1.0 / g.loss_div,
-                                      g.loss_scaler.scale_ptr, pixel_logits.grad, link_logits.grad)
-        else:
-            ops.balanced_loss_bwd(d, pixel_logits.data, link_logits.data, pl, ll, pw, thr, sums, g.seed_scale(),
-                                  pixel_logits.grad, link_logits.grad)
+        launch_seed(g.loss_seed(), (ops.balanced_loss_bwd, ops.balanced_loss_bwd_dyn),
+                    (d, pixel_logits.data, link_logits.data, pl, ll, pw, thr, sums), (pixel_logits.grad, link_logits.grad))
     g.record(backward)
     res = Scalar(out)
     res.ohnm_threshold = thr

@@ -6,8 +6,9 @@ EAST's RBOX geometry (reference nets/model.py:76-80) on the merge branch of `mod
 import numpy as np
 import torch
 
-from .. import head_layers, layers, ops
+from .. import head_layers, layers, losses, ops
 from ..graph import F32, get_default_graph
+from ..losses import Scalar, launch_seed, to_device as _to_device      # (the names this module had for its own copies)
 from . import vgg
 
 
@@ -24,12 +25,6 @@ def mean_image_subtraction(images, means=(123.68, 116.78, 103.94), graph=None):
     if len(means) != images.shape[-1]:
         raise ValueError('len(means) must match the number of channels')
     return layers.prep_images(g, _to_device(g, images))
-
-
-def _to_device(g, arr, dtype=F32):
-    if isinstance(arr, torch.Tensor):
-        return arr.to(device=g.device, dtype=dtype).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).to(g.device)
 
 
 def _merge_branch(images, weight_decay, is_training, g, blocks):
@@ -106,19 +101,6 @@ def model_vgg(images, weight_decay=1e-5, is_training=True, graph=None):
     return pixel_cls, link_cls
 
 
-class Scalar:
-    """Device scalar (the loss) with its components; `.item()` syncs."""
-
-    def __init__(self, buf):
-        self.data = buf
-
-    def item(self):
-        return float(self.data[0].item())
-
-    def terms(self):
-        return self.data[1:10].detach().cpu().numpy()
-
-
 def dice_coefficient(y_true_cls, y_pred_cls, training_mask, graph=None):
     """nets/model_vgg_16.py:179-193 for one map (host convenience: builds the 9-map call with
     zero link maps and returns the pixel term)."""
@@ -144,11 +126,8 @@ def loss(y_true_pixel, y_pred_pixel, y_true_link, y_pred_link, training_mask, gr
     def backward():
         y_pred_pixel.grad = g.empty(y_pred_pixel.data.shape, F32)
         y_pred_link.grad = g.empty(y_pred_link.data.shape, F32)
-        if g.loss_scaler is not None:       # dynamic loss scaling: the kernel reads the scale from the device state
-            ops.dice_loss_bwd_dyn(ytp, ytl, m, sums, 1.0 / g.loss_div, g.loss_scaler.scale_ptr, y_pred_pixel.grad,
-                                  y_pred_link.grad)
-        else:
-            ops.dice_loss_bwd(ytp, ytl, m, sums, g.seed_scale(), y_pred_pixel.grad, y_pred_link.grad)
+        launch_seed(g.loss_seed(), (ops.dice_loss_bwd, ops.dice_loss_bwd_dyn), (ytp, ytl, m, sums),
+                    (y_pred_pixel.grad, y_pred_link.grad))
     g.record(backward)
     res = Scalar(out)
     g.collections["losses"].append(res)
@@ -169,11 +148,8 @@ def loss_rbox(y_true_cls, y_pred_cls, y_true_geo, y_pred_geo, training_mask, gra
     def backward():
         y_pred_cls.grad = g.empty(y_pred_cls.data.shape, F32)
         y_pred_geo.grad = g.empty(y_pred_geo.data.shape, F32)
-        if g.loss_scaler is not None:       # dynamic loss scaling: the kernel reads the scale from the device state
-            ops.rbox_loss_bwd_dyn(ytc, ytg, y_pred_geo.data, m, sums, 1.0 / g.loss_div, g.loss_scaler.scale_ptr,
-                                  y_pred_cls.grad, y_pred_geo.grad)
-        else:
-            ops.rbox_loss_bwd(ytc, ytg, y_pred_geo.data, m, sums, g.seed_scale(), y_pred_cls.grad, y_pred_geo.grad)
+        launch_seed(g.loss_seed(), (ops.rbox_loss_bwd, ops.rbox_loss_bwd_dyn), (ytc, ytg, y_pred_geo.data, m, sums),
+                    (y_pred_cls.grad, y_pred_geo.grad))
     g.record(backward)
     res = Scalar(out)
     g.collections["losses"].append(res)
@@ -183,10 +159,8 @@ def loss_rbox(y_true_cls, y_pred_cls, y_true_geo, y_pred_geo, training_mask, gra
 def ohem_loss(y_true_pixel, y_pred_pixel, y_true_link, y_pred_link, training_mask, graph=None):
     """nets/model_vgg_16.py:243-282 (with cal_link_loss :227-241): despite the name no mining —
     pixel CE over positives / n_pos, link CEs weighted by the positive-pixel mask, L_pixel*2 + L_link."""
-    from .. import losses
     g = graph or get_default_graph()
-    return losses.softmax_loss(g, y_pred_pixel, y_pred_link, y_true_pixel, y_true_link,
-                               pixel_rule=1, label_rule=0, link_gate=True)
+    return losses.softmax_loss(g, y_pred_pixel, y_pred_link, y_true_pixel, y_true_link, pixel_rule=1, label_rule=0, link_gate=True)
 
 
 def cal_link_loss(link_gt, link_pred, W_pixel, graph=None):
@@ -230,9 +204,6 @@ def cal_link_loss(link_gt, link_pred, W_pixel, graph=None):
     if handle is not None:
         def backward():
             handle.grad = g.empty(pr_t.shape, F32)
-            if g.loss_scaler is not None:
-                ops.link_ce_bwd_dyn(gt_t, gs, pr_t, ps, W, P, sums, 1.0 / g.loss_div, g.loss_scaler.scale_ptr, handle.grad, 2)
-            else:
-                ops.link_ce_bwd(gt_t, gs, pr_t, ps, W, P, sums, g.seed_scale(), handle.grad, 2)
+            launch_seed(g.loss_seed(), (ops.link_ce_bwd, ops.link_ce_bwd_dyn), (gt_t, gs, pr_t, ps, W, P, sums), (handle.grad, 2))
         g.record(backward)
     return Scalar(out)

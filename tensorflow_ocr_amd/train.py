@@ -41,19 +41,6 @@ def pixellink_lr(global_step, base_lr=0.01):
     return base_lr * f
 
 
-def _regularization_loss(opt):
-    """Sum of tf.GraphKeys.REGULARIZATION_LOSSES (multigpu_train.py:36): slim.l2_regularizer(wd) on
-    every regularised variable = wd/2 * sum(w^2) over the head of the flat buffer.  One device
-    reduction; returns a 1-element f32 device tensor (read it with .item() where the loss is logged)."""
-    st = opt.g.store
-    if getattr(opt, "_reg_out", None) is None:
-        opt._reg_out = torch.zeros(1, dtype=F32, device=st.flat.device)
-    if st.n_reg > 0 and opt.wd:
-        opt.g.workspace()
-        ops.sum_squares(st.flat[:st.n_reg], 0.5 * opt.wd, opt._reg_out, opt.g.ws_small)
-    return opt._reg_out
-
-
 class GradClip:
     """Global-norm gradient clipping decided on the device (ocr_grad_clip_state, include/ocr_hip.h): the optimisers'
     `clip_norm=c`.  Per step one pass over the reduced flat gradient buffer leaves norm = |g * base|, coef =
@@ -71,15 +58,6 @@ class GradClip:
         self.state = torch.zeros(ops.GRAD_CLIP_WORDS, dtype=torch.int32, device=flat_grad.device)     # = ocr_grad_clip_init
         self.ws = torch.empty(max(1, ops.grad_clip_workspace(flat_grad.numel()) // 8), dtype=torch.float64,
                               device=flat_grad.device)
-
-    def run(self, graph, grad, grad_scale):
-        """The clip pass on `grad`; afterwards the `_clip` step reads `self.state`."""
-        sc = graph.loss_scaler
-        if sc is not None:
-            ops.grad_check_clip(grad, sc.state, sc.growth_factor, sc.backoff_factor, sc.growth_interval, sc.min_scale,
-                                sc.max_scale, self.state, self.clip_norm, grad_scale, self.ws)
-        else:
-            ops.grad_clip(grad, self.state, self.clip_norm, grad_scale / graph.loss_scale, self.ws)
 
     def _words(self):
         return self.state.cpu().numpy()
@@ -109,6 +87,101 @@ def check_accumulate_steps(k):
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
         raise ValueError("accumulate_steps must be an integer >= 1, got %r" % (k,))
     return int(k)
+
+
+class StaticFactor:
+    """The gradient factor policy of a constant loss scale.  A policy says which factor multiplies the gradients in the
+    optimiser step and where it lives: the pass over the flat gradient buffer in front of the step (`pre_step`), the
+    suffix of the step entry and that entry's trailing arguments (`suffix`, `step_args`), the (mul_host, mul_dev) pair
+    of `TrainStep.summary_factor`, and what the drivers log and write of it.  An optimiser picks one, once (`grad_factor`).
+
+    Constant scale: no pass; the step entry takes grad_scale / loss_scale."""
+    suffix = ""
+
+    def __init__(self, graph):
+        self.g = graph
+
+    def pre_step(self, grad, grad_scale):
+        pass
+
+    def clip_pass(self, clip, grad, grad_scale):
+        """The pass of a `ClippedFactor` around this policy: one launch more than without clipping."""
+        ops.grad_clip(grad, clip.state, clip.clip_norm, grad_scale / self.g.loss_scale, clip.ws)
+
+    def step_args(self, grad_scale, ema_decay):
+        return grad_scale / self.g.loss_scale, ema_decay
+
+    def summary_factor(self, grad_scale):
+        return grad_scale / self.g.loss_scale, None
+
+    def log_lines(self):
+        """What a driver prints behind its loss line (READS THE DEVICE, like `scalars`: for logging only)."""
+        return []
+
+    def scalars(self):
+        return {}
+
+
+class DynamicFactor(StaticFactor):
+    """Dynamic loss scaling (graph.DynamicLossScale): the check sees the REDUCED gradients (inf / NaN survive a sum
+    all-reduce, so every rank decides alike), the guarded `_dyn` step reads 1 / scale from the scaler's block and writes
+    nothing when the check found one.  The optimiser's host counters advance either way: no device read in the step."""
+    suffix = "_dyn"
+
+    def __init__(self, graph):
+        self.scaler = graph.loss_scaler
+
+    def pre_step(self, grad, grad_scale):
+        self.scaler.check(grad)
+
+    def clip_pass(self, clip, grad, grad_scale):
+        """The check pass also sums the norm: two launches, as without clipping."""
+        sc = self.scaler
+        ops.grad_check_clip(grad, sc.state, sc.growth_factor, sc.backoff_factor, sc.growth_interval, sc.min_scale,
+                            sc.max_scale, clip.state, clip.clip_norm, grad_scale, clip.ws)
+
+    def step_args(self, grad_scale, ema_decay):
+        return grad_scale, ema_decay, self.scaler.state
+
+    def summary_factor(self, grad_scale):
+        return grad_scale, self.scaler.state[ops.LS_INV_SCALE_USED:ops.LS_INV_SCALE_USED + 1].view(torch.float32)
+
+    def log_lines(self):
+        return ['loss scale {:g}, {:d} steps skipped'.format(self.scaler.scale(), self.scaler.skipped_steps())]
+
+    def scalars(self):
+        return {'loss_scale': self.scaler.scale()}
+
+
+class ClippedFactor:
+    """Global-norm clipping (`GradClip`) around either policy above: the inner policy's clip pass leaves g_mul and skip in
+    the clip block, and the `_clip` step takes no factor but that block."""
+    suffix = "_clip"
+
+    def __init__(self, inner, clip):
+        self.inner, self.clip = inner, clip
+
+    def pre_step(self, grad, grad_scale):
+        self.inner.clip_pass(self.clip, grad, grad_scale)
+
+    def step_args(self, grad_scale, ema_decay):
+        return ema_decay, self.clip.state
+
+    def summary_factor(self, grad_scale):
+        return 1.0, self.clip.state[ops.GC_G_MUL:ops.GC_G_MUL + 1].view(torch.float32)
+
+    def log_lines(self):
+        return self.inner.log_lines() + ['grad norm {:.4g}, {:d} steps clipped'.format(self.clip.grad_norm(),
+                                                                                     self.clip.clipped_steps())]
+
+    def scalars(self):
+        return dict(self.inner.scalars(), grad_norm=self.clip.grad_norm())
+
+
+def grad_factor(graph, clip):
+    """The policy of (graph.loss_scaler, clip): the one place that tells the cases apart."""
+    inner = DynamicFactor(graph) if graph.loss_scaler is not None else StaticFactor(graph)
+    return ClippedFactor(inner, clip) if clip is not None else inner
 
 
 class GradAccum:
@@ -190,10 +263,71 @@ class GradAccum:
         return int(self.state.cpu().numpy()[ops.GA_WINDOWS_TOTAL])
 
 
-class _ClipReadout:
-    """grad_norm() / clipped_steps() / nonfinite_steps() of an optimiser built with clip_norm: each READS THE DEVICE (a
-    sync), for logging only."""
+class Optimizer:
+    """What the two optimisers share: the construction order (clip check, flat buffers, slots, EMA shadows, clip block,
+    gradient factor policy), the EMA warm-up, the checkpoint dictionaries and the step's skeleton.  A subclass names its
+    step entry (`STEP`), its checkpoint slots and the attribute each lives in (`SLOTS`, `BUFFERS`), and has
+    `learning_rate()`, `scalar_state_dict()` and `_launch(entry, st, tail)`: the one step launch, `tail` being the
+    policy's trailing arguments."""
+    STEP, SLOTS, BUFFERS = None, (), {}
 
+    def __init__(self, graph, moving_average_decay, weight_decay, clip_norm):
+        if clip_norm is not None:
+            check_clip_norm(clip_norm)               # before anything is allocated
+        self.g = graph
+        graph.ensure_materialised()
+        st = graph.store
+        for name in self.SLOTS:
+            setattr(self, self.BUFFERS[name], torch.zeros_like(st.flat))
+        self.ema = st.flat.clone() if moving_average_decay else None
+        self.mad, self.wd = moving_average_decay, weight_decay
+        self.clip = GradClip(clip_norm, st.flat_grad) if clip_norm is not None else None
+        self.factor = grad_factor(graph, self.clip)
+        self.global_step = 0
+        self._reg_out = None
+
+    def ema_decay(self):
+        """ExponentialMovingAverage(decay, num_updates=global_step): the warm-up min(decay, (1 + n) / (10 + n)); 0 = no shadows."""
+        return min(self.mad, (1.0 + self.global_step) / (10.0 + self.global_step)) if self.mad else 0.0
+
+    def apply_gradients(self, grad_scale=1.0):
+        st = self.g.store
+        self.factor.pre_step(st.flat_grad, grad_scale)
+        self._launch(getattr(ops, self.STEP + self.factor.suffix), st, self.factor.step_args(grad_scale, self.ema_decay()))
+        st.version += 1
+        self.global_step += 1
+
+    def shadow_state_dict(self):
+        """EMA shadows by variable name (what test.py:149-150 restores)."""
+        return self.g.store.by_variable(self.ema)
+
+    def slot_state_dict(self):
+        return {name: self.g.store.by_variable(getattr(self, self.BUFFERS[name])) for name in self.SLOTS}
+
+    def load_state(self, global_step=None, slots=None, ema=None):
+        st = self.g.store
+        if slots:
+            for name in self.SLOTS:
+                st.load_by_variable(getattr(self, self.BUFFERS[name]), slots.get(name, {}))
+        if ema and self.ema is not None:
+            st.load_by_variable(self.ema, ema)
+        if global_step is not None:
+            self.global_step = int(global_step)
+
+    def regularization_loss(self):
+        """Sum of tf.GraphKeys.REGULARIZATION_LOSSES (multigpu_train.py:36): slim.l2_regularizer(wd) on
+        every regularised variable = wd/2 * sum(w^2) over the head of the flat buffer.  One device
+        reduction; returns a 1-element f32 device tensor (read it with .item() where the loss is logged)."""
+        st = self.g.store
+        if self._reg_out is None:
+            self._reg_out = torch.zeros(1, dtype=F32, device=st.flat.device)
+        if st.n_reg > 0 and self.wd:
+            self.g.workspace()
+            ops.sum_squares(st.flat[:st.n_reg], 0.5 * self.wd, self._reg_out, self.g.ws_small)
+        return self._reg_out
+
+    # grad_norm() / clipped_steps() / nonfinite_steps() of an optimiser built with clip_norm: each READS THE DEVICE (a
+    # sync), for logging only
     def _clip_or_raise(self):
         if self.clip is None:
             raise RuntimeError("this optimiser was built without clip_norm")
@@ -210,145 +344,50 @@ class _ClipReadout:
         return self._clip_or_raise().nonfinite_steps()
 
 
-class AdamOptimizer(_ClipReadout):
+class AdamOptimizer(Optimizer):
     """tf.train.AdamOptimizer + ExponentialMovingAverage(decay, num_updates=global_step) + slim L2
     regulariser gradient, as ONE fused launch over the tower's flat parameter buffer."""
+    # `tf.train.Saver(tf.global_variables())` (multigpu_train.py:144) also saves the optimiser's slot
+    # variables `<var>/Adam`, `<var>/Adam_1`, the scalars `beta1_power`, `beta2_power` and
+    # `global_step`; a resumed run continues the LR staircase, the bias correction and the EMA warm-up
+    STEP, SLOTS, BUFFERS = "adam_step", ("Adam", "Adam_1"), {"Adam": "m", "Adam_1": "v"}
 
     def __init__(self, graph, learning_rate=1e-4, decay_steps=5000, decay_rate=0.94,
                  moving_average_decay=0.997, weight_decay=1e-5, beta1=0.9, beta2=0.999, epsilon=1e-8,
                  clip_norm=None):
-        if clip_norm is not None:
-            check_clip_norm(clip_norm)               # before anything is allocated
-        self.g = graph
-        graph.ensure_materialised()
-        st = graph.store
-        self.m = torch.zeros_like(st.flat)
-        self.v = torch.zeros_like(st.flat)
-        self.ema = st.flat.clone() if moving_average_decay else None
+        super().__init__(graph, moving_average_decay, weight_decay, clip_norm)
         self.lr0, self.decay_steps, self.decay_rate = learning_rate, decay_steps, decay_rate
-        self.mad, self.wd = moving_average_decay, weight_decay
         self.b1, self.b2, self.eps = beta1, beta2, epsilon
-        self.clip = GradClip(clip_norm, st.flat_grad) if clip_norm is not None else None
-        self.global_step = 0
 
     def learning_rate(self):
         return exponential_decay(self.lr0, self.global_step, self.decay_steps, self.decay_rate, True)
 
-    def apply_gradients(self, grad_scale=1.0):
-        st = self.g.store
+    def _launch(self, entry, st, tail):
         t = self.global_step + 1
-        lr = self.learning_rate()
-        lr_t = lr * math.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
-        ema_d = min(self.mad, (1.0 + self.global_step) / (10.0 + self.global_step)) if self.mad else 0.0
-        scaler = self.g.loss_scaler
-        if self.clip is not None:
-            # global-norm clipping (GradClip): with a scaler its check pass also sums the norm, two launches as without
-            # clipping; with a numeric loss scale the clip pass is one launch more.  The step reads g_mul / skip.
-            self.clip.run(self.g, st.flat_grad, grad_scale)
-            ops.adam_step_clip(st.flat, st.flat_grad, self.m, self.v, self.ema, st.n_reg, lr_t, self.b1, self.b2,
-                               self.eps, self.wd, ema_d, self.clip.state)
-        elif scaler is not None:
-            # dynamic loss scaling (graph.DynamicLossScale): the check sees the REDUCED gradients (inf / NaN survive a sum
-            # all-reduce, so every rank decides alike), the guarded step writes nothing when it found one.  The host
-            # counters below advance either way: no device read in the step.
-            scaler.check(st.flat_grad)
-            ops.adam_step_dyn(st.flat, st.flat_grad, self.m, self.v, self.ema, st.n_reg, lr_t, self.b1, self.b2,
-                              self.eps, self.wd, grad_scale, ema_d, scaler.state)
-        else:
-            ops.adam_step(st.flat, st.flat_grad, self.m, self.v, self.ema, st.n_reg, lr_t, self.b1, self.b2,
-                          self.eps, self.wd, grad_scale / self.g.loss_scale, ema_d)
-        st.version += 1
-        self.global_step += 1
-
-    def shadow_state_dict(self):
-        """EMA shadows by variable name (what test.py:149-150 restores)."""
-        return self.g.store.by_variable(self.ema)
-
-    # `tf.train.Saver(tf.global_variables())` (multigpu_train.py:144) also saves the optimiser's slot
-    # variables `<var>/Adam`, `<var>/Adam_1`, the scalars `beta1_power`, `beta2_power` and
-    # `global_step`; a resumed run continues the LR staircase, the bias correction and the EMA warm-up
-    SLOTS = ("Adam", "Adam_1")
-
-    def slot_state_dict(self):
-        st = self.g.store
-        return {"Adam": st.by_variable(self.m), "Adam_1": st.by_variable(self.v)}
+        lr_t = self.learning_rate() * math.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
+        entry(st.flat, st.flat_grad, self.m, self.v, self.ema, st.n_reg, lr_t, self.b1, self.b2, self.eps, self.wd, *tail)
 
     def scalar_state_dict(self):
         t = self.global_step
         return {"beta1_power": np.float32(self.b1 ** (t + 1)), "beta2_power": np.float32(self.b2 ** (t + 1))}
 
-    def load_state(self, global_step=None, slots=None, ema=None):
-        st = self.g.store
-        if slots:
-            st.load_by_variable(self.m, slots.get("Adam", {}))
-            st.load_by_variable(self.v, slots.get("Adam_1", {}))
-        if ema and self.ema is not None:
-            st.load_by_variable(self.ema, ema)
-        if global_step is not None:
-            self.global_step = int(global_step)
 
-    def regularization_loss(self):
-        return _regularization_loss(self)
-
-
-class MomentumOptimizer(_ClipReadout):
+class MomentumOptimizer(Optimizer):
     """tf.train.MomentumOptimizer(lr, 0.9) with the PixelLink schedule (train_pixellink.py:222-243)."""
+    STEP, SLOTS, BUFFERS = "momentum_step", ("Momentum",), {"Momentum": "acc"}
 
     def __init__(self, graph, base_lr=0.01, momentum=0.9, weight_decay=5e-4, moving_average_decay=None, clip_norm=None):
-        if clip_norm is not None:
-            check_clip_norm(clip_norm)
-        self.g = graph
-        graph.ensure_materialised()
-        st = graph.store
-        self.acc = torch.zeros_like(st.flat)
-        self.ema = st.flat.clone() if moving_average_decay else None
-        self.base_lr, self.momentum, self.wd, self.mad = base_lr, momentum, weight_decay, moving_average_decay
-        self.clip = GradClip(clip_norm, st.flat_grad) if clip_norm is not None else None
-        self.global_step = 0
+        super().__init__(graph, moving_average_decay, weight_decay, clip_norm)
+        self.base_lr, self.momentum = base_lr, momentum
 
     def learning_rate(self):
         return pixellink_lr(self.global_step, self.base_lr)
 
-    SLOTS = ("Momentum",)
-
-    def shadow_state_dict(self):
-        return self.g.store.by_variable(self.ema)
-
-    def slot_state_dict(self):
-        return {"Momentum": self.g.store.by_variable(self.acc)}
+    def _launch(self, entry, st, tail):
+        entry(st.flat, st.flat_grad, self.acc, self.ema, st.n_reg, self.learning_rate(), self.momentum, self.wd, *tail)
 
     def scalar_state_dict(self):
         return {}
-
-    def load_state(self, global_step=None, slots=None, ema=None):
-        st = self.g.store
-        if slots:
-            st.load_by_variable(self.acc, slots.get("Momentum", {}))
-        if ema and self.ema is not None:
-            st.load_by_variable(self.ema, ema)
-        if global_step is not None:
-            self.global_step = int(global_step)
-
-    def regularization_loss(self):
-        return _regularization_loss(self)
-
-    def apply_gradients(self, grad_scale=1.0):
-        st = self.g.store
-        ema_d = min(self.mad, (1.0 + self.global_step) / (10.0 + self.global_step)) if self.mad else 0.0
-        scaler = self.g.loss_scaler
-        if self.clip is not None:            # as in AdamOptimizer.apply_gradients
-            self.clip.run(self.g, st.flat_grad, grad_scale)
-            ops.momentum_step_clip(st.flat, st.flat_grad, self.acc, self.ema, st.n_reg, self.learning_rate(),
-                                   self.momentum, self.wd, ema_d, self.clip.state)
-        elif scaler is not None:             # as in AdamOptimizer.apply_gradients
-            scaler.check(st.flat_grad)
-            ops.momentum_step_dyn(st.flat, st.flat_grad, self.acc, self.ema, st.n_reg, self.learning_rate(),
-                                  self.momentum, self.wd, grad_scale, ema_d, scaler.state)
-        else:
-            ops.momentum_step(st.flat, st.flat_grad, self.acc, self.ema, st.n_reg, self.learning_rate(),
-                              self.momentum, self.wd, grad_scale / self.g.loss_scale, ema_d)
-        st.version += 1
-        self.global_step += 1
 
 
 class TrainStep:
@@ -461,13 +500,7 @@ class TrainStep:
         optimiser: the factor that step's optimiser kernel multiplied the gradients with, its device part left on the
         device (a 1-element f32 view of the clip state's g_mul or of the loss-scale state's inv_scale_used; None: 1).
         No device read."""
-        gs = self._grad_scale()
-        if self.opt.clip is not None:
-            return 1.0, self.opt.clip.state[ops.GC_G_MUL:ops.GC_G_MUL + 1].view(torch.float32)
-        sc = self.g.loss_scaler
-        if sc is not None:
-            return gs, sc.state[ops.LS_INV_SCALE_USED:ops.LS_INV_SCALE_USED + 1].view(torch.float32)
-        return gs / self.g.loss_scale, None
+        return self.opt.factor.summary_factor(self._grad_scale())
 
     # -- eager / recording path --------------------------------------------------------------
     def _eager(self, batch, record):

@@ -26,20 +26,7 @@ import time
 import numpy as np
 import torch
 
-
-def _sweep_arg(text):
-    from tensorflow_ocr_amd.evaluate import sweep_arg
-    return sweep_arg(text)
-
-
-def _scales_arg(text):
-    from tensorflow_ocr_amd.tool.rbox import scales_arg
-    return scales_arg(text)
-
-
-def _sweep_help():
-    from tensorflow_ocr_amd.evaluate import SWEEP_HELP
-    return SWEEP_HELP % "LANMS's merged score, a sum of pixel scores (not a probability, not --box_thresh's mean)"
+from tensorflow_ocr_amd import cli
 
 
 def parse(argv=None):
@@ -70,8 +57,9 @@ def parse(argv=None):
     ap.add_argument('--eval_protocol', choices=['raster', 'icdar15'], default='raster', help="with --gt_path: raster = the "
                     "reference's rule above; icdar15 = the official ICDAR-2015 protocol (polygon IoU, ### as don't-care "
                     "regions), the line then ends in [icdar15]")
-    ap.add_argument('--eval_sweep', type=_sweep_arg, default=None, metavar='LO:HI:N', help="with --gt_path: " + _sweep_help())
-    ap.add_argument('--scales', type=_scales_arg, default=None, metavar='S1,S2,..', help="RBOX only: multi-scale testing, e.g. "
+    ap.add_argument('--eval_sweep', type=cli.sweep_arg, default=None, metavar='LO:HI:N', help="with --gt_path: " + cli.sweep_help(
+                    "LANMS's merged score, a sum of pixel scores (not a probability, not --box_thresh's mean)"))
+    ap.add_argument('--scales', type=cli.scales_arg, default=None, metavar='S1,S2,..', help="RBOX only: multi-scale testing, e.g. "
                     "0.5,1,2 — the image is resized from the original to each scale (then by the sizing rule), one forward per "
                     "scale, the per-scale detections are pooled in original-image pixels and fused on the device "
                     "(tool/rbox.detect_multiscale).  The fused quads carry the mean pixel score, in [0, 1]; with --gt_path "

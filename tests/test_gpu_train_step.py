@@ -1,6 +1,8 @@
 """GPU: the full training step (forward, dice loss, backward, Adam+EMA) — eager vs recorded/replayed
 execution must agree bit for bit (every kernel is deterministic: slab reductions, no atomics), the
 Adam update must match the oracle's formula on the device gradients, and the loss must go down."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -86,6 +88,74 @@ def test_pixellink_replay_equals_eager_on_a_fresh_batch_every_step(device):
     assert le == lr, (le, lr)
     assert all(np.isfinite(le))
     assert torch.equal(ge.store.flat, gr.store.flat)
+
+
+TAIL_PLANS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_tail_plans.json")
+TAIL_CASES = [(w, m) for w in ("adam", "momentum") for m in ("static", "dynamic", "clip_static", "clip_dynamic")]
+
+
+def plan_names(plan):
+    """A plan without its pointers: [C entry, tag] per call, [kind, label] for a fork, a join or a host callback."""
+    from tensorflow_ocr_amd import step_plan
+    return [[e[3], list(e[4]) if e[4] is not None else None] if e[0] == "c" else [e[0], step_plan.py_label(e)] for e in plan]
+
+
+def run_tail_case(device, which, mode):
+    """Both towers of one case over four batches: (the recorded plan's names, replayed step, its eager twin)."""
+    from tensorflow_ocr_amd import synthetic
+    from tensorflow_ocr_amd.graph import DynamicLossScale, Graph
+    from tensorflow_ocr_amd.nets import model_vgg_16 as M
+    from tensorflow_ocr_amd.nets import pixellink
+    from tensorflow_ocr_amd.train import AdamOptimizer, MomentumOptimizer, TrainStep
+    clip = 1.0 if mode.startswith("clip") else None
+
+    def tower(replay):
+        g = Graph(device, loss_scale=DynamicLossScale(init_scale=1024.0) if mode.endswith("dynamic") else 1024.0, seed=3)
+        if which == "adam":
+            def fl(gr, im, px, lk, mk):
+                a, b = M.model_vgg(im, graph=gr)
+                return M.loss(px, a, lk, b, mk, graph=gr)
+            return g, TrainStep(g, fl, lambda gr: AdamOptimizer(gr, learning_rate=1e-3, clip_norm=clip), replay=replay)
+
+        def fl(gr, im, px, lk):
+            return pixellink.PixelLinkNet(im, graph=gr).build_loss(px, lk)
+        return g, TrainStep(g, fl, lambda gr: MomentumOptimizer(gr, base_lr=1e-3, clip_norm=clip), replay=replay)
+    (gr, sr), (ge, se) = tower(True), tower(False)
+    for i in range(4):                                  # two eager steps, the recorded third, one replay
+        if which == "adam":
+            b = [torch.from_numpy(a).to(device) for a in synthetic.make_batch(np.random.default_rng(40 + i), 2, 64)]
+        else:
+            b = _pixellink_batch(device, 40 + i)
+            b[0] = (b[0] - 120.0) / 60.0
+        sr(*[t.clone() for t in b])
+        se(*b)
+        if i == 2:
+            names = plan_names(sr.plan)
+    torch.cuda.synchronize()
+    return names, sr, se
+
+
+@pytest.mark.parametrize("which,mode", TAIL_CASES)
+def test_every_tail_mode_records_the_parents_plan_and_replays_the_eager_step(device, which, mode):
+    """Both optimisers under each gradient-factor policy (constant or dynamic loss scale, with and without clip_norm): the
+    third step's plan is, entry for entry and tag for tag, the one recorded on the commit before the policies were pulled
+    out of the optimisers (tests/golden/train_tail_plans.json, written by tests/golden/make_train_tail_plans.py), and the
+    replayed fourth step leaves the parameters of a fourth eager step, bit for bit."""
+    import json
+    with open(TAIL_PLANS) as f:
+        gold = json.load(f)
+    want = gold["plans"][gold["cases"]["%s %s" % (which, mode)]]
+    names, sr, se = run_tail_case(device, which, mode)
+    got = json.loads(json.dumps(names))
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert a == b, (i, a, b)
+    assert len(got) == len(want)
+    assert sr.plan is not None and se.plan is None and sr.opt.global_step == se.opt.global_step == 4
+    assert (sr.opt.clip is not None) == mode.startswith("clip") and (sr.g.loss_scaler is not None) == mode.endswith("dynamic")
+    assert torch.equal(sr.g.store.flat, se.g.store.flat) and torch.isfinite(sr.g.store.flat).all()
+    assert torch.equal(sr.g.store.flat_aux, se.g.store.flat_aux)
+    if sr.opt.ema is not None:
+        assert torch.equal(sr.opt.ema, se.opt.ema)
 
 
 def test_recording_refuses_torch_operators_inside_the_step(device):

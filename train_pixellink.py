@@ -29,15 +29,8 @@ import time
 import numpy as np
 import torch
 
-
-def _sweep_arg(text):
-    from tensorflow_ocr_amd.evaluate import sweep_arg
-    return sweep_arg(text)
-
-
-def _map_scales_arg(text):
-    from tensorflow_ocr_amd.tool.pixellink_fn import map_scales_arg
-    return map_scales_arg(text)
+from tensorflow_ocr_amd import cli
+from tensorflow_ocr_amd.cli import window as _window
 
 
 def parse(argv=None):
@@ -61,22 +54,11 @@ def parse(argv=None):
     ap.add_argument('--dataset_dir', type=str, default=None)
     ap.add_argument('--train_image_width', type=int, default=512)
     ap.add_argument('--train_image_height', type=int, default=512)
-    # not a reference flag (TF-1.4 trains in f32): the f16 loss scale, a number or "dynamic" (graph.DynamicLossScale:
-    # a step whose gradients overflow is skipped and the scale backs off; it grows again after a run of clean steps)
-    ap.add_argument('--loss_scale', type=_loss_scale_arg, default=1024.0)
-    # not a reference flag: clip the un-scaled gradients to this global L2 norm on the device (train.GradClip); a step whose
-    # norm is not finite is skipped.  Off by default.
-    ap.add_argument('--clip_norm', type=_clip_norm_arg, default=None)
-    # not a reference flag: gradient accumulation (train.TrainStep(accumulate_steps=K)): one optimiser step on the mean gradient
-    # of K micro-batches of --batch_size, so one card reaches the effective batch of K.  The step counters
-    # below (--max_number_of_steps, --log_every_n_steps, the checkpoint interval, the staircase) count OPTIMISER steps.  1 = off.
-    ap.add_argument('--accumulate_steps', type=_accumulate_steps_arg, default=1)
     # not a reference flag (the reference's slim.learning.train writes its summaries on a timer): every N optimiser steps
-    # rank 0 adds the loss, the learning rate and the input image to a TensorBoard event file in --train_dir and, with
-    # --summary_variables, the four per-variable summaries of `sum_gradients` (:190-193) from one device pass over the
-    # flat buffers (summary.TensorStats).  0 = off: no event file.
+    # rank 0 adds the loss, the learning rate and the input image to a TensorBoard event file in --train_dir (and what
+    # --summary_variables adds).  0 = off: no event file.
     ap.add_argument('--save_summary_steps', type=int, default=0)
-    ap.add_argument('--summary_variables', action='store_true')
+    cli.add_step_flags(ap, '--batch_size')
     # not a reference flag: the pixel loss.  'mean' is what the reference's build_loss computes (nets/pixellink.py:160, the
     # mean CE over all pixels); 'instance_balanced' is the paper's loss the reference left commented out (:138-168,
     # :191-192): every text instance weighs the same, --max_neg_pos_ratio hardest negatives per positive are mined, `###`
@@ -84,38 +66,21 @@ def parse(argv=None):
     ap.add_argument('--pixel_loss', choices=('mean', 'instance_balanced'), default='mean')
     # config.max_neg_pos_ratio (nets/pixellink.py:116); read by --pixel_loss instance_balanced only
     ap.add_argument('--max_neg_pos_ratio', type=_neg_ratio_arg, default=3.0)
-    # not reference flags: held-out evaluation between steps (tensorflow_ocr_amd.evaluate.TrainEval on a LinkEvaluator).
-    # Every --eval_steps optimiser steps (0 = off) rank 0 runs the images of --eval_data_path (images + gt_*.txt, at most
-    # --eval_max_images of them), resized to --eval_image_height x --eval_image_width, through forward -> link components ->
-    # boxes -> matching on the device and reports precision / recall / hmean; --eval_weights: ema = the moving averages
-    # (needs --using_moving_average), raw = the weights being trained
-    ap.add_argument('--eval_data_path', type=str, default=None, metavar='DIR')
-    ap.add_argument('--eval_steps', type=int, default=0, metavar='N')
-    ap.add_argument('--eval_max_images', type=int, default=None, metavar='M')
-    ap.add_argument('--eval_weights', choices=['ema', 'raw'], default='ema')
+    # between-steps evaluation on a LinkEvaluator: the images are resized to --eval_image_height x --eval_image_width and go
+    # through forward -> link components -> boxes -> matching; --eval_weights ema needs --using_moving_average; --eval_sweep's
+    # order key is the component's mean pixel score, in [0, 1]
+    cli.add_train_eval_flags(ap)
     ap.add_argument('--eval_image_width', type=int, default=1280)
     ap.add_argument('--eval_image_height', type=int, default=768)
-    # --eval_protocol: raster = the reference's matching rule, icdar15 = the official ICDAR-2015 protocol (polygon IoU)
-    ap.add_argument('--eval_protocol', choices=['raster', 'icdar15'], default='raster')
-    # --eval_sweep LO:HI:N (or a comma list): every pass also reports the precision / recall curve over the component's mean
-    # pixel score (in [0, 1]), its best row and AP, from the one matching pass (evaluate.LinkEvaluator's sweep)
-    ap.add_argument('--eval_sweep', type=_sweep_arg, default=None, metavar='LO:HI:N')
     # --eval_map_scales S1,S2,... [--eval_flip]: multi-scale / flip testing of every pass by score-map fusion (the flags
     # --map_scales / --flip of eval_pixellink_fast.py: evaluate.LinkEvaluator's map_scales / flip; build-defined, its effect
     # on the F-measure unmeasured; activation memory grows with the square of the largest scale)
-    ap.add_argument('--eval_map_scales', type=_map_scales_arg, default=None, metavar='S1,S2,...')
+    ap.add_argument('--eval_map_scales', type=cli.map_scales_arg, default=None, metavar='S1,S2,...')
     ap.add_argument('--eval_flip', action='store_true')
     FLAGS = ap.parse_args(argv)
-    if (FLAGS.eval_map_scales is not None or FLAGS.eval_flip) and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
+    if (FLAGS.eval_map_scales is not None or FLAGS.eval_flip) and not cli.eval_on(FLAGS):
         ap.error('--eval_map_scales and --eval_flip need --eval_data_path and --eval_steps')
-    if FLAGS.eval_sweep is not None and not (FLAGS.eval_steps > 0 and FLAGS.eval_data_path):
-        ap.error('--eval_sweep needs --eval_data_path and --eval_steps')
-    if FLAGS.eval_steps < 0 or (FLAGS.eval_max_images is not None and FLAGS.eval_max_images < 1):
-        ap.error('--eval_steps must not be negative and --eval_max_images must be positive')
-    if FLAGS.eval_steps > 0 and not FLAGS.eval_data_path:
-        ap.error('--eval_steps needs --eval_data_path')
-    if FLAGS.eval_weights == 'ema' and FLAGS.eval_steps > 0 and not FLAGS.using_moving_average:
-        ap.error('--eval_weights ema needs --using_moving_average')
+    cli.check_train_eval_flags(ap, FLAGS, FLAGS.using_moving_average, '--eval_weights ema needs --using_moving_average')
     return FLAGS
 
 
@@ -124,30 +89,6 @@ def _neg_ratio_arg(text):
     if not v >= 0.0:
         raise argparse.ArgumentTypeError('--max_neg_pos_ratio must be a number >= 0, got %r' % text)
     return v
-
-
-def _accumulate_steps_arg(text):
-    from tensorflow_ocr_amd.train import check_accumulate_steps
-    try:
-        return check_accumulate_steps(int(text))
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-
-
-def _clip_norm_arg(text):
-    from tensorflow_ocr_amd.train import check_clip_norm
-    try:
-        return check_clip_norm(float(text))
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-
-
-def _loss_scale_arg(text):
-    from tensorflow_ocr_amd.graph import parse_loss_scale
-    try:
-        return parse_loss_scale(text)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
 
 
 def staircase_lr(step, base, breakpoints, decays):
@@ -218,17 +159,6 @@ def synthetic_weights(ids, device, rects=8):
     return weight
 
 
-def _window(step, K, next_batch):
-    """One optimiser step: K calls of `step`, each on a batch of its own.  Returns the mean of the micro-step losses as a
-    device tensor (summed on the device: no read here)."""
-    total = None
-    for _ in range(K):
-        loss = step(*next_batch())
-        if K > 1:
-            total = loss.clone() if total is None else total + loss
-    return loss if K == 1 else total / K
-
-
 def make_train_eval(FLAGS, g, step):
     """The between-steps evaluation of --eval_data_path / --eval_steps (None when off): PixelLinkNet on the training graph
     (it has no batch norm: the inference forward is the training forward without a loss) with the weights --eval_weights
@@ -249,16 +179,7 @@ def make_train_eval(FLAGS, g, step):
 
 
 def _evaluate(train_eval, summaries, opt):
-    """One pass between two steps (rank 0; the other ranks meet it at the next exchange): the line eval_pixellink_fast.py
-    prints, and eval/precision, eval/recall, eval/hmean (with --eval_sweep also eval/ap, eval/best_hmean,
-    eval/best_threshold) in the event file where one is open."""
-    from tensorflow_ocr_amd import evaluate
-    res = train_eval.run()
-    print('global step %d: ' % opt.global_step + evaluate.format_line(res), flush=True)
-    if 'sweep' in res:
-        print(evaluate.format_sweep(res), flush=True)
-    if summaries is not None:
-        train_eval.write(summaries.writer, opt.global_step)
+    cli.report_eval(train_eval, summaries, opt, 'global step {:d}: ')       # ... and the line eval_pixellink_fast.py prints
 
 
 def main():
@@ -330,10 +251,7 @@ def main():
                 from tensorflow_ocr_amd.summary import TrainingSummaries
                 summaries = TrainingSummaries(FLAGS.train_dir, step, variables=FLAGS.summary_variables)
             scalars = {'total_loss': loss.item(), 'learning_rate': step.opt.learning_rate()}
-            if g.loss_scaler is not None:
-                scalars['loss_scale'] = g.loss_scaler.scale()
-            if step.opt.clip is not None:
-                scalars['grad_norm'] = step.opt.grad_norm()
+            scalars.update(cli.grad_factor_scalars(step.opt))
             summaries.write(step.opt.global_step, scalars, [('input', last[0][0][0])])
         if train_eval is not None and train_eval.due(it + 1):
             _evaluate(train_eval, summaries, step.opt)
@@ -344,10 +262,7 @@ def main():
             if rank == 0:
                 print('global step %d: loss = %.4f (%.3f sec/step), lr %.6f' % (
                     it, v, dt, staircase_lr(it, FLAGS.learning_rate, bps, dcs)), flush=True)
-                if g.loss_scaler is not None:       # (the loss was just read: one more device read costs nothing here)
-                    print('loss scale %g, %d steps skipped' % (g.loss_scaler.scale(), g.loss_scaler.skipped_steps()), flush=True)
-                if step.opt.clip is not None:
-                    print('grad norm {:.4g}, {:d} steps clipped'.format(step.opt.grad_norm(), step.opt.clipped_steps()), flush=True)
+                cli.log_grad_factor(step.opt)
             if dist.any_rank(bool(np.isnan(v))):     # collective: no rank leaves the all-reduce alone
                 break
         if FLAGS.train_dir and rank == 0 and it > 0 and it % 1000 == 0:
