@@ -13,6 +13,9 @@ raster-IoU matching (tool/bboxes.py:171-240; not the official ICDAR-2015 protoco
     python eval_pixellink_fast.py ... --map_scales 0.5,1,2 --flip      (multi-scale and flip testing: the passes' score maps
                                                                         are fused on the device and decoded once; build-defined,
                                                                         its effect on the F-measure is unmeasured)
+    python eval_pixellink_fast.py ... --eval_grid_pixel 0.5:0.9:5 --eval_grid_link 0.5:0.9:5
+                                                                       (search the two decode thresholds: every pair is decoded
+                                                                        and matched behind the one forward, one line per pair)
 
 Flag names and defaults are test_pixellink_fast.py's where the two scripts share them; that script itself is unchanged and
 writes the same `res_<name>.txt` files as before.  Unlike it, images of any size are taken: each is resized on the device
@@ -58,7 +61,9 @@ def parse(argv=None):
                     help=cli.sweep_help("the component's mean pixel score, in [0, 1]"))
     ap.add_argument('--map_scales', type=cli.map_scales_arg, default=None, metavar='S1,S2,...', help=MAP_SCALES_HELP)
     ap.add_argument('--flip', action='store_true', help=FLIP_HELP)
+    cli.add_grid_flags(ap)
     FLAGS = ap.parse_args(argv)
+    cli.check_grid_flags(ap, FLAGS)
     if FLAGS.min_side < 0 or FLAGS.min_area < 0:
         ap.error('--min_side and --min_area must not be negative')
     if FLAGS.batch_size < 1:
@@ -103,12 +108,14 @@ def main(argv=None):
                                 link_conf_threshold=FLAGS.link_conf_threshold, min_side=FLAGS.min_side,
                                 min_area=FLAGS.min_area, eval_image_height=H, eval_image_width=W,
                                 protocol=FLAGS.eval_protocol, sweep=FLAGS.eval_sweep, map_scales=FLAGS.map_scales,
-                                flip=FLAGS.flip)
+                                flip=FLAGS.flip, grid=cli.grid_option(FLAGS))
     try:
         res = ev.run()
         print(evaluate.format_line(res), flush=True)
         if FLAGS.eval_sweep is not None:
             print(evaluate.format_sweep(res), flush=True)
+        if 'grid' in res:
+            print(evaluate.format_grid(res), flush=True)
     finally:
         if tmp is not None:
             tmp.cleanup()

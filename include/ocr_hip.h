@@ -1132,6 +1132,10 @@ int ocr_eval_record_init(void* record_i64, void* stream);
  * fusion grid and adds them to an accumulator ocr_link_cc reads as it is: its entry and comment block are in a header of
  * their own, part of this ABI. */
 #include "ocr_map_fuse.h"
+/* The link decode over a grid of (pixel threshold, link threshold) pairs: ocr_link_cc and ocr_component_scores with the
+ * grid point in the launch, reading one set of maps: its entries and their comment block are in a header of their own,
+ * part of this ABI. */
+#include "ocr_decode_grid.h"
 
 /* ------------------------------------------------------------------------- *
  * Link-geometry detections on the device (csrc/link_boxes.hip): what lies between ocr_min_area_rects and

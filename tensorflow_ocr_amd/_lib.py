@@ -223,6 +223,7 @@ def csrc_fingerprint():
     files.append(os.path.join(os.path.dirname(_HERE), "include", "ocr_eval_curve.h"))     # included by ocr_hip.h
     files.append(os.path.join(os.path.dirname(_HERE), "include", "ocr_multiscale.h"))     # included by ocr_hip.h
     files.append(os.path.join(os.path.dirname(_HERE), "include", "ocr_map_fuse.h"))       # included by ocr_hip.h
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "ocr_decode_grid.h"))    # included by ocr_hip.h
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:

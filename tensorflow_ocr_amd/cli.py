@@ -48,6 +48,35 @@ def map_scales_arg(text):
     return arg(text)
 
 
+def grid_axis_arg(text):
+    """one axis of the decode-threshold grid: the sweep's syntax, LO:HI:N or a comma list"""
+    return sweep_arg(text)
+
+
+def add_grid_flags(ap):
+    """--eval_grid_pixel / --eval_grid_link: the decode-threshold grid of the link geometry (evaluate.LinkEvaluator's grid)"""
+    from .evaluate import GRID_HELP
+    # (no attribute without the flag: a run that does not ask for a grid parses to the namespace it always parsed to;
+    # read them with `grid_option`)
+    ap.add_argument('--eval_grid_pixel', type=grid_axis_arg, default=argparse.SUPPRESS, metavar='LO:HI:N',
+                    help=GRID_HELP % 'eval_')
+    ap.add_argument('--eval_grid_link', type=grid_axis_arg, default=argparse.SUPPRESS, metavar='LO:HI:N',
+                    help='the link thresholds of --eval_grid_pixel')
+
+
+def grid_option(FLAGS):
+    """the `grid=` option of evaluate.LinkEvaluator the flags ask for: (pixel thresholds, link thresholds), or None"""
+    pixel_list, link_list = getattr(FLAGS, 'eval_grid_pixel', None), getattr(FLAGS, 'eval_grid_link', None)
+    return None if pixel_list is None or link_list is None else (pixel_list, link_list)
+
+
+def check_grid_flags(ap, FLAGS):
+    """one grid flag without the other, a grid with --eval_sweep, more than 64 pairs: argparse errors -> `grid_option`"""
+    from .evaluate import check_grid_flags as check
+    return check(ap, getattr(FLAGS, 'eval_grid_pixel', None), getattr(FLAGS, 'eval_grid_link', None), FLAGS.eval_sweep,
+                 prefix='eval_')
+
+
 def add_step_flags(ap, batch_flag_name):
     """The training flags that are not the reference's (TF-1.4 trains in f32, unclipped, one batch per step)."""
     # the f16 loss scale, a number or "dynamic" (graph.DynamicLossScale: a step whose gradients overflow is skipped and the
@@ -115,12 +144,16 @@ def window(step, K, next_batch):
 def report_eval(train_eval, summaries, opt, prefix):
     """One pass between two steps (rank 0; the other ranks meet it at the next exchange): behind `prefix` (formatted with
     the optimiser step) the line the script's inference counterpart prints, and eval/precision, eval/recall, eval/hmean
-    (with --eval_sweep also eval/ap, eval/best_hmean, eval/best_threshold) in the event file where one is open."""
+    (with --eval_sweep also eval/ap, eval/best_hmean, eval/best_threshold; with the grid flags the grid's lines and
+    eval/grid_best_hmean, eval/grid_best_pixel_threshold, eval/grid_best_link_threshold) in the event file where one is
+    open."""
     from . import evaluate
     res = train_eval.run()
     print(prefix.format(opt.global_step) + evaluate.format_line(res), flush=True)
     if 'sweep' in res:
         print(evaluate.format_sweep(res), flush=True)
+    if 'grid' in res:
+        print(evaluate.format_grid(res), flush=True)
     if summaries is not None:
         train_eval.write(summaries.writer, opt.global_step)
 

@@ -17,6 +17,7 @@
 //                       component is its smallest pixel index, ids are dense in ascending root
 //                       order, so labels are bit-reproducible.
 #include "common.h"
+#include "cc_union.h"
 
 namespace {
 
@@ -43,34 +44,8 @@ __global__ void pixel_detect_kernel(const float* __restrict__ score, const float
   mask[i] = ok ? 1 : 0;
 }
 
-// ---- union-find on pixel indices (roots = smallest index of the set) -----------------------
-__device__ __forceinline__ int uf_load(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int uf_find(int* parent, int i) {
-  for (;;) {
-    const int p = uf_load(parent + i);
-    if (p == i) return i;
-    i = p;
-  }
-}
-__device__ __forceinline__ void uf_unite(int* parent, int a, int b) {
-  for (int guard = 0; guard < (1 << 22); ++guard) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }       // attach the larger root under the smaller
-    const int old = atomicMin(parent + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
-struct CcP {
-  int n, h, w, min_size;
-  float tp, tl;
-  int ls, lo;   // element stride / offset inside link_score (1,0: [8][n][h][w]; 2,1: [8][n][h][w][2])
-};
+// (the union-find on pixel indices — uf_find, uf_unite, lds_find, lds_unite — and CcP: cc_union.h, shared with
+// decode_grid.hip)
 
 // link_logits [m][16] -> out [8][m][2]: tf.stack([softmax(link_cls[..., 2i:2i+2]) for i in 0..7])
 __global__ void link_softmax_stack_kernel(const float* __restrict__ x, float* __restrict__ y, size_t m) {
@@ -215,24 +190,6 @@ __global__ void cc_init_mask_kernel(CcP p, const unsigned char* __restrict__ mas
 // (the smallest index of its tile-local set, written as a global index), and a second launch unites only
 // the edges that cross a tile border.  Roots are still the smallest pixel index of each component, so
 // labels do not change.  MODE 0: link-gated 8 directions on interior pixels; 1 / 2: 4- / 8-connected mask.
-__device__ __forceinline__ int lds_find(volatile int* lp, int i) {
-  for (;;) {
-    const int p = lp[i];
-    if (p == i) return i;
-    i = p;
-  }
-}
-__device__ __forceinline__ void lds_unite(int* lp, int a, int b) {
-  for (int guard = 0; guard < (1 << 20); ++guard) {
-    a = lds_find(lp, a);
-    b = lds_find(lp, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(lp + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
 
 template <int MODE, bool BORDER>
 __global__ __launch_bounds__(1024) void cc_union_tile_kernel(CcP p, const float* __restrict__ link,

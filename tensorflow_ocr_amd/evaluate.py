@@ -151,6 +151,93 @@ def format_sweep(result):
     return '\n'.join(lines)
 
 
+# -- the decode-threshold grid of the link geometry ----------------------------------------
+GRID_MAX_POINTS = 64                    # the most (pixel, link) pairs one grid takes; the evaluator's own pair is a 65th
+GRID_MAX_SLICES = 512                   # default grid_chunk: the most points x images decoded in one launch sequence
+GRID_HELP = ("search the decode thresholds in ONE pass: with the other --%sgrid_* flag, every (pixel, link) pair of the two "
+             "lists (LO:HI:N = N evenly spaced values, or a comma list; at most 64 pairs) is decoded and matched on the device "
+             "behind the same forward, and one line per pair is printed, the best hmean marked.  The line of the run itself "
+             "stays that of --pixel_conf_threshold / --link_conf_threshold")
+
+
+def check_grid(grid):
+    """grid = (pixel_list, link_list), two non-empty sequences of finite numbers whose product has 1..64 points -> the
+    points [(pixel, link)] in pixel-major order; ValueError otherwise."""
+    import math
+    try:
+        pixel_list, link_list = grid
+        pixel_list, link_list = [float(v) for v in pixel_list], [float(v) for v in link_list]
+    except (TypeError, ValueError):
+        raise ValueError('grid is (pixel thresholds, link thresholds), two sequences of numbers, got %r' % (grid,))
+    if not pixel_list or not link_list:
+        raise ValueError('a grid needs at least one pixel threshold and one link threshold')
+    for v in pixel_list + link_list:
+        if not math.isfinite(v):
+            raise ValueError('a grid threshold must be finite, got %r' % (v,))
+    if len(pixel_list) * len(link_list) > GRID_MAX_POINTS:
+        raise ValueError('a grid takes at most %d points, got %d x %d' % (GRID_MAX_POINTS, len(pixel_list), len(link_list)))
+    return [(p, l) for p in pixel_list for l in link_list]
+
+
+def check_grid_flags(ap, pixel_list, link_list, sweep, prefix=''):
+    """the cross-checks of --<prefix>grid_pixel / --<prefix>grid_link as argparse errors -> the `grid=` option or None"""
+    names = ('--%sgrid_pixel' % prefix, '--%sgrid_link' % prefix)
+    if (pixel_list is None) != (link_list is None):
+        ap.error('%s and %s come together' % names)
+    if pixel_list is None:
+        return None
+    if sweep is not None:
+        ap.error('%s / %s and the score sweep are separate passes: give one of them' % names)
+    try:
+        check_grid((pixel_list, link_list))
+    except ValueError as e:
+        ap.error(str(e))
+    return (pixel_list, link_list)
+
+
+def grid_rows(points, records, overflow):
+    """records [G] of (num_gt, tp, fp, n_det) and overflow [G] (> 0: that point lost candidates) -> the rows of a result,
+    one per point in the order given.  A point that overflowed reports 'overflow' and None for its metrics."""
+    from .tool import metrics
+    out = []
+    for (pixel, link), (num_gt, tp, fp, n_det), over in zip(points, records, overflow):
+        row = {'pixel_conf_threshold': pixel, 'link_conf_threshold': link}
+        if over > 0:
+            row.update(dict.fromkeys(('precision', 'recall', 'hmean', 'tp', 'fp', 'num_det', 'num_gt')), overflow=int(over))
+        else:
+            precision, recall = metrics.precision_recall(num_gt, tp, fp)
+            hmean = metrics.fmean(precision, recall) if precision + recall > 0 else 0.0
+            row.update(precision=precision, recall=recall, hmean=hmean, tp=tp, fp=fp, num_det=n_det, num_gt=num_gt)
+        out.append(row)
+    return out
+
+
+def grid_best(rows):
+    """the row of highest hmean, ties to the lowest index; a row that overflowed cannot be it (None if all did)"""
+    best = None
+    for row in rows:
+        if 'overflow' not in row and (best is None or row['hmean'] > best['hmean']):
+            best = row
+    return best
+
+
+def format_grid(result):
+    """the lines of a result's grid: one per point (row 0 is the run's own pair), the best one marked"""
+    lines = []
+    for row in result['grid']:
+        head = '  pixel > %-8.6g link > %-8.6g ' % (row['pixel_conf_threshold'], row['link_conf_threshold'])
+        if 'overflow' in row:
+            lines.append(head + 'overflow: %d candidates more than the limits hold' % row['overflow'])
+        else:
+            lines.append(head + 'precision %.4f recall %.4f hmean %.4f (tp %d fp %d det %d)%s' % (
+                row['precision'], row['recall'], row['hmean'], row['tp'], row['fp'], row['num_det'],
+                ' *' if row is result['grid_best'] else ''))
+    best = result['grid_best']
+    lines.append('  best hmean %.4f at pixel > %.6g, link > %.6g' % (
+        best['hmean'], best['pixel_conf_threshold'], best['link_conf_threshold']))
+    return '\n'.join(lines)
+
+
 # -- resizing on the device: the evaluator's detectors and test.py ---------------------------------------------
 def to_device(im, device):
     """an image uint8 [h,w,3] on the device"""
@@ -304,13 +391,33 @@ class LinkSingleScale:
         inv_ratio = ratio_rows(merged.shape[0], device=self.g.device)
         return merged, keep, n_keep, passed, inv_ratio, (total - merged.shape[1])[:, None]
 
-    def detect(self, batch, srcs):
+    def maps(self, srcs):
+        """(pixel_score [n,h,w], link_score) of a batch: what the decode reads, at any thresholds"""
         from .tool import pixellink_fn
-        box_scales = self.scales(*batch[0][0].shape[:2])
         pixel_cls, link_cls = self.forward(resize_batch(srcs, *self.eval_hw))
         pixel_score = pixellink_fn.pixel_scores(pixel_cls, graph=self.g)[..., 1].contiguous()
         link_score = pixellink_fn.link_scores(link_cls, graph=self.g)
-        return self._decode(pixellink_fn.detect_device, (pixel_score, link_score), box_scales)
+        return pixel_score, link_score
+
+    def detect(self, batch, srcs):
+        from .tool import pixellink_fn
+        box_scales = self.scales(*batch[0][0].shape[:2])
+        return self._decode(pixellink_fn.detect_device, self.maps(srcs), box_scales)
+
+    def detect_grid(self, batch, srcs, points, chunk):
+        """`detect` at every (pixel, link) pair of `points` behind ONE `maps`: yields per chunk of at most `chunk` points
+        (merged, keep, n_keep, passed, inv_ratio, overflow) with leading dimension len(chunk) * n, point-major —
+        pixellink_fn.detect_device_grid's slices.  A generator: a chunk's tensors can go before the next is decoded."""
+        from .tool import pixellink_fn
+        box_scales = self.scales(*batch[0][0].shape[:2])
+        pixel_score, link_score = self.maps(srcs)
+        for lo in range(0, len(points), chunk):
+            part = points[lo:lo + chunk]
+            merged, keep, n_keep, passed, total = pixellink_fn.detect_device_grid(
+                pixel_score, link_score, [p for p, _ in part], [l for _, l in part], self.min_size, *box_scales,
+                max_comps=self.max_comps, min_side=self.min_side, min_area=self.min_area, graph=self.g)
+            inv_ratio = ratio_rows(merged.shape[0], device=self.g.device)
+            yield merged, keep, n_keep, passed, inv_ratio, (total - merged.shape[1])[:, None]
 
 
 class LinkFused(LinkSingleScale):
@@ -340,12 +447,19 @@ class LinkFused(LinkSingleScale):
                 pixel_cls, link_cls = self.forward(torch.flip(x, dims=[2]))
                 yield pixel_cls, link_cls, True
 
+    def _fusion(self, srcs):
+        """fuse_score_maps' leading arguments: the passes, their weights, the fusion grid"""
+        weights = np.repeat(np.asarray(self.scale_weights, np.float64), 2 if self.flip else 1)
+        return self._passes(srcs), weights, (self.eval_hw[0] // 4, self.eval_hw[1] // 4)
+
+    def maps(self, srcs):
+        """the fused maps: views of fuse_score_maps' accumulator, which the decode reads as they are"""
+        from .tool import pixellink_fn
+        return pixellink_fn.fuse_score_maps(*self._fusion(srcs), graph=self.g)
+
     def detect(self, batch, srcs):
         from .tool import pixellink_fn
-        weights = np.repeat(np.asarray(self.scale_weights, np.float64), 2 if self.flip else 1)
-        grid = (self.eval_hw[0] // 4, self.eval_hw[1] // 4)
-        return self._decode(pixellink_fn.detect_device_multiscale, (self._passes(srcs), weights, grid),
-                            self.scales(*batch[0][0].shape[:2]))
+        return self._decode(pixellink_fn.detect_device_multiscale, self._fusion(srcs), self.scales(*batch[0][0].shape[:2]))
 
 
 # -- the pass driver -------------------------------------------------------------------------------------------
@@ -372,26 +486,35 @@ class Evaluator:
     'num_det'}), 'best' (its row of highest hmean, ties to the lowest index) and 'ap' (average precision over the pooled
     detection scores of the pass); still one device read.  The threshold is on the MATCHER'S ORDER KEY, ocr_eval_collect's
     det_score, which each detector's docstring names.  Sweeping box_thresh, score_map_thresh or the link threshold would
-    change the detection set or its order and is not what this does.
+    change the detection set or its order and is not what this does; for the link geometry's two decode thresholds that
+    search is `LinkEvaluator(grid=...)`, which this geometry refuses.
 
     A detector's options read as attributes of the evaluator (`ev.max_k`, `ev.eval_hw`, `ev.scales(h, w)`)."""
 
     def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, score_map_thresh=0.8,
                  nms_thres=0.2, box_thresh=None, max_k=None, max_d=ops.EVAL_MAX_D, max_side_len=3000, gt_path=None,
-                 protocol='raster', sweep=None, scales=None, fuse='nms', max_pool=1024):
+                 protocol='raster', sweep=None, scales=None, fuse='nms', max_pool=1024, grid=None):
         _check_protocol(protocol)                     # (its error comes before the scale options', as it always did)
+        if grid is not None:
+            raise ValueError('the decode-threshold grid (grid=...) is built for the link geometry only: LinkEvaluator')
         scales = RboxMultiScale.check(scales, fuse, max_pool)
         self._init_pass(graph, data, batch_size, max_images, matching_threshold, max_d, gt_path, protocol, sweep)
         options = (self.g, forward, score_map_thresh, nms_thres, box_thresh, max_k, max_side_len)
         self.detector = RboxSingleScale(*options) if scales is None else \
             RboxMultiScale(*options, scales=scales, fuse=fuse, max_pool=max_pool)
 
-    def _init_pass(self, graph, data, batch_size, max_images, matching_threshold, max_d, gt_path, protocol, sweep):
-        """the driver's own state: the samples, the matcher's options, the record and the curve"""
+    def _init_pass(self, graph, data, batch_size, max_images, matching_threshold, max_d, gt_path, protocol, sweep,
+                   grid_points=None, grid_chunk=None):
+        """the driver's own state: the samples, the matcher's options, the record and the curve — or, with grid_points
+        (the base pair, then check_grid's points), one record per point"""
         from .tool import metrics
         _check_protocol(protocol)
         self.protocol, self.area_prec_thr, self.invalid_gt = protocol, 0.5, 0
         self.sweep = None if sweep is None else check_sweep(sweep)
+        self.grid_points = grid_points
+        if grid_chunk is not None and int(grid_chunk) < 1:
+            raise ValueError('grid_chunk must be positive')
+        self.grid_chunk = None if grid_chunk is None else int(grid_chunk)
         self.g = graph or get_default_graph()
         if not os.path.isdir(data):
             raise FileNotFoundError('no evaluation directory %r' % (data,))
@@ -415,7 +538,7 @@ class Evaluator:
             raise ValueError('max_d must be in [1, %d]' % ops.EVAL_MAX_D)
         self.batch_size = max(1, int(batch_size))
         self.matching_threshold, self.max_d = float(matching_threshold), int(max_d)
-        self.acc = metrics.DeviceTpFp(self.g)
+        self.acc = metrics.DeviceTpFp(self.g) if grid_points is None else metrics.DeviceGrid(len(grid_points), self.g)
         self.curve = None if self.sweep is None else metrics.DeviceCurve(self.sweep, len(self.samples), self.max_d, self.g)
         self.last = None          # the device tensors of the last chain (tests and the cost script look at them)
 
@@ -453,13 +576,32 @@ class Evaluator:
         """one batch -> its overflow counts int32 [n,m+1]: the detector's columns, then nd_total - max_d"""
         srcs = self._sources(batch)
         ground_truths = self._ground_truths(batch)
+        if self.grid_points is not None:
+            return self._grid_chain(batch, srcs, ground_truths)
         *rows, overflow = self.detector.detect(batch, srcs)
         return torch.cat([overflow, self._match(*rows, *ground_truths)[:, None]], dim=1)
 
-    def _match(self, merged, keep, n_keep, passed, inv_ratio, gts, ng, gign, mask_hw):
-        """detection rows -> ordered detection list -> matching, the counters added to the record (-> the curve).  Returns
-        nd_total - max_d (> 0: detections were lost), a device tensor like everything here."""
-        from .tool import bboxes
+    def _grid_chain(self, batch, srcs, ground_truths):
+        """one batch at every grid point -> the points' overflow maxima over the batch, int32 [G,m+1] (columns as
+        `_chain`'s).  Per chunk of points one decode and one collect on points x images slices; then the matcher runs
+        once per point on that point's n contiguous slices, with the batch's own ground truths, into that point's record:
+        every row is the plain pass's arithmetic."""
+        n = len(batch)
+        chunk = self.grid_chunk or max(1, GRID_MAX_SLICES // n)
+        worst, lo = [], 0
+        for *rows, overflow in self.detector.detect_grid(batch, srcs, self.grid_points, chunk):
+            dets, det_score, nd, nd_total = self._collect(*rows)
+            over = torch.cat([overflow, (nd_total - self.max_d)[:, None]], dim=1)
+            points = over.shape[0] // n
+            for k in range(points):
+                s = slice(k * n, (k + 1) * n)
+                self._count(dets[s], det_score[s], nd[s], nd_total[s], *ground_truths, self.acc.records[lo + k])
+            worst.append(over.view(points, n, -1).max(dim=1).values)
+            lo += points
+        return torch.cat(worst)
+
+    def _collect(self, merged, keep, n_keep, passed, inv_ratio):
+        """detection rows -> the ordered detection lists (dets, det_score, nd, nd_total) of ocr_eval_collect"""
         g = self.g
         n = merged.shape[0]
         dets = torch.empty((n, self.max_d, 4, 2), dtype=torch.int32, device=g.device)
@@ -468,26 +610,37 @@ class Evaluator:
         nd_total = torch.empty_like(nd)
         ops.eval_collect(merged, keep, n_keep, None if passed is None else passed.to(torch.uint8), inv_ratio, dets,
                          det_score, nd, nd_total)
+        return dets, det_score, nd, nd_total
+
+    def _count(self, dets, det_score, nd, nd_total, gts, ng, gign, mask_hw, record):
+        """ordered detection lists -> matching, the counters added to `record` (-> the curve)"""
+        from .tool import bboxes
+        g = self.g
         if self.protocol == 'icdar15':
             det_match, gt_match, _ = bboxes.ic15_matching_batch(dets, nd, gts, ng, gign, self.matching_threshold,
-                                                                self.area_prec_thr, record=self.acc.record, graph=g)
+                                                                self.area_prec_thr, record=record, graph=g)
             self.last = dict(dets=dets, det_score=det_score, nd=nd, nd_total=nd_total, det_match=det_match,
                              gt_match=gt_match, gts=gts, ng=ng, gdontcare=gign)
             if self.curve is not None:
                 self.curve.add_ic15(det_match, gt_match, det_score, nd, ng)
-            return nd_total - self.max_d
-        tp, fp, _ = bboxes.bboxes_matching_batch(dets, nd, gts, ng, gign, self.matching_threshold, record=self.acc.record,
+            return
+        tp, fp, _ = bboxes.bboxes_matching_batch(dets, nd, gts, ng, gign, self.matching_threshold, record=record,
                                                  graph=g, mask_hw=mask_hw)
         self.last = dict(dets=dets, det_score=det_score, nd=nd, nd_total=nd_total, tp=tp, fp=fp, gts=gts, ng=ng)
         if self.curve is not None:
             self.last['gignored'] = gign
             self.curve.add_raster(tp, fp, det_score, nd, ng, gign if gign.dtype == torch.uint8 else gign.to(torch.uint8))
+
+    def _match(self, merged, keep, n_keep, passed, inv_ratio, gts, ng, gign, mask_hw):
+        """detection rows -> ordered detection list -> matching, the counters added to the record (-> the curve).  Returns
+        nd_total - max_d (> 0: detections were lost), a device tensor like everything here."""
+        dets, det_score, nd, nd_total = self._collect(merged, keep, n_keep, passed, inv_ratio)
+        self._count(dets, det_score, nd, nd_total, gts, ng, gign, mask_hw, self.acc.record)
         return nd_total - self.max_d
 
     # -- one pass --------------------------------------------------------------------------------
     def run(self):
         from .datasets import icdar
-        from .tool import metrics
         self.acc.reset()
         if self.curve is not None:
             self.curve.reset()
@@ -501,6 +654,10 @@ class Evaluator:
                 overflow.append(self._chain(buckets.pop(key)))
         for key in sorted(buckets):
             overflow.append(self._chain(buckets[key]))
+        messages = self.detector.overflow_messages + (
+            lambda over: 'an image kept %d detections more than max_d = %d' % (over, self.max_d),)
+        if self.grid_points is not None:
+            return self._grid_result(torch.stack(overflow).max(dim=0).values, messages)
         # the single read of the pass: the record and the overflow columns' maxima in one device-to-host copy
         worst = torch.cat(overflow).max(dim=0).values
         if self.curve is None:
@@ -508,17 +665,10 @@ class Evaluator:
         else:       # ... and the curve, the order flag and AP in the same copy
             self.curve.finish(self.acc.record)
             (num_gt, tp, fp, n_det), worst, rows, unsorted, ap = self.curve.value_with(self.acc, worst)
-        messages = self.detector.overflow_messages + (
-            lambda over: 'an image kept %d detections more than max_d = %d' % (over, self.max_d),)
         for over, message in zip(worst, messages):
             if over > 0:
                 raise ValueError(message(over))
-        precision, recall = metrics.precision_recall(num_gt, tp, fp)
-        hmean = metrics.fmean(precision, recall) if precision + recall > 0 else 0.0
-        result = {'precision': precision, 'recall': recall, 'hmean': hmean, 'num_gt': num_gt, 'tp': tp, 'fp': fp,
-                  'num_det': n_det, 'images': len(self.samples)}
-        if self.protocol == 'icdar15':
-            result.update(invalid_gt=self.invalid_gt, protocol=self.protocol)
+        result = self._result(num_gt, tp, fp, n_det)
         if self.curve is not None:
             if unsorted:
                 raise ValueError('the detection scores of an image are not in descending order (NaNs last): the sweep '
@@ -527,19 +677,66 @@ class Evaluator:
             result.update(sweep=sweep, best=best, ap=ap)
         return result
 
+    def _result(self, num_gt, tp, fp, n_det):
+        """a record -> the result's own fields"""
+        from .tool import metrics
+        precision, recall = metrics.precision_recall(num_gt, tp, fp)
+        hmean = metrics.fmean(precision, recall) if precision + recall > 0 else 0.0
+        result = {'precision': precision, 'recall': recall, 'hmean': hmean, 'num_gt': num_gt, 'tp': tp, 'fp': fp,
+                  'num_det': n_det, 'images': len(self.samples)}
+        if self.protocol == 'icdar15':
+            result.update(invalid_gt=self.invalid_gt, protocol=self.protocol)
+        return result
+
+    def _grid_result(self, worst, messages):
+        """the single read of a grid pass — every point's record and its overflow maxima (worst int32 [G,m+1]) in one
+        device-to-host copy — and the result: row 0's fields, 'grid' and 'grid_best'.  An overflow at row 0 raises what a
+        plain pass raises; at another row it is that row's 'overflow' (the first positive column, in the order the limits
+        are reported), and the pass goes on."""
+        m = worst.shape[1]
+        records, flat = self.acc.value_with(worst)
+        columns = [flat[k * m:(k + 1) * m] for k in range(len(records))]
+        for over, message in zip(columns[0], messages):
+            if over > 0:
+                raise ValueError(message(over))
+        result = self._result(*records[0])
+        rows = grid_rows(self.grid_points, records, [next((v for v in c if v > 0), 0) for c in columns])
+        result.update(grid=rows, grid_best=grid_best(rows))
+        return result
+
 
 class LinkEvaluator(Evaluator):
     """The pass driver with the link geometry's detectors: `LinkSingleScale`, or with map_scales / flip `LinkFused` (flip
     without map_scales is scale 1 plus its mirror; scale_weights default to equal).  The options are
     test_pixellink_fast.py's flags and the detectors' docstrings describe them; `scales=` (box-level fusion) is refused
-    for this geometry.  `protocol`, `sweep`, max_d and the single device read per pass are `Evaluator`'s."""
+    for this geometry.  `protocol`, `sweep`, max_d and the single device read per pass are `Evaluator`'s.
+
+    grid=(pixel_list, link_list): the DECODE-THRESHOLD grid (include/ocr_decode_grid.h) — two sequences
+    of finite numbers whose product has 1 to 64 points.  The pass then runs every forward once and decodes, collects and
+    matches every (pixel, link) pair on the device behind the same score maps (fused ones with map_scales / flip), one record
+    per point, still one device read.  Row 0 is always the constructor's own (pixel_conf_threshold, link_conf_threshold)
+    pair: the result's own fields are row 0's, equal to a run without `grid`, and it gains 'grid' — a list of
+    {'pixel_conf_threshold', 'link_conf_threshold', 'precision', 'recall', 'hmean', 'tp', 'fp', 'num_det', 'num_gt'}, row 0
+    then the pairs in pixel-major order — and 'grid_best', the row of highest hmean (ties to the lowest index).  Overflow is
+    per point: at row 0 it raises what it raises without a grid; at another row that row reports 'overflow': k and None for
+    its metrics, cannot be the best, and the pass goes on.  grid_chunk: the most grid points decoded in one launch sequence
+    (default: points x batch images <= 512; memory grows with it, the result does not depend on it).  `grid` with `sweep`
+    is refused: the sweep thresholds the matcher's order key of ONE detection set, the grid changes the set."""
 
     def __init__(self, graph, forward, data, batch_size=8, max_images=None, matching_threshold=0.5, pixel_conf_threshold=0.8,
                  link_conf_threshold=0.9, min_size=10, max_comps=4096, min_side=0.0, min_area=0.0, max_d=ops.EVAL_MAX_D,
                  eval_image_height=768, eval_image_width=1280, gt_path=None, protocol='raster', sweep=None, scales=None,
-                 map_scales=None, flip=False, scale_weights=None):
+                 map_scales=None, flip=False, scale_weights=None, grid=None, grid_chunk=None):
         if scales is not None:
             raise ValueError('multi-scale evaluation (scales=...) is built for the RBOX geometry only')
+        grid_points = None
+        if grid is not None:
+            if sweep is not None:
+                raise ValueError('grid and sweep are separate passes: the sweep thresholds the scores of one detection set, '
+                                 'the grid changes the set')
+            grid_points = [(float(pixel_conf_threshold), float(link_conf_threshold))] + check_grid(grid)
+        elif grid_chunk is not None:
+            raise ValueError('grid_chunk comes with grid')
         from .tool import pixellink_fn
         flip = bool(flip)
         if map_scales is None and scale_weights is not None:
@@ -548,7 +745,8 @@ class LinkEvaluator(Evaluator):
             map_scales = [1.0]                       # flip alone: scale 1 and its mirror
         if map_scales is not None:
             map_scales, scale_weights = pixellink_fn.check_map_scales(map_scales, scale_weights)
-        self._init_pass(graph, data, batch_size, max_images, matching_threshold, max_d, gt_path, protocol, sweep)
+        self._init_pass(graph, data, batch_size, max_images, matching_threshold, max_d, gt_path, protocol, sweep,
+                        grid_points, grid_chunk)
         options = (self.g, forward, (eval_image_height, eval_image_width), pixel_conf_threshold, link_conf_threshold,
                    min_size, max_comps, min_side, min_area)
         self.detector = LinkSingleScale(*options) if map_scales is None else \
@@ -589,7 +787,8 @@ class TrainEval:
     step was built).  `last` holds the latest result.  sweep: None, or the score thresholds of the evaluator's `sweep`
     (the pass still reads the device once; `write` then adds eval/ap, eval/best_hmean, eval/best_threshold).
     scales / fuse / max_pool: the evaluator's multi-scale options (None = single scale; the RBOX `Evaluator` only).
-    `LinkEvaluator`'s map_scales / flip / scale_weights travel in **evaluator_kw."""
+    `LinkEvaluator`'s map_scales / flip / scale_weights and its grid / grid_chunk (the decode-threshold grid: `write` then
+    adds eval/grid_best_hmean, eval/grid_best_pixel_threshold, eval/grid_best_link_threshold) travel in **evaluator_kw."""
 
     def __init__(self, graph, step, network, data, every, max_images=None, weights='ema', batch_size=8, evaluator=Evaluator,
                  sweep=None, scales=None, fuse='nms', max_pool=1024, **evaluator_kw):
@@ -634,11 +833,17 @@ class TrainEval:
 
     def write(self, writer, global_step):
         """eval/precision, eval/recall, eval/hmean of the latest pass as one event of a summary.FileWriter; with a sweep
-        also eval/ap, eval/best_hmean, eval/best_threshold."""
+        also eval/ap, eval/best_hmean, eval/best_threshold; with a grid also eval/grid_best_hmean,
+        eval/grid_best_pixel_threshold, eval/grid_best_link_threshold."""
         for k in ('precision', 'recall', 'hmean'):
             writer.add_scalar('eval/' + k, self.last[k])
         if 'sweep' in self.last:
             writer.add_scalar('eval/ap', self.last['ap'])
             writer.add_scalar('eval/best_hmean', self.last['best']['hmean'])
             writer.add_scalar('eval/best_threshold', self.last['best']['threshold'])
+        if 'grid' in self.last:
+            best = self.last['grid_best']
+            writer.add_scalar('eval/grid_best_hmean', best['hmean'])
+            writer.add_scalar('eval/grid_best_pixel_threshold', best['pixel_conf_threshold'])
+            writer.add_scalar('eval/grid_best_link_threshold', best['link_conf_threshold'])
         writer.flush_step(global_step)

@@ -1538,6 +1538,73 @@ def link_boxes(hull_n, hull_head, calipers, comp_score, ncomp, min_side, min_are
            ptr(total), _st())
 
 
+# ------------------------------------------------------------------ the link decode over a threshold grid (csrc/decode_grid.hip)
+GRID_MAX_POINTS = 65          # 64 grid points and the base pair (include/ocr_decode_grid.h)
+
+
+def _grid_table(values, name):
+    import ctypes
+    vals = [float(v) for v in values]
+    if not 1 <= len(vals) <= GRID_MAX_POINTS:
+        raise ValueError("%s: 1 to %d grid points, got %d" % (name, GRID_MAX_POINTS, len(vals)))
+    return (ctypes.c_float * len(vals))(*vals)
+
+
+def link_cc_grid(pixel_score, link_score, stride, offset, pixel_thresholds, link_thresholds, min_size, labels, ncomp, comps,
+                 ws):
+    """ocr_link_cc for G (pixel, link) threshold pairs in one launch sequence (include/ocr_decode_grid.h:
+    ocr_link_cc_grid): pixel_score f32 [n,h,w], link_score as `link_cc` takes it, the thresholds two sequences of G
+    numbers (host values: they travel in the kernel arguments) -> labels int32 [G*n,h,w], ncomp int32 [G*n], comps int32
+    [G*n,max_comps,2]; slice g*n + i is image i at point g."""
+    n, h, w = pixel_score.shape
+    tp, tl = _grid_table(pixel_thresholds, "link_cc_grid"), _grid_table(link_thresholds, "link_cc_grid")
+    G = len(tp)
+    if len(tl) != G:
+        raise ValueError("link_cc_grid: %d pixel thresholds for %d link thresholds" % (G, len(tl)))
+    if labels.dim() != 3 or comps.dim() != 3:
+        raise ValueError("link_cc_grid: labels [G*n,h,w], comps [G*n,max_comps,2]")
+    max_comps = comps.shape[1]
+    if tuple(labels.shape) != (G * n, h, w) or ncomp.numel() != G * n or tuple(comps.shape) != (G * n, max_comps, 2):
+        raise ValueError("link_cc_grid: tensors do not match G, n, h, w, max_comps")
+    if pixel_score.dtype != torch.float32 or link_score.dtype != torch.float32 or labels.dtype != torch.int32 or \
+            ncomp.dtype != torch.int32 or comps.dtype != torch.int32:
+        raise ValueError("link_cc_grid: pixel_score / link_score f32, labels / ncomp / comps int32")
+    if link_score.numel() != 8 * n * h * w * stride:
+        raise ValueError("link_cc_grid: link_score does not hold [8,n,h,w] elements of stride %d" % stride)
+    for t in (pixel_score, link_score, labels, ncomp, comps):
+        if not t.is_contiguous():
+            raise ValueError("link_cc_grid: contiguous tensors only")
+    nbytes = L.call_size("ocr_link_cc_grid_workspace", c_int(G), c_int(n), c_int(h), c_int(w))
+    buf = ws.get(nbytes)
+    L.call("ocr_link_cc_grid", ptr(pixel_score), ptr(link_score), c_int(stride), c_int(offset), c_int(n), c_int(h), c_int(w),
+           c_int(G), tp, tl, c_int(min_size), ptr(labels), ptr(ncomp), ptr(comps), c_int(max_comps), ptr(buf),
+           c_size_t(nbytes), _st())
+
+
+def component_scores_grid(labels, pixel_score, ncomp, comp_score, ws):
+    """`component_scores` for labels int32 [G*n,h,w] against pixel_score f32 [n,h,w], slice b reading map b mod n ->
+    comp_score f32 [G*n,max_comps] (include/ocr_decode_grid.h: ocr_component_scores_grid)."""
+    if labels.dim() != 3 or pixel_score.dim() != 3 or comp_score.dim() != 2:
+        raise ValueError("component_scores_grid: labels [G*n,h,w], pixel_score [n,h,w], comp_score [G*n,max_comps]")
+    N, h, w = labels.shape
+    n = pixel_score.shape[0]
+    max_comps = comp_score.shape[1]
+    if n < 1 or N % n or tuple(pixel_score.shape) != (n, h, w) or ncomp.numel() != N or \
+            tuple(comp_score.shape) != (N, max_comps):
+        raise ValueError("component_scores_grid: tensors do not match G*n, n, h, w, max_comps")
+    if labels.dtype != torch.int32 or pixel_score.dtype != torch.float32 or ncomp.dtype != torch.int32 or \
+            comp_score.dtype != torch.float32:
+        raise ValueError("component_scores_grid: labels / ncomp int32, pixel_score / comp_score f32")
+    for t in (labels, pixel_score, ncomp, comp_score):
+        if not t.is_contiguous():
+            raise ValueError("component_scores_grid: contiguous tensors only")
+    G = N // n
+    nbytes = L.call_size("ocr_component_scores_grid_workspace", c_int(G), c_int(n), c_int(max_comps))
+    buf = ws.get(nbytes)
+    L.call("ocr_component_scores_grid", ptr(labels), ptr(pixel_score), ptr(ncomp), c_int(G), c_int(n), c_int(h), c_int(w),
+           c_int(max_comps), ptr(comp_score), ptr(buf), c_size_t(nbytes), _st())
+
+
 # -------------------------------------------------------------------------- optimiser
 def adam_step(w, g, m, v, ema, n_reg, lr_t, beta1, beta2, eps, wd, inv_scale, ema_decay):
     L.call("ocr_adam_step", ptr(w), ptr(g), ptr(m), ptr(v), ptr(ema), c_int64(w.numel()),

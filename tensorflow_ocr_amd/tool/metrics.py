@@ -63,6 +63,38 @@ class DeviceTpFp:
         return tuple(host[:4]), host[4:]
 
 
+class DeviceGrid:
+    """`DeviceTpFp` for a decode-threshold grid (evaluate.LinkEvaluator(grid=...)): owns the int64 [G,4] records, one
+    `DeviceTpFp.record` per grid point — the matcher of point g adds to `records[g]`; `record` is row 0, the evaluator's own
+    pair.  `value_with(extra)` is the single host read of a pass: ([(num_gbboxes, tp, fp, n_det)] * G, [extra values]) in
+    ONE device-to-host copy, as `DeviceTpFp.value_with` makes it.  `reads` counts its calls."""
+
+    def __init__(self, points, graph=None):
+        import torch
+        from .. import ops
+        from ..graph import get_default_graph
+        self.g = graph or get_default_graph()
+        self.G = int(points)
+        if self.G < 1:
+            raise ValueError('a grid holds at least one point')
+        self.records = torch.empty((self.G, 4), dtype=torch.int64, device=self.g.device)
+        self.record = self.records[0]
+        self.reads = 0
+        self._init = ops.eval_record_init
+        self.reset()
+
+    def reset(self):
+        for row in self.records:
+            self._init(row)
+
+    def value_with(self, extra):
+        import torch
+        self.reads += 1
+        host = [int(v) for v in torch.cat([self.records.reshape(-1), extra.reshape(-1).to(torch.int64)]).cpu().tolist()]
+        rows = [tuple(host[4 * k:4 * k + 4]) for k in range(self.G)]
+        return rows, host[4 * self.G:]
+
+
 class DeviceCurve:
     """The score-threshold sweep of a pass beside `DeviceTpFp` (include/ocr_eval_curve.h): owns, on the device, the int64
     [T,4] curve (row t = the record's four slots with only the detections of score >= thresholds[t] kept, so

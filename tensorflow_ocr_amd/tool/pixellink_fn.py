@@ -226,12 +226,19 @@ def link_boxes_device(labels, ncomp, pixel_score, scale_x, scale_y, max_comps=40
     ps = _dev(g, pixel_score)
     if tuple(ps.shape) != tuple(labels.shape):
         raise ValueError("pixel_score must have the shape of labels")
+    return _boxes_of_labels(g, labels, ncomp, ps, ops.component_scores, scale_x, scale_y, max_comps, min_side, min_area)
+
+
+def _boxes_of_labels(g, labels, ncomp, ps, component_scores, scale_x, scale_y, max_comps, min_side, min_area):
+    """link_boxes_device's launch sequence on checked device tensors; `component_scores` is ops.component_scores
+    (ps has the shape of labels) or ops.component_scores_grid (labels [G*n,h,w] against ps [n,h,w])"""
+    n, dev = labels.shape[0], g.device
     hull_n = torch.zeros((n, max_comps), dtype=torch.int32, device=dev)
     head = torch.zeros((n, max_comps, 4), dtype=torch.int32, device=dev)
     cal = torch.zeros((n, max_comps, 6), dtype=F32, device=dev)
     ops.min_area_rects(labels, ncomp, max_comps, float(scale_x), float(scale_y), hull_n, head, cal, g.workspace())
     comp_score = torch.empty((n, max_comps), dtype=F32, device=dev)
-    ops.component_scores(labels, ps, ncomp, comp_score, g.workspace())
+    component_scores(labels, ps, ncomp, comp_score, g.workspace())
     merged = torch.empty((n, max_comps, 9), dtype=F32, device=dev)
     keep = torch.empty((n, max_comps), dtype=torch.int32, device=dev)
     n_keep = torch.empty((n,), dtype=torch.int32, device=dev)
@@ -251,6 +258,39 @@ def detect_device(pixel_score, link_score, pixel_conf_threshold=0.8, link_conf_t
     labels, ncomp, _ = link_cc_decode(ps, link_score, pixel_conf_threshold, link_conf_threshold, min_size=min_size,
                                       max_comps=max_comps, graph=g)
     return link_boxes_device(labels, ncomp, ps, scale_x, scale_y, max_comps, min_side, min_area, graph=g)
+
+
+def link_cc_decode_grid(pixel_score, link_score, pixel_thresholds, link_thresholds, min_size=10, max_comps=4096, graph=None):
+    """`link_cc_decode` (union mode) for G (pixel, link) threshold pairs in one launch sequence (ops.link_cc_grid): the
+    same maps, pixel_thresholds / link_thresholds two sequences of G numbers.  Returns (labels int32 [G*N,h,w], ncomp int32
+    [G*N], comps int32 [G*N,max_comps,2]); slice g*N + i is image i at point g, bit for bit what `link_cc_decode` gives
+    for it.  The maps are read where they are, never replicated."""
+    g = graph or get_default_graph()
+    ps = _dev(g, pixel_score)
+    lk = _dev(g, link_score)
+    n, h, w = ps.shape
+    stride, off = (2, 1) if lk.dim() == 5 else (1, 0)
+    N = len(pixel_thresholds) * n
+    labels = torch.empty((N, h, w), dtype=torch.int32, device=g.device)
+    ncomp = torch.empty((N,), dtype=torch.int32, device=g.device)
+    comps = torch.zeros((N, max_comps, 2), dtype=torch.int32, device=g.device)
+    ops.link_cc_grid(ps, lk, stride, off, pixel_thresholds, link_thresholds, int(min_size), labels, ncomp, comps,
+                     g.workspace())
+    return labels, ncomp, comps
+
+
+def detect_device_grid(pixel_score, link_score, pixel_thresholds, link_thresholds, min_size=10, scale_x=4.0, scale_y=4.0,
+                       max_comps=4096, min_side=0.0, min_area=0.0, graph=None):
+    """`detect_device` at G (pixel, link) threshold pairs behind ONE set of score maps, NO synchronisation:
+    link_cc_decode_grid -> ocr_min_area_rects -> ocr_component_scores_grid -> ocr_link_boxes on G*N slices.  pixel_score
+    [N,h,w], link_score [8,N,h,w,2] or [8,N,h,w] — `fuse_score_maps`' views of its accumulator are taken as they are.
+    Returns link_boxes_device's five device tensors with leading dimension G*N: rows g*N .. g*N + N - 1 are, bit for bit,
+    what `detect_device` returns at (pixel_thresholds[g], link_thresholds[g])."""
+    g = graph or get_default_graph()
+    ps = _dev(g, pixel_score)
+    labels, ncomp, _ = link_cc_decode_grid(ps, link_score, pixel_thresholds, link_thresholds, min_size=min_size,
+                                           max_comps=max_comps, graph=g)
+    return _boxes_of_labels(g, labels, ncomp, ps, ops.component_scores_grid, scale_x, scale_y, max_comps, min_side, min_area)
 
 
 # ------------------------------------------------------------------ multi-scale / flip testing: score-map fusion

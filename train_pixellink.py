@@ -77,9 +77,15 @@ def parse(argv=None):
     # on the F-measure unmeasured; activation memory grows with the square of the largest scale)
     ap.add_argument('--eval_map_scales', type=cli.map_scales_arg, default=None, metavar='S1,S2,...')
     ap.add_argument('--eval_flip', action='store_true')
+    # --eval_grid_pixel LIST --eval_grid_link LIST: every pass also decodes and matches every (pixel, link) threshold pair of
+    # the two lists behind its one forward (evaluate.LinkEvaluator's grid; the flags of eval_pixellink_fast.py) and reports
+    # the best pair: eval/grid_best_hmean, eval/grid_best_pixel_threshold, eval/grid_best_link_threshold in the event file
+    cli.add_grid_flags(ap)
     FLAGS = ap.parse_args(argv)
     if (FLAGS.eval_map_scales is not None or FLAGS.eval_flip) and not cli.eval_on(FLAGS):
         ap.error('--eval_map_scales and --eval_flip need --eval_data_path and --eval_steps')
+    if cli.check_grid_flags(ap, FLAGS) is not None and not cli.eval_on(FLAGS):
+        ap.error('--eval_grid_pixel and --eval_grid_link need --eval_data_path and --eval_steps')
     cli.check_train_eval_flags(ap, FLAGS, FLAGS.using_moving_average, '--eval_weights ema needs --using_moving_average')
     return FLAGS
 
@@ -175,7 +181,8 @@ def make_train_eval(FLAGS, g, step):
                               weights=FLAGS.eval_weights, batch_size=max(1, int(FLAGS.batch_size / FLAGS.num_gpus)),
                               evaluator=evaluate.LinkEvaluator, eval_image_height=FLAGS.eval_image_height,
                               eval_image_width=FLAGS.eval_image_width, protocol=FLAGS.eval_protocol,
-                              sweep=FLAGS.eval_sweep, map_scales=FLAGS.eval_map_scales, flip=FLAGS.eval_flip)
+                              sweep=FLAGS.eval_sweep, map_scales=FLAGS.eval_map_scales, flip=FLAGS.eval_flip,
+                              grid=cli.grid_option(FLAGS))
 
 
 def _evaluate(train_eval, summaries, opt):
