@@ -915,7 +915,18 @@ int ocr_py27_dict_order(const float* pixel_score_host, float pixel_thresh, int h
  * (SURVEY.md D2); build-defined, pinned bit for bit against oracle/lanms_oracle.c.
  * boxes f32 [n_images][max_k][9] (x1,y1,..,x4,y4,score; row-major scan order), counts i32
  * [n_images].  Outputs: merged [n_images][max_k][9], n_merged [n_images], keep_idx
- * [n_images][max_k] (indices into merged, in keep order), n_keep [n_images].
+ * [n_images][max_k] (indices into merged, in keep order), n_keep [n_images].  Rows of merged at or
+ * beyond n_merged and of keep_idx at or beyond n_keep are not written.  Coordinates and scores are
+ * finite; counts are not negative.  A count above max_k is clamped to max_k: the first max_k rows of
+ * that image are processed, the buffers hold no more.
+ * Two internal paths switch on max_k alone, with the same results on either side: the merge chain
+ * keeps an image's quads in LDS while 73 * max_k <= 144 KB (max_k <= 2019) and walks them in global
+ * memory from max_k = 2020 on; the greedy sweep holds one 64-bit mask word per lane while
+ * (max_k + 63) / 64 <= 64 (max_k <= 4096) and up to eight per lane from max_k = 4097 on.
+ * Status: OCR_ERR_INVALID_ARG for a null pointer or a non-positive n_images or max_k,
+ * OCR_ERR_UNSUPPORTED for max_k > 32768, OCR_ERR_WORKSPACE for ws_bytes below
+ * ocr_lanms_workspace(n_images, max_k); nothing is written on error.
+ * (tests/test_gpu_nms_matrix.py runs every path edge in a workspace of exactly that size.)
  * ------------------------------------------------------------------------- */
 size_t ocr_lanms_workspace(int n_images, int max_k);
 int ocr_lanms(const void* boxes, const void* counts, int n_images, int max_k, float iou_thresh,
