@@ -1,11 +1,18 @@
-"""Thin, typed wrappers over the C ABI (include/ocr_hip.h).
+"""Wrappers over the C ABI (include/ocr_hip.h).
 
 Every function takes torch CUDA tensors purely as device-memory handles, passes raw
 pointers + the current HIP stream through ctypes, and returns nothing new except
 tensors it was asked to allocate.  There is no torch compute and no CPU fallback
 here: without libocr_hip.so every call raises `_lib.OcrHipError`.
+
+The wrappers of the training step and the inference forward (everything above `softmax_pairs`, the optimiser block
+and the f32 / f16x2 block) check nothing: layer code that allocates every buffer itself calls them once, at record
+time, and the replay never comes back here.  The decode, NMS, label, resize, evaluation, multi-scale, map-fusion, grid
+and summary wrappers are called by tools, the feeder thread and users with tensors of their own, so each states its
+operands once, as rows of `_operands`, which refuses a wrong shape, dtype, layout or device before a pointer is taken.
 """
 import ctypes
+import os
 from ctypes import byref, c_double, c_float, c_int, c_int64, c_size_t
 
 import torch
@@ -82,9 +89,8 @@ def conv2d_variant(d):
     key = (d.n, d.h, d.w, d.cin, d.cout, d.kh, d.kw, d.stride, d.dilation)
     v = _VARIANTS.get(key)
     if v is None:
-        import ctypes
         buf = ctypes.create_string_buffer(96)
-        L.call_int("ocr_conv2d_variant", byref(d), buf, ctypes.c_size_t(96))
+        L.call_int("ocr_conv2d_variant", byref(d), buf, c_size_t(96))
         v = _VARIANTS[key] = buf.value.decode()
     return v
 
@@ -244,7 +250,7 @@ def bn_relu_bwd_apply(y, scale, shift, save_mean, save_invstd, da_full, relu, pa
 
 # --- guest forms (csrc/guest_bn.hip): <= 56 registers per lane, one launch, placed beside a resident weight-gradient
 # workgroup; the recorded step runs them on a second stream (train.TrainStep: tags "pre" / "guest") -------------------
-GUEST_BN = __import__("os").environ.get("OCR_GUEST_BN", "1") == "1"
+GUEST_BN = os.environ.get("OCR_GUEST_BN", "1") == "1"
 
 
 def guest_apply_ok(shape):
@@ -492,7 +498,6 @@ class PackBatch:
     (ld_ck = 32: a fuse head's [32][cin] / [cin][32] zero-padded pair; w then is the [cin][C] master)."""
 
     def __init__(self, entries, device):
-        import ctypes
         n = len(entries)
         vp = ctypes.c_void_p * n
         ci = ctypes.c_int * n
@@ -1001,39 +1006,102 @@ def link_ce_bwd_dyn(gt, gt_stride, pred, pred_stride, w_pixel, count, sums4, gra
            ptr(sums4), c_float(grad_scale), ptr(loss_scale), ptr(d_pred), c_int(d_stride), _st())
 
 
+# ----------------------------------------------------------------------------- operand checks
+I32, I64, U8, F64 = torch.int32, torch.int64, torch.uint8, torch.float64
+OPTIONAL = True
+_DTYPE_WORDS = {F32: "f32", torch.float16: "f16", torch.bfloat16: "bf16", I32: "int32", I64: "int64", U8: "uint8", F64: "float64"}
+
+
+def _dims(what, name, t, rank=None):
+    """The shape of operand `name`, which wrapper `what` reads free sizes from: a tensor (of `rank` dimensions), or refused."""
+    shape = getattr(t, "shape", None)
+    if shape is None or (rank is not None and len(shape) != rank):
+        raise ValueError("%s: tensors do not match (%s is %s, wants %s)" % (
+            what, name, None if shape is None else tuple(shape), "a tensor" if rank is None else "%d dimensions" % rank))
+    return shape
+
+
+def _operands(what, sizes, *rows):
+    """The operand statement of wrapper `what`, enforced.  `sizes` names its free sizes; a row is (name, tensor, dtype,
+    shape[, OPTIONAL]): shape a tuple of ints, an int (that many elements, any shape) or None (any), dtype None for a
+    byte buffer of any element type, OPTIONAL for an operand that may be None.  Metadata only, nothing launches or
+    synchronises.  Raises ValueError as three passes would, so that a call with several faults reports a shape before
+    a dtype before a layout: every shape; every dtype; then contiguity and the device, which is the first operand's."""
+    first = dtype_fault = layout_fault = None
+    for row in rows:
+        t, shape = row[1], row[3]
+        if t is None and len(row) == 5:
+            continue
+        if t is None or (shape is not None and (t.numel() if type(shape) is int else t.shape) != shape):
+            raise ValueError("%s: tensors do not match %s (%s is %s, wants %s)" % (
+                what, sizes, row[0], None if t is None else tuple(t.shape), "%d elements" % shape if type(shape) is int else shape))
+        if first is None:
+            first, device = row[0], t.device
+        if row[2] is not None and t.dtype != row[2] and dtype_fault is None:
+            dtype_fault = "%s: %s is %s, wants %s" % (what, row[0], _DTYPE_WORDS.get(t.dtype, t.dtype), _DTYPE_WORDS[row[2]])
+        if layout_fault is None:
+            if not t.is_contiguous():
+                layout_fault = "%s: contiguous tensors only (%s)" % (what, row[0])
+            elif t.device != device:
+                layout_fault = "%s: tensors on one device only (%s is on %s, %s on %s)" % (what, first, device, row[0], t.device)
+    if dtype_fault or layout_fault:
+        raise ValueError(dtype_fault or layout_fault)
+
+
+def _workspace(ws, size_entry, *args):
+    """(pointer, byte count) of the scratch that `size_entry(*args)` asks of the arena `ws`: an entry's two workspace arguments"""
+    nbytes = L.call_size(size_entry, *args)
+    return ptr(ws.get(nbytes)), c_size_t(nbytes)
+
+
 # ----------------------------------------------------------------------------- decode
 def softmax_pairs(logits, probs):
-    L.call("ocr_softmax_pairs", ptr(logits), c_int64(logits.numel() // 2), ptr(probs), _st())
+    pairs = _dims("softmax_pairs", "logits", logits).numel() // 2
+    _operands("softmax_pairs", "pairs", ("logits", logits, F32, 2 * pairs), ("probs", probs, F32, 2 * pairs))
+    L.call("ocr_softmax_pairs", ptr(logits), c_int64(pairs), ptr(probs), _st())
 
 
 def link_softmax_stack(link_logits, out):
-    L.call("ocr_link_softmax_stack", ptr(link_logits), c_int64(link_logits.numel() // 16), ptr(out), _st())
+    m = _dims("link_softmax_stack", "link_logits", link_logits).numel() // 16
+    _operands("link_softmax_stack", "m", ("link_logits", link_logits, F32, 16 * m), ("out", out, F32, 16 * m))
+    L.call("ocr_link_softmax_stack", ptr(link_logits), c_int64(m), ptr(out), _st())
 
 
 def pixel_detect(score_map, link_scores, n, h, w, score_thresh, link_thresh, mask):
+    _operands("pixel_detect", "n, h, w",
+              ("score_map", score_map, F32, n * h * w), ("link_scores", link_scores, F32, 16 * n * h * w), ("mask", mask, U8, h * w))
     L.call("ocr_pixel_detect", ptr(score_map), ptr(link_scores), c_int(n), c_int(h), c_int(w),
            c_float(score_thresh), c_float(link_thresh), ptr(mask), _st())
 
 
+def _link_cc_rows(pixel_score, link_score, stride, n, h, w):
+    # link_score by element count: the callers pass [8,n,h,w,2] read at stride 2, offset 1, or [8,n,h,w] at stride 1
+    return ("pixel_score", pixel_score, F32, n * h * w), ("link_score", link_score, F32, 8 * n * h * w * stride)
+
+
 def link_cc(pixel_score, link_score, stride, offset, n, h, w, pixel_thresh, link_thresh, min_size, labels,
             ncomp, comps, ws):
-    nbytes = L.call_size("ocr_link_cc_workspace", c_int(n), c_int(h), c_int(w))
-    buf = ws.get(nbytes)
+    max_comps = _dims("link_cc", "comps", comps, 3)[1]
+    _operands("link_cc", "n, h, w, stride, max_comps", *_link_cc_rows(pixel_score, link_score, stride, n, h, w),
+              ("labels", labels, I32, n * h * w), ("ncomp", ncomp, I32, n), ("comps", comps, I32, (n, max_comps, 2)))
     L.call("ocr_link_cc", ptr(pixel_score), ptr(link_score), c_int(stride), c_int(offset), c_int(n), c_int(h),
            c_int(w), c_float(pixel_thresh), c_float(link_thresh), c_int(min_size), ptr(labels), ptr(ncomp),
-           ptr(comps), c_int(comps.shape[1]), ptr(buf), c_size_t(nbytes), _st())
+           ptr(comps), c_int(max_comps), *_workspace(ws, "ocr_link_cc_workspace", c_int(n), c_int(h), c_int(w)), _st())
 
 
 def link_cc_directed(pixel_score, link_score, stride, offset, n, h, w, pixel_thresh, link_thresh, min_size,
                      union_labels, union_ncomp, labels, ncomp, comps, ws, seed_order=None):
     """The reference's directed-DFS grouping, refining ocr_link_cc's components (include/ocr_hip.h).
     seed_order: int32 [n, h*w] device tensor from `py27_dict_order` (None: ascending pixel index)."""
-    nbytes = L.call_size("ocr_link_cc_directed_workspace", c_int(n), c_int(h), c_int(w))
-    buf = ws.get(nbytes)
+    max_comps = _dims("link_cc_directed", "comps", comps, 3)[1]
+    _operands("link_cc_directed", "n, h, w, stride, max_comps", *_link_cc_rows(pixel_score, link_score, stride, n, h, w),
+              ("union_labels", union_labels, I32, n * h * w), ("union_ncomp", union_ncomp, I32, n),
+              ("seed_order", seed_order, I32, n * h * w, OPTIONAL), ("labels", labels, I32, n * h * w), ("ncomp", ncomp, I32, n),
+              ("comps", comps, I32, (n, max_comps, 2)))
     L.call("ocr_link_cc_directed", ptr(pixel_score), ptr(link_score), c_int(stride), c_int(offset), c_int(n),
            c_int(h), c_int(w), c_float(pixel_thresh), c_float(link_thresh), c_int(min_size), ptr(union_labels),
-           ptr(union_ncomp), ptr(seed_order), ptr(labels), ptr(ncomp), ptr(comps), c_int(comps.shape[1]), ptr(buf),
-           c_size_t(nbytes), _st())
+           ptr(union_ncomp), ptr(seed_order), ptr(labels), ptr(ncomp), ptr(comps), c_int(max_comps),
+           *_workspace(ws, "ocr_link_cc_directed_workspace", c_int(n), c_int(h), c_int(w)), _st())
 
 
 def py27_dict_order(pixel_score_host, pixel_thresh):
@@ -1052,11 +1120,12 @@ def py27_dict_order(pixel_score_host, pixel_thresh):
 
 
 def lanms(boxes, counts, iou_thresh, merged, n_merged, keep_idx, n_keep, ws):
-    n_images, max_k, _ = boxes.shape
-    nbytes = L.call_size("ocr_lanms_workspace", c_int(n_images), c_int(max_k))
-    buf = ws.get(nbytes)
-    L.call("ocr_lanms", ptr(boxes), ptr(counts), c_int(n_images), c_int(max_k), c_float(iou_thresh),
-           ptr(merged), ptr(n_merged), ptr(keep_idx), ptr(n_keep), ptr(buf), c_size_t(nbytes), _st())
+    n, max_k, _ = _dims("lanms", "boxes", boxes, 3)
+    _operands("lanms", "n, max_k",
+              ("boxes", boxes, F32, (n, max_k, 9)), ("counts", counts, I32, n), ("merged", merged, F32, (n, max_k, 9)),
+              ("n_merged", n_merged, I32, n), ("keep_idx", keep_idx, I32, (n, max_k)), ("n_keep", n_keep, I32, n))
+    L.call("ocr_lanms", ptr(boxes), ptr(counts), c_int(n), c_int(max_k), c_float(iou_thresh), ptr(merged), ptr(n_merged),
+           ptr(keep_idx), ptr(n_keep), *_workspace(ws, "ocr_lanms_workspace", c_int(n), c_int(max_k)), _st())
 
 
 # ------------------------------------------------------------------------------- EAST RBOX geometry (csrc/rbox.hip)
@@ -1108,94 +1177,119 @@ def rbox_loss_bwd_dyn(yt_cls, yt_geo, yp_geo, mask, sums5, grad_scale, loss_scal
 
 def rbox_decode(score, geo, n, h, w, score_thresh, scale, boxes, counts, total, ws):
     """score [n,h,w], geo [n,h,w,5] -> boxes [n,max_k,9] in raster order, counts / total int32 [n]."""
-    max_k = boxes.shape[1]
-    if score.numel() != n * h * w or geo.numel() != 5 * n * h * w or boxes.numel() != n * max_k * 9 or \
-            counts.numel() != n or total.numel() != n:
-        raise ValueError("rbox_decode: tensors do not match n, h, w, max_k")
-    nbytes = L.call_size("ocr_rbox_decode_workspace", c_int(n), c_int(h), c_int(w))
-    buf = ws.get(nbytes)
+    max_k = _dims("rbox_decode", "boxes", boxes, 3)[1]
+    _operands("rbox_decode", "n, h, w, max_k",
+              ("score", score, F32, n * h * w), ("geo", geo, F32, 5 * n * h * w), ("boxes", boxes, F32, (n, max_k, 9)),
+              ("counts", counts, I32, n), ("total", total, I32, n))
     L.call("ocr_rbox_decode", ptr(score), ptr(geo), c_int(n), c_int(h), c_int(w), c_float(score_thresh), c_float(scale),
-           c_int(max_k), ptr(boxes), ptr(counts), ptr(total), ptr(buf), c_size_t(nbytes), _st())
+           c_int(max_k), ptr(boxes), ptr(counts), ptr(total),
+           *_workspace(ws, "ocr_rbox_decode_workspace", c_int(n), c_int(h), c_int(w)), _st())
 
 
 def quad_mean_score(quads, score, inv_scale, mean):
     """quads f32 [k,8] (image px), score f32 [h,w] -> mean f32 [k]: the score's mean over the fillPoly raster of each quad's
     vertices floor(trunc(coord) * inv_scale); 0 for an empty raster."""
-    k = quads.shape[0]
-    h, w = score.shape
-    if quads.numel() != 8 * k or mean.numel() != k or not (quads.is_contiguous() and score.is_contiguous()):
-        raise ValueError("quad_mean_score: quads [k,8], score [h,w], mean [k], contiguous")
+    k = _dims("quad_mean_score", "quads", quads, 2)[0]
+    h, w = _dims("quad_mean_score", "score", score, 2)
+    _operands("quad_mean_score", "k, h, w", ("quads", quads, F32, (k, 8)), ("score", score, F32, (h, w)), ("mean", mean, F32, k))
     L.call("ocr_quad_mean_score", ptr(quads), c_int(k), ptr(score), c_int(h), c_int(w), c_float(inv_scale), ptr(mean), _st())
 
 
+def _hull_rows(n, max_comps, hull_n, hull_head, calipers):
+    return (("hull_n", hull_n, I32, (n, max_comps)), ("hull_head", hull_head, I32, (n, max_comps, 4)),
+            ("calipers", calipers, F32, (n, max_comps, 6)))
+
+
 def min_area_rects(labels, ncomp, max_comps, scale_x, scale_y, hull_n, hull_head, calipers, ws):
-    n, h, w = labels.shape
-    nbytes = L.call_size("ocr_min_area_rects_workspace", c_int(n), c_int(h), c_int(w), c_int(max_comps))
-    buf = ws.get(nbytes)
+    n, h, w = _dims("min_area_rects", "labels", labels, 3)
+    _operands("min_area_rects", "n, h, w, max_comps", ("labels", labels, I32, (n, h, w)), ("ncomp", ncomp, I32, n),
+              *_hull_rows(n, max_comps, hull_n, hull_head, calipers))
     L.call("ocr_min_area_rects", ptr(labels), ptr(ncomp), c_int(n), c_int(h), c_int(w), c_int(max_comps),
-           c_double(scale_x), c_double(scale_y), ptr(hull_n), ptr(hull_head), ptr(calipers), ptr(buf),
-           c_size_t(nbytes), _st())
+           c_double(scale_x), c_double(scale_y), ptr(hull_n), ptr(hull_head), ptr(calipers),
+           *_workspace(ws, "ocr_min_area_rects_workspace", c_int(n), c_int(h), c_int(w), c_int(max_comps)), _st())
 
 
 def mask_cc(mask, value, connectivity, labels, ncomp, comps, ws):
-    n, h, w = mask.shape
-    nbytes = L.call_size("ocr_link_cc_workspace", c_int(n), c_int(h), c_int(w))
-    buf = ws.get(nbytes)
+    n, h, w = _dims("mask_cc", "mask", mask, 3)
+    max_comps = _dims("mask_cc", "comps", comps, 3)[1]
+    _operands("mask_cc", "n, h, w, max_comps", ("mask", mask, U8, (n, h, w)), ("labels", labels, I32, n * h * w),
+              ("ncomp", ncomp, I32, n), ("comps", comps, I32, (n, max_comps, 2)))
     L.call("ocr_mask_cc", ptr(mask), c_int(value), c_int(connectivity), c_int(n), c_int(h), c_int(w), ptr(labels),
-           ptr(ncomp), ptr(comps), c_int(comps.shape[1]), ptr(buf), c_size_t(nbytes), _st())
+           ptr(ncomp), ptr(comps), c_int(max_comps), *_workspace(ws, "ocr_link_cc_workspace", c_int(n), c_int(h), c_int(w)), _st())
 
 
 def hole_border_rects(mask, zlabels, nregions, max_regions, scale_x, scale_y, hull_n, hull_head, calipers, ws):
-    n, h, w = mask.shape
-    nbytes = L.call_size("ocr_hole_border_rects_workspace", c_int(n), c_int(h), c_int(w), c_int(max_regions))
-    buf = ws.get(nbytes)
+    n, h, w = _dims("hole_border_rects", "mask", mask, 3)
+    _operands("hole_border_rects", "n, h, w, max_regions", ("mask", mask, U8, (n, h, w)), ("zlabels", zlabels, I32, n * h * w),
+              ("nregions", nregions, I32, n), *_hull_rows(n, max_regions, hull_n, hull_head, calipers))
     L.call("ocr_hole_border_rects", ptr(mask), ptr(zlabels), ptr(nregions), c_int(n), c_int(h), c_int(w),
            c_int(max_regions), c_double(scale_x), c_double(scale_y), ptr(hull_n), ptr(hull_head), ptr(calipers),
-           ptr(buf), c_size_t(nbytes), _st())
+           *_workspace(ws, "ocr_hole_border_rects_workspace", c_int(n), c_int(h), c_int(w), c_int(max_regions)), _st())
 
 
 def east_pixel_detect(score, link16, h, w, score_thresh, link_thresh, mask, first_second):
+    _operands("east_pixel_detect", "h, w", ("score", score, F32, h * w), ("link16", link16, F32, 16 * h * w),
+              ("mask", mask, U8, h * w), ("first_second", first_second, I32, (2, 8)))
     L.call("ocr_east_pixel_detect", ptr(score), ptr(link16), c_int(h), c_int(w), c_float(score_thresh),
            c_float(link_thresh), ptr(mask), ptr(first_second), _st())
 
 
 def contour_parents(labels, zlabels, comps, ncomp, zcomps, nregions, parent_c, parent_z):
-    h, w = labels.shape[-2:]
+    """The two `mask_cc` labellings of one mask [h,w] and their first ncomp / nregions comps rows -> parent_c int32
+    [>= ncomp], parent_z int32 [>= nregions] (include/ocr_hip.h: ocr_contour_parents)."""
+    h, w = _dims("contour_parents", "labels", labels)[-2:]
+    _operands("contour_parents", "h, w", ("labels", labels, I32, h * w), ("zlabels", zlabels, I32, h * w),
+              ("comps", comps, I32, None), ("zcomps", zcomps, I32, None), ("parent_c", parent_c, I32, None),
+              ("parent_z", parent_z, I32, None))
+    if comps.numel() < 2 * ncomp or zcomps.numel() < 2 * nregions or parent_c.numel() < ncomp or parent_z.numel() < nregions:
+        raise ValueError("contour_parents: comps / zcomps / parent_c / parent_z hold fewer than ncomp = %d / nregions = %d rows"
+                         % (ncomp, nregions))
     L.call("ocr_contour_parents", ptr(labels), ptr(zlabels), ptr(comps), c_int(ncomp), ptr(zcomps), c_int(nregions),
            c_int(h), c_int(w), ptr(parent_c), ptr(parent_z), _st())
 
 
 def zero_pixels(mask, idx):
+    """mask uint8 (any shape), idx int32: up to 256 flat indices into it."""
+    _operands("zero_pixels", "count", ("mask", mask, U8, None), ("idx", idx, I32, None))
     L.call("ocr_zero_pixels_u8", ptr(mask), ptr(idx), c_int(idx.numel()), _st())
 
 
 # ----------------------------------------------------------------------------- labels
 def poly_cover(polys, counts, ignore, h, w, cover):
-    n, P, V, _ = polys.shape
+    n, P, V, _ = _dims("poly_cover", "polys", polys, 4)
+    _operands("poly_cover", "n, max_polys, verts, h, w", ("polys", polys, I32, (n, P, V, 2)), ("counts", counts, I32, n),
+              ("ignore", ignore, U8, (n, P)), ("cover", cover, I32, n * h * w))
     L.call("ocr_poly_cover", ptr(polys), ptr(counts), ptr(ignore), c_int(n), c_int(P), c_int(V), c_int(h),
            c_int(w), ptr(cover), _st())
 
 
 def icdar_labels(cover, step, score, geo, mask):
-    n, h, w = cover.shape
+    n, h, w = _dims("icdar_labels", "cover", cover, 3)
+    cells = n * -(-h // max(step, 1)) * -(-w // max(step, 1))
+    _operands("icdar_labels", "n, h, w, step", ("cover", cover, I32, (n, h, w)), ("score", score, F32, cells),
+              ("geo", geo, F32, 8 * cells), ("mask", mask, F32, cells))
     L.call("ocr_icdar_labels", ptr(cover), c_int(n), c_int(h), c_int(w), c_int(step), ptr(score), ptr(geo),
            ptr(mask), _st())
 
 
 def rbox_labels(cover_score, cover_full, rects, step, score, geo, mask):
-    """Two cover maps [n,h,w] (shrunk / full polygons) + rects f32 [n,P,5,3] -> score, geo [..,5], mask at every step-th pixel."""
-    n, h, w = cover_score.shape
-    P = rects.shape[1]
-    oh, ow = -(-h // max(step, 1)), -(-w // max(step, 1))
-    if tuple(cover_full.shape) != (n, h, w) or tuple(rects.shape) != (n, P, 5, 3) or score.numel() != n * oh * ow or \
-            geo.numel() != 5 * n * oh * ow or mask.numel() != n * oh * ow:
-        raise ValueError("rbox_labels: tensors do not match n, h, w, step, max_polys")
+    """Two cover maps int32 [n,h,w] (shrunk / full polygons) + rects f32 [n,P,5,3] -> score f32 [n,oh,ow,1], geo f32
+    [n,oh,ow,5], mask f32 [n,oh,ow,1] at every step-th pixel."""
+    n, h, w = _dims("rbox_labels", "cover_score", cover_score, 3)
+    P = _dims("rbox_labels", "rects", rects, 4)[1]
+    cells = n * -(-h // max(step, 1)) * -(-w // max(step, 1))
+    _operands("rbox_labels", "n, h, w, step, max_polys",
+              ("cover_score", cover_score, I32, (n, h, w)), ("cover_full", cover_full, I32, (n, h, w)),
+              ("rects", rects, F32, (n, P, 5, 3)), ("score", score, F32, cells), ("geo", geo, F32, 5 * cells),
+              ("mask", mask, F32, cells))
     L.call("ocr_icdar_rbox_labels", ptr(cover_score), ptr(cover_full), ptr(rects), c_int(n), c_int(P), c_int(h), c_int(w),
            c_int(step), ptr(score), ptr(geo), ptr(mask), _st())
 
 
 def pixellink_labels(cover, new_h, new_w, score, link):
-    n, h, w = cover.shape
+    n, h, w = _dims("pixellink_labels", "cover", cover, 3)
+    _operands("pixellink_labels", "n, h, w, new_h, new_w", ("cover", cover, I32, (n, h, w)),
+              ("score", score, F32, n * new_h * new_w), ("link", link, F32, 8 * n * new_h * new_w))
     L.call("ocr_pixellink_labels", ptr(cover), c_int(n), c_int(h), c_int(w), c_int(new_h), c_int(new_w),
            ptr(score), ptr(link), _st())
 
@@ -1203,42 +1297,47 @@ def pixellink_labels(cover, new_h, new_w, score, link):
 def pixellink_instance_weights(cover, ignore, new_h, new_w, area, weight):
     """Instance-balanced weight map of the label cells (include/ocr_hip.h: ocr_pixellink_instance_weights): cover int32
     [n,h,w] (ocr_poly_cover), ignore uint8 [n,P] -> area int32 [n,P] (cells owned per polygon), weight f32 [n,new_h,new_w]."""
-    n, h, w = cover.shape
-    P = ignore.shape[1]
-    if tuple(ignore.shape) != (n, P) or ignore.dtype != torch.uint8 or tuple(area.shape) != (n, P) or \
-            area.dtype != torch.int32 or weight.numel() != n * new_h * new_w or weight.dtype != torch.float32:
-        raise ValueError("pixellink_instance_weights: tensors do not match n, max_polys, new_h, new_w")
+    n, h, w = _dims("pixellink_instance_weights", "cover", cover, 3)
+    P = _dims("pixellink_instance_weights", "ignore", ignore, 2)[1]
+    _operands("pixellink_instance_weights", "n, max_polys, new_h, new_w",
+              ("cover", cover, I32, (n, h, w)), ("ignore", ignore, U8, (n, P)), ("area", area, I32, (n, P)),
+              ("weight", weight, F32, n * new_h * new_w))
     L.call("ocr_pixellink_instance_weights", ptr(cover), ptr(ignore), c_int(n), c_int(P), c_int(h), c_int(w),
            c_int(new_h), c_int(new_w), ptr(area), ptr(weight), _st())
 
 
 def resize_linear_u8(src_u8, dst_f32):
-    H, W, cn = src_u8.shape
-    dh, dw, _ = dst_f32.shape
+    H, W, cn = _dims("resize_linear_u8", "src_u8", src_u8, 3)
+    dh, dw, _ = _dims("resize_linear_u8", "dst_f32", dst_f32, 3)
+    _operands("resize_linear_u8", "H, W, cn, dh, dw", ("src_u8", src_u8, U8, (H, W, cn)), ("dst_f32", dst_f32, F32, (dh, dw, cn)))
     L.call("ocr_resize_linear_u8", ptr(src_u8), c_int(H), c_int(W), c_int(cn), ptr(dst_f32), c_int(dh),
            c_int(dw), _st())
 
 
 def augment_u8_batch(slab, desc, n, S, dst):
     """One launch for a batch (include/ocr_hip.h: ocr_augment_u8_batch): slab uint8 [bytes] holding the n source images,
-    desc uint8 [n * sizeof(ocr_augment_desc)] (datasets/augment.py: DESC_DTYPE), dst f32 [n,S,S,3]; all on the device."""
-    assert slab.dtype == torch.uint8 and desc.dtype == torch.uint8 and dst.dtype == torch.float32
-    assert desc.numel() >= 112 * n and tuple(dst.shape) == (n, S, S, 3) and dst.is_contiguous()
+    desc uint8 [>= n * sizeof(ocr_augment_desc)] (datasets/augment.py: DESC_DTYPE), dst f32 [n,S,S,3]; all on the device."""
+    _operands("augment_u8_batch", "n, S", ("slab", slab, U8, None), ("desc", desc, U8, None), ("dst", dst, F32, (n, S, S, 3)))
+    if desc.numel() < 112 * n:
+        raise ValueError("augment_u8_batch: desc holds %d bytes, fewer than %d records of 112" % (desc.numel(), n))
     L.call("ocr_augment_u8_batch", ptr(slab), ptr(desc), c_int(n), c_int(S), ptr(dst), _st())
 
 
 def resize_cubic_f32(src_f32, dst_f32, pre_scale=1.0, post_scale=1.0):
     """src f32 [planes,h,w] -> dst f32 [planes,dh,dw] (cv2.resize INTER_CUBIC per plane)."""
-    planes, h, w = src_f32.shape
-    p2, dh, dw = dst_f32.shape
-    assert planes == p2 and src_f32.dtype == torch.float32 and dst_f32.dtype == torch.float32
+    planes, h, w = _dims("resize_cubic_f32", "src_f32", src_f32, 3)
+    _, dh, dw = _dims("resize_cubic_f32", "dst_f32", dst_f32, 3)
+    _operands("resize_cubic_f32", "planes, h, w, dh, dw",
+              ("src_f32", src_f32, F32, (planes, h, w)), ("dst_f32", dst_f32, F32, (planes, dh, dw)))
     L.call("ocr_resize_cubic_f32", ptr(src_f32), c_int(planes), c_int(h), c_int(w), ptr(dst_f32), c_int(dh),
            c_int(dw), c_float(pre_scale), c_float(post_scale), _st())
 
 
 def quad_iou(dets, gts, mask_h, mask_w, inter, uni):
-    nd, V, _ = dets.shape
-    ng = gts.shape[0]
+    nd, V, _ = _dims("quad_iou", "dets", dets, 3)
+    ng = _dims("quad_iou", "gts", gts, 3)[0]
+    _operands("quad_iou", "nd, ng, verts", ("dets", dets, I32, (nd, V, 2)), ("gts", gts, I32, (ng, V, 2)),
+              ("inter", inter, I32, (nd, ng)), ("uni", uni, I32, (nd, ng)))
     L.call("ocr_quad_iou", ptr(dets), c_int(nd), ptr(gts), c_int(ng), c_int(V), c_int(mask_h), c_int(mask_w),
            ptr(inter), ptr(uni), _st())
 
@@ -1247,23 +1346,25 @@ def quad_iou(dets, gts, mask_h, mask_w, inter, uni):
 EVAL_MAX_D, EVAL_MAX_G = 1024, 254      # the most detections / ground truths per image the matcher takes
 
 
+def _lanms_rows(merged, keep_idx, n_keep, n, max_k):
+    """ocr_lanms's output layout, which the collect, pool and box entries read or write"""
+    return ("merged", merged, F32, (n, max_k, 9)), ("keep_idx", keep_idx, I32, (n, max_k)), ("n_keep", n_keep, I32, n)
+
+
+def _quad_rows(dets, nd, gts, ng, n, max_d, max_g):
+    """the detection and ground-truth lists of both matchers"""
+    return (("dets", dets, I32, (n, max_d, 4, 2)), ("nd", nd, I32, n), ("gts", gts, I32, (n, max_g, 4, 2)), ("ng", ng, I32, n))
+
+
 def eval_collect(merged, keep_idx, n_keep, passed, inv_ratio, dets, det_score, nd, nd_total):
     """LANMS output (merged f32 [n,max_k,9], keep_idx int32 [n,max_k], n_keep int32 [n]; passed uint8 [n,max_k] or None) ->
     dets int32 [n,max_d,4,2] (kept quads / the resize ratios inv_ratio f32 [n,2] = (ratio_w, ratio_h), truncated), det_score
     f32 [n,max_d], in descending score order; nd = min(nd_total, max_d), nd_total int32 [n] (include/ocr_hip.h)."""
-    n, max_k, _ = merged.shape
-    max_d = dets.shape[1]
-    if tuple(keep_idx.shape) != (n, max_k) or n_keep.numel() != n or tuple(inv_ratio.shape) != (n, 2) or \
-            tuple(dets.shape) != (n, max_d, 4, 2) or tuple(det_score.shape) != (n, max_d) or nd.numel() != n or \
-            nd_total.numel() != n or (passed is not None and (tuple(passed.shape) != (n, max_k) or passed.dtype != torch.uint8)):
-        raise ValueError("eval_collect: tensors do not match n, max_k, max_d")
-    if merged.dtype != torch.float32 or keep_idx.dtype != torch.int32 or n_keep.dtype != torch.int32 or \
-            inv_ratio.dtype != torch.float32 or dets.dtype != torch.int32 or det_score.dtype != torch.float32 or \
-            nd.dtype != torch.int32 or nd_total.dtype != torch.int32:
-        raise ValueError("eval_collect: merged / inv_ratio / det_score f32, the index and count tensors int32")
-    for t in (merged, keep_idx, n_keep, inv_ratio, dets, det_score, nd, nd_total) + (() if passed is None else (passed,)):
-        if not t.is_contiguous():
-            raise ValueError("eval_collect: contiguous tensors only")
+    n, max_k, _ = _dims("eval_collect", "merged", merged, 3)
+    max_d = _dims("eval_collect", "dets", dets, 4)[1]
+    _operands("eval_collect", "n, max_k, max_d", *_lanms_rows(merged, keep_idx, n_keep, n, max_k),
+              ("passed", passed, U8, (n, max_k), OPTIONAL), ("inv_ratio", inv_ratio, F32, (n, 2)), ("dets", dets, I32, (n, max_d, 4, 2)),
+              ("det_score", det_score, F32, (n, max_d)), ("nd", nd, I32, n), ("nd_total", nd_total, I32, n))
     L.call("ocr_eval_collect", ptr(merged), ptr(keep_idx), ptr(n_keep), ptr(passed), ptr(inv_ratio), c_int(n), c_int(max_k),
            c_int(max_d), ptr(dets), ptr(det_score), ptr(nd), ptr(nd_total), _st())
 
@@ -1271,22 +1372,13 @@ def eval_collect(merged, keep_idx, n_keep, passed, inv_ratio, dets, det_score, n
 def eval_match_batch(dets, nd, gts, ng, gignored, threshold, mask_h, mask_w, tp, fp, record, ws):
     """bboxes_matching of n images in one call: dets int32 [n,max_d,4,2] / nd int32 [n] in matching order, gts int32
     [n,max_g,4,2] / ng int32 [n], gignored uint8 [n,max_g] -> tp, fp uint8 [n,max_d]; record int64 [4] is added to."""
-    n, max_d = dets.shape[:2]
-    max_g = gts.shape[1]
-    if tuple(dets.shape) != (n, max_d, 4, 2) or tuple(gts.shape) != (n, max_g, 4, 2) or nd.numel() != n or ng.numel() != n or \
-            tuple(gignored.shape) != (n, max_g) or tuple(tp.shape) != (n, max_d) or tuple(fp.shape) != (n, max_d) or \
-            record.numel() != 4:
-        raise ValueError("eval_match_batch: tensors do not match n, max_d, max_g")
-    if dets.dtype != torch.int32 or gts.dtype != torch.int32 or nd.dtype != torch.int32 or ng.dtype != torch.int32 or \
-            gignored.dtype != torch.uint8 or tp.dtype != torch.uint8 or fp.dtype != torch.uint8 or record.dtype != torch.int64:
-        raise ValueError("eval_match_batch: quads and counts int32, flags uint8, record int64")
-    for t in (dets, nd, gts, ng, gignored, tp, fp, record):
-        if not t.is_contiguous():
-            raise ValueError("eval_match_batch: contiguous tensors only")
-    nbytes = L.call_size("ocr_eval_match_workspace", c_int(n), c_int(max_d), c_int(max_g))
-    buf = ws.get(nbytes)
+    n, max_d = _dims("eval_match_batch", "dets", dets, 4)[:2]
+    max_g = _dims("eval_match_batch", "gts", gts, 4)[1]
+    _operands("eval_match_batch", "n, max_d, max_g", *_quad_rows(dets, nd, gts, ng, n, max_d, max_g),
+              ("gignored", gignored, U8, (n, max_g)), ("tp", tp, U8, (n, max_d)), ("fp", fp, U8, (n, max_d)), ("record", record, I64, 4))
     L.call("ocr_eval_match_batch", ptr(dets), ptr(nd), ptr(gts), ptr(ng), ptr(gignored), c_int(n), c_int(max_d), c_int(max_g),
-           c_float(threshold), c_int(mask_h), c_int(mask_w), ptr(tp), ptr(fp), ptr(record), ptr(buf), c_size_t(nbytes), _st())
+           c_float(threshold), c_int(mask_h), c_int(mask_w), ptr(tp), ptr(fp), ptr(record),
+           *_workspace(ws, "ocr_eval_match_workspace", c_int(n), c_int(max_d), c_int(max_g)), _st())
 
 
 def eval_ic15_match_batch(dets, nd, gts, ng, gdontcare, iou_thr, area_prec_thr, det_match, gt_match, record, ws, inter=None):
@@ -1294,30 +1386,18 @@ def eval_ic15_match_batch(dets, nd, gts, ng, gdontcare, iou_thr, area_prec_thr, 
     ocr_eval_collect's order, gts int32 [n,max_g,4,2] / ng int32 [n], gdontcare uint8 [n,max_g] -> det_match int32 [n,max_d]
     (gt index, -1 unmatched, -2 don't-care), gt_match int32 [n,max_g] (det index, -1, -2); record int64 [4] is added to;
     inter: optional float64 [n,max_g,max_d], the pair intersection areas."""
-    n, max_d = dets.shape[:2]
-    max_g = gts.shape[1]
-    if tuple(dets.shape) != (n, max_d, 4, 2) or tuple(gts.shape) != (n, max_g, 4, 2) or nd.numel() != n or ng.numel() != n or \
-            tuple(gdontcare.shape) != (n, max_g) or tuple(det_match.shape) != (n, max_d) or \
-            tuple(gt_match.shape) != (n, max_g) or record.numel() != 4 or \
-            (inter is not None and tuple(inter.shape) != (n, max_g, max_d)):
-        raise ValueError("eval_ic15_match_batch: tensors do not match n, max_d, max_g")
-    if dets.dtype != torch.int32 or gts.dtype != torch.int32 or nd.dtype != torch.int32 or ng.dtype != torch.int32 or \
-            gdontcare.dtype != torch.uint8 or det_match.dtype != torch.int32 or gt_match.dtype != torch.int32 or \
-            record.dtype != torch.int64 or (inter is not None and inter.dtype != torch.float64):
-        raise ValueError("eval_ic15_match_batch: quads, counts and matches int32, flags uint8, record int64, inter float64")
-    for t in (dets, nd, gts, ng, gdontcare, det_match, gt_match, record) + (() if inter is None else (inter,)):
-        if not t.is_contiguous():
-            raise ValueError("eval_ic15_match_batch: contiguous tensors only")
-    nbytes = L.call_size("ocr_eval_ic15_workspace", c_int(n), c_int(max_d), c_int(max_g))
-    buf = ws.get(nbytes)
+    n, max_d = _dims("eval_ic15_match_batch", "dets", dets, 4)[:2]
+    max_g = _dims("eval_ic15_match_batch", "gts", gts, 4)[1]
+    _operands("eval_ic15_match_batch", "n, max_d, max_g", *_quad_rows(dets, nd, gts, ng, n, max_d, max_g),
+              ("gdontcare", gdontcare, U8, (n, max_g)), ("det_match", det_match, I32, (n, max_d)),
+              ("gt_match", gt_match, I32, (n, max_g)), ("record", record, I64, 4), ("inter", inter, F64, (n, max_g, max_d), OPTIONAL))
     L.call("ocr_eval_ic15_match_batch", ptr(dets), ptr(nd), ptr(gts), ptr(ng), ptr(gdontcare), c_int(n), c_int(max_d),
            c_int(max_g), c_double(iou_thr), c_double(area_prec_thr), ptr(det_match), ptr(gt_match), ptr(inter), ptr(record),
-           ptr(buf), c_size_t(nbytes), _st())
+           *_workspace(ws, "ocr_eval_ic15_workspace", c_int(n), c_int(max_d), c_int(max_g)), _st())
 
 
 def eval_record_init(record):
-    if record.numel() != 4 or record.dtype != torch.int64 or not record.is_contiguous():
-        raise ValueError("eval_record_init: record is int64 [4]")
+    _operands("eval_record_init", "its four counters", ("record", record, I64, 4))
     L.call("ocr_eval_record_init", ptr(record), _st())
 
 
@@ -1325,36 +1405,26 @@ def eval_record_init(record):
 EVAL_MAX_T = 64                         # the most thresholds one sweep takes
 
 
-def _curve_operands(what, det_score, nd, ng, thresholds, curve, unsorted, pool, n, max_d):
-    """the checks the two curve entries share -> (T, pool pointers)"""
-    T = thresholds.numel()
-    if tuple(det_score.shape) != (n, max_d) or nd.numel() != n or ng.numel() != n or thresholds.dim() != 1 or \
-            tuple(curve.shape) != (T, 4) or unsorted.numel() != 1:
-        raise ValueError("%s: tensors do not match n, max_d, max_g, T" % what)
-    if det_score.dtype != torch.float32 or nd.dtype != torch.int32 or ng.dtype != torch.int32 or \
-            thresholds.dtype != torch.float32 or curve.dtype != torch.int64 or unsorted.dtype != torch.int32:
-        raise ValueError("%s: scores and thresholds f32, counts and the flag int32, curve int64" % what)
-    ts = [det_score, nd, ng, thresholds, curve, unsorted]
-    if pool is not None:
-        pool_score, pool_cum, pool_nd = pool
-        if tuple(pool_score.shape) != (n, max_d) or tuple(pool_cum.shape) != (n, max_d, 2) or pool_nd.numel() != n:
-            raise ValueError("%s: tensors do not match n, max_d, max_g, T" % what)
-        if pool_score.dtype != torch.float32 or pool_cum.dtype != torch.int32 or pool_nd.dtype != torch.int32:
-            raise ValueError("%s: pool scores f32, pool counts int32" % what)
-        ts += [pool_score, pool_cum, pool_nd]
-    for t in ts:
-        if not t.is_contiguous():
-            raise ValueError("%s: contiguous tensors only" % what)
-    return T, [ptr(t) for t in (pool if pool is not None else (None, None, None))]
+def _pool_rows(pool_score, pool_cum, pool_nd, n, max_d):
+    """rows of the AP pool"""
+    return ("pool_score", pool_score, F32, (n, max_d)), ("pool_cum", pool_cum, I32, (n, max_d, 2)), ("pool_nd", pool_nd, I32, n)
+
+
+def _curve_rows(what, det_score, nd, ng, thresholds, curve, unsorted, pool, n, max_d):
+    """the operands the two curve entries share -> (T, their rows, the three pool tensors or None)"""
+    T = _dims(what, "thresholds", thresholds, 1)[0]
+    rows = (("det_score", det_score, F32, (n, max_d)), ("nd", nd, I32, n), ("ng", ng, I32, n), ("thresholds", thresholds, F32, (T,)),
+            ("curve", curve, I64, (T, 4)), ("unsorted", unsorted, I32, 1))
+    if pool is None:
+        return T, rows, (None, None, None)
+    return T, rows + _pool_rows(*pool, n, max_d), pool
 
 
 def eval_curve_init(curve, unsorted, ap=None):
     """zeroes curve int64 [T,4], the order flag int32 [1] and, when given, ap float64 [1] (include/ocr_eval_curve.h)"""
-    if curve.dim() != 2 or curve.shape[1] != 4 or curve.dtype != torch.int64 or unsorted.numel() != 1 or \
-            unsorted.dtype != torch.int32 or (ap is not None and (ap.numel() != 1 or ap.dtype != torch.float64)) or \
-            not curve.is_contiguous():
-        raise ValueError("eval_curve_init: curve int64 [T,4], unsorted int32 [1], ap float64 [1]")
-    L.call("ocr_eval_curve_init", ptr(curve), c_int(curve.shape[0]), ptr(unsorted), ptr(ap), _st())
+    T = _dims("eval_curve_init", "curve", curve, 2)[0]
+    _operands("eval_curve_init", "T", ("curve", curve, I64, (T, 4)), ("unsorted", unsorted, I32, 1), ("ap", ap, F64, 1, OPTIONAL))
+    L.call("ocr_eval_curve_init", ptr(curve), c_int(T), ptr(unsorted), ptr(ap), _st())
 
 
 def eval_curve_batch(tp, fp, det_score, nd, ng, gignored, thresholds, curve, unsorted, pool=None):
@@ -1362,53 +1432,35 @@ def eval_curve_batch(tp, fp, det_score, nd, ng, gignored, thresholds, curve, uns
     [n,max_d], det_score f32 [n,max_d], nd, ng int32 [n], gignored uint8 [n,max_g], thresholds f32 [T] -> curve int64 [T,4]
     is added to, unsorted int32 [1] OR-ed into; pool: None or (pool_score f32 [n,max_d], pool_cum int32 [n,max_d,2],
     pool_nd int32 [n]), these images' rows of the AP pool."""
-    n, max_d = tp.shape
-    max_g = gignored.shape[1]
-    if tuple(fp.shape) != (n, max_d) or tuple(gignored.shape) != (n, max_g):
-        raise ValueError("eval_curve_batch: tensors do not match n, max_d, max_g, T")
-    if tp.dtype != torch.uint8 or fp.dtype != torch.uint8 or gignored.dtype != torch.uint8:
-        raise ValueError("eval_curve_batch: flags uint8")
-    T, pp = _curve_operands("eval_curve_batch", det_score, nd, ng, thresholds, curve, unsorted, pool, n, max_d)
-    for t in (tp, fp, gignored):
-        if not t.is_contiguous():
-            raise ValueError("eval_curve_batch: contiguous tensors only")
+    n, max_d = _dims("eval_curve_batch", "tp", tp, 2)
+    max_g = _dims("eval_curve_batch", "gignored", gignored, 2)[1]
+    T, rows, pool = _curve_rows("eval_curve_batch", det_score, nd, ng, thresholds, curve, unsorted, pool, n, max_d)
+    _operands("eval_curve_batch", "n, max_d, max_g, T", ("tp", tp, U8, (n, max_d)), ("fp", fp, U8, (n, max_d)),
+              ("gignored", gignored, U8, (n, max_g)), *rows)
     L.call("ocr_eval_curve_batch", ptr(tp), ptr(fp), ptr(det_score), ptr(nd), ptr(ng), ptr(gignored), ptr(thresholds), c_int(n),
-           c_int(max_d), c_int(max_g), c_int(T), ptr(curve), ptr(unsorted), pp[0], pp[1], pp[2], _st())
+           c_int(max_d), c_int(max_g), c_int(T), ptr(curve), ptr(unsorted), ptr(pool[0]), ptr(pool[1]), ptr(pool[2]), _st())
 
 
 def eval_ic15_curve_batch(det_match, gt_match, det_score, nd, ng, thresholds, curve, unsorted, pool=None):
     """`eval_curve_batch` from the ICDAR-2015 matcher's outputs: det_match int32 [n,max_d], gt_match int32 [n,max_g]."""
-    n, max_d = det_match.shape
-    max_g = gt_match.shape[1]
-    if gt_match.shape[0] != n:
-        raise ValueError("eval_ic15_curve_batch: tensors do not match n, max_d, max_g, T")
-    if det_match.dtype != torch.int32 or gt_match.dtype != torch.int32:
-        raise ValueError("eval_ic15_curve_batch: matches int32")
-    T, pp = _curve_operands("eval_ic15_curve_batch", det_score, nd, ng, thresholds, curve, unsorted, pool, n, max_d)
-    for t in (det_match, gt_match):
-        if not t.is_contiguous():
-            raise ValueError("eval_ic15_curve_batch: contiguous tensors only")
+    n, max_d = _dims("eval_ic15_curve_batch", "det_match", det_match, 2)
+    max_g = _dims("eval_ic15_curve_batch", "gt_match", gt_match, 2)[1]
+    T, rows, pool = _curve_rows("eval_ic15_curve_batch", det_score, nd, ng, thresholds, curve, unsorted, pool, n, max_d)
+    _operands("eval_ic15_curve_batch", "n, max_d, max_g, T", ("det_match", det_match, I32, (n, max_d)),
+              ("gt_match", gt_match, I32, (n, max_g)), *rows)
     L.call("ocr_eval_ic15_curve_batch", ptr(det_match), ptr(gt_match), ptr(det_score), ptr(nd), ptr(ng), ptr(thresholds),
-           c_int(n), c_int(max_d), c_int(max_g), c_int(T), ptr(curve), ptr(unsorted), pp[0], pp[1], pp[2], _st())
+           c_int(n), c_int(max_d), c_int(max_g), c_int(T), ptr(curve), ptr(unsorted), ptr(pool[0]), ptr(pool[1]), ptr(pool[2]), _st())
 
 
 def eval_ap(pool_score, pool_cum, pool_nd, record, ap, ws):
     """Average precision over the pool of a pass (include/ocr_eval_curve.h: ocr_eval_ap): pool_score f32 [n_img,max_d],
     pool_cum int32 [n_img,max_d,2], pool_nd int32 [n_img], record int64 [4] (slot 0 = G, read on the device) -> ap
     float64 [1]."""
-    n_img, max_d = pool_score.shape
-    if tuple(pool_cum.shape) != (n_img, max_d, 2) or pool_nd.numel() != n_img or record.numel() != 4 or ap.numel() != 1:
-        raise ValueError("eval_ap: tensors do not match n_img, max_d")
-    if pool_score.dtype != torch.float32 or pool_cum.dtype != torch.int32 or pool_nd.dtype != torch.int32 or \
-            record.dtype != torch.int64 or ap.dtype != torch.float64:
-        raise ValueError("eval_ap: pool scores f32, pool counts int32, record int64, ap float64")
-    for t in (pool_score, pool_cum, pool_nd, record, ap):
-        if not t.is_contiguous():
-            raise ValueError("eval_ap: contiguous tensors only")
-    nbytes = L.call_size("ocr_eval_ap_workspace", c_int(n_img), c_int(max_d))
-    buf = ws.get(nbytes)
+    n_img, max_d = _dims("eval_ap", "pool_score", pool_score, 2)
+    _operands("eval_ap", "n_img, max_d", *_pool_rows(pool_score, pool_cum, pool_nd, n_img, max_d), ("record", record, I64, 4),
+              ("ap", ap, F64, 1))
     L.call("ocr_eval_ap", ptr(pool_score), ptr(pool_cum), ptr(pool_nd), c_int(n_img), c_int(max_d), ptr(record), ptr(ap),
-           ptr(buf), c_size_t(nbytes), _st())
+           *_workspace(ws, "ocr_eval_ap_workspace", c_int(n_img), c_int(max_d)), _st())
 
 
 # ------------------------------------------------------------------ multi-scale pooling and fusion (csrc/multiscale.hip)
@@ -1422,22 +1474,12 @@ def ms_pool_append(merged, keep_idx, n_keep, passed, mean, ratio, scale_id, pool
     None, per keep slot; mean f32 [n,max_k], the pooled score of each keep slot; ratio f32 [n,2] = (ratio_w, ratio_h)) is
     appended in keep order to pool f32 [n,max_pool,9] / pool_scale int32 [n,max_pool] after pool_count int32 [n]; pool_total
     keeps the true count, pool_nonfinite the dropped non-finite rows (include/ocr_multiscale.h: ocr_ms_pool_append)."""
-    n, max_k, _ = merged.shape
-    max_pool = pool.shape[1]
-    if tuple(merged.shape) != (n, max_k, 9) or tuple(keep_idx.shape) != (n, max_k) or n_keep.numel() != n or \
-            tuple(mean.shape) != (n, max_k) or tuple(ratio.shape) != (n, 2) or tuple(pool.shape) != (n, max_pool, 9) or \
-            tuple(pool_scale.shape) != (n, max_pool) or pool_count.numel() != n or pool_total.numel() != n or \
-            pool_nonfinite.numel() != n or (passed is not None and tuple(passed.shape) != (n, max_k)):
-        raise ValueError("ms_pool_append: tensors do not match n, max_k, max_pool")
-    if merged.dtype != torch.float32 or keep_idx.dtype != torch.int32 or n_keep.dtype != torch.int32 or \
-            mean.dtype != torch.float32 or ratio.dtype != torch.float32 or pool.dtype != torch.float32 or \
-            pool_scale.dtype != torch.int32 or pool_count.dtype != torch.int32 or pool_total.dtype != torch.int32 or \
-            pool_nonfinite.dtype != torch.int32 or (passed is not None and passed.dtype != torch.uint8):
-        raise ValueError("ms_pool_append: merged / mean / ratio / pool f32, passed uint8, the index and count tensors int32")
-    for t in (merged, keep_idx, n_keep, mean, ratio, pool, pool_scale, pool_count, pool_total, pool_nonfinite) + \
-            (() if passed is None else (passed,)):
-        if not t.is_contiguous():
-            raise ValueError("ms_pool_append: contiguous tensors only")
+    n, max_k, _ = _dims("ms_pool_append", "merged", merged, 3)
+    max_pool = _dims("ms_pool_append", "pool", pool, 3)[1]
+    _operands("ms_pool_append", "n, max_k, max_pool", *_lanms_rows(merged, keep_idx, n_keep, n, max_k),
+              ("passed", passed, U8, (n, max_k), OPTIONAL), ("mean", mean, F32, (n, max_k)), ("ratio", ratio, F32, (n, 2)),
+              ("pool", pool, F32, (n, max_pool, 9)), ("pool_scale", pool_scale, I32, (n, max_pool)), ("pool_count", pool_count, I32, n),
+              ("pool_total", pool_total, I32, n), ("pool_nonfinite", pool_nonfinite, I32, n))
     L.call("ocr_ms_pool_append", ptr(merged), ptr(keep_idx), ptr(n_keep), ptr(passed), ptr(mean), ptr(ratio), c_int(scale_id),
            c_int(n), c_int(max_k), c_int(max_pool), ptr(pool), ptr(pool_scale), ptr(pool_count), ptr(pool_total),
            ptr(pool_nonfinite), _st())
@@ -1447,27 +1489,19 @@ def quad_fuse(pool, pool_count, iou_thresh, mode, fused, keep_idx, n_keep, owner
     """Score-ordered NMS over each image's pooled list (include/ocr_multiscale.h: ocr_quad_fuse): pool f32 [n,max_pool,9],
     pool_count int32 [n], mode 'nms' / 'vote' (or 0 / 1) -> fused f32 [n,max_pool,9], keep_idx int32 [n,max_pool], n_keep int32
     [n] (ocr_lanms's layout: ocr_eval_collect takes them as they are), owner int32 [n,max_pool]."""
-    n, max_pool, _ = pool.shape
+    n, max_pool, _ = _dims("quad_fuse", "pool", pool, 3)
     mode = FUSE_MODES.get(mode, mode)
     if mode not in (0, 1):
         raise ValueError("quad_fuse: mode is 'nms' (0) or 'vote' (1), got %r" % (mode,))
-    if tuple(pool.shape) != (n, max_pool, 9) or pool_count.numel() != n or tuple(fused.shape) != (n, max_pool, 9) or \
-            tuple(keep_idx.shape) != (n, max_pool) or n_keep.numel() != n or tuple(owner.shape) != (n, max_pool):
-        raise ValueError("quad_fuse: tensors do not match n, max_pool")
     if max_pool > FUSE_MAX_POOL:
         raise ValueError("quad_fuse: max_pool %d is beyond the %d pooled quads per image it takes" % (max_pool, FUSE_MAX_POOL))
-    if pool.dtype != torch.float32 or pool_count.dtype != torch.int32 or fused.dtype != torch.float32 or \
-            keep_idx.dtype != torch.int32 or n_keep.dtype != torch.int32 or owner.dtype != torch.int32:
-        raise ValueError("quad_fuse: pool / fused f32, the index and count tensors int32")
-    for t in (pool, pool_count, fused, keep_idx, n_keep, owner):
-        if not t.is_contiguous():
-            raise ValueError("quad_fuse: contiguous tensors only")
+    _operands("quad_fuse", "n, max_pool", ("pool", pool, F32, (n, max_pool, 9)), ("pool_count", pool_count, I32, n),
+              ("fused", fused, F32, (n, max_pool, 9)), ("keep_idx", keep_idx, I32, (n, max_pool)), ("n_keep", n_keep, I32, n),
+              ("owner", owner, I32, (n, max_pool)))
     if fused.data_ptr() == pool.data_ptr():
         raise ValueError("quad_fuse: fused must not be the pool")
-    nbytes = L.call_size("ocr_quad_fuse_workspace", c_int(n), c_int(max_pool))
-    buf = ws.get(nbytes)
     L.call("ocr_quad_fuse", ptr(pool), ptr(pool_count), c_int(n), c_int(max_pool), c_float(iou_thresh), c_int(mode), ptr(fused),
-           ptr(keep_idx), ptr(n_keep), ptr(owner), ptr(buf), c_size_t(nbytes), _st())
+           ptr(keep_idx), ptr(n_keep), ptr(owner), *_workspace(ws, "ocr_quad_fuse_workspace", c_int(n), c_int(max_pool)), _st())
 
 
 # ------------------------------------------------------------------ score-map fusion of the link geometry (csrc/map_fuse.hip)
@@ -1476,18 +1510,10 @@ def link_map_accumulate(pixel_logits, link_logits, flip, weight, first, acc):
     on the fusion grid, times `weight` (a normalised weight, finite and > 0), stored in (`first`) or added to acc f32
     [9,n,hf,wf]: plane 0 = P(text), 1 + d = P(link d); `flip`: the pass saw the images mirrored left to right
     (include/ocr_map_fuse.h: ocr_link_map_accumulate)."""
-    if pixel_logits.dim() != 4 or link_logits.dim() != 4 or acc.dim() != 4:
-        raise ValueError("link_map_accumulate: pixel_logits [n,hs,ws,2], link_logits [n,hs,ws,16], acc [9,n,hf,wf]")
-    n, hs, ws, _ = pixel_logits.shape
-    hf, wf = acc.shape[2:]
-    if tuple(pixel_logits.shape) != (n, hs, ws, 2) or tuple(link_logits.shape) != (n, hs, ws, 16) or \
-            tuple(acc.shape) != (9, n, hf, wf):
-        raise ValueError("link_map_accumulate: tensors do not match n, hs, ws (logits [..,2] and [..,16]) or acc is not [9,n,hf,wf]")
-    if pixel_logits.dtype != torch.float32 or link_logits.dtype != torch.float32 or acc.dtype != torch.float32:
-        raise ValueError("link_map_accumulate: logits and acc f32")
-    for t in (pixel_logits, link_logits, acc):
-        if not t.is_contiguous():
-            raise ValueError("link_map_accumulate: contiguous tensors only")
+    n, hs, ws, _ = _dims("link_map_accumulate", "pixel_logits", pixel_logits, 4)
+    hf, wf = _dims("link_map_accumulate", "acc", acc, 4)[2:]
+    _operands("link_map_accumulate", "n, hs, ws, hf, wf", ("pixel_logits", pixel_logits, F32, (n, hs, ws, 2)),
+              ("link_logits", link_logits, F32, (n, hs, ws, 16)), ("acc", acc, F32, (9, n, hf, wf)))
     weight = float(weight)
     if not (weight > 0.0 and weight != float("inf")):
         raise ValueError("link_map_accumulate: weight must be finite and positive, got %r" % (weight,))
@@ -1499,40 +1525,22 @@ def link_map_accumulate(pixel_logits, link_logits, flip, weight, first, acc):
 def component_scores(labels, pixel_score, ncomp, comp_score, ws):
     """labels int32 [n,h,w] (ocr_link_cc), pixel_score f32 [n,h,w], ncomp int32 [n] -> comp_score f32 [n,max_comps]: the
     mean pixel score of every component, summed as exact integers (include/ocr_hip.h: ocr_component_scores)."""
-    n, h, w = labels.shape
-    max_comps = comp_score.shape[1]
-    if tuple(pixel_score.shape) != (n, h, w) or ncomp.numel() != n or tuple(comp_score.shape) != (n, max_comps):
-        raise ValueError("component_scores: tensors do not match n, h, w, max_comps")
-    if labels.dtype != torch.int32 or pixel_score.dtype != torch.float32 or ncomp.dtype != torch.int32 or \
-            comp_score.dtype != torch.float32:
-        raise ValueError("component_scores: labels / ncomp int32, pixel_score / comp_score f32")
-    for t in (labels, pixel_score, ncomp, comp_score):
-        if not t.is_contiguous():
-            raise ValueError("component_scores: contiguous tensors only")
-    nbytes = L.call_size("ocr_component_scores_workspace", c_int(n), c_int(max_comps))
-    buf = ws.get(nbytes)
+    n, h, w = _dims("component_scores", "labels", labels, 3)
+    max_comps = _dims("component_scores", "comp_score", comp_score, 2)[1]
+    _operands("component_scores", "n, h, w, max_comps", ("labels", labels, I32, (n, h, w)), ("pixel_score", pixel_score, F32, (n, h, w)),
+              ("ncomp", ncomp, I32, n), ("comp_score", comp_score, F32, (n, max_comps)))
     L.call("ocr_component_scores", ptr(labels), ptr(pixel_score), ptr(ncomp), c_int(n), c_int(h), c_int(w), c_int(max_comps),
-           ptr(comp_score), ptr(buf), c_size_t(nbytes), _st())
+           ptr(comp_score), *_workspace(ws, "ocr_component_scores_workspace", c_int(n), c_int(max_comps)), _st())
 
 
 def link_boxes(hull_n, hull_head, calipers, comp_score, ncomp, min_side, min_area, merged, keep_idx, n_keep, passed, total):
     """ocr_min_area_rects' outputs + comp_score f32 [n,max_comps] + ncomp int32 [n] -> the rows ocr_eval_collect reads:
     merged f32 [n,max_comps,9] (truncated corners, score), keep_idx int32 [n,max_comps] (identity), n_keep int32 [n],
     passed uint8 [n,max_comps], total int32 [n] (include/ocr_hip.h: ocr_link_boxes)."""
-    n, max_comps = hull_n.shape
-    if tuple(hull_head.shape) != (n, max_comps, 4) or tuple(calipers.shape) != (n, max_comps, 6) or \
-            tuple(comp_score.shape) != (n, max_comps) or ncomp.numel() != n or tuple(merged.shape) != (n, max_comps, 9) or \
-            tuple(keep_idx.shape) != (n, max_comps) or n_keep.numel() != n or tuple(passed.shape) != (n, max_comps) or \
-            total.numel() != n:
-        raise ValueError("link_boxes: tensors do not match n, max_comps")
-    if hull_n.dtype != torch.int32 or hull_head.dtype != torch.int32 or calipers.dtype != torch.float32 or \
-            comp_score.dtype != torch.float32 or ncomp.dtype != torch.int32 or merged.dtype != torch.float32 or \
-            keep_idx.dtype != torch.int32 or n_keep.dtype != torch.int32 or passed.dtype != torch.uint8 or \
-            total.dtype != torch.int32:
-        raise ValueError("link_boxes: calipers / comp_score / merged f32, passed uint8, everything else int32")
-    for t in (hull_n, hull_head, calipers, comp_score, ncomp, merged, keep_idx, n_keep, passed, total):
-        if not t.is_contiguous():
-            raise ValueError("link_boxes: contiguous tensors only")
+    n, max_comps = _dims("link_boxes", "hull_n", hull_n, 2)
+    _operands("link_boxes", "n, max_comps", *_hull_rows(n, max_comps, hull_n, hull_head, calipers),
+              ("comp_score", comp_score, F32, (n, max_comps)), ("ncomp", ncomp, I32, n),
+              *_lanms_rows(merged, keep_idx, n_keep, n, max_comps), ("passed", passed, U8, (n, max_comps)), ("total", total, I32, n))
     L.call("ocr_link_boxes", ptr(hull_n), ptr(hull_head), ptr(calipers), ptr(comp_score), ptr(ncomp), c_int(n),
            c_int(max_comps), c_float(min_side), c_float(min_area), ptr(merged), ptr(keep_idx), ptr(n_keep), ptr(passed),
            ptr(total), _st())
@@ -1543,7 +1551,6 @@ GRID_MAX_POINTS = 65          # 64 grid points and the base pair (include/ocr_de
 
 
 def _grid_table(values, name):
-    import ctypes
     vals = [float(v) for v in values]
     if not 1 <= len(vals) <= GRID_MAX_POINTS:
         raise ValueError("%s: 1 to %d grid points, got %d" % (name, GRID_MAX_POINTS, len(vals)))
@@ -1556,53 +1563,31 @@ def link_cc_grid(pixel_score, link_score, stride, offset, pixel_thresholds, link
     ocr_link_cc_grid): pixel_score f32 [n,h,w], link_score as `link_cc` takes it, the thresholds two sequences of G
     numbers (host values: they travel in the kernel arguments) -> labels int32 [G*n,h,w], ncomp int32 [G*n], comps int32
     [G*n,max_comps,2]; slice g*n + i is image i at point g."""
-    n, h, w = pixel_score.shape
+    n, h, w = _dims("link_cc_grid", "pixel_score", pixel_score, 3)
     tp, tl = _grid_table(pixel_thresholds, "link_cc_grid"), _grid_table(link_thresholds, "link_cc_grid")
     G = len(tp)
     if len(tl) != G:
         raise ValueError("link_cc_grid: %d pixel thresholds for %d link thresholds" % (G, len(tl)))
-    if labels.dim() != 3 or comps.dim() != 3:
-        raise ValueError("link_cc_grid: labels [G*n,h,w], comps [G*n,max_comps,2]")
-    max_comps = comps.shape[1]
-    if tuple(labels.shape) != (G * n, h, w) or ncomp.numel() != G * n or tuple(comps.shape) != (G * n, max_comps, 2):
-        raise ValueError("link_cc_grid: tensors do not match G, n, h, w, max_comps")
-    if pixel_score.dtype != torch.float32 or link_score.dtype != torch.float32 or labels.dtype != torch.int32 or \
-            ncomp.dtype != torch.int32 or comps.dtype != torch.int32:
-        raise ValueError("link_cc_grid: pixel_score / link_score f32, labels / ncomp / comps int32")
-    if link_score.numel() != 8 * n * h * w * stride:
-        raise ValueError("link_cc_grid: link_score does not hold [8,n,h,w] elements of stride %d" % stride)
-    for t in (pixel_score, link_score, labels, ncomp, comps):
-        if not t.is_contiguous():
-            raise ValueError("link_cc_grid: contiguous tensors only")
-    nbytes = L.call_size("ocr_link_cc_grid_workspace", c_int(G), c_int(n), c_int(h), c_int(w))
-    buf = ws.get(nbytes)
+    max_comps = _dims("link_cc_grid", "comps", comps, 3)[1]
+    _operands("link_cc_grid", "G, n, h, w, stride, max_comps", *_link_cc_rows(pixel_score, link_score, stride, n, h, w),
+              ("labels", labels, I32, (G * n, h, w)), ("ncomp", ncomp, I32, G * n), ("comps", comps, I32, (G * n, max_comps, 2)))
     L.call("ocr_link_cc_grid", ptr(pixel_score), ptr(link_score), c_int(stride), c_int(offset), c_int(n), c_int(h), c_int(w),
-           c_int(G), tp, tl, c_int(min_size), ptr(labels), ptr(ncomp), ptr(comps), c_int(max_comps), ptr(buf),
-           c_size_t(nbytes), _st())
+           c_int(G), tp, tl, c_int(min_size), ptr(labels), ptr(ncomp), ptr(comps), c_int(max_comps),
+           *_workspace(ws, "ocr_link_cc_grid_workspace", c_int(G), c_int(n), c_int(h), c_int(w)), _st())
 
 
 def component_scores_grid(labels, pixel_score, ncomp, comp_score, ws):
     """`component_scores` for labels int32 [G*n,h,w] against pixel_score f32 [n,h,w], slice b reading map b mod n ->
     comp_score f32 [G*n,max_comps] (include/ocr_decode_grid.h: ocr_component_scores_grid)."""
-    if labels.dim() != 3 or pixel_score.dim() != 3 or comp_score.dim() != 2:
-        raise ValueError("component_scores_grid: labels [G*n,h,w], pixel_score [n,h,w], comp_score [G*n,max_comps]")
-    N, h, w = labels.shape
-    n = pixel_score.shape[0]
-    max_comps = comp_score.shape[1]
-    if n < 1 or N % n or tuple(pixel_score.shape) != (n, h, w) or ncomp.numel() != N or \
-            tuple(comp_score.shape) != (N, max_comps):
-        raise ValueError("component_scores_grid: tensors do not match G*n, n, h, w, max_comps")
-    if labels.dtype != torch.int32 or pixel_score.dtype != torch.float32 or ncomp.dtype != torch.int32 or \
-            comp_score.dtype != torch.float32:
-        raise ValueError("component_scores_grid: labels / ncomp int32, pixel_score / comp_score f32")
-    for t in (labels, pixel_score, ncomp, comp_score):
-        if not t.is_contiguous():
-            raise ValueError("component_scores_grid: contiguous tensors only")
-    G = N // n
-    nbytes = L.call_size("ocr_component_scores_grid_workspace", c_int(G), c_int(n), c_int(max_comps))
-    buf = ws.get(nbytes)
+    N, h, w = _dims("component_scores_grid", "labels", labels, 3)
+    n = _dims("component_scores_grid", "pixel_score", pixel_score, 3)[0]
+    max_comps = _dims("component_scores_grid", "comp_score", comp_score, 2)[1]
+    G = N // max(n, 1)
+    _operands("component_scores_grid", "G, n, h, w, max_comps", ("labels", labels, I32, (G * n, h, w)),
+              ("pixel_score", pixel_score, F32, (n, h, w)), ("ncomp", ncomp, I32, N), ("comp_score", comp_score, F32, (N, max_comps)))
     L.call("ocr_component_scores_grid", ptr(labels), ptr(pixel_score), ptr(ncomp), c_int(G), c_int(n), c_int(h), c_int(w),
-           c_int(max_comps), ptr(comp_score), ptr(buf), c_size_t(nbytes), _st())
+           c_int(max_comps), ptr(comp_score), *_workspace(ws, "ocr_component_scores_grid_workspace", c_int(G), c_int(n), c_int(max_comps)),
+           _st())
 
 
 # -------------------------------------------------------------------------- optimiser
@@ -1749,7 +1734,10 @@ def tensor_stats_workspace(n_chunks):
 
 def tensor_stats(x, table, n_segments, mul_host, mul_dev, records, ws):
     """Per-segment records of the f32 buffer `x` times mul_host * mul_dev[0] (mul_dev: a 1-element f32 device view or None)."""
-    assert records.numel() * records.element_size() >= n_segments * tensor_stats_record_bytes()
+    _operands("tensor_stats", "n_segments", ("x", x, F32, None), ("table", table, None, None), ("mul_dev", mul_dev, F32, 1, OPTIONAL),
+              ("records", records, None, None), ("ws", ws, None, None))
+    if records.numel() * records.element_size() < n_segments * tensor_stats_record_bytes():
+        raise ValueError("tensor_stats: records holds fewer than n_segments = %d records" % n_segments)
     L.call("ocr_tensor_stats_f32", ptr(x), ptr(table), c_int(n_segments), c_float(mul_host), ptr(mul_dev), ptr(records),
            ptr(ws), c_size_t(ws.numel() * ws.element_size()), _st())
 
@@ -1760,9 +1748,10 @@ def summary_image_workspace():
 
 def summary_image_u8(x, out, ws):
     """One image [h, w, c] f32 -> u8 [h, w, c] by tf.summary.image's float rule."""
-    h, w, c = x.shape
-    assert x.is_contiguous() and out.is_contiguous() and out.numel() == x.numel() and out.element_size() == 1
-    assert ws.numel() * ws.element_size() >= summary_image_workspace()
+    h, w, c = _dims("summary_image_u8", "x", x, 3)
+    _operands("summary_image_u8", "h, w, c", ("x", x, F32, (h, w, c)), ("out", out, U8, h * w * c), ("ws", ws, None, None))
+    if ws.numel() * ws.element_size() < summary_image_workspace():
+        raise ValueError("summary_image_u8: ws holds fewer than the %d bytes it takes" % summary_image_workspace())
     L.call("ocr_summary_image_u8", ptr(x), c_int(h), c_int(w), c_int(c), ptr(out), ptr(ws), _st())
 
 
@@ -1781,7 +1770,7 @@ def fill_(x, value=0.0):
 # (product library: matrix-core f32 convolution + element-wise f32 kernels, csrc/f32_infer.hip; the plain direct
 #  convolution of libocr_verify.so / include/ocr_verify.h is its independent checker: F32_CONV = "direct";
 #  F32_CONV = "split" runs every convolution of an f32 graph as Graph(precision="f16x2") does, csrc/f16x2_infer.hip)
-F32_CONV = __import__("os").environ.get("OCR_F32_CONV", "mfma")
+F32_CONV = os.environ.get("OCR_F32_CONV", "mfma")
 
 
 def conv2d_f32_split_workspace(d):

@@ -126,6 +126,26 @@ def test_cal_link_loss_value_slices_and_gradient(device):
         MV.cal_link_loss(gt_d[..., 0:1], pr_d[..., 0:2], W[:-1], graph=g)
 
 
+def test_a_count_tensor_left_on_the_host_is_refused_before_the_launch(device):
+    """`ops.lanms` with `counts` on the CPU and `ops.link_cc` with `ncomp` on the CPU: a ValueError that names the operand,
+    raised on the host — the library is not reached, the sentinel-filled outputs stay as they were."""
+    from tensorflow_ocr_amd import ops
+    from tensorflow_ocr_amd.graph import Graph
+    g = Graph(device)
+    full = lambda *s, dt=torch.int32: torch.full(s, -7, dtype=dt, device=device)
+    f32 = torch.float32
+    boxes = torch.zeros((2, 4, 9), dtype=f32, device=device)
+    outs = [full(2, 4, 9, dt=f32), full(2), full(2, 4), full(2)]
+    with pytest.raises(ValueError, match=r"lanms: .*\bcounts\b"):
+        ops.lanms(boxes, torch.full((2,), 4, dtype=torch.int32), 0.2, *outs, g.workspace())
+    maps = torch.zeros((1, 8, 8), dtype=f32, device=device), torch.zeros((8, 1, 8, 8), dtype=f32, device=device)
+    labels, comps = full(1, 8, 8), full(1, 4, 2)
+    with pytest.raises(ValueError, match=r"link_cc: .*\bncomp\b"):
+        ops.link_cc(*maps, 1, 0, 1, 8, 8, 0.5, 0.5, 0, labels, torch.zeros((1,), dtype=torch.int32), comps, g.workspace())
+    torch.cuda.synchronize()
+    assert all(bool((t == -7).all()) for t in outs + [labels, comps])
+
+
 def test_tf_pixellink_get_rbox(device):
     from oracle import labels as OL
     from tensorflow_ocr_amd.graph import Graph
